@@ -12,7 +12,10 @@ architecture, BatchNorm statistics randomised; the licensed SMPL-H asset and the
 Windows are independent, so ranks shard them with no data-path collective (weak scaling); the only RCCL traffic is an
 all-gather of per-rank result checksums / counts at the end.
 
-Rank 0 prints ONE JSON line. Besides the contract fields it carries
+Rank 0 prints ONE JSON line. A plain run sets up, warms up, times the --steps steps, writes the outputs of the last
+timed step when --dump-outputs DIR is given (DIR/<name>.npy, float32, at most 64 MB: a fixed, seeded sample of the
+windows when the whole output is larger) and prints the contract fields.  With --full the line also carries
+  fp32_mfma_path  the same timed region once more with the whole path on the fp32 MFMA instruction;
   roofline      the dominant kernel (mlp_fused_kernel: both update MLPs, all layers, one launch per LGD iteration; the
                 hidden-layer GEMM launch when the batch is too small for it) against the fp32 matrix-core peak, from
                 HIP events recorded around every launch on the launch stream (empose_profile_*), in a profiling pass
@@ -20,7 +23,9 @@ Rank 0 prints ONE JSON line. Besides the contract fields it carries
   cpu_baseline  the oracle (oracle/torch_ref.py: dense full-mesh SMPL-H + autograd, the reference's algorithm) timed on
                 the host cores on a bounded sample of the same workload (rank 0, N=1 only); the sample's outputs are
                 also compared with the HIP outputs for the same windows: `mpjpe_hip_vs_oracle_mm` (the "MPJPE vs ref"
-                half of the metric) and `max_abs_diff_pose_shape_joints` (north-star tolerance: 1e-4).
+                half of the metric) and `max_abs_diff_pose_shape_joints` (north-star tolerance: 1e-4);
+  secondary     the other BASELINE configs and the full-mesh workload (secondary_workloads).
+The --no_* switches turn single parts of --full off again.
 """
 import argparse
 import json
@@ -41,6 +46,8 @@ PEAK_BF16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: bf16 dense (v_mfma_f32_32
 X3_PRODUCTS = 6                 # bf16 piece products per fp32 product in mlp_fused_x3.hip (three pieces per operand)
 PEAK_HBM_GBS = 8000.0
 MODEL_SEED = 1615200973  # the released LGD-RNN-12 model id (BASELINE.json configs[2])
+DUMP_LIMIT_BYTES = 64 * 10**6   # --dump-outputs: all files together
+DUMP_SEED = 0
 
 
 def build_net(n_markers, rnn, N):
@@ -72,6 +79,26 @@ def make_inputs(net, dev, B, F, seed):
         return pos.cpu().numpy(), ori.cpu().numpy()
     w = synthetic.make_windows(B, F, seed, sensors)
     return w, [torch.from_numpy(w[k]).to(dev) for k in ('marker_pos', 'marker_oris', 'offset_t', 'offset_r')]
+
+
+def dump_outputs(path, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every tensor of `arrays` ({name: (tensor, batch axis)}, one batch size n for all) as
+    path/<name>.npy in float32.  When they exceed `limit` bytes together, the same fixed, seeded sample of batch indices
+    (sorted) is taken along every batch axis, as many as fit."""
+    n = {t.shape[ax] for t, ax in arrays.values()}
+    assert len(n) == 1, n
+    n = n.pop()
+    row_bytes = sum(4 * t.numel() // n for t, _ in arrays.values())
+    keep = None
+    if row_bytes * n > limit:
+        k = limit // row_bytes
+        assert k > 0, 'one batch entry of the outputs is larger than %d bytes' % limit
+        keep = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+    os.makedirs(path, exist_ok=True)
+    for name, (t, ax) in arrays.items():
+        if keep is not None:
+            t = t.index_select(ax, torch.from_numpy(keep).to(t.device))
+        np.save(os.path.join(path, name + '.npy'), t.detach().to(torch.float32).cpu().numpy())
 
 
 def flops_per_frame(net):
@@ -275,7 +302,7 @@ def vertices_numbers(smpl, dev, T, steps, warmup):
     V = smpl.n_vertices
     bytes_frame = 66 * 4 + 10 * 4 + V * 3 * 4 + 66 * 4
     flops_frame = 2.0 * 200 * (V * 3 + 66) + V * 3 * (4 * 8 + 8)
-    return {'fps': T * steps / wall, 'wall_ms': 1000.0 * wall / steps, 'dev_ms': dev_ms, 'V': V,
+    return {'fps': T * steps / wall, 'wall_ms': 1000.0 * wall / steps, 'dev_ms': dev_ms, 'V': V, 'out': (v, j),
             'bytes_frame': bytes_frame, 'flops_frame': flops_frame,
             'hbm': bytes_frame * T / (dev_ms * 1e-3) / 1e9, 'tfl': flops_frame * T / (dev_ms * 1e-3) / 1e12,
             'tfl_contraction': 2.0 * 200 * (V * 3 + 66) * T / (dev_ms * 1e-3) / 1e12}
@@ -305,9 +332,11 @@ def run_vertices(args, dev):
     smpl = SMPLLayer(synthetic.make_model(), arithmetic=args.arith).to(dev)
     T = args.batch * args.frames
     n = vertices_numbers(smpl, dev, T, args.steps, args.warmup)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'vertices': (n['out'][0], 0), 'joints': (n['out'][1], 0)})
     label, kname, pieces = vertices_arithmetic(args.arith)
-    traffic, traffic_src = None, 'skipped (--no_traffic)'
-    if not args.no_traffic:
+    traffic, traffic_src = None, 'skipped (--no_traffic)' if args.full else 'not measured (needs --full)'
+    if args.full and not args.no_traffic:
         tail = ['--workload', 'vertices', '--arith', args.arith, '--batch', str(args.batch), '--frames', str(args.frames),
                 '--no_traffic'] + [a for kv in args.option for a in ('--option', kv)]
         traffic, traffic_src = pmc_traffic_live(tail, kname)
@@ -407,7 +436,7 @@ def secondary_workloads(args, dev, model):
                                                'frac': n['hbm'] / PEAK_HBM_GBS,
                                                'algorithmic_bytes_per_frame': n['bytes_frame']},
                                   'arithmetic': label}
-        del smpl
+        del smpl, n
     except Exception as e:    # noqa: BLE001
         sec['vertices_t16384'] = {'error': '%s: %s' % (type(e).__name__, e)}
     torch.cuda.empty_cache()
@@ -456,6 +485,13 @@ def main():
     ap.add_argument('--arith', default='f32', choices=['f32', 'bf16x3'],
                     help="vertices workload only: 'bf16x3' = the explicitly labelled split-bf16 variant of the blend-shape "
                          "contraction (not the reference's arithmetic; the headline never uses it)")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure what the headline figure does not need: the fp32 MFMA line, the roofline and '
+                         'per-kernel breakdown (with rocprofv3 --pmc child passes), the CPU baseline with its parity '
+                         'sample and the `secondary` workloads; the --no_* switches below leave single parts out')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float32, '
+                         'at most 64 MB in all: a fixed, seeded sample of the windows / frames when larger)')
     ap.add_argument('--no_cpu_baseline', action='store_true')
     ap.add_argument('--no_profile', action='store_true')
     ap.add_argument('--no_fp32_line', action='store_true',
@@ -468,6 +504,8 @@ def main():
     ap.add_argument('--option', action='append', default=[], metavar='NAME=INT',
                     help='kernel-variant switch of the library (empose_set_option), for A/B runs; repeatable')
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     # `python bench.py --gpus N` as a plain command spawns its own N ranks (one per GPU, RCCL over 127.0.0.1); under
     # `python -m torch.distributed.run` the ranks already exist and this returns at once.  --force_dist sends even one
@@ -526,6 +564,11 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     _lib.check(_lib.lib().empose_async_status())   # a cooperative LSTM kernel that gave up on a poll wrote NaN: not a result
+    if rank == 0 and args.dump_outputs:
+        arrays = {k: (out[k], 0) for k in ('pose', 'shape', 'joints')}
+        if out['state'] is not None:
+            arrays.update(h_n=(out['state'][0], 1), c_n=(out['state'][1], 1))
+        dump_outputs(args.dump_outputs, arrays)
     if dist is not None:
         cdev = D.collective_device(dev)     # the GPU under RCCL (the host under the gloo self-test)
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -548,7 +591,7 @@ def main():
     x3_on = lib0.empose_get_option(b'mlp_x3') != 0 and net.config.m_hidden_size % 64 == 0 and B * F >= 64 * 128
     x3_options = {k: lib0.empose_get_option(k) for k in (b'mlp_x3', b'lstm_x3', b'rows_x3')}
     fp32_line = None
-    if x3_on and not args.no_fp32_line:
+    if x3_on and args.full and not args.no_fp32_line:
         for k in x3_options:          # the whole path on the fp32 MFMA instruction: update MLPs, LSTM steps, heads, blend GEMMs
             _lib.check(lib0.empose_set_option(k, 0))
         for _ in range(max(args.warmup, 1)):
@@ -599,7 +642,7 @@ def main():
         }
         if fp32_line is not None:
             result['fp32_mfma_path'] = fp32_line
-    if rank == 0 and not args.no_profile:
+    if rank == 0 and args.full and not args.no_profile:
         lib = _lib.lib()
         lib.empose_profile_enable(1)
         psteps = 3
@@ -673,9 +716,10 @@ def main():
                               'hbm_frac_on_algorithmic_bytes': value * 1162.0 / 1e9 / PEAK_HBM_GBS}
         result['breakdown_ms_per_step'] = {k: v[0] / psteps for k, v in sorted(prof.items(), key=lambda kv: -kv[1][0])}
         result['breakdown_ms_per_step']['sum_of_kernels'] = total / psteps
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         result['cpu_baseline'] = cpu_baseline(net, model, w, hip_out=out)
-    if rank == 0 and world == 1 and not args.no_secondary and not args.no_rnn and (B, F, args.n_markers) == (1024, 32, 12):
+    if rank == 0 and world == 1 and args.full and not args.no_secondary and not args.no_rnn and \
+            (B, F, args.n_markers) == (1024, 32, 12):
         # (only beside the headline configuration; `value` / `metric` / `config` above are untouched by it)
         del inputs, out
         torch.cuda.empty_cache()

@@ -172,7 +172,7 @@ def test_bench_with_more_gpus_than_the_box_has_exits_with_the_count():
 
 @pytest.mark.gpu
 def test_bench_prints_one_json_line_with_the_contract_fields():
-    r = _run(['--steps', '2', '--warmup', '1', '--batch', '64', '--no_cpu_baseline'])
+    r = _run(['--steps', '2', '--warmup', '1', '--batch', '64', '--full', '--no_cpu_baseline'])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
@@ -193,11 +193,57 @@ def test_bench_prints_one_json_line_with_the_contract_fields():
 
 
 @pytest.mark.gpu
+def test_plain_bench_times_only_the_steps_and_dumps_the_last_outputs(tmp_path):
+    """A plain run (no --full) prints the contract fields of the steps it timed and nothing measured elsewhere; with
+    --dump-outputs it writes what the last timed step returned, and the same arguments give the same outputs."""
+    lines = []
+    for d in ('a', 'b'):
+        r = _run(['--steps', '3', '--warmup', '1', '--batch', '64', '--dump-outputs', str(tmp_path / d)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines += [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 2
+    d = json.loads(lines[0])
+    assert d['steps'] == 3 and d['warmup'] == 1 and d['unit'] == 'frames/sec' and d['higher_is_better'] is True
+    assert d['dtype'] == 'f32' and d['value'] == pytest.approx(64 * 32 / (d['ms_per_step'] * 1e-3), rel=1e-6)
+    for key in ('fp32_mfma_path', 'roofline', 'breakdown_ms_per_step', 'cpu_baseline', 'secondary'):
+        assert key not in d, key
+    import numpy as np
+    shapes = {'pose': (64, 32, 66), 'shape': (64, 32, 10), 'joints': (64, 32, 66), 'h_n': (2, 64, 512),
+              'c_n': (2, 64, 512)}
+    assert sorted(p.name for p in (tmp_path / 'a').iterdir()) == sorted(k + '.npy' for k in shapes)
+    for k, shape in shapes.items():
+        a, b = np.load(str(tmp_path / 'a' / (k + '.npy'))), np.load(str(tmp_path / 'b' / (k + '.npy')))
+        assert a.dtype == np.float32 and a.shape == shape and np.isfinite(a).all(), k
+        np.testing.assert_allclose(a, b, rtol=0, atol=1e-5, err_msg=k)
+
+
+def test_dump_outputs_keeps_one_seeded_sample_of_windows_under_the_limit(tmp_path):
+    import numpy as np
+    import bench
+    n = 100
+    arrays = {'pose': (torch.arange(n, dtype=torch.float32).reshape(n, 1, 1).expand(n, 4, 66), 0),
+              'h_n': (torch.arange(n, dtype=torch.float64).reshape(1, n, 1).expand(2, n, 8), 1)}
+    bench.dump_outputs(str(tmp_path / 'all'), arrays)
+    whole = np.load(str(tmp_path / 'all' / 'pose.npy'))
+    assert whole.dtype == np.float32 and np.array_equal(whole, arrays['pose'][0].numpy())
+    assert np.load(str(tmp_path / 'all' / 'h_n.npy')).dtype == np.float32
+    limit = 30 * (4 * 66 + 2 * 8) * 4 + 100
+    for d in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / d), arrays, limit=limit)
+    pose, h = np.load(str(tmp_path / 's1' / 'pose.npy')), np.load(str(tmp_path / 's1' / 'h_n.npy'))
+    assert pose.shape == (30, 4, 66) and h.shape == (2, 30, 8) and pose.nbytes + h.nbytes <= limit
+    idx = pose[:, 0, 0]
+    assert (np.diff(idx) > 0).all() and np.array_equal(h[0, :, 0], idx) and np.array_equal(h[1, :, 7], idx)
+    assert np.array_equal(np.load(str(tmp_path / 's2' / 'pose.npy')), pose)
+    assert np.array_equal(np.load(str(tmp_path / 's2' / 'h_n.npy')), h)
+
+
+@pytest.mark.gpu
 def test_bench_secondary_object_carries_the_other_configs():
     """The headline line of `bench.py` (BASELINE configs[2] shape) carries a `secondary` object: configs[1], the full-mesh
     workload, the configs[3] stand-in under both drivers and the configs[4] step at 12 and 256 windows -- each with what it
     ran, its rate and a roofline fraction where one applies; `value` / `metric` / `config` are the headline's own."""
-    r = _run(['--steps', '5', '--warmup', '2', '--no_cpu_baseline', '--no_traffic', '--no_fp32_line'])
+    r = _run(['--steps', '5', '--warmup', '2', '--full', '--no_cpu_baseline', '--no_traffic', '--no_fp32_line'])
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1
