@@ -9,35 +9,36 @@ namespace empose {
 
 constexpr int MJ = 22;
 
-__device__ inline void jacobi_eig3(double B[9], double V[9]) {
-  // cyclic Jacobi on a symmetric 3x3; on return B is diagonal (eigenvalues) and the columns of V are eigenvectors
+__device__ inline void svd3_one_sided(double W[9], double V[9]) {
+  // one-sided (Hestenes) Jacobi: rotate pairs of columns of W (= A on entry) until they are orthogonal; on return
+  // W = A V = U S (columns u_c s_c) and V is orthogonal.  Works on A itself, not on A^T A, so a singular value is
+  // resolved down to ~1e-16 of the largest one (A^T A squares the condition number: s3 below ~1e-8 s1 was noise)
   for (int i = 0; i < 9; ++i) V[i] = (i % 4 == 0) ? 1.0 : 0.0;
-  for (int sweep = 0; sweep < 12; ++sweep) {
-    const double off = fabs(B[1]) + fabs(B[2]) + fabs(B[5]);
-    if (off < 1e-300) break;
+  for (int sweep = 0; sweep < 30; ++sweep) {
+    bool rotated = false;
     for (int p = 0; p < 2; ++p)
       for (int q = p + 1; q < 3; ++q) {
-        const double apq = B[p * 3 + q];
-        if (fabs(apq) < 1e-300) continue;
-        const double theta = (B[q * 3 + q] - B[p * 3 + p]) / (2.0 * apq);
-        const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-        const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-        for (int k = 0; k < 3; ++k) {  // B <- B J
-          const double bkp = B[k * 3 + p], bkq = B[k * 3 + q];
-          B[k * 3 + p] = c * bkp - s * bkq;
-          B[k * 3 + q] = s * bkp + c * bkq;
+        double al = 0, be = 0, ga = 0;
+        for (int r = 0; r < 3; ++r) {
+          al += W[r * 3 + p] * W[r * 3 + p];
+          be += W[r * 3 + q] * W[r * 3 + q];
+          ga += W[r * 3 + p] * W[r * 3 + q];
         }
-        for (int k = 0; k < 3; ++k) {  // B <- J^T B
-          const double bpk = B[p * 3 + k], bqk = B[q * 3 + k];
-          B[p * 3 + k] = c * bpk - s * bqk;
-          B[q * 3 + k] = s * bpk + c * bqk;
-        }
-        for (int k = 0; k < 3; ++k) {
-          const double vkp = V[k * 3 + p], vkq = V[k * 3 + q];
-          V[k * 3 + p] = c * vkp - s * vkq;
-          V[k * 3 + q] = s * vkp + c * vkq;
+        if (!(fabs(ga) > 1e-15 * sqrt(al * be))) continue;   // orthogonal to rounding (or NaN: left as it is)
+        rotated = true;
+        const double zeta = (be - al) / (2.0 * ga);
+        const double t = (zeta >= 0 ? 1.0 : -1.0) / (fabs(zeta) + sqrt(1.0 + zeta * zeta));
+        const double c = 1.0 / sqrt(1.0 + t * t), s = c * t;
+        for (int r = 0; r < 3; ++r) {
+          const double wp = W[r * 3 + p], wq = W[r * 3 + q];
+          W[r * 3 + p] = c * wp - s * wq;
+          W[r * 3 + q] = s * wp + c * wq;
+          const double vp = V[r * 3 + p], vq = V[r * 3 + q];
+          V[r * 3 + p] = c * vp - s * vq;
+          V[r * 3 + q] = s * vp + c * vq;
         }
       }
+    if (!rotated) break;
   }
 }
 
@@ -85,53 +86,42 @@ __global__ void metrics_rows_kernel(MetricsArgs a) {
   }
   const double normX = sqrt(ssX), normY = sqrt(ssY);
   for (int i = 0; i < 9; ++i) A[i] /= (normX * normY);
-  // SVD of A via the eigen-decomposition of A^T A:  A = U S V^T
-  double B[9], V[9];
-  for (int i = 0; i < 3; ++i)
-    for (int k = 0; k < 3; ++k) {
-      double s = 0;
-      for (int m = 0; m < 3; ++m) s += A[m * 3 + i] * A[m * 3 + k];
-      B[i * 3 + k] = s;
-    }
-  jacobi_eig3(B, V);
+  // SVD A = U S V^T by one-sided Jacobi, singular values in descending order
+  double W[9], V[9], nrm[3];
+  for (int i = 0; i < 9; ++i) W[i] = A[i];
+  svd3_one_sided(W, V);
+  for (int c = 0; c < 3; ++c) nrm[c] = sqrt(W[c] * W[c] + W[3 + c] * W[3 + c] + W[6 + c] * W[6 + c]);
   int ord[3] = {0, 1, 2};
-  double lam[3] = {B[0], B[4], B[8]};
   for (int i = 0; i < 2; ++i)
     for (int k = i + 1; k < 3; ++k)
-      if (lam[ord[k]] > lam[ord[i]]) { const int tmp = ord[i]; ord[i] = ord[k]; ord[k] = tmp; }
+      if (nrm[ord[k]] > nrm[ord[i]]) { const int tmp = ord[i]; ord[i] = ord[k]; ord[k] = tmp; }
   double Vs[9], U[9], S[3];
   for (int c = 0; c < 3; ++c) {
-    S[c] = sqrt(lam[ord[c]] > 0 ? lam[ord[c]] : 0.0);
+    S[c] = nrm[ord[c]];
     for (int r = 0; r < 3; ++r) Vs[r * 3 + c] = V[r * 3 + ord[c]];
   }
-  for (int c = 0; c < 2; ++c) {
+  // U is built right-handed: u1, u2 from the columns (any unit vector orthogonal to u1 when s2 == 0: collinear points),
+  // u3 = u1 x u2 and s3 = u3 . A v3 signed, so that A = U S V^T holds whatever s3 is (a normalised A v3 is rounding
+  // noise, not orthogonal to u1 and u2, when s3 is tiny: near-planar ground truth).  A NaN A (no spread) stays NaN in S.
+  double u1[3], u2[3];
+  for (int r = 0; r < 3; ++r) u1[r] = S[0] > 0 ? W[r * 3 + ord[0]] / S[0] : (r == 0 ? 1.0 : 0.0);
+  if (S[1] > 0) {
+    for (int r = 0; r < 3; ++r) u2[r] = W[r * 3 + ord[1]] / S[1];
+  } else {
+    int k = 0;  // e_k with the smallest |u1_k|, minus its u1 part
+    for (int r = 1; r < 3; ++r)
+      if (fabs(u1[r]) < fabs(u1[k])) k = r;
     double n = 0;
     for (int r = 0; r < 3; ++r) {
-      double s = 0;
-      for (int m = 0; m < 3; ++m) s += A[r * 3 + m] * Vs[m * 3 + c];
-      U[r * 3 + c] = s;
-      n += s * s;
+      u2[r] = (r == k ? 1.0 : 0.0) - u1[k] * u1[r];
+      n += u2[r] * u2[r];
     }
     n = sqrt(n);
-    for (int r = 0; r < 3; ++r) U[r * 3 + c] = n > 0 ? U[r * 3 + c] / n : (r == c ? 1.0 : 0.0);
+    for (int r = 0; r < 3; ++r) u2[r] /= n;
   }
-  {  // third left vector: A v3 / s3 when well defined, else completes a right-handed/any orthonormal basis
-    double u3[3], n = 0;
-    for (int r = 0; r < 3; ++r) {
-      double s = 0;
-      for (int m = 0; m < 3; ++m) s += A[r * 3 + m] * Vs[m * 3 + 2];
-      u3[r] = s;
-      n += s * s;
-    }
-    n = sqrt(n);
-    if (n > 1e-12 * (S[0] > 0 ? S[0] : 1.0)) {
-      for (int r = 0; r < 3; ++r) U[r * 3 + 2] = u3[r] / n;
-    } else {
-      U[2] = U[3] * U[7] - U[6] * U[4];
-      U[5] = U[6] * U[1] - U[0] * U[7];
-      U[8] = U[0] * U[4] - U[3] * U[1];
-    }
-  }
+  const double u3[3] = {u1[1] * u2[2] - u1[2] * u2[1], u1[2] * u2[0] - u1[0] * u2[2], u1[0] * u2[1] - u1[1] * u2[0]};
+  S[2] = u3[0] * W[ord[2]] + u3[1] * W[3 + ord[2]] + u3[2] * W[6 + ord[2]];
+  for (int r = 0; r < 3; ++r) { U[r * 3] = u1[r]; U[r * 3 + 1] = u2[r]; U[r * 3 + 2] = u3[r]; }
   double Tm[9];
   for (int i = 0; i < 3; ++i)
     for (int k = 0; k < 3; ++k) {

@@ -369,7 +369,9 @@ def evaluate_sequences_batched(net, batches, smpl_model, device, window_size=256
             net.iter_stream = side
         lap('valid_frames')
         me_chunks = MetricsEngine(smpl_model)
-        placed = on_gpu and me_chunks.angle_glob and hasattr(smpl_model, 'fk_joints')   # (the device path of `compute`)
+        # placed: `compute` queues device rows (its device path); otherwise it accumulates on the host and the rows are
+        # split per recording after the loop
+        placed = me_chunks.queues_device_rows(dev)
         # Where every frame's row goes: recording i owns rows base[i] .. base[i + 1] of one block, its valid frames in
         # frame order (what the sequential driver accumulates, recording after recording); frames that do not count go to
         # a spare row past the end.
@@ -438,9 +440,13 @@ def evaluate_sequences_batched(net, batches, smpl_model, device, window_size=256
                         t.record_stream(side)
                 if c == 0:   # the first chunk's shape estimate stands for the whole recording (evaluate_real.py:63-68)
                     first_shape = out['shape_hat'][:, 0].contiguous()
-                me_chunks.compute(chunk.poses_body, chunk.shapes, out['pose_hat'], first_shape[:k], chunk.seq_lengths,
-                                  chunk.poses_root, out['root_ori_hat'], frame_mask=chunk.marker_masks,
-                                  valid=torch.from_numpy(np.ascontiguousarray(valid_np)))
+                queued = me_chunks.compute(chunk.poses_body, chunk.shapes, out['pose_hat'], first_shape[:k],
+                                           chunk.seq_lengths, chunk.poses_root, out['root_ori_hat'],
+                                           frame_mask=chunk.marker_masks,
+                                           valid=torch.from_numpy(np.ascontiguousarray(valid_np)))
+                if queued != placed:
+                    raise RuntimeError('MetricsEngine.compute %s device rows, the driver expected the opposite'
+                                       % ('queued' if queued else 'did not queue'))
                 if placed:
                     (rows, _, _), = me_chunks.take_device_rows()
                     if side is not None:

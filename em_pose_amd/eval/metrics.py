@@ -212,15 +212,21 @@ class MetricsEngine(object):
         else:
             self._add_eucl(js, js_hat)
 
+    def queues_device_rows(self, device):
+        """Whether `compute` on tensors of `device` takes the device path, i.e. queues its rows (`take_device_rows`)
+        instead of accumulating them on the host."""
+        return torch.device(device).type == 'cuda' and self.angle_glob and hasattr(self.smpl_model, 'fk_joints')
+
     def compute(self, pose, shape, pose_hat, shape_hat=None, seq_lengths=None, pose_root=None, pose_root_hat=None,
                 frame_mask=None, valid=None):
         """Same arguments as the reference (metrics.py:183-241).  `valid` (optional, bool (n, f), any device): the
         frames that count, for a caller that already has `seq_lengths` / `frame_mask` on the host (`valid_frames`) --
-        the device path then launches nothing for the mask."""
+        the device path then launches nothing for the mask.  Returns True when it queued ONE entry of device rows
+        (`queues_device_rows`), False when it accumulated on the host."""
         n, f = pose.shape[0], pose.shape[1]
         shape_hat = shape if shape_hat is None else shape_hat
         mask = valid if valid is not None else self._mask(seq_lengths, n, f, frame_mask, pose.device)
-        if pose.is_cuda and self.angle_glob and hasattr(self.smpl_model, 'fk_joints'):
+        if self.queues_device_rows(pose.device):
             # device path (SURVEY.md 8f-1): joints-only forward kinematics + one metrics kernel over ALL n * f frames;
             # the valid rows are picked when the accumulators are read (`_flush`), so nothing here waits for the
             # device -- no compaction by a boolean mask, no emptiness test
@@ -234,11 +240,11 @@ class MetricsEngine(object):
                                              torch.cat([per_frame(shape), per_frame(shape_hat)]),
                                              poses_root=torch.cat([root_f, root_hat_f]))
             self._add_device_rows(both[:n * f], both[n * f:], flat(pose), flat(pose_hat), valid=mask.reshape(n * f))
-            return
+            return True
         if valid is not None:
             mask = mask.to(pose.device)
         if mask.sum() == 0:
-            return
+            return False
 
         def shapes(s):
             return s[mask] if s.dim() == 3 else s.unsqueeze(1).repeat(1, f, 1)[mask]
@@ -266,6 +272,7 @@ class MetricsEngine(object):
             g = rotvec_to_matrix(p.reshape(p.shape[0], -1, 3))
             gh = rotvec_to_matrix(ph.reshape(ph.shape[0], -1, 3))
         self.angle_diffs.append(geodesic_degrees(g, gh))
+        return False
 
     def compute_angle_dist(self, pose, pose_hat, seq_lengths=None, frame_mask=None, rep='aa'):
         """Joint-angle metric only, on the angles as given (no kinematic chain; reference metrics.py:267-287):

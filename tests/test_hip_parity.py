@@ -1008,12 +1008,10 @@ def test_graphed_training_step_equals_eager(rnn, n_markers):
         step(batch_of(4, nb=B + 1))
 
 
-def test_batched_streaming_equals_sequential():
-    """Chunk c of all recordings as one ragged batch (state carried per row) gives the per-recording results of the
-    one-recording-at-a-time driver."""
+def _streaming_recordings():
+    """LGD-RNN-6 on the small model and four synthetic recordings of 300 / 700 / 256 / 40 frames."""
     from em_pose_amd.data.data import RealBatch, RealSample
     from em_pose_amd.data.transforms import NormalizeRealMarkers, NormalizeRoot, ToTensor
-    from em_pose_amd.eval.helpers import evaluate_sequences, evaluate_sequences_batched
     case = H.load_case('lgdrnn6_n2')
     meta = case['meta']
     model = H.small_model()
@@ -1034,6 +1032,14 @@ def test_batched_streaming_equals_sequential():
                        d['smpl_poses'], d['smpl_shape'], d['smpl_trans'],
                        {'means': d['offset_means'], 'covs': d['offset_covs'], 'r': d['offset_r']})
         batches.append(NormalizeRoot()(RealBatch.from_sample_list([ToTensor()(NormalizeRealMarkers()(s))])))
+    return net, smpl, batches
+
+
+def test_batched_streaming_equals_sequential():
+    """Chunk c of all recordings as one ragged batch (state carried per row) gives the per-recording results of the
+    one-recording-at-a-time driver."""
+    from em_pose_amd.eval.helpers import evaluate_sequences, evaluate_sequences_batched
+    net, smpl, batches = _streaming_recordings()
     a_all, a_seq, a_frames = evaluate_sequences(net, batches, smpl, torch.device(DEV))
     b_all, b_seq, b_frames = evaluate_sequences_batched(net, batches, smpl, torch.device(DEV))
     assert a_frames == b_frames == 1296
@@ -1056,6 +1062,32 @@ def test_batched_streaming_equals_sequential():
     sc = c_all.state()
     for key in sb:
         assert np.array_equal(sb[key], sc[key]), key
+
+
+def test_batched_driver_with_a_host_metrics_model_takes_the_unplaced_path():
+    """A body model without joints-only forward kinematics (`fk_joints`) sends MetricsEngine.compute down its host path
+    (NumPy SVD and angles) even with the network on the device: the batched driver must then split the host rows per
+    recording (not place device rows that were never queued) and give the table of the device path."""
+    from em_pose_amd.eval.helpers import evaluate_sequences_batched
+    from em_pose_amd.eval.metrics import MetricsEngine
+    net, smpl, batches = _streaming_recordings()
+
+    class HostFK(object):            # what compute's host path needs: fk() only
+        def __init__(self, inner):
+            self.fk = inner.fk
+
+    host = HostFK(smpl)
+    assert MetricsEngine(smpl).queues_device_rows(DEV) and not MetricsEngine(host).queues_device_rows(DEV)
+    d_all, d_seq, d_frames = evaluate_sequences_batched(net, batches, smpl, torch.device(DEV))
+    h_all, h_seq, h_frames = evaluate_sequences_batched(net, batches, host, torch.device(DEV))
+    assert d_frames == h_frames == 1296 and [i for i, _ in d_seq] == [i for i, _ in h_seq]
+    for (idd, md), (_, mh) in zip(d_seq, h_seq):
+        for k in md:
+            assert mh[k] == pytest.approx(md[k], rel=1e-5, abs=1e-4), (idd, k)
+    sd, sh = d_all.state(), h_all.state()
+    for key in sd:
+        assert sd[key].shape == sh[key].shape, key
+        np.testing.assert_allclose(sh[key], sd[key], rtol=1e-4, atol=1e-4, err_msg=key)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
