@@ -1,0 +1,283 @@
+"""
+Per-element error allowances for the kernels that form fp32 products on the bf16 matrix cores (three bf16 pieces per
+operand, csrc/bf16x3.h), and the check that holds an output to them.
+
+A global tolerance lets one wrong element hide below the worst honest rounding error of the whole output.  Here every
+output element gets its own allowance from a float64 MAGNITUDE `m` -- the same operation evaluated on absolute values --
+as `gamma * u * m` with u = 2^-24 and one constant gamma per kernel family, carried through the layers of a network as a
+running bound (PReLU, sigmoid and tanh are Lipschitz; the errors of earlier layers pass a product root-sum-square,
+`propagate`).  `check` reports the violations by
+their position inside the kernels' tiles, (row mod 64, column mod 32) -- or mod 16 for the 16 x 16 x 32 instruction -- and
+by coordinate for the mesh, so that a footprint such as one accumulator element of the MFMA (rows 5 / 37 of a 64-row
+block, columns 16..31 of a 32-column tile) is recognisable from the failure message alone.
+
+Everything here is float64 torch on whatever device the inputs are on; nothing needs a GPU.
+"""
+import collections
+
+import torch
+
+U = 2.0 ** -24
+
+
+def _abs64(t):
+    return t.detach().double().abs()
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Linear / GEMM  y = A W^T + b
+def linear_magnitude(a, w, b=None):
+    m = _abs64(a) @ _abs64(w).t()
+    return m if b is None else m + _abs64(b)
+
+
+def propagate(e, w):
+    """The error e (rows, K) of an input carried through y = x W^T, root-sum-square: sqrt(e^2 (W^2)^T).  The worst
+    case |W| e grows about 5x per 512-wide layer (|W| row sums of the released initialisation) and is vacuous after
+    two layers; the rounding errors of the layers below are independent of the signs of W, so their sum over K
+    cancels like a random walk.  The local term of every layer stays the worst case gamma u m."""
+    w = w.detach().double().to(e.device)
+    return torch.sqrt((e * e) @ (w * w).t())
+
+
+def linear_allowance(a, w, b, gamma, e_a=None):
+    """|y - y64| <= gamma u (|A| |W|^T + |b|) (+ propagate(e_a, W) for an input that carries an error e_a)."""
+    e = gamma * U * linear_magnitude(a, w, b)
+    return e if e_a is None else e + propagate(e_a, w)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Update MLPs: Linear - BatchNorm - PReLU blocks, then a Linear (oracle/torch_ref.py::mlp_forward)
+def eval_mlp_layers(sd, prefix, num_layers=2, eps=1e-5):
+    """The dense layers of an eval-mode MLP in order: dicts of float64 weight, bias, BatchNorm (scale, mean, beta) or
+    None, PReLU slope or None.  BatchNorm is the affine map s (z - mean) + beta, s = weight / sqrt(var + eps)."""
+    def dense(lin, bn, act):
+        d = {'w': sd[lin + 'weight'].double(), 'b': sd[lin + 'bias'].double(), 'bn': None, 'slope': None}
+        if bn is not None:
+            s = sd[bn + 'weight'].double() / torch.sqrt(sd[bn + 'running_var'].double() + eps)
+            d['bn'] = (s, sd[bn + 'running_mean'].double(), sd[bn + 'bias'].double())
+        if act is not None:
+            d['slope'] = sd[act + 'weight'].double()
+        return d
+    out = [dense(prefix + 'input_to_hidden.', prefix + 'batch_norm.', prefix + 'activation_fn.')]
+    for h in range(num_layers):
+        base = prefix + 'hidden_layers.{}.layers.'.format(h)
+        for k in range(2):
+            out.append(dense(base + '{}.'.format(4 * k), base + '{}.'.format(4 * k + 1), base + '{}.'.format(4 * k + 2)))
+    out.append(dense(prefix + 'hidden_to_output.', None, None))
+    return out
+
+
+def _prelu(y, slope):
+    return torch.where(y >= 0, y, slope * y)
+
+
+def eval_mlp_reference(layers, x, gamma):
+    """float64 output of the eval-mode MLP and its per-element allowance.  Layer by layer, with h the float64 activation,
+    z = W h + b and the BatchNorm magnitude  m = |s| (|W| |h| + |b| + |mean|) + |beta|:
+        e_l = max(1, |slope|) (|s| P(e_{l-1}, W) + gamma u m_l) + gamma u |h_l|,
+    and for the output layer  e = P(e, W) + gamma u (|W| |h| + |b|), with P = `propagate`."""
+    h = x.detach().double()
+    e = torch.zeros_like(h)
+    for d in layers:
+        w, b = d['w'].to(h.device), d['b'].to(h.device)
+        z = h @ w.t() + b
+        mag = linear_magnitude(h, w, b)
+        prop = propagate(e, w)
+        if d['bn'] is not None:
+            s, mean, beta = (t.to(h.device) for t in d['bn'])
+            z = s * (z - mean) + beta
+            mag = s.abs() * (mag + mean.abs()) + beta.abs()
+            prop = s.abs() * prop
+        if d['slope'] is not None:
+            slope = d['slope'].to(h.device)
+            lip = torch.clamp(slope.abs(), min=1.0)
+            h_new = _prelu(z, slope)
+            e = lip * (prop + gamma * U * mag) + gamma * U * h_new.abs()
+        else:
+            h_new = z
+            e = prop + gamma * U * mag
+        h = h_new
+    return h, e
+
+
+def train_mlp_reference(layers, x, gamma, eps=1e-5):
+    """Train-mode forward (BatchNorm over the batch with its own statistics, biased variance): float64 output and
+    allowance.  `layers`: dicts of w, b, bn = (weight, bias) or None, slope.  z = W h + b gets
+    propagate(e, W) + gamma u (|W| |h| + |b|).  Per BatchNorm layer, with z's allowance
+    e_z, r = 1 / sqrt(var + eps) and xh = (z - mean) r:
+        mean:      e_mu = sqrt(rowmean(e_z^2) / M) + gamma u rowmean(|z|)          (the statistics' own error)
+        rstd:      |dr| / r <= r^2 (sqrt(rowmean((z - mean)^2 e_z^2) / M) + |mean| e_mu + gamma u rowmean(z^2))
+    The statistics are sums over the M rows of errors that are independent from row to row: root-sum-square, as in
+    `propagate` (the worst case, rowmean(e_z), triples the allowance at every layer and is vacuous at the output).
+        xh:        e_xh = r (e_z + e_mu + gamma u (|z| + |mean|)) + |xh| |dr| / r
+        affine:    e_y = |weight| e_xh + gamma u (|weight| |xh| + |bias|),  PReLU: max(1, |slope|), + gamma u |h|."""
+    h = x.detach().double()
+    e = torch.zeros_like(h)
+    gu = gamma * U
+    for d in layers:
+        w, b = d['w'].to(h.device), d['b'].to(h.device)
+        z = h @ w.t() + b
+        ez = propagate(e, w) + gu * linear_magnitude(h, w, b)
+        if d['bn'] is not None:
+            bw, bb = (t.to(h.device) for t in d['bn'])
+            mean, var = z.mean(0), z.var(0, unbiased=False)
+            r = 1.0 / torch.sqrt(var + eps)
+            xh = (z - mean) * r
+            M = z.shape[0]
+            e_mu = torch.sqrt((ez * ez).mean(0) / M) + gu * z.abs().mean(0)
+            dr_rel = r * r * (torch.sqrt(((z - mean) ** 2 * ez * ez).mean(0) / M) + mean.abs() * e_mu + gu * (z * z).mean(0))
+            e_xh = r * (ez + e_mu + gu * (z.abs() + mean.abs())) + xh.abs() * dr_rel
+            z = xh * bw + bb
+            ez = bw.abs() * e_xh + gu * (bw.abs() * xh.abs() + bb.abs())
+        if d['slope'] is not None:
+            slope = d['slope'].to(h.device)
+            h = _prelu(z, slope)
+            e = torch.clamp(slope.abs(), min=1.0) * ez + gu * h.abs()
+        else:
+            h, e = z, ez
+    return h, e
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# LSTM: one step from a known state (gate order i, f, g, o)
+def sigmoid_finish(z):
+    """Absolute error of the kernels' sigmoid rcp(1 + __expf(-z)): __expf carries a relative error of (|z| + 4) u (the
+    rounding of z log2(e) and v_exp_f32), which reaches the result times s (1 - s); the sum and v_rcp_f32 add 2 u s."""
+    s = torch.sigmoid(z)
+    return s * (1 - s) * (z.abs() + 4) * U + 2 * U * s
+
+
+def tanh_finish(z):
+    """Absolute error of the kernels' tanh 1 - 2 rcp(1 + __expf(2z)): the relative error (2|z| + 4) u of __expf reaches
+    the result times (1 - t^2) / 2; the sum, v_rcp_f32 and the final subtraction add at most 3 u."""
+    t = torch.tanh(z)
+    return (1 - t * t) * (z.abs() + 2) * U + 3 * U
+
+
+def lstm_step_reference(w_ih, w_hh, bias, x, h, c, gamma, e_x=None, e_h=None, e_c=None):
+    """One LSTM step in float64 from (x, h, c) and its allowance.  The pre-activations get the GEMM bound
+    gamma u (|W_ih| |x| + |W_hh| |h| + |b|) plus propagate(e_x, W_ih) + propagate(e_h, W_hh); the gates Lipschitz 1/4 (sigmoid)
+    and 1 (tanh) plus the finish terms of the approximate __expf / rcp (sigmoid_finish, tanh_finish -- stated, not folded
+    into gamma); then
+        e_c' = |f| e_c + |c| e_f + |g| e_i + |i| e_g + gamma u (|f c| + |i g|)
+        e_h' = |tanh c'| e_o + |o| (e_c' + tanh_finish(c')) + gamma u |h'|.
+    Returns (h', c', e_h', e_c') in float64."""
+    x, h, c = (t.detach().double() for t in (x, h, c))
+    w_ih, w_hh, bias = (t.detach().double().to(x.device) for t in (w_ih, w_hh, bias))
+    H = w_hh.shape[1]
+    z = x @ w_ih.t() + h @ w_hh.t() + bias
+    ez = gamma * U * (x.abs() @ w_ih.abs().t() + h.abs() @ w_hh.abs().t() + bias.abs())
+    if e_x is not None:
+        ez = ez + propagate(e_x, w_ih)
+    if e_h is not None:
+        ez = ez + propagate(e_h, w_hh)
+    zi, zf, zg, zo = (z[:, k * H:(k + 1) * H] for k in range(4))
+    ei, ef, eg, eo = (ez[:, k * H:(k + 1) * H] for k in range(4))
+    i, f, g, o = torch.sigmoid(zi), torch.sigmoid(zf), torch.tanh(zg), torch.sigmoid(zo)
+    ei, ef, eo = (0.25 * e + sigmoid_finish(zz) for e, zz in ((ei, zi), (ef, zf), (eo, zo)))
+    eg = eg + tanh_finish(zg)
+    c_new = f * c + i * g
+    e_c_new = f.abs() * (0 if e_c is None else e_c) + c.abs() * ef + g.abs() * ei + i.abs() * eg \
+        + gamma * U * ((f * c).abs() + (i * g).abs())
+    tc = torch.tanh(c_new)
+    h_new = o * tc
+    e_h_new = tc.abs() * eo + o.abs() * (e_c_new + tanh_finish(c_new)) + gamma * U * h_new.abs()
+    return h_new, c_new, e_h_new, e_c_new
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Full mesh: x3 against the fp32-instruction kernel
+def mesh_magnitude(bm, pose_body, betas, root, trans=None):
+    """Per vertex coordinate (n, V, 3), float64:
+        sum_j w_vj (|R_j| (|v_t| + |S| |beta| + |P| |f|) + |t_j|) + |trans|
+    with R_j, t_j the skinning transforms and f the pose features of the float64 evaluation (as magnitudes only).  Both
+    kernels share the forward kinematics; what differs is the blend-shape contraction and the skinning sums after it.
+    Memory: about 200 bytes per (frame, vertex); callers chunk the frames."""
+    from oracle import torch_ref as R
+    dt, dev = torch.float64, pose_body.device
+    n = pose_body.shape[0]
+    pose_body, betas, root = (t.detach().to(dt) for t in (pose_body, betas, root))
+    v_t = bm.v_template.to(dev, dt)[0]                         # (V, 3)
+    S = bm.shapedirs.to(dev, dt)                               # (V, 3, 10)
+    P = bm.posedirs.to(dev, dt)                                # (459, V*3)
+    Wt = bm.weights.to(dev, dt)                                # (V, 52)
+    Jreg = bm.J_regressor.to(dev, dt)
+    full_pose = torch.cat([root, pose_body, torch.zeros(n, 90, dtype=dt, device=dev)], dim=1)
+    v_shaped = v_t[None] + torch.einsum('bl,mkl->bmk', betas, S)
+    J = torch.einsum('bik,ji->bjk', v_shaped, Jreg)
+    n_j = J.shape[1]
+    Rm = R.rodrigues(full_pose.reshape(-1, 3), getattr(bm, 'rodrigues_convention', 'smplx')).view(n, n_j, 3, 3)
+    feat = (Rm[:, 1:] - torch.eye(3, dtype=dt, device=dev)).reshape(n, -1)
+    rel = J.clone()
+    rel[:, 1:] = J[:, 1:] - J[:, bm.parents[1:]]
+    G = [None] * n_j
+    for j in range(n_j):
+        T = torch.zeros(n, 4, 4, dtype=dt, device=dev)
+        T[:, :3, :3], T[:, :3, 3], T[:, 3, 3] = Rm[:, j], rel[:, j], 1.0
+        G[j] = T if j == 0 else G[bm.parents[j]] @ T
+    G = torch.stack(G, dim=1)
+    Rj = G[:, :, :3, :3]
+    tj = G[:, :, :3, 3] - (Rj @ J[..., None])[..., 0]
+    base = v_t.abs()[None] + torch.einsum('bl,mkl->bmk', betas.abs(), S.abs()) \
+        + (feat.abs() @ P.abs()).view(n, -1, 3)                # (n, V, 3)
+    skin_r = (Wt.abs() @ Rj.abs().reshape(n, n_j, 9)).view(n, -1, 3, 3)      # sum_j w_vj |R_j|
+    skin_t = Wt.abs() @ tj.abs()                                               # sum_j w_vj |t_j|
+    out = (skin_r @ base[..., None])[..., 0] + skin_t
+    if trans is not None:
+        out = out + trans.detach().to(dt).abs()[:, None, :]
+    return out
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+class Report(object):
+    """Result of `check`: `n_bad` violations, `worst` = the largest err / allowance and its `worst_index`, and the
+    `message` with the violations counted by their place in the kernels' tiles."""
+
+    def __init__(self, n_bad, worst, worst_index, ratio_um, message):
+        self.n_bad, self.worst, self.worst_index, self.ratio_um, self.message = n_bad, worst, worst_index, ratio_um, message
+
+    @property
+    def ok(self):
+        return self.n_bad == 0
+
+    def __bool__(self):
+        return self.ok
+
+
+def _top(counter, k=12):
+    return ', '.join('%s: %d' % (key, cnt) for key, cnt in counter.most_common(k))
+
+
+def check(name, got, want, allowance, gamma=None, row_mod=64, col_mod=32):
+    """Hold `got` to `want` (float64) within `allowance` at every element.  2-D outputs (rows, columns) are classed by
+    (row mod `row_mod`, column mod `col_mod`); 3-D mesh outputs (frames, vertices, 3) by coordinate as well.  `gamma`
+    (the family constant the allowance was built with) turns the worst ratio into the gamma it would have needed.
+    Non-finite values are violations."""
+    got64 = got.detach().double().to(want.device)
+    err = (got64 - want).abs()
+    err = torch.where(torch.isfinite(got64), err, torch.full_like(err, float('inf')))
+    ratio = err / allowance.clamp_min(1e-300)
+    bad = ratio > 1.0
+    n_bad = int(bad.sum())
+    flat = int(torch.argmax(torch.where(torch.isnan(ratio), torch.full_like(ratio, float('inf')), ratio)))
+    idx = tuple(int(i) for i in torch.unravel_index(torch.tensor(flat), ratio.shape))
+    worst = float(ratio.reshape(-1)[flat])
+    ratio_um = None if gamma is None else worst * gamma
+    msg = ['%s: %d of %d elements over the allowance; worst err / allowance %.3g at %s (err %.3g, allowance %.3g%s)'
+           % (name, n_bad, err.numel(), worst, idx, float(err[idx]), float(allowance[idx]),
+              '' if gamma is None else ', i.e. err / (u m) = %.3g against gamma = %g' % (ratio_um, gamma))]
+    if n_bad:
+        where = bad.nonzero().cpu()
+        if got.dim() == 3:        # mesh: (frame, vertex, coordinate)
+            by_coord = collections.Counter(int(c) for c in where[:, 2])
+            by_fv = collections.Counter((int(r) % row_mod, int(v) % col_mod) for r, v in where[:, :2])
+            msg.append('  by coordinate: ' + _top(by_coord))
+            msg.append('  by (frame mod %d, vertex mod %d): %s' % (row_mod, col_mod, _top(by_fv)))
+        else:
+            rows, cols = where[:, 0] % row_mod, (where[:, 1] % col_mod if where.shape[1] > 1 else where[:, 0] * 0)
+            msg.append('  by (row mod %d, column mod %d): %s' % (row_mod, col_mod,
+                                                                 _top(collections.Counter(zip(rows.tolist(), cols.tolist())))))
+            msg.append('  by row mod %d: %s' % (row_mod, _top(collections.Counter(rows.tolist()))))
+            msg.append('  by column mod %d: %s' % (col_mod, _top(collections.Counter(cols.tolist()), 32)))
+    return Report(n_bad, worst, idx, ratio_um, '\n'.join(msg))

@@ -16,6 +16,7 @@ from em_pose_amd.helpers.configuration import CONSTANTS as CONST
 from em_pose_amd.helpers.configuration import lgd_config
 from em_pose_amd.nn.models import create_model
 from oracle import torch_ref as R
+from tests import helpers as H
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -288,9 +289,7 @@ def test_three_piece_kernels_keep_their_bits_beside_a_storing_kernel_on_another_
     big = torch.randn(1 << 26, device=DEV)
     stop = []
     for rep in range(4):
-        with torch.cuda.stream(side):
-            for _ in range(400):
-                big.mul_(1.0000001).add_(1e-9)
+        H.queue_storing_kernels(side, big)
         got = run()
         for a, b in zip(got, alone):
             assert torch.equal(a, b)

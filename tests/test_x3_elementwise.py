@@ -1,0 +1,371 @@
+"""
+Every output element of the kernels on three bf16 pieces per operand (csrc/bf16x3.h) against float64, each within its own
+allowance (tests/elementwise.py): the update MLPs (mlp_fused_x3.hip), the LSTM step kernels (lstm_x3, lstm_rows_x3,
+lstm_mid_x3, lstm_mid16_x3, lstm_midseq_x3), the full mesh (mesh_x3.hip) and the forward products of large training
+batches (gemm_train_x3_kernel).  The hardware hazard these kernels work round (scripts/dev/bf16_hazard_repro.md) corrupts
+ONE accumulator element -- rows 5 / 37 of a 64-row block, columns 16..31 of a 32-column tile -- by an amount that a global
+tolerance, sampled rows or run-against-run comparisons do not see.  Each case also runs the kernel on the fp32 MFMA
+instruction as a control, held to the same allowance.
+
+gamma, one per family, is at most 16.  Measured on the MI355X, the worst err / (u m) over every element of this module
+(the LSTM figures include the stated __expf / rcp finish terms in the denominator, scaled like gamma: a lower bound of
+what gamma alone would need), fp32-instruction control next to the three-piece kernels:
+    update MLPs (eval):         mlp_x3 = 0: 2.53,  mlp_x3 = 1: 2.22                                  GAMMA_MLP = 4
+    LSTM steps:                 fp32 steps 2.73, fp32 lstm_seq 2.81, fp32 persist 1.08;
+                                x3 chain 2.81, rows 2.70, mid 2.32, mid16 2.32, midseq 2.32          GAMMA_LSTM = 4
+    full mesh, x3 vs fp32:      1.95 of 2 u m (all three mesh_x3 options)                            GAMMA_MESH = 4
+    training forward products:  train_x3 = 0: 0.33,  train_x3 = 1: 0.29                             GAMMA_TRAIN = 1
+
+Pruning of the LSTM grid (all of B x H x In x options would take an hour): every batch size of the issue runs once, with
+H and In rotated over {64, 256, 512} x {72, 144, 296}; options run per case only where they select a different kernel
+(`_lstm_kernel` mirrors the dispatcher of api.hip), and tests/test_elementwise_bounds.py checks that the grid reaches every
+three-piece kernel at its smallest and largest batch.
+"""
+import numpy as np
+import pytest
+import torch
+
+from em_pose_amd import _lib, synthetic
+from em_pose_amd.bodymodels.smpl import SMPLLayer
+from em_pose_amd.helpers.configuration import lgd_config
+from em_pose_amd.nn.models import create_model
+from oracle import torch_ref as R
+from tests import elementwise as E
+from tests import helpers as H
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda:0'
+
+GAMMA_MLP = 4
+GAMMA_LSTM = 4
+GAMMA_MESH = 4
+GAMMA_TRAIN = 1
+
+
+def _set(**opts):
+    lib = _lib.lib()
+    for k, v in opts.items():
+        _lib.check(lib.empose_set_option(k.encode(), int(v)))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# a. Update nets
+def _update_net():
+    from tests.test_hip_round5 import _randomize_bn
+    torch.manual_seed(11)
+    net = create_model(lgd_config(12, False, 1), SMPLLayer(H.small_model()))
+    _randomize_bn(net, 12)
+    net.vertex_ids = synthetic.small_vertex_ids(160)
+    return net.to(DEV).eval()
+
+
+def _update_nets_fwd(net, xg):
+    lib = _lib.lib()
+    T = xg.shape[0]
+    handle = net._ensure_handle(torch.device(DEV))
+    dp, ds = torch.full((T, 66), 7.0, device=DEV), torch.full((T, 10), 7.0, device=DEV)
+    nbytes = lib.empose_update_workspace_bytes(handle, T)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=DEV)
+    _lib.check(lib.empose_update_nets_fwd(handle, T, _lib.dptr(xg), 296, _lib.dptr(dp), _lib.dptr(ds), _lib.dptr(ws),
+                                          nbytes, _lib.current_stream()))
+    return dp, ds
+
+
+def _update_net_refs(net, xg):
+    sd = {k: v.detach() for k, v in net.state_dict().items() if not k.startswith('smpl.')}
+    return [E.eval_mlp_reference(E.eval_mlp_layers(sd, p), xg, GAMMA_MLP) for p in ('pose_net_iter.', 'shape_net_iter.')]
+
+
+def _check_update_nets(net, xg, refs, tag, side=None):
+    reports = []
+    for x3 in (0, 1):
+        _set(mlp_x3=x3)
+        if side is not None:
+            H.queue_storing_kernels(*side)
+        outs = _update_nets_fwd(net, xg)
+        torch.cuda.synchronize()
+        for name, got, (want, allow) in zip(('pose', 'shape'), outs, refs):
+            reports.append(E.check('update nets %s mlp_x3=%d %s' % (tag, x3, name), got, want, allow, GAMMA_MLP))
+    for r in reports:
+        print(r.message.splitlines()[0])
+    bad = [r.message for r in reports if not r.ok]
+    assert not bad, '\n'.join(bad)
+
+
+@pytest.mark.parametrize('T', [1, 63, 65, 4096 + 17, 16384 + 71])
+@pytest.mark.parametrize('scale', [1.0, 30.0], ids=['unit_inputs', 'gradient_scale_inputs'])
+def test_update_nets_every_element_within_its_allowance(T, scale):
+    net = _update_net()
+    g = torch.Generator().manual_seed(T)
+    xg = (torch.randn(T, 296, generator=g) * scale).to(DEV)
+    _check_update_nets(net, xg, _update_net_refs(net, xg), 'T=%d scale=%g' % (T, scale))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# b. LSTM
+_LSTM_DEFAULTS = dict(lstm_x3=1, lstm_mid_x3=1, lstm_mid16=1, lstm_midseq=0, lstm_seq=0, lstm_persist=1)
+_LSTM_OPTIONS = [dict(lstm_x3=0), dict(), dict(lstm_x3=2), dict(lstm_mid16=0), dict(lstm_midseq=1, lstm_persist=0),
+                 dict(lstm_seq=1), dict(lstm_x3=0, lstm_seq=1)]
+
+
+def _lstm_kernel(B, F, opts):
+    """The kernel the dispatcher of api.hip (empose_rnn_fwd, uni-directional, H % 32 == 0, In % 4 == 0) picks."""
+    o = dict(_LSTM_DEFAULTS, **opts)
+    if F >= 4 and B <= 16 and o['lstm_persist']:
+        return 'fp32 persist'
+    if F >= 4 and B >= 257 and o['lstm_seq']:
+        return 'fp32 seq'
+    if o['lstm_x3'] == 0:
+        return 'fp32 steps'
+    if F >= 4 and o['lstm_mid_x3'] and o['lstm_midseq'] and 4 <= B <= 64:
+        return 'x3 midseq'
+    if o['lstm_mid_x3'] and o['lstm_mid16'] and 9 <= B <= 64:
+        return 'x3 mid16'
+    if o['lstm_mid_x3'] and 17 <= B <= 256:
+        return 'x3 mid'
+    if B >= 257:
+        return 'x3 rows' if o['lstm_x3'] == 2 else 'x3 chain'
+    return 'fp32 steps'
+
+
+def _lstm_runs(B, F):
+    """Option sets of a case, one per distinct kernel."""
+    seen, runs = set(), []
+    for opts in _LSTM_OPTIONS:
+        k = _lstm_kernel(B, F, opts)
+        if k not in seen:
+            seen.add(k)
+            runs.append((k, opts))
+    return runs
+
+
+LSTM_STEP_CASES = [(1, 512, 296, 1), (8, 256, 72, 2), (9, 512, 144, 1), (16, 64, 72, 2), (17, 512, 296, 2),
+                   (31, 256, 144, 1), (32, 512, 72, 1), (33, 64, 296, 2), (63, 512, 144, 2), (64, 256, 296, 1),
+                   (65, 512, 72, 1), (128, 64, 144, 2), (255, 512, 296, 1), (256, 256, 72, 2), (257, 512, 144, 2),
+                   (300, 64, 296, 1), (1024, 512, 72, 2)]
+LSTM_SEQ_CASES = [(1, 33, 512, 296), (9, 17, 256, 144), (17, 33, 512, 72), (33, 9, 64, 144), (64, 33, 512, 296),
+                  (65, 5, 256, 72), (256, 12, 512, 144), (257, 33, 512, 296), (300, 4, 256, 144), (1024, 7, 64, 72)]
+
+
+def _lstm_layer(In, Hd, L, seed):
+    from em_pose_amd.nn.layers import RNNLayer
+    torch.manual_seed(seed)
+    layer = RNNLayer(In, Hd, L).eval()
+    with torch.no_grad():
+        for p in layer.lstm.parameters():
+            p.mul_(2.0)
+    return layer
+
+
+def _unit(layer, l):
+    sd = layer.lstm.state_dict()
+    return (sd['weight_ih_l%d' % l].to(DEV), sd['weight_hh_l%d' % l].to(DEV),
+            (sd['bias_ih_l%d' % l] + sd['bias_hh_l%d' % l]).to(DEV))
+
+
+def _col_mod(kernel):
+    return 16 if kernel == 'x3 mid16' else 32
+
+
+@pytest.mark.parametrize('B,Hd,In,L', LSTM_STEP_CASES)
+def test_lstm_single_step_every_element_within_its_allowance(B, Hd, In, L):
+    """F = 1 from a given random (h0, c0); for L = 2 the second layer's input carries the first layer's allowance."""
+    layer = _lstm_layer(In, Hd, L, B + Hd + In)
+    g = torch.Generator().manual_seed(B)
+    x = torch.randn(B, 1, In, generator=g).to(DEV)
+    h0, c0 = (0.5 * torch.randn(L, B, Hd, generator=g)).to(DEV), (0.5 * torch.randn(L, B, Hd, generator=g)).to(DEV)
+    lens = torch.ones(B, dtype=torch.int64)
+    refs, inp, e_in = [], x[:, 0], None
+    for l in range(L):
+        h1, c1, eh, ec = E.lstm_step_reference(*_unit(layer, l), inp, h0[l], c0[l], GAMMA_LSTM, e_x=e_in)
+        refs.append((h1, c1, eh, ec))
+        inp, e_in = h1, eh
+    g_ = layer.to(DEV)
+    reports = []
+    for kernel, opts in _lstm_runs(B, 1):
+        _set(**dict(_LSTM_DEFAULTS, **opts))
+        g_.init_state = (h0, c0)
+        y = g_(x, lens.to(DEV))
+        torch.cuda.synchronize()
+        hn, cn = g_.final_state
+        tag = 'lstm step B=%d H=%d In=%d L=%d %s' % (B, Hd, In, L, kernel)
+        cm = _col_mod(kernel)
+        reports.append(E.check(tag + ' y', y[:, 0], refs[-1][0], refs[-1][2], GAMMA_LSTM, col_mod=cm))
+        for l in range(L):
+            reports.append(E.check(tag + ' h_n[%d]' % l, hn[l], refs[l][0], refs[l][2], GAMMA_LSTM, col_mod=cm))
+            reports.append(E.check(tag + ' c_n[%d]' % l, cn[l], refs[l][1], refs[l][3], GAMMA_LSTM, col_mod=cm))
+    g_.release()
+    for r in reports:
+        print(r.message.splitlines()[0])
+    bad = [r.message for r in reports if not r.ok]
+    assert not bad, '\n'.join(bad)
+
+
+@pytest.mark.parametrize('B,F,Hd,In', LSTM_SEQ_CASES)
+def test_lstm_sequence_every_step_within_its_allowance(B, F, Hd, In):
+    """Every forget-gate bias at -120: f = 0 in fp32 (__expf(120) overflows, rcp(inf) = 0; below 1e-35 in any
+    implementation), so step t depends on x_t and the kernel's OWN h_{t-1} = y[:, t-1] only, and each live element of
+    y[:, t] is checked against one float64 step from those inputs -- including the hidden-state pieces every step writes
+    for the next one, which an F = 1 case never reads.  Rows past their length give exactly 0; the final state is that of
+    the last live step."""
+    layer = _lstm_layer(In, Hd, 1, B + F)
+    with torch.no_grad():
+        layer.lstm.bias_ih_l0[Hd:2 * Hd] = -120.0
+        layer.lstm.bias_hh_l0[Hd:2 * Hd] = 0.0
+    g = torch.Generator().manual_seed(B * F)
+    x = torch.randn(B, F, In, generator=g).to(DEV)
+    lens = torch.randint(1, F + 1, (B,), generator=g)
+    lens[0], lens[-1] = F, 1
+    if B > 2:
+        lens[B // 2] = 1
+    h0, c0 = (0.5 * torch.randn(1, B, Hd, generator=g)).to(DEV), (0.5 * torch.randn(1, B, Hd, generator=g)).to(DEV)
+    unit = _unit(layer, 0)
+    lens_d = lens.to(DEV)
+    live = torch.arange(F, device=DEV)[None, :] < lens_d[:, None]                  # (B, F)
+    g_ = layer.to(DEV)
+    reports, exact = [], []
+    for kernel, opts in _lstm_runs(B, F):
+        _set(**dict(_LSTM_DEFAULTS, **opts))
+        g_.init_state = (h0, c0)
+        y = g_(x, lens_d)
+        torch.cuda.synchronize()
+        hn, cn = g_.final_state
+        tag = 'lstm sequence B=%d F=%d H=%d In=%d %s' % (B, F, Hd, In, kernel)
+        h_prev = torch.cat([h0[0][:, None], y[:, :-1]], dim=1)                     # (B, F, H): the kernel's own states
+        zeros = torch.zeros(B, Hd, device=DEV, dtype=torch.float64)
+        want_h, allow_h = [], []
+        for t in range(F):
+            h1, c1, eh, _ = E.lstm_step_reference(*unit, x[:, t], h_prev[:, t], zeros, GAMMA_LSTM)
+            want_h.append(h1)
+            allow_h.append(eh)
+        want_h, allow_h = torch.stack(want_h, 1), torch.stack(allow_h, 1)         # (B, F, H)
+        got = torch.where(live[..., None], y, torch.zeros_like(y))
+        want = torch.where(live[..., None], want_h, torch.zeros_like(want_h))
+        # (rows, columns) = (row, step * H + unit): H is a multiple of 32, so the column classes are those of the units
+        reports.append(E.check(tag + ' y', got.reshape(B, F * Hd), want.reshape(B, F * Hd), allow_h.reshape(B, F * Hd),
+                               GAMMA_LSTM, col_mod=_col_mod(kernel)))
+        exact.append((tag, bool((y[~live] == 0).all()),
+                      bool(torch.equal(hn[0], y[torch.arange(B, device=DEV), lens_d - 1]))))
+        # the final cell state: c = i g of the last live step, from the kernel's h before it
+        last = lens_d - 1
+        rows = torch.arange(B, device=DEV)
+        _, c1, _, ec = E.lstm_step_reference(*unit, x[rows, last], h_prev[rows, last], zeros, GAMMA_LSTM)
+        reports.append(E.check(tag + ' c_n', cn[0], c1, ec, GAMMA_LSTM, col_mod=_col_mod(kernel)))
+    g_.release()
+    for r in reports:
+        print(r.message.splitlines()[0])
+    bad = [r.message for r in reports if not r.ok]
+    assert not bad, '\n'.join(bad)
+    for tag, zero_pad, final in exact:
+        assert zero_pad, tag + ': rows past their length are not exactly 0'
+        assert final, tag + ': the final hidden state is not the output of the last live step'
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# c. Full mesh
+@pytest.fixture(scope='module')
+def big_model():
+    return synthetic.make_model()
+
+
+def _bm64_on_device(model):
+    bm = R.BodyModelTensors(model, dtype=torch.float64)
+    for k in ('v_template', 'shapedirs', 'posedirs', 'J_regressor', 'weights'):
+        setattr(bm, k, getattr(bm, k).to(DEV))
+    return bm
+
+
+def _mesh_inputs(n):
+    rng = np.random.default_rng(n)
+    f = lambda sd, shape: torch.from_numpy(rng.normal(0, sd, size=shape).astype(np.float32)).to(DEV)
+    return dict(poses_body=f(0.5, (n, 63)), betas=f(1.5, (n, 10)), poses_root=f(0.5, (n, 3)), trans=f(1.0, (n, 3)))
+
+
+def _check_mesh(big_model, n, kw, side=None, chunk=1024):
+    smpl = SMPLLayer(big_model).to(DEV)
+    bm = _bm64_on_device(big_model)
+    out = {}
+    for opt in (0, 1, 2, 3):
+        _set(mesh_x3=opt)
+        if side is not None:
+            H.queue_storing_kernels(*side)
+        out[opt] = smpl(**kw)[0]
+        torch.cuda.synchronize()
+    worst = {}
+    bad = []
+    for s in range(0, n, chunk):
+        e = min(n, s + chunk)
+        part = {k: v[s:e] for k, v in kw.items()}
+        m = E.mesh_magnitude(bm, part['poses_body'], part['betas'], part['poses_root'], part['trans'])
+        allow = 2 * GAMMA_MESH * E.U * m
+        v64, _ = R.smpl_fk(bm, part['poses_body'].double(), part['betas'].double(), part['poses_root'].double(),
+                           part['trans'].double())
+        for opt in (1, 2, 3):
+            r = E.check('mesh n=%d frames %d..%d mesh_x3=%d vs mesh_x3=0' % (n, s, e - 1, opt), out[opt][s:e],
+                        out[0][s:e].double(), allow, GAMMA_MESH)
+            worst[opt] = max(worst.get(opt, 0.0), r.worst)
+            if not r.ok:
+                bad.append(r.message)
+        for opt in (0, 1):         # every frame against float64 at the bar of test_full_mesh_vertices_vs_oracle
+            err = float((out[opt][s:e].double() - v64).abs().max())
+            worst['f64_%d' % opt] = max(worst.get('f64_%d' % opt, 0.0), err)
+    print('mesh n=%d: worst err / allowance x3 vs fp32 %s; max |v - v64| fp32 %.2e, x3 %.2e'
+          % (n, ', '.join('%d: %.3g' % (o, worst[o]) for o in (1, 2, 3)), worst['f64_0'], worst['f64_1']))
+    assert not bad, '\n'.join(bad)
+    assert worst['f64_1'] < 2e-5 and worst['f64_0'] < 2e-5, worst
+
+
+@pytest.mark.parametrize('n', [1, 65, 4096 + 17, 16384])
+def test_full_mesh_every_vertex_within_its_allowance(big_model, n):
+    _check_mesh(big_model, n, _mesh_inputs(n))
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# d. Training forward products
+def _train_layers(net):
+    from tests.test_hip_round6 import _dense_names
+    sd = {k: v.detach().double() for k, v in net.state_dict().items()}
+    out = []
+    for lin, bn, act in _dense_names(net):
+        out.append({'w': sd[lin + '.weight'], 'b': sd[lin + '.bias'],
+                    'bn': None if bn is None else (sd[bn + '.weight'], sd[bn + '.bias']),
+                    'slope': None if act is None else sd[act + '.weight']})
+    return out
+
+
+@pytest.mark.parametrize('M', [1024, 2048 + 40, 8192])
+def test_training_forward_products_every_element_within_its_allowance(M):
+    from tests.test_hip_round5 import _mlp_pair, _run_mlp_train
+    in_dim, hidden = 296, 512
+    g = torch.Generator().manual_seed(M)
+    x = torch.randn(M, in_dim, generator=g).to(DEV)
+    d_outs = [torch.zeros(M, 68, device=DEV), torch.zeros(M, 12, device=DEV)]
+    refs = [E.train_mlp_reference(_train_layers(n), x, GAMMA_TRAIN) for n in _mlp_pair(in_dim, hidden, 5)]
+    reports = []
+    for opt in (0, 1):
+        _set(train_x3=opt)
+        res = _run_mlp_train(_mlp_pair(in_dim, hidden, 5), x, d_outs, M, pair=False, deferred=False)
+        for i, (want, allow) in enumerate(refs):
+            reports.append(E.check('training forward M=%d train_x3=%d net %d' % (M, opt, i), res['out'][i], want, allow,
+                                   GAMMA_TRAIN))
+    for r in reports:
+        print(r.message.splitlines()[0])
+    bad = [r.message for r in reports if not r.ok]
+    assert not bad, '\n'.join(bad)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# e. Beside a storing stream
+def test_update_nets_and_full_mesh_within_their_allowances_beside_a_storing_stream(big_model):
+    """One case of (a) and one of (c), each launch with the store loop of
+    test_three_piece_kernels_keep_their_bits_beside_a_storing_kernel_on_another_stream queued on a second stream."""
+    side = (torch.cuda.Stream(), torch.randn(1 << 26, device=DEV))
+    torch.cuda.synchronize()
+    net = _update_net()
+    T = 16384 + 71
+    xg = (torch.randn(T, 296, generator=torch.Generator().manual_seed(T)) * 30.0).to(DEV)
+    _check_update_nets(net, xg, _update_net_refs(net, xg), 'T=%d beside a storing stream' % T, side=side)
+    side[0].synchronize()
+    n = 16384
+    _check_mesh(big_model, n, _mesh_inputs(n), side=side)
+    side[0].synchronize()
