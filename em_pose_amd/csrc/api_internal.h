@@ -1,0 +1,214 @@
+// What the pieces of the C ABI (api.hip, api_model.hip, api_lstm.hip, api_train.hip, api_mesh.hip) share: the error
+// state, the profiler, workspace carving and upload, the packed model, and the LSTM dispatcher.  Host code only.
+#pragma once
+#include "../../include/empose_hip.h"
+#include "kernels.h"
+
+#include <cstring>
+#include <vector>
+
+namespace empose {
+namespace api __attribute__((visibility("hidden"))) {
+
+// ---- errors ---------------------------------------------------------------------------------------------------
+int fail(int code, const char* fmt, ...);   // sets the message empose_last_error() returns; returns `code`
+
+#define HIP_TRY(expr)                                                                            \
+  do {                                                                                           \
+    hipError_t e_ = (expr);                                                                      \
+    if (e_ != hipSuccess) return fail(EMPOSE_EHIP, "%s: %s", #expr, hipGetErrorString(e_));       \
+  } while (0)
+
+#define HIP_CHECK(expr, msg)                                                                     \
+  do {                                                                                           \
+    hipError_t e_ = (expr);                                                                      \
+    if (e_ != hipSuccess) return fail(EMPOSE_EHIP, msg ": %s", hipGetErrorString(e_));           \
+  } while (0)
+
+#define TRY(expr)            \
+  do {                       \
+    int rc_ = (expr);        \
+    if (rc_ != EMPOSE_OK) return rc_; \
+  } while (0)
+
+// A poll of a cooperative kernel launched by an EARLIER call gave up (that call's outputs are NaN): reported by every entry
+// point that launches or consumes such kernels -- the recurrences and, round 6, the training layers (empose_mlp_train_*,
+// empose_lstm_train_*) -- without synchronising (the counter is a host-mapped word), and STICKY until
+// empose_async_status() has reported and cleared it.
+int earlier_poll_timeouts();
+
+// ---- optional per-launch timing (HIP events on the launch stream), used by bench.py for the roofline numbers ---------
+enum ProfTag { P_PACK = 0, P_LSTM_STEP, P_HEADS, P_UPDATE_FEAT, P_BLEND_GEMM, P_CHAIN, P_BLEND_T_GEMM,
+               P_ROD_BWD, P_MLP_IN, P_MLP_HIDDEN, P_MLP_OUT, P_MLP_FUSED, P_INIT_MLP, P_COPY, P_EVENT_PAIR, P_END, P_NTAGS };
+void prof_mark(int tag, hipStream_t stream);
+void prof_end_forward(hipStream_t stream);   // P_END, and in single-kernel mode the empty calibration pair
+
+// ---- workspace carving and upload -----------------------------------------------------------------------------
+inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+struct Carver {
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* p) : base(static_cast<char*>(p)) {}
+  float* f(size_t count) {
+    float* r = base ? reinterpret_cast<float*>(base + off) : nullptr;
+    off += align_up(count * sizeof(float));
+    return r;
+  }
+};
+
+template <typename T>
+int upload(std::vector<void*>& allocs, const T* host, size_t count, T** dev) {
+  *dev = nullptr;
+  if (count == 0) return EMPOSE_OK;
+  if (!host) return fail(EMPOSE_EINVAL, "null host pointer in model descriptor");
+  void* p = nullptr;
+  HIP_TRY(hipMalloc(&p, count * sizeof(T)));
+  allocs.push_back(p);
+  HIP_TRY(hipMemcpy(p, host, count * sizeof(T), hipMemcpyHostToDevice));
+  *dev = static_cast<T*>(p);
+  return EMPOSE_OK;
+}
+
+// ---- three bf16 pieces per weight (bf16x3.h) ------------------------------------------------------------------------
+// Round to nearest even; Inf and NaN pass through as they are.
+inline unsigned short bf16_round(float x) {
+  unsigned u;
+  std::memcpy(&u, &x, 4);
+  if ((u & 0x7f800000u) == 0x7f800000u) return (unsigned short)(u >> 16);   // inf / nan: as they are
+  u += 0x7fffu + ((u >> 16) & 1u);
+  return (unsigned short)(u >> 16);
+}
+inline float bf16_value(unsigned short h) {
+  const unsigned u = (unsigned)h << 16;
+  float f;
+  std::memcpy(&f, &u, 4);
+  return f;
+}
+// w = p[0] + p[1] + p[2], every piece the round-to-nearest bf16 of what the previous ones leave: 8 + 8 + 8 mantissa bits,
+// all of an fp32's 24.
+inline void split3(float w, unsigned short p[3]) {
+  p[0] = bf16_round(w);
+  const float r = w - bf16_value(p[0]);
+  p[1] = bf16_round(r);
+  p[2] = bf16_round(r - bf16_value(p[1]));
+}
+// A table of bf16 pieces goes to the device as it is; `out` is typed as the kernels that read it take it.
+template <typename T>
+int upload_bf16(std::vector<void*>& allocs, const std::vector<unsigned short>& buf, T** out) {
+  unsigned short* dev = nullptr;
+  TRY(upload(allocs, buf.data(), buf.size(), &dev));
+  *out = reinterpret_cast<T*>(dev);
+  return EMPOSE_OK;
+}
+
+// ---- the packed model -----------------------------------------------------------------------------------------
+// A packed Linear(+BN)(+PReLU): device weight and the per-column epilogue (scale, shift).
+struct Dense {
+  int in_dim = 0, out_dim = 0;
+  float* w = nullptr;      // [out][in]
+  float* wp = nullptr;     // the same weights in MFMA fragment order (mlp_fused.hip), only for MLP layers
+  float* wp3 = nullptr;    // ... and as three bf16 pieces per weight in bf16-MFMA fragment order (mlp_fused_x3.hip)
+  float* scale = nullptr;  // nullptr => 1
+  float* shift = nullptr;  // bias (and folded BN)
+  int act = 0;
+  float slope = 0.f;
+};
+
+struct Mlp {
+  int n_layers = 0, skip = 0;
+  Dense layers[EMPOSE_MAX_DENSE];
+};
+
+struct Lstm {   // unit u = layer * dirs + direction
+  int num_layers = 0, input_size = 0, H = 0, dirs = 1;
+  float* w_ih[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  float* w_hh[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  float* bias[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // b_ih + b_hh
+  // the same matrices as three bf16 pieces per weight in the fragment order of lstm_x3.hip (uni-directional stacks only)
+  unsigned short* w3_ih[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  unsigned short* w3_hh[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // ... and in the fragment order of lstm_mid_x3.hip (8-unit blocks, the four gates of a unit in one 32-column tile)
+  unsigned short* w3m_ih[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  unsigned short* w3m_hh[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  // ... and in the order of lstm_mid16_x3.hip (4-unit blocks, k-steps of 32)
+  unsigned short* w3q_ih[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  unsigned short* w3q_hh[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+};
+
+// Uploads an LSTM stack (api_lstm.hip): fp32 weights, summed biases and, for uni-directional stacks with H % 32 == 0, the
+// three-piece bf16 weights in the orders of the x3 step kernels.
+int pack_lstm(std::vector<void*>& allocs, const empose_lstm_desc& r, int dirs, const float* const* w_ih,
+              const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, Lstm* out);
+
+// ---- the LSTM dispatcher (api_lstm.hip) ------------------------------------------------------------------------
+// The static choice (plan_lstm) for a stack and a batch under the options of the moment: which whole-sequence
+// cooperative kernels get buffers, and which kernel runs the steps.  The cooperative launches may still fall back to
+// the steps at run time.
+enum class LstmStep { wave, chain_x3, rows_x3, mid_x3, mid16_x3 };
+struct LstmPlan {
+  bool persist = false;   // lstm_persist_kernel, small batches (its exchange words; the launch checks option lstm_persist)
+  bool seq = false;       // lstm_seq_kernel, large batches (third hidden buffers + counters; the launch checks lstm_seq)
+  bool midseq = false;    // lstm_midseq_x3.hip, medium batches
+  bool x3 = false;        // the bf16 piece planes of the inputs and hidden states (a three-piece step kernel or midseq)
+  LstmStep step = LstmStep::wave;   // wave: lstm_wave (fp32); else the three-piece step kernel
+};
+
+struct LstmWs {
+  LstmPlan plan;
+  float* h[8][2];
+  float* c[8];
+  float* yb[2];   // [B][F][2H] ping-pong between the layers of a bidirectional stack
+  float* xch;     // exchange words of the whole-sequence small-batch kernel (lstm_persist_kernel), or nullptr
+  float* h3[8];   // third hidden-state buffer per unit + counters of the whole-sequence large-batch kernel, or nullptr
+  unsigned* seq_cnt;
+  // lstm_x3.hip: the stored input of every time step and the hidden states (ping-pong) as bf16 piece planes, or nullptr
+  unsigned short* x3; size_t x3_t_stride;
+  unsigned short* a3[8][2];
+  // lstm_midseq_x3.hip: [F + 1] sets of hidden-state planes per layer and the progress counters, or nullptr
+  unsigned short* xa[8];
+  unsigned* midseq_flags;
+};
+LstmWs carve_lstm_of(Carver& c, const Lstm& r, int B, int F);
+// State layout of h0/c0/h_n/c_n: [num_layers * dirs][B][H], unit u = layer * dirs + direction (PyTorch's order).
+int run_lstm(const Lstm& r, int B, int F, const float* x, int ldx, const int* seq_lengths, const float* h0,
+             const float* c0, float* y, float* h_n, float* c_n, const LstmWs& ws, hipStream_t stream);
+
+}  // namespace api
+}  // namespace empose
+
+struct empose_model {
+  std::vector<void*> allocs;
+  empose::SmplTables tab;
+  float* wc_frag = nullptr;    // tab.wc / tab.wct in MFMA fragment order (row-block GEMM)
+  float* wct_frag = nullptr;
+  int n_markers = 12;
+  int marker_idx[12];
+  int used_slot[12];
+  int N = 4;
+  float step = 0.1f;
+  int shape_avg = 1, use_gradient = 1, rnn_init = 1;
+  int d_in = 144, d_x = 296;
+  empose::api::Lstm rnn;
+  empose::api::Dense pose_head, shape_head;
+  float* heads_frag = nullptr;   // both heads stacked ([66 + 10][H]) in fragment order, and their stacked bias
+  float* heads_frag3 = nullptr;  // ... as three bf16 pieces per weight (x3_rows_layer)
+  float* heads_bias = nullptr;
+  empose::api::Mlp pose_init, shape_init, pose_iter, shape_iter;
+  int hidden_max = 0;
+  int any_skip = 0;
+  int smpl_only = 0;
+  int rod_conv = 0;            // EMPOSE_RODRIGUES_*
+  // frame-per-lane path (smpl_tile.hip): tables, the blend matrix with per-patch vertex copies in fragment order
+  int tile_ok = 0, ncp2 = 0, tile_nloc = 0, tile_nbl = 0;
+  empose::TileTables* tile_tab = nullptr;
+  float* wc2_frag = nullptr;   // [ncp2][200]
+  float* wc2t_frag = nullptr;  // [200][ncp2]
+  float* wc2_frag3 = nullptr;  // the same two as three bf16 pieces per weight (x3_rows_layer)
+  float* wc2t_frag3 = nullptr;
+};
+
+struct empose_rnn {
+  std::vector<void*> allocs;
+  empose::api::Lstm rnn;
+};

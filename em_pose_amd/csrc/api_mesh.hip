@@ -1,0 +1,311 @@
+// C ABI (include/empose_hip.h), full mesh: packing and evaluation of the posed vertices and joints, the metrics rows
+// and the virtual sensors.
+#include "api_internal.h"
+
+#include <algorithm>
+
+using namespace empose;
+using namespace empose::api;
+
+struct empose_mesh {
+  std::vector<void*> allocs;
+  int V = 0, j_off = 0, ncp = 0, kb = 0;
+  int n_joints = 22;            // posed joints returned (22 body, or all 52 of SMPL-H)
+  int rod_conv = 0;             // EMPOSE_RODRIGUES_*
+  float* wc = nullptr;
+  float* wc_frag = nullptr;     // vertex rows of wc in matrix-core fragment order, per 32-vertex tile (mesh.hip)
+  int* skin_idx = nullptr;
+  float* skin_w = nullptr;
+  int* skin_idx4 = nullptr;     // first four bones / weights per vertex, padded to whole tiles
+  float* skin_w4 = nullptr;
+  int* parents = nullptr;
+  unsigned short* wc_bf16 = nullptr;   // split-bf16 pieces of wc in fragment order (only when the handle asked for them)
+  unsigned short* wc_x3 = nullptr;     // three bf16 pieces of wc in fragment order (mesh_x3.hip), kb <= 4
+  unsigned short* skin_bf16 = nullptr; // dense skin weights per 32-vertex tile, bf16 hi + lo, B-fragment order (ditto)
+};
+
+namespace {
+
+// Tables of mesh_rows_kernel: for every 32-vertex tile, k-group of 8 and coordinate c, lane (v = lane & 31,
+// half = lane >> 5) owns wc[(tile * 32 + v) * 3 + c][kg * 8 + half * 4 .. + 3] -- the three coordinate planes of a tile
+// are separate 32-column operands, so a lane's accumulators hold x, y and z of the same vertex.  Vertices past V are
+// zero.  Skinning tables: the first four (bone, weight) pairs per vertex, zero-padded.
+int pack_mesh_tiles(empose_mesh* m, const empose_mesh_desc* d) {
+  const int V = d->n_vertices, NT = (V + 31) / 32, KG = 25, K = 200;
+  std::vector<float> buf((size_t)NT * KG * 3 * 256, 0.f);
+  for (int t = 0; t < NT; ++t)
+    for (int kg = 0; kg < KG; ++kg)
+      for (int c = 0; c < 3; ++c)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int v = t * 32 + (lane & 31);
+          if (v >= V) continue;
+          const float* src = d->wc + ((size_t)v * 3 + c) * K + kg * 8 + (lane >> 5) * 4;
+          float* dst = &buf[((((size_t)t * KG + kg) * 3 + c) * 64 + lane) * 4];
+          for (int e = 0; e < 4; ++e) dst[e] = src[e];
+        }
+  TRY(upload(m->allocs, buf.data(), buf.size(), &m->wc_frag));
+  std::vector<int> idx4((size_t)NT * 32 * 4, 0);
+  std::vector<float> w4((size_t)NT * 32 * 4, 0.f);
+  for (int v = 0; v < V; ++v)
+    for (int k = 0; k < 4 && k < d->kb; ++k) {
+      idx4[(size_t)v * 4 + k] = d->skin_idx[(size_t)v * d->kb + k];
+      w4[(size_t)v * 4 + k] = d->skin_w[(size_t)v * d->kb + k];
+    }
+  TRY(upload(m->allocs, idx4.data(), idx4.size(), &m->skin_idx4));
+  TRY(upload(m->allocs, w4.data(), w4.size(), &m->skin_w4));
+  return EMPOSE_OK;
+}
+
+// Tables of mesh_rows_x3_kernel (mesh_x3.hip): per 32-vertex tile, k-step of 16, coordinate plane c and piece p one
+// fragment of 1 KB -- lane (v = lane & 31, half = lane >> 5) owns the eight values k = kstep * 16 + half * 8 .. + 7 of
+// row (tile * 32 + v) * 3 + c, as piece p of their three-piece bf16 split (bf16x3.h); k >= 200 and vertices past V are zero.
+int pack_mesh_tiles_x3(empose_mesh* m, const empose_mesh_desc* d) {
+  const int V = d->n_vertices, NT = (V + 31) / 32, K = 200, KS = 13;
+  const size_t tile_shorts = MESH_X3_TILE_BYTES / 2;
+  std::vector<unsigned short> buf((size_t)NT * tile_shorts, 0);
+  for (int t = 0; t < NT; ++t)
+    for (int lane = 0; lane < 64; ++lane) {
+      const int v = t * 32 + (lane & 31), half = lane >> 5;
+      if (v >= V) continue;
+      for (int c = 0; c < 3; ++c) {
+        const float* row = d->wc + ((size_t)v * 3 + c) * K;
+        for (int ks = 0; ks < KS; ++ks)
+          for (int e = 0; e < 8; ++e) {
+            const int k = ks * 16 + half * 8 + e;
+            if (k >= K) continue;
+            unsigned short p[3];
+            split3(row[k], p);
+            unsigned short* dst = &buf[(size_t)t * tile_shorts + ((size_t)((ks * 3 + c) * 3) * 64 + lane) * 8 + e];
+            dst[0] = p[0]; dst[64 * 8] = p[1]; dst[2 * 64 * 8] = p[2];
+          }
+      }
+    }
+  return upload_bf16(m->allocs, buf, &m->wc_x3);
+}
+
+// Tables of mesh_rows_bf16_kernel: per 32-vertex tile, k-step of 16, coordinate plane and (hi, lo) piece, lane
+// (v = lane & 31, half = lane >> 5) owns the eight values k = kstep * 16 + half * 8 .. + 7 of row (tile * 32 + v) * 3 + c.
+// Columns (mesh.hip): 0..188 pose, (hi, lo) = (w0, w1); 189..199 shape/template, (b0, b2); 200..210 the same
+// coefficients again, (b1, b0); zero up to 223.
+int pack_mesh_tiles_bf16(empose_mesh* m, const empose_mesh_desc* d) {
+  const int V = d->n_vertices, NT = (V + 31) / 32, K = 200, KS = 14;
+  const size_t tile_shorts = MESH_BF16_TILE_BYTES / 2;
+  std::vector<unsigned short> buf((size_t)NT * tile_shorts, 0);
+  for (int t = 0; t < NT; ++t)
+    for (int lane = 0; lane < 64; ++lane) {
+      const int v = t * 32 + (lane & 31), half = lane >> 5;
+      if (v >= V) continue;
+      for (int c = 0; c < 3; ++c) {
+        const float* row = d->wc + ((size_t)v * 3 + c) * K;
+        for (int ks = 0; ks < KS; ++ks)
+          for (int e = 0; e < 8; ++e) {
+            const int k = ks * 16 + half * 8 + e;
+            if (k >= 211) continue;
+            unsigned short p[3];
+            split3(row[k < 200 ? k : k - 11], p);
+            unsigned short* dst = &buf[(size_t)t * tile_shorts + ((size_t)((ks * 3 + c) * 2) * 64 + lane) * 8 + e];
+            dst[0] = k < 200 ? p[0] : p[1];                            // hi: w0 | b0 | b1
+            dst[64 * 8] = k < 189 ? p[1] : (k < 200 ? p[2] : p[0]);    // lo: w1 | b2 | b0
+          }
+      }
+    }
+  TRY(upload_bf16(m->allocs, buf, &m->wc_bf16));
+  // The skin weights as a dense [32 bone slots][32 vertices] block per tile for the bone blend on the matrix cores
+  // (mesh.hip mesh_rows_bf16s_kernel): k-step ks, piece p, lane (vertex = lane & 31, half = lane >> 5) holds the eight
+  // weights of bones 16 ks + 8 half + 0..7 -- hi = bf16(w), lo = bf16(w - hi); bones a vertex does not have, and the
+  // slots past the 22 body bones, are zero.  Weights of the same bone listed twice add up.
+  {
+    const size_t tile = MESH_SKIN_BF16_TILE_BYTES / 2;
+    std::vector<unsigned short> sk((size_t)NT * tile, 0);
+    std::vector<float> dense(32);
+    for (int t = 0; t < NT; ++t)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int v = t * 32 + (lane & 31), half = lane >> 5;
+        if (v >= V) continue;
+        std::fill(dense.begin(), dense.end(), 0.f);
+        for (int k = 0; k < d->kb; ++k) {
+          const int b = d->skin_idx[(size_t)v * d->kb + k];
+          if (b < 0 || b >= NB) return fail(EMPOSE_EINVAL, "skin index %d of vertex %d outside the %d body bones", b, v, NB);
+          dense[b] += d->skin_w[(size_t)v * d->kb + k];
+        }
+        for (int ks = 0; ks < 2; ++ks)
+          for (int e = 0; e < 8; ++e) {
+            unsigned short p[3];   // hi, lo: the first two pieces
+            split3(dense[ks * 16 + half * 8 + e], p);
+            unsigned short* dst = &sk[(size_t)t * tile + ((size_t)(ks * 2) * 64 + lane) * 8 + e];
+            dst[0] = p[0];
+            dst[64 * 8] = p[1];
+          }
+      }
+    TRY(upload_bf16(m->allocs, sk, &m->skin_bf16));
+  }
+  return EMPOSE_OK;
+}
+
+const int MESH_SLAB = 16384;  // frames per pass: bounds the scratch (rot, feat, rest joints, transforms)
+
+struct MeshWs { float *rot, *feat, *jrest, *xf; };
+MeshWs carve_mesh(Carver& c, const empose_mesh* mesh, size_t S) {
+  MeshWs w;
+  w.rot = c.f(S * 198); w.feat = c.f(S * 200); w.jrest = c.f(S * (size_t)(mesh->ncp - mesh->j_off));
+  w.xf = c.f(S * 264);
+  return w;
+}
+
+// Slab by slab: Rodrigues + feature row, rest joints (the joint rows of wc), kinematic chain (all n_joints posed
+// joints + the 22 skinning transforms) and, when `vertices` is given, the full-mesh kernel.
+int run_mesh(const empose_mesh_t* mesh, int T, const float* poses, const float* betas, const float* trans,
+                    float* vertices, float* joints, void* workspace, hipStream_t stream, bool bf16x3 = false) {
+  const int S = T < MESH_SLAB ? T : MESH_SLAB;
+  const int jw = mesh->ncp - mesh->j_off, nj = mesh->n_joints;
+  Carver c(workspace);
+  const MeshWs w = carve_mesh(c, mesh, (size_t)S);
+  for (int t0 = 0; t0 < T; t0 += S) {
+    const int n = (T - t0) < S ? (T - t0) : S;
+    FeatArgs fa;   // plain evaluation: the caller's rows are read in place
+    fa.theta = const_cast<float*>(poses) + (size_t)t0 * 66; fa.ld_theta = 66;
+    fa.beta = const_cast<float*>(betas) + (size_t)t0 * 10; fa.ld_beta = 10;
+    fa.d_theta = nullptr; fa.d_beta = nullptr; fa.theta_step = 0.f; fa.beta_keep = 1.f; fa.beta_step = 0.f;
+    fa.shape_avg = 0; fa.rot = w.rot; fa.feat = w.feat;
+    fa.out_theta = fa.out_beta = fa.out_theta2 = fa.out_beta2 = nullptr;
+    fa.T = n; fa.F = 1; fa.rod_conv = mesh->rod_conv;
+    HIP_CHECK(launch_update_feat(fa, stream), "update_feat kernel");
+    GemmBatch b;
+    b.count = 1;
+    GemmProb& p = b.p[0];
+    p.A = w.feat; p.lda = 200; p.W = mesh->wc + (size_t)mesh->j_off * 200; p.ldw = 200; p.C = w.jrest; p.ldc = jw;
+    p.M = n; p.N = jw; p.K = 200;
+    p.scale = nullptr; p.shift = nullptr; p.resid = nullptr; p.ldr = 0; p.act = 0; p.slope = 0.f;
+    HIP_CHECK(launch_gemm(b, stream), "rest-joint gemm");
+    const float* tr = trans ? trans + (size_t)t0 * 3 : nullptr;
+    MeshChainArgs ca;
+    ca.rot = w.rot; ca.out = w.jrest; ca.ncp = jw; ca.j_off = 0; ca.parents = mesh->parents;
+    ca.trans = tr; ca.xf = w.xf; ca.joints = joints + (size_t)t0 * nj * 3; ca.T = n; ca.n_joints = nj;
+    HIP_CHECK(launch_mesh_chain(ca, stream), "mesh chain");
+    if (!vertices) continue;
+    MeshSkinArgs sa;
+    sa.feat = w.feat; sa.wc = mesh->wc; sa.xf = w.xf; sa.skin_idx = mesh->skin_idx; sa.skin_w = mesh->skin_w;
+    sa.kb = mesh->kb; sa.trans = tr; sa.vertices = vertices + (size_t)t0 * mesh->V * 3; sa.T = n; sa.V = mesh->V;
+    sa.wc_frag = mesh->wc_frag; sa.skin_idx4 = mesh->skin_idx4; sa.skin_w4 = mesh->skin_w4;
+    sa.wc_bf16 = mesh->wc_bf16; sa.skin_bf16 = mesh->skin_bf16; sa.wc_x3 = mesh->wc_x3;
+    // default: the three-piece bf16 contraction (fp32-equivalent); `bf16x3`: the explicitly selected two-piece variant
+    hipError_t e;
+    if (bf16x3)
+      e = options().mesh_skin_mfma && mesh->skin_bf16 ? launch_mesh_rows_bf16s(sa, stream) : launch_mesh_rows_bf16(sa, stream);
+    else if (options().mesh_x3 != 0 && mesh->wc_x3 && mesh->kb <= 4) {
+      sa.stagger = options().mesh_x3 == 1;
+      e = launch_mesh_rows_x3(sa, options().mesh_x3 == 3, stream);
+    }
+    else
+      e = launch_mesh_rows(sa, stream);
+    if (e != hipSuccess) return fail(EMPOSE_EHIP, "fused mesh kernel: %s", hipGetErrorString(e));
+  }
+  return EMPOSE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int empose_virtual_sensors_fwd(int T, int V, const float* vertices, int M, int max_deg, const int* center,
+                               const int* helper, const int* deg, const int* faces, float* pos, float* ori,
+                               float* normals, empose_stream_t stream_) {
+  if (!vertices || !center || !helper || !deg || !faces || !pos || !ori) return fail(EMPOSE_EINVAL, "null argument");
+  if (T <= 0 || V <= 0 || M <= 0 || max_deg <= 0) return fail(EMPOSE_EINVAL, "sizes must be positive");
+  VirtualSensorArgs a;
+  a.vertices = vertices; a.center = center; a.helper = helper; a.deg = deg; a.faces = faces;
+  a.pos = pos; a.ori = ori; a.normals = normals; a.T = T; a.V = V; a.M = M; a.max_deg = max_deg;
+  HIP_CHECK(launch_virtual_sensors(a, static_cast<hipStream_t>(stream_)), "virtual sensors kernel");
+  return EMPOSE_OK;
+}
+
+int empose_metrics_rows(int T, const float* joints_gt, const float* joints_hat, const float* pose_gt,
+                        const float* pose_hat, const int* parents_host, double* rows, empose_stream_t stream_) {
+  if (!joints_gt || !joints_hat || !parents_host || !rows) return fail(EMPOSE_EINVAL, "null argument");
+  if ((pose_gt == nullptr) != (pose_hat == nullptr)) return fail(EMPOSE_EINVAL, "pose_gt and pose_hat go together");
+  if (T <= 0) return fail(EMPOSE_EINVAL, "T must be positive");
+  MetricsArgs a;
+  a.joints_gt = joints_gt; a.joints_hat = joints_hat; a.pose_gt = pose_gt; a.pose_hat = pose_hat; a.rows = rows; a.T = T;
+  for (int j = 0; j < 22; ++j) {
+    if (parents_host[j] >= j) return fail(EMPOSE_EINVAL, "parents must be topologically ordered");
+    a.parents[j] = parents_host[j] < 0 ? 0 : parents_host[j];
+  }
+  HIP_CHECK(launch_metrics_rows(a, static_cast<hipStream_t>(stream_)), "metrics kernel");
+  return EMPOSE_OK;
+}
+
+// ---- full mesh -----------------------------------------------------------------------------------------------
+void empose_mesh_destroy(empose_mesh_t* mesh) {
+  if (!mesh) return;
+  for (void* p : mesh->allocs) (void)hipFree(p);
+  delete mesh;
+}
+
+int empose_mesh_create(const empose_mesh_desc* d, empose_mesh_t** out) {
+  if (!d || !out) return fail(EMPOSE_EINVAL, "null argument");
+  *out = nullptr;
+  const int nj = d->n_joints == 0 ? 22 : d->n_joints;
+  if (nj < 22 || nj > MESH_MAX_JOINTS) return fail(EMPOSE_EINVAL, "n_joints must be in [22, %d]", MESH_MAX_JOINTS);
+  if (d->rodrigues != EMPOSE_RODRIGUES_SMPLX && d->rodrigues != EMPOSE_RODRIGUES_SO3)
+    return fail(EMPOSE_EINVAL, "unknown Rodrigues convention %d", d->rodrigues);
+  if (d->n_vertices <= 0 || d->ncp % 4 != 0 || d->j_off != d->n_vertices * 3 || d->j_off + nj * 3 > d->ncp ||
+      d->ncp - d->j_off > nj * 3 + 3 || d->kb <= 0 || !d->parents)
+    return fail(EMPOSE_EINVAL, "inconsistent mesh table sizes");
+  for (int j = 0; j < nj; ++j)
+    if (d->parents[j] >= j || (j > 0 && d->parents[j] < 0))
+      return fail(EMPOSE_EINVAL, "parents must be topologically ordered with a single root");
+  empose_mesh* m = new empose_mesh();
+  m->V = d->n_vertices; m->j_off = d->j_off; m->ncp = d->ncp; m->kb = d->kb;
+  m->n_joints = nj; m->rod_conv = d->rodrigues;
+  int rc;
+  if ((rc = upload(m->allocs, d->wc, (size_t)d->ncp * 200, &m->wc)) ||
+      (rc = upload(m->allocs, d->skin_idx, (size_t)d->n_vertices * d->kb, &m->skin_idx)) ||
+      (rc = upload(m->allocs, d->skin_w, (size_t)d->n_vertices * d->kb, &m->skin_w)) ||
+      (rc = upload(m->allocs, d->parents, (size_t)nj, &m->parents)) || (rc = pack_mesh_tiles(m, d)) ||
+      (d->kb <= 4 && (rc = pack_mesh_tiles_x3(m, d))) ||
+      (d->with_bf16x3 && (rc = pack_mesh_tiles_bf16(m, d)))) {
+    empose_mesh_destroy(m);
+    return rc;
+  }
+  *out = m;
+  return EMPOSE_OK;
+}
+
+int empose_mesh_n_joints(const empose_mesh_t* mesh) { return mesh ? mesh->n_joints : 0; }
+
+size_t empose_mesh_workspace_bytes(const empose_mesh_t* mesh, int T) {
+  if (!mesh || T <= 0) return 0;
+  Carver c(nullptr);
+  carve_mesh(c, mesh, T < MESH_SLAB ? T : MESH_SLAB);
+  return c.off;
+}
+
+int empose_mesh_vertices_fwd(const empose_mesh_t* mesh, int T, const float* poses, const float* betas,
+                             const float* trans, float* vertices, float* joints, void* workspace,
+                             size_t workspace_bytes, empose_stream_t stream_) {
+  if (!mesh || !poses || !betas || !vertices || !joints || !workspace) return fail(EMPOSE_EINVAL, "null argument");
+  if (T <= 0) return fail(EMPOSE_EINVAL, "T must be positive");
+  if (workspace_bytes < empose_mesh_workspace_bytes(mesh, T)) return fail(EMPOSE_ENOMEM, "workspace too small");
+  return run_mesh(mesh, T, poses, betas, trans, vertices, joints, workspace, static_cast<hipStream_t>(stream_));
+}
+
+int empose_mesh_vertices_fwd_bf16x3(const empose_mesh_t* mesh, int T, const float* poses, const float* betas,
+                                    const float* trans, float* vertices, float* joints, void* workspace,
+                                    size_t workspace_bytes, empose_stream_t stream_) {
+  if (!mesh || !poses || !betas || !vertices || !joints || !workspace) return fail(EMPOSE_EINVAL, "null argument");
+  if (!mesh->wc_bf16) return fail(EMPOSE_EINVAL, "the mesh handle was created without with_bf16x3");
+  if (T <= 0) return fail(EMPOSE_EINVAL, "T must be positive");
+  if (workspace_bytes < empose_mesh_workspace_bytes(mesh, T)) return fail(EMPOSE_ENOMEM, "workspace too small");
+  return run_mesh(mesh, T, poses, betas, trans, vertices, joints, workspace, static_cast<hipStream_t>(stream_), true);
+}
+
+int empose_mesh_joints_fwd(const empose_mesh_t* mesh, int T, const float* poses, const float* betas,
+                           const float* trans, float* joints, void* workspace, size_t workspace_bytes,
+                           empose_stream_t stream_) {
+  if (!mesh || !poses || !betas || !joints || !workspace) return fail(EMPOSE_EINVAL, "null argument");
+  if (T <= 0) return fail(EMPOSE_EINVAL, "T must be positive");
+  if (workspace_bytes < empose_mesh_workspace_bytes(mesh, T)) return fail(EMPOSE_ENOMEM, "workspace too small");
+  return run_mesh(mesh, T, poses, betas, trans, nullptr, joints, workspace, static_cast<hipStream_t>(stream_));
+}
+
+}  // extern "C"

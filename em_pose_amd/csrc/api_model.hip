@@ -1,0 +1,794 @@
+// C ABI (include/empose_hip.h), the LGD model: weight packing, empose_model_create, the SMPL / update-net / LGD
+// workspaces and the launch sequence of the LGD loop; the stand-alone SMPL and update-net entry points.
+#include "api_internal.h"
+
+#include <cmath>
+
+using namespace empose;
+using namespace empose::api;
+
+namespace {
+
+// Packs every index/weight table the chain kernel needs into one array of 32-bit words (staged into LDS per block).
+int build_chain_blob(const empose_smpl_desc& s, std::vector<uint32_t>& blob, ChainTabs& off, int* n_chunks) {
+  auto put_i = [&](const std::vector<int>& v) { int o = (int)blob.size(); for (int x : v) blob.push_back((uint32_t)x); return o; };
+  auto put_f = [&](const float* p, size_t n) {
+    int o = (int)blob.size();
+    for (size_t i = 0; i < n; ++i) { uint32_t u; std::memcpy(&u, p + i, 4); blob.push_back(u); }
+    return o;
+  };
+  std::vector<int> path_mask(22, 0), sub_mask(22, 0), parents(s.parents, s.parents + 22);
+  for (int j = 0; j < 22; ++j) {
+    for (int q = s.path_ptr[j]; q < s.path_ptr[j + 1]; ++q) path_mask[j] |= 1 << s.path[q];
+    for (int q = s.sub_ptr[j]; q < s.sub_ptr[j + 1]; ++q) sub_mask[j] |= 1 << s.sub[q];
+  }
+  off.path_mask = put_i(path_mask);
+  off.sub_mask = put_i(sub_mask);
+  off.parents = put_i(parents);
+  {
+    // depth-first pre-order: every subtree is a contiguous range, so a subtree sum is a difference of prefix sums
+    std::vector<int> pos(22, 0), size(22, 0), stack, order;
+    stack.push_back(0);
+    while (!stack.empty()) {
+      const int j = stack.back();
+      stack.pop_back();
+      pos[j] = (int)order.size();
+      order.push_back(j);
+      for (int c = 21; c >= 1; --c)
+        if (parents[c] == j) stack.push_back(c);
+    }
+    for (int j = 0; j < 22; ++j) size[j] = __builtin_popcount((unsigned)sub_mask[j]);
+    off.dfs_pos = put_i(pos);
+    off.sub_size = put_i(size);
+  }
+  off.skin_idx = put_i(std::vector<int>(s.skin_idx, s.skin_idx + (size_t)s.nv * s.kb));
+  off.skin_w = put_f(s.skin_w, (size_t)s.nv * s.kb);
+  // per-bone (vertex, weight) lists cut into chunks of CHAIN_CHUNK pairs, each chunk padded with (vertex 0, weight 0)
+  std::vector<int> cb, cbeg, bcp(23, 0), pv;
+  std::vector<float> pw;
+  for (int b = 0; b < 22; ++b) {
+    bcp[b] = (int)cb.size();
+    for (int q = s.bone_ptr[b]; q < s.bone_ptr[b + 1]; q += CHAIN_CHUNK) {
+      cb.push_back(b);
+      cbeg.push_back((int)pv.size());
+      for (int k = 0; k < CHAIN_CHUNK; ++k) {
+        const bool in = q + k < s.bone_ptr[b + 1];
+        pv.push_back(in ? s.bone_vert[q + k] : 0);
+        pw.push_back(in ? s.bone_w[q + k] : 0.f);
+      }
+    }
+  }
+  bcp[22] = (int)cb.size();
+  *n_chunks = (int)cb.size();
+  off.chunk_bone = put_i(cb); off.chunk_beg = put_i(cbeg);
+  off.bone_chunk_ptr = put_i(bcp);
+  off.bone_vert = put_i(pv);
+  off.bone_w = put_f(pw.data(), pw.size());
+  off.s_center = put_i(std::vector<int>(s.s_center, s.s_center + 12));
+  off.s_helper = put_i(std::vector<int>(s.s_helper, s.s_helper + 12));
+  off.s_deg = put_i(std::vector<int>(s.s_deg, s.s_deg + 12));
+  {
+    std::vector<int> faces(s.s_faces, s.s_faces + (size_t)12 * s.max_deg * 3);
+    for (int m = 0; m < 12; ++m)
+      for (int k = s.s_deg[m]; k < s.max_deg; ++k)
+        for (int c = 0; c < 3; ++c) faces[((size_t)m * s.max_deg + k) * 3 + c] = s.s_center[m];
+    off.s_faces = put_i(faces);
+  }
+  // Incidence lists of P4d as packed words (see the kernel): offsets are relative to the frame's LDS record.
+  const ChainLds lay = chain_layout(s.nv, s.ncp, s.max_deg, *n_chunks);
+  if (lay.total >= (1 << 13)) return fail(EMPOSE_EINVAL, "sensor sub-mesh too large for the packed incidence words");
+  if (s.max_deg > 64) return fail(EMPOSE_EINVAL, "more than 64 faces around a sensor vertex");
+  auto pack = [](int a, int b, int use_b, int neg) {
+    return (int)((uint32_t)a | ((uint32_t)b << 13) | ((uint32_t)use_b << 26) | ((uint32_t)neg << 27));
+  };
+  std::vector<int> inc_ptr(s.nv + 1, 0), inc_code;
+  for (int v = 0; v < s.nv; ++v) {
+    inc_ptr[v] = (int)inc_code.size();
+    for (int m = 0; m < 12; ++m) {
+      if (s.s_center[m] == v) { const int o = lay.scr + m * 9 + 3; inc_code.push_back(pack(o, o, 0, 0)); }
+      if (s.s_helper[m] == v) { const int o = lay.scr + m * 9 + 6; inc_code.push_back(pack(o, o, 0, 0)); }
+      for (int k = 0; k < s.s_deg[m]; ++k)
+        for (int c = 0; c < 3; ++c)
+          if (s.s_faces[((size_t)m * s.max_deg + k) * 3 + c] == v) {
+            const int fg = lay.fg + (m * s.max_deg + k) * 6;
+            if (c == 0) inc_code.push_back(pack(fg, fg + 3, 1, 1));       // v0: -(d e1 + d e2)
+            else if (c == 1) inc_code.push_back(pack(fg, fg, 0, 0));      // v1: + d e1
+            else inc_code.push_back(pack(fg + 3, fg + 3, 0, 0));          // v2: + d e2
+          }
+    }
+    while ((inc_code.size() - (size_t)inc_ptr[v]) % 4 != 0) inc_code.push_back((int)(1u << 28));   // null
+  }
+  inc_ptr[s.nv] = (int)inc_code.size();
+  off.inc_ptr = put_i(inc_ptr);
+  off.inc_code = put_i(inc_code);
+  while (blob.size() % 4 != 0) blob.push_back(0u);   // staged into LDS in 16-byte pieces
+  off.total = (int)blob.size();
+  return EMPOSE_OK;
+}
+
+int pack_dense(std::vector<void*>& allocs, const empose_dense_desc& d, Dense* out) {
+  if (d.in_dim <= 0 || d.out_dim <= 0 || !d.weight) return fail(EMPOSE_EINVAL, "dense layer: bad dims / null weight");
+  if (d.in_dim % 4 != 0) return fail(EMPOSE_EINVAL, "dense layer: in_dim %d must be a multiple of 4", d.in_dim);
+  out->in_dim = d.in_dim;
+  out->out_dim = d.out_dim;
+  TRY(upload(allocs, d.weight, (size_t)d.in_dim * d.out_dim, &out->w));
+  std::vector<float> shift(d.out_dim, 0.f), scale;
+  if (d.bn_weight) {
+    if (!d.bn_bias || !d.bn_mean || !d.bn_var) return fail(EMPOSE_EINVAL, "dense layer: incomplete batch norm");
+    scale.resize(d.out_dim);
+    for (int n = 0; n < d.out_dim; ++n) {
+      const double s = (double)d.bn_weight[n] / std::sqrt((double)d.bn_var[n] + (double)d.bn_eps);
+      const double b = d.bias ? (double)d.bias[n] : 0.0;
+      scale[n] = (float)s;
+      shift[n] = (float)((b - (double)d.bn_mean[n]) * s + (double)d.bn_bias[n]);
+    }
+    TRY(upload(allocs, scale.data(), scale.size(), &out->scale));
+  } else if (d.bias) {
+    for (int n = 0; n < d.out_dim; ++n) shift[n] = d.bias[n];
+  }
+  TRY(upload(allocs, shift.data(), shift.size(), &out->shift));
+  out->act = d.has_prelu ? 1 : 0;
+  out->slope = d.prelu;
+  return EMPOSE_OK;
+}
+
+// Weights in the order the matrix cores consume them (mlp_fused.hip): for every k-group of 8 and every 32-column tile,
+// lane (n = lane & 31, half = lane >> 5) owns W[tile * 32 + n][kg * 8 + half * 4 .. + 3]; columns / k past the matrix
+// are zero, so a wave's fragment is one coalesced 1 KB read and ragged K needs no masking on this operand.
+int pack_fragments_raw(std::vector<void*>& allocs, const float* weight, int N, int K, float** out) {
+  const int KG = (K + 7) / 8, NT = (N + 31) / 32;
+  const int KG4 = (KG + 3) & ~3;   // the kernels walk four k-groups per iteration
+  std::vector<float> buf((size_t)KG4 * NT * 256, 0.f);
+  for (int kg = 0; kg < KG; ++kg)
+    for (int nt = 0; nt < NT; ++nt)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int n = nt * 32 + (lane & 31);
+        if (n >= N) continue;
+        for (int e = 0; e < 4; ++e) {
+          const int k = kg * 8 + (lane >> 5) * 4 + e;
+          if (k < K) buf[(((size_t)kg * NT + nt) * 64 + lane) * 4 + e] = weight[(size_t)n * K + k];
+        }
+      }
+  return upload(allocs, buf.data(), buf.size(), out);
+}
+
+// The same weights as three bf16 pieces each (split3) in the order v_mfma_f32_32x32x16_bf16 consumes them
+// (mlp_fused_x3.hip): for every k-step of 16, every 32-column tile and every piece one 1 KB wave fragment -- lane
+// (n = lane & 31, half = lane >> 5) owns piece[tile * 32 + n][ks * 16 + half * 8 .. + 7]; k-steps padded with zeros to a
+// multiple of four (the kernel walks quads).  6 bytes per weight.
+int pack_fragments_x3_raw(std::vector<void*>& allocs, const float* weight, int N, int K, float** out) {
+  const int KS = (K + 15) / 16, NT = (N + 31) / 32;
+  const int KS4 = (KS + 3) & ~3;
+  std::vector<unsigned short> buf((size_t)KS4 * NT * 3 * 512, 0);
+  for (int ks = 0; ks < KS; ++ks)
+    for (int nt = 0; nt < NT; ++nt)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int n = nt * 32 + (lane & 31);
+        if (n >= N) continue;
+        for (int e = 0; e < 8; ++e) {
+          const int k = ks * 16 + (lane >> 5) * 8 + e;
+          if (k >= K) continue;
+          unsigned short p[3];
+          split3(weight[(size_t)n * K + k], p);
+          const size_t at = (((size_t)ks * NT + nt) * 3) * 512 + (size_t)lane * 8 + e;
+          buf[at] = p[0]; buf[at + 512] = p[1]; buf[at + 1024] = p[2];
+        }
+      }
+  return upload_bf16(allocs, buf, out);
+}
+
+int pack_fragments(std::vector<void*>& allocs, const empose_dense_desc& d, Dense* out) {
+  TRY(pack_fragments_x3_raw(allocs, d.weight, d.out_dim, d.in_dim, &out->wp3));
+  return pack_fragments_raw(allocs, d.weight, d.out_dim, d.in_dim, &out->wp);
+}
+
+int pack_mlp(std::vector<void*>& allocs, const empose_mlp_desc& d, Mlp* out, int* hidden_max, int* any_skip) {
+  out->n_layers = d.n_layers;
+  out->skip = d.skip;
+  if (d.n_layers == 0) return EMPOSE_OK;
+  if (d.skip) *any_skip = 1;
+  if (d.n_layers < 2 || d.n_layers > EMPOSE_MAX_DENSE || (d.n_layers % 2) != 0)
+    return fail(EMPOSE_EINVAL, "mlp: n_layers=%d unsupported", d.n_layers);
+  for (int i = 0; i < d.n_layers; ++i) {
+    TRY(pack_dense(allocs, d.layers[i], &out->layers[i]));
+    TRY(pack_fragments(allocs, d.layers[i], &out->layers[i]));
+    if (i > 0 && d.layers[i].in_dim != d.layers[i - 1].out_dim) return fail(EMPOSE_EINVAL, "mlp: layer dims do not chain");
+    if (i + 1 < d.n_layers && d.layers[i].out_dim > *hidden_max) *hidden_max = d.layers[i].out_dim;
+  }
+  return EMPOSE_OK;
+}
+
+// ---- workspace layouts ------------------------------------------------------------------------------------------
+struct SmplWs {
+  float *rot, *feat, *out, *d_out, *d_feat, *d_rot;
+  float* theta_t;   // theta in tile layout for the frame-per-lane kernel
+  float* tgt_t;     // targets in tile layout (stand-alone entry points; the LGD loop has its own copy)
+};
+constexpr int D_FEAT_T_COLS = 224;   // the 200 feature cotangents in tile layout, whole 32-column tiles
+SmplWs carve_smpl(Carver& c, const empose_model* m, int T) {
+  // Either path fits: row-major [T][cols] for chain_sensors_kernel, tile layout [ceil(T / 64)][cols][64] for
+  // smpl_tile_kernel (which does not use `rot`: it evaluates Rodrigues itself).
+  SmplWs w;
+  const size_t Tp = (size_t)(T + TL_FR - 1) / TL_FR * TL_FR;
+  const size_t ncp = m->tab.ncp > m->ncp2 ? m->tab.ncp : m->ncp2;
+  w.rot = c.f((size_t)T * 198);
+  w.feat = c.f((size_t)T * 200);
+  w.out = c.f(Tp * ncp);
+  w.d_out = c.f(Tp * ncp);
+  w.d_feat = c.f(Tp * D_FEAT_T_COLS);
+  w.d_rot = c.f(Tp * 198);
+  w.theta_t = c.f(Tp * 66);
+  w.tgt_t = c.f(Tp * 144);
+  return w;
+}
+// The frame-per-lane path pays once its 64-frame workgroups fill the 256 CUs (one per CU, 152 KB of LDS each): from
+// 16384 frames on.  Measured at 8192 frames (the training step at 256 windows): 2 % slower than the general kernel.
+// Option "smpl_tile": 0 never, 1 by size, 2 always (tests).
+bool use_tile_path(const empose_model* m, int T, const float* cot_joints = nullptr) {
+  const int opt = options().smpl_tile;
+  return m->tile_ok && opt != 0 && !cot_joints && (opt == 2 || T >= 16384);
+}
+
+struct UpdWs {
+  float* buf[3];  // [2 nets][T][hidden_max] each; buf[2] only when a net uses skip connections
+};
+UpdWs carve_upd(Carver& c, const empose_model* m, int T) {
+  UpdWs w;
+  w.buf[0] = c.f((size_t)2 * T * m->hidden_max);
+  w.buf[1] = c.f((size_t)2 * T * m->hidden_max);
+  w.buf[2] = m->any_skip ? c.f((size_t)2 * T * m->hidden_max) : nullptr;
+  return w;
+}
+
+GemmProb linear_prob(const float* A, int lda, const Dense& d, float* C, int ldc, int M) {
+  GemmProb p;
+  p.A = A; p.lda = lda; p.W = d.w; p.ldw = d.in_dim; p.C = C; p.ldc = ldc;
+  p.M = M; p.N = d.out_dim; p.K = d.in_dim;
+  p.scale = d.scale; p.shift = d.shift; p.resid = nullptr; p.ldr = 0; p.act = d.act; p.slope = d.slope;
+  return p;
+}
+
+// Runs one or two MLPs that share the input x (the update nets / the init nets) layer by layer, both nets per launch.
+// Hidden blocks are layer pairs (1,2), (3,4), ...; with skip connections the block input is added to the block
+// output (reference layers.py:35-43), which needs the block input kept alive in a third buffer.
+int run_mlps(const Mlp* nets[2], int n_nets, float* outs[2], const int out_ld[2], const float* x, int ldx, int T,
+             const UpdWs& ws, int hidden_max, hipStream_t stream, bool init_net = false) {
+  const int L = nets[0]->n_layers;
+  for (int i = 1; i < n_nets; ++i)
+    if (nets[i]->n_layers != L) return fail(EMPOSE_EINVAL, "paired MLPs must have the same depth");
+
+  // Large batches: every layer of both nets in ONE launch (mlp_fused.hip); a workgroup keeps 128 rows through all the
+  // layers. Needs enough row panels to fill the chip and layers no wider than the four 128-column waves.
+  {
+    bool ok = options().mlp_fused != 0 && L <= FUSED_MAX_LAYERS && (long)((T + 63) / 64) * n_nets >= 256;
+    for (int i = 0; i < n_nets && ok; ++i) {
+      if (nets[i]->skip || nets[i]->layers[0].in_dim > FUSED_MAX_WIDTH) ok = false;   // no room for a block input
+      for (int l = 0; l < L; ++l) {
+        const Dense& d = nets[i]->layers[l];
+        if (d.out_dim > FUSED_MAX_WIDTH || d.act > 1) ok = false;
+      }
+    }
+    if (ok) {
+      // fp32 products from three bf16 pieces per operand on the bf16 matrix path (mlp_fused_x3.hip; fp32-equivalent, 2.7
+      // times the fp32 instruction's rate): needs every hidden width to be whole quads of k-steps of the next layer
+      bool x3 = options().mlp_x3 != 0;
+      for (int i = 0; i < n_nets && x3; ++i)
+        for (int l = 0; l + 1 < L; ++l)
+          if (nets[i]->layers[l].out_dim % 64 != 0 || !nets[i]->layers[l].wp3) x3 = false;
+      FusedMlpArgs fa;
+      fa.count = n_nets; fa.M = T;
+      for (int i = 0; i < n_nets; ++i) {
+        FusedNet& fn = fa.net[i];
+        fn.x = x; fn.ldx = ldx; fn.out = outs[i]; fn.ld_out = out_ld[i];
+        fn.n_layers = L;   // the activations stay in LDS: no scratch
+        for (int l = 0; l < L; ++l) {
+          const Dense& d = nets[i]->layers[l];
+          FusedLayer& fl = fn.layer[l];
+          fl.W = x3 ? d.wp3 : d.wp; fl.K = d.in_dim; fl.N = d.out_dim; fl.scale = d.scale; fl.shift = d.shift;
+          fl.slope = d.slope; fl.act = d.act;
+        }
+      }
+      prof_mark(init_net ? P_INIT_MLP : P_MLP_FUSED, stream);
+      HIP_CHECK(x3 ? launch_mlp_fused_x3(fa, stream) : launch_mlp_fused(fa, stream), "fused mlp launch");
+      prof_mark(P_END, stream);   // close the dominant kernel's interval at its completion, not at the next launch
+      return EMPOSE_OK;
+    }
+  }
+
+  int cur[2] = {-1, -1}, block_in[2] = {-1, -1};
+  for (int l = 0; l < L; ++l) {
+    GemmBatch b;
+    b.count = n_nets;
+    int nxt[2] = {-1, -1};
+    for (int i = 0; i < n_nets; ++i) {
+      const Dense& d = nets[i]->layers[l];
+      auto buf = [&](int k) { return ws.buf[k] + (size_t)i * T * hidden_max; };
+      const float* in = (l == 0) ? x : buf(cur[i]);
+      const int ld_in = (l == 0) ? ldx : nets[i]->layers[l - 1].out_dim;
+      const bool block_first = (l >= 1) && (l % 2 == 1) && (l < L - 1);
+      const bool block_last = (l >= 2) && (l % 2 == 0) && (l < L - 1);
+      if (block_first) block_in[i] = cur[i];
+      float* out;
+      int ld_out;
+      if (l == L - 1) {
+        out = outs[i];
+        ld_out = out_ld[i];
+      } else {
+        int k = 0;
+        while (k == cur[i] || (nets[i]->skip && k == block_in[i])) ++k;
+        if (k > 2 || !ws.buf[k]) return fail(EMPOSE_EINVAL, "internal: MLP scratch buffers exhausted");
+        nxt[i] = k;
+        out = buf(k);
+        ld_out = d.out_dim;
+      }
+      b.p[i] = linear_prob(in, ld_in, d, out, ld_out, T);
+      if (block_last && nets[i]->skip) {
+        b.p[i].resid = buf(block_in[i]);
+        b.p[i].ldr = d.out_dim;
+      }
+    }
+    b.role = (!init_net && l > 0 && l < L - 1) ? 1 : 0;
+    prof_mark(init_net ? P_INIT_MLP : (l == 0 ? P_MLP_IN : (l == L - 1 ? P_MLP_OUT : P_MLP_HIDDEN)), stream);
+    HIP_CHECK(launch_gemm(b, stream), "gemm launch");
+    for (int i = 0; i < n_nets; ++i) cur[i] = nxt[i];
+  }
+  return EMPOSE_OK;
+}
+
+// Where the residual gradient of one SMPL evaluation goes (null: no gradient wanted).
+struct GradOut {
+  float* g_theta; int ld_g; float* g_beta; int ld_gb;
+  float* trace_g_theta; float* trace_g_beta;
+};
+// One SMPL evaluation: pose / shape update + feature row (fa: what to update and where the copies go; rot / feat /
+// theta_t are filled in here), blend GEMM, chain + skinning + sensors (+ reverse), transposed GEMM, Rodrigues reverse.
+// On the frame-per-lane path the first and the last step ride on the GEMMs (option "smpl_fuse", default on).
+int run_smpl_eval(const empose_model* m, int T, int F, const SmplWs& ws, FeatArgs fa, const float* offset_r,
+                  const float* offset_t, const float* tgt, int ld_tgt, const float* frame_scale, float* pos, float* ori,
+                  float* joints, float* pos2, float* ori2, float* joints2, hipStream_t stream,
+                  const float* cot_pos = nullptr, const float* cot_ori = nullptr, const float* cot_joints = nullptr,
+                  const float* tgt_t = nullptr, const GradOut* go = nullptr) {
+  const bool bwd = tgt || cot_pos;
+  const bool tile = use_tile_path(m, T, cot_joints);
+  const bool fuse = tile && options().smpl_fuse != 0;
+  fa.rot = tile ? nullptr : ws.rot; fa.feat = ws.feat; fa.theta_t = tile ? ws.theta_t : nullptr;
+  fa.T = T; fa.F = F; fa.rod_conv = m->rod_conv;
+  if (bwd && !go) return fail(EMPOSE_EINVAL, "gradient outputs missing");
+  if (!fuse) {
+    prof_mark(P_UPDATE_FEAT, stream);
+    HIP_CHECK(launch_update_feat(fa, stream), "update_feat kernel");
+  }
+  if (tile) {
+    // frame-per-lane path: blend GEMM -> tile layout -> smpl_tile_kernel -> tile layout -> transposed GEMM
+    prof_mark(P_BLEND_GEMM, stream);
+    const bool rx3 = options().rows_x3 != 0 && m->wc2_frag3 && m->wc2t_frag3;
+    HIP_CHECK(fuse ? launch_blend_feat_gemm(fa, rx3 ? m->wc2_frag3 : m->wc2_frag, ws.out, m->ncp2, m->ncp2, rx3, stream)
+                   : launch_gemm_rows_t(ws.feat, 200, false, m->wc2_frag, ws.out, m->ncp2, T, m->ncp2, 200, stream),
+              "blend gemm (tile)");
+    TileArgs a;
+    a.tab = m->tile_tab; a.theta = fa.theta; a.ld_theta = fa.ld_theta; a.out_t = ws.out;
+    a.theta_t = ws.theta_t; a.tgt_t = tgt ? tgt_t : nullptr;
+    a.offset_r = offset_r; a.offset_t = offset_t; a.tgt = tgt; a.ld_tgt = ld_tgt; a.frame_scale = frame_scale;
+    a.n_markers = m->n_markers;
+    for (int i = 0; i < 12; ++i) a.used_slot[i] = m->used_slot[i];
+    a.pos = pos; a.ori = ori; a.joints = joints; a.pos2 = pos2; a.ori2 = ori2; a.joints2 = joints2;
+    a.d_out_t = ws.d_out; a.d_rot_t = ws.d_rot; a.T = T; a.F = F; a.rod_conv = m->rod_conv;
+    a.cot_pos = cot_pos; a.cot_ori = cot_ori;
+    prof_mark(P_CHAIN, stream);
+    HIP_CHECK(launch_smpl_tile(a, bwd, m->tile_nloc, m->tile_nbl, stream), "smpl tile kernel");
+    if (bwd) {
+      RodBwdTArgs ra;
+      ra.theta = fa.theta; ra.ld_theta = fa.ld_theta; ra.theta_t = ws.theta_t; ra.d_rot_t = ws.d_rot;
+      ra.d_feat_t = ws.d_feat; ra.ld_feat_t = D_FEAT_T_COLS;
+      ra.g_theta = go->g_theta; ra.ld_g = go->ld_g; ra.g_beta = go->g_beta; ra.ld_gb = go->ld_gb;
+      ra.trace_g_theta = go->trace_g_theta; ra.trace_g_beta = go->trace_g_beta;
+      ra.T = T; ra.rod_conv = m->rod_conv;
+      prof_mark(P_BLEND_T_GEMM, stream);
+      if (fuse) {
+        HIP_CHECK(launch_blend_t_gemm_rod(ws.d_out, m->ncp2, rx3 ? m->wc2t_frag3 : m->wc2t_frag, m->ncp2, ra, rx3, stream), "blend^T gemm + rodrigues_bwd (tile)");
+        return EMPOSE_OK;
+      }
+      HIP_CHECK(launch_gemm_rows_t(ws.d_out, m->ncp2, true, m->wc2t_frag, ws.d_feat, D_FEAT_T_COLS, T, 200, m->ncp2, stream), "blend^T gemm (tile)");
+      prof_mark(P_ROD_BWD, stream);
+      HIP_CHECK(launch_rodrigues_bwd_t(ra, stream), "rodrigues_bwd (tile) kernel");
+    }
+    return EMPOSE_OK;
+  }
+  GemmBatch b;
+  b.count = 1;
+  GemmProb& p = b.p[0];
+  p.A = ws.feat; p.lda = 200; p.W = m->tab.wc; p.ldw = 200; p.C = ws.out; p.ldc = m->tab.ncp;
+  p.M = T; p.N = m->tab.ncp; p.K = 200;
+  p.scale = nullptr; p.shift = nullptr; p.resid = nullptr; p.ldr = 0; p.act = 0; p.slope = 0.f;
+  prof_mark(P_BLEND_GEMM, stream);
+  HIP_CHECK((m->wc_frag && gemm_rows_applicable(T, m->tab.ncp, 200))
+                ? launch_gemm_rows(ws.feat, 200, m->wc_frag, ws.out, m->tab.ncp, T, m->tab.ncp, 200, stream)
+                : launch_gemm(b, stream), "blend gemm");
+  ChainArgs c;
+  c.tab = m->tab;
+  c.rot = ws.rot; c.out = ws.out; c.offset_r = offset_r; c.offset_t = offset_t;
+  c.tgt = tgt; c.ld_tgt = ld_tgt; c.frame_scale = frame_scale;
+  c.n_markers = m->n_markers;
+  for (int i = 0; i < 12; ++i) c.used_slot[i] = m->used_slot[i];
+  c.pos = pos; c.ori = ori; c.joints = joints; c.pos2 = pos2; c.ori2 = ori2; c.joints2 = joints2;
+  c.d_out = ws.d_out; c.d_rot = ws.d_rot; c.T = T; c.F = F;
+  c.cot_pos = cot_pos; c.cot_ori = cot_ori; c.cot_joints = cot_joints;
+  prof_mark(P_CHAIN, stream);
+  HIP_CHECK(launch_chain_sensors(c, stream), "chain kernel");
+  if (tgt || cot_pos) {
+    p.A = ws.d_out; p.lda = m->tab.ncp; p.W = m->tab.wct; p.ldw = m->tab.ncp; p.C = ws.d_feat; p.ldc = 200;
+    p.M = T; p.N = 200; p.K = m->tab.ncp;
+    prof_mark(P_BLEND_T_GEMM, stream);
+    HIP_CHECK((m->wct_frag && gemm_rows_applicable(T, 200, m->tab.ncp))
+                  ? launch_gemm_rows(ws.d_out, m->tab.ncp, m->wct_frag, ws.d_feat, 200, T, 200, m->tab.ncp, stream)
+                  : launch_gemm(b, stream), "blend^T gemm");
+    RodBwdArgs ra;
+    ra.theta = fa.theta; ra.ld_theta = fa.ld_theta; ra.d_rot = ws.d_rot; ra.d_feat = ws.d_feat;
+    ra.g_theta = go->g_theta; ra.ld_g = go->ld_g; ra.g_beta = go->g_beta; ra.ld_gb = go->ld_gb;
+    ra.trace_g_theta = go->trace_g_theta; ra.trace_g_beta = go->trace_g_beta; ra.T = T; ra.rod_conv = m->rod_conv;
+    prof_mark(P_ROD_BWD, stream);
+    HIP_CHECK(launch_rodrigues_bwd(ra, stream), "rodrigues_bwd kernel");
+  }
+  return EMPOSE_OK;
+}
+
+struct LgdWs {
+  float *x, *scale, *d_pose, *d_shape, *pos, *ori, *joints;
+  float* x_t;   // the sensor columns of x in tile layout (targets of the frame-per-lane kernel)
+  SmplWs smpl;
+  UpdWs upd;
+  LstmWs lstm;
+  float* y;
+};
+LgdWs carve_lgd(Carver& c, const empose_model* m, int B, int F) {
+  LgdWs w;
+  const size_t T = (size_t)B * F;
+  w.x = c.f(T * m->d_x);
+  w.scale = c.f(T);
+  w.d_pose = c.f(T * 66);
+  w.d_shape = c.f(T * 10);
+  w.pos = c.f(T * 36);
+  w.ori = c.f(T * 108);
+  w.joints = c.f(T * 66);
+  w.x_t = c.f((T + TL_FR - 1) / TL_FR * TL_FR * m->d_in);
+  w.smpl = carve_smpl(c, m, (int)T);
+  w.upd = carve_upd(c, m, (int)T);
+  if (m->rnn_init) {
+    w.lstm = carve_lstm_of(c, m->rnn, B, F);
+    w.y = c.f(T * m->rnn.H);
+  } else {
+    w.y = nullptr;
+  }
+  return w;
+}
+
+}  // namespace
+
+extern "C" {
+
+void empose_model_destroy(empose_model_t* model) {
+  if (!model) return;
+  for (void* p : model->allocs) (void)hipFree(p);
+  delete model;
+}
+
+int empose_model_create(const empose_model_desc* d, empose_model_t** out) {
+  if (!d || !out) return fail(EMPOSE_EINVAL, "null argument");
+  *out = nullptr;
+  const empose_smpl_desc& s = d->smpl;
+  if (s.n_sensors != EMPOSE_N_SENSORS) return fail(EMPOSE_EINVAL, "n_sensors must be 12");
+  if (s.nv <= 0 || s.ncp % 4 != 0 || s.j_off < s.nv * 3 || s.j_off + 66 > s.ncp || s.kb <= 0 || s.max_deg <= 0)
+    return fail(EMPOSE_EINVAL, "inconsistent SMPL table sizes");
+  if (d->n_markers != 6 && d->n_markers != 12) return fail(EMPOSE_EINVAL, "n_markers must be 6 or 12");
+  if (d->n_iterations < 0) return fail(EMPOSE_EINVAL, "n_iterations < 0");
+  if (s.rodrigues != EMPOSE_RODRIGUES_SMPLX && s.rodrigues != EMPOSE_RODRIGUES_SO3)
+    return fail(EMPOSE_EINVAL, "unknown Rodrigues convention %d", s.rodrigues);
+  empose_model* m = new empose_model();
+  m->rod_conv = s.rodrigues;
+  auto bail = [&](int rc) { empose_model_destroy(m); return rc; };
+#define MTRY(expr) do { int rc_ = (expr); if (rc_ != EMPOSE_OK) return bail(rc_); } while (0)
+  SmplTables& t = m->tab;
+  t.n_sensors = s.n_sensors; t.nv = s.nv; t.j_off = s.j_off; t.ncp = s.ncp; t.kb = s.kb; t.max_deg = s.max_deg;
+  float* fp; int* ip;
+  MTRY(upload(m->allocs, s.wc, (size_t)s.ncp * 200, &fp)); t.wc = fp;
+  MTRY(upload(m->allocs, s.wct, (size_t)s.ncp * 200, &fp)); t.wct = fp;
+  MTRY(pack_fragments_raw(m->allocs, s.wc, s.ncp, 200, &m->wc_frag));     // the same two matrices in MFMA fragment order
+  MTRY(pack_fragments_raw(m->allocs, s.wct, 200, s.ncp, &m->wct_frag));
+  MTRY(upload(m->allocs, s.parents, 22, &ip)); t.parents = ip;
+  MTRY(upload(m->allocs, s.skin_idx, (size_t)s.nv * s.kb, &ip)); t.skin_idx = ip;
+  MTRY(upload(m->allocs, s.skin_w, (size_t)s.nv * s.kb, &fp)); t.skin_w = fp;
+  if (!s.bone_ptr || !s.path_ptr || !s.sub_ptr) return bail(fail(EMPOSE_EINVAL, "null CSR pointer"));
+  MTRY(upload(m->allocs, s.bone_ptr, 23, &ip)); t.bone_ptr = ip;
+  MTRY(upload(m->allocs, s.bone_vert, (size_t)s.bone_ptr[22], &ip)); t.bone_vert = ip;
+  MTRY(upload(m->allocs, s.bone_w, (size_t)s.bone_ptr[22], &fp)); t.bone_w = fp;
+  MTRY(upload(m->allocs, s.s_center, 12, &ip)); t.s_center = ip;
+  MTRY(upload(m->allocs, s.s_helper, 12, &ip)); t.s_helper = ip;
+  MTRY(upload(m->allocs, s.s_deg, 12, &ip)); t.s_deg = ip;
+  MTRY(upload(m->allocs, s.s_faces, (size_t)12 * s.max_deg * 3, &ip)); t.s_faces = ip;
+  MTRY(upload(m->allocs, s.path_ptr, 23, &ip)); t.path_ptr = ip;
+  MTRY(upload(m->allocs, s.path, (size_t)s.path_ptr[22], &ip)); t.path = ip;
+  MTRY(upload(m->allocs, s.sub_ptr, 23, &ip)); t.sub_ptr = ip;
+  MTRY(upload(m->allocs, s.sub, (size_t)s.sub_ptr[22], &ip)); t.sub = ip;
+  {
+    for (int i = 0; i < 12; ++i)
+      if (s.s_deg[i] < 1 || s.s_deg[i] > s.max_deg) return bail(fail(EMPOSE_EINVAL, "sensor degree out of range"));
+    std::vector<uint32_t> blob;
+    MTRY(build_chain_blob(s, blob, t.off, &t.n_chunks));
+    uint32_t* bp;
+    MTRY(upload(m->allocs, blob.data(), blob.size(), &bp));
+    t.blob = bp;
+  }
+  {
+    // frame-per-lane path: only for patches that are closed fans of at most TL_NR faces over at most TL_NBL bones
+    // (closed manifold meshes; anything else keeps chain_sensors_kernel)
+    TileTables tt;
+    std::vector<float> wc2;
+    if (s.n_sensors == 12 && build_tile_tables(s.nv, s.kb, s.max_deg, s.j_off, s.wc, s.parents, s.skin_idx, s.skin_w,
+                                               s.s_center, s.s_helper, s.s_deg, s.s_faces, &tt, &wc2)) {
+      std::vector<float> wc2t((size_t)200 * tt.ncp2);
+      for (int r = 0; r < tt.ncp2; ++r)
+        for (int k = 0; k < 200; ++k) wc2t[(size_t)k * tt.ncp2 + r] = wc2[(size_t)r * 200 + k];
+      MTRY(upload(m->allocs, &tt, 1, &m->tile_tab));
+      MTRY(pack_fragments_raw(m->allocs, wc2.data(), tt.ncp2, 200, &m->wc2_frag));
+      MTRY(pack_fragments_raw(m->allocs, wc2t.data(), 200, tt.ncp2, &m->wc2t_frag));
+      MTRY(pack_fragments_x3_raw(m->allocs, wc2.data(), tt.ncp2, 200, &m->wc2_frag3));
+      MTRY(pack_fragments_x3_raw(m->allocs, wc2t.data(), 200, tt.ncp2, &m->wc2t_frag3));
+      m->ncp2 = tt.ncp2; m->tile_nloc = tt.nloc; m->tile_nbl = tt.nbl;
+      m->tile_ok = tt.ncp2 <= 320;   // the widest tile gemm_rows_t_kernel covers
+    }
+  }
+
+  m->n_markers = d->n_markers;
+  for (int i = 0; i < 12; ++i) { m->marker_idx[i] = 0; m->used_slot[i] = -1; }
+  for (int i = 0; i < d->n_markers; ++i) {
+    const int v = d->marker_idx[i];
+    if (v < 0 || v >= 12) return bail(fail(EMPOSE_EINVAL, "marker_idx out of range"));
+    m->marker_idx[i] = v;
+    m->used_slot[v] = i;
+  }
+  m->N = d->n_iterations; m->step = d->step_size; m->shape_avg = d->shape_avg; m->use_gradient = d->use_gradient;
+  m->rnn_init = d->rnn_init;
+  m->d_in = d->n_markers * 12;
+  m->d_x = m->d_in + 76 + (d->use_gradient ? 76 : 0);
+
+  if (d->rnn_init) {
+    const empose_lstm_desc& r = d->rnn;
+    if (r.num_layers > 4 || r.input_size != m->d_in) return bail(fail(EMPOSE_EINVAL, "unsupported LSTM configuration"));
+    MTRY(pack_lstm(m->allocs, r, 1, r.w_ih, r.w_hh, r.b_ih, r.b_hh, &m->rnn));
+    MTRY(pack_dense(m->allocs, d->pose_head, &m->pose_head));
+    MTRY(pack_dense(m->allocs, d->shape_head, &m->shape_head));
+    if (d->pose_head.out_dim == 66 && d->shape_head.out_dim == 10 && d->pose_head.in_dim == d->shape_head.in_dim &&
+        !d->pose_head.bn_weight && !d->shape_head.bn_weight && !d->pose_head.has_prelu && !d->shape_head.has_prelu) {
+      const int K = d->pose_head.in_dim;
+      std::vector<float> wst((size_t)76 * K), bst(76, 0.f);
+      std::memcpy(wst.data(), d->pose_head.weight, (size_t)66 * K * sizeof(float));
+      std::memcpy(wst.data() + (size_t)66 * K, d->shape_head.weight, (size_t)10 * K * sizeof(float));
+      for (int n = 0; n < 66; ++n) bst[n] = d->pose_head.bias ? d->pose_head.bias[n] : 0.f;
+      for (int n = 0; n < 10; ++n) bst[66 + n] = d->shape_head.bias ? d->shape_head.bias[n] : 0.f;
+      MTRY(pack_fragments_raw(m->allocs, wst.data(), 76, K, &m->heads_frag));
+      MTRY(pack_fragments_x3_raw(m->allocs, wst.data(), 76, K, &m->heads_frag3));
+      MTRY(upload(m->allocs, bst.data(), bst.size(), &m->heads_bias));
+    }
+    if (m->pose_head.out_dim != 66 || m->shape_head.out_dim != 10 || m->pose_head.in_dim != r.hidden_size)
+      return bail(fail(EMPOSE_EINVAL, "init head dims"));
+  } else if (d->pose_init.n_layers == 0 && d->n_iterations == 0) {
+    // body-model-only handle: serves empose_smpl_sensors_fwd_bwd / _vjp (training path), not empose_lgd_forward
+    m->smpl_only = 1;
+  } else {
+    MTRY(pack_mlp(m->allocs, d->pose_init, &m->pose_init, &m->hidden_max, &m->any_skip));
+    MTRY(pack_mlp(m->allocs, d->shape_init, &m->shape_init, &m->hidden_max, &m->any_skip));
+    if (m->pose_init.n_layers == 0 || m->pose_init.layers[0].in_dim != m->d_in)
+      return bail(fail(EMPOSE_EINVAL, "init MLP dims"));
+  }
+  if (m->N > 0) {
+    MTRY(pack_mlp(m->allocs, d->pose_iter, &m->pose_iter, &m->hidden_max, &m->any_skip));
+    MTRY(pack_mlp(m->allocs, d->shape_iter, &m->shape_iter, &m->hidden_max, &m->any_skip));
+    if (m->pose_iter.n_layers == 0 || m->pose_iter.layers[0].in_dim != m->d_x ||
+        m->pose_iter.layers[m->pose_iter.n_layers - 1].out_dim != 66 ||
+        m->shape_iter.layers[m->shape_iter.n_layers - 1].out_dim != 10)
+      return bail(fail(EMPOSE_EINVAL, "update MLP dims (expected input %d)", m->d_x));
+  }
+  if (m->hidden_max == 0) m->hidden_max = 4;
+#undef MTRY
+  *out = m;
+  return EMPOSE_OK;
+}
+
+int empose_smpl_tile_supported(const empose_model_t* m) { return m && m->tile_ok ? 1 : 0; }
+
+size_t empose_smpl_workspace_bytes(const empose_model_t* m, int T) {
+  Carver c(nullptr);
+  carve_smpl(c, m, T);
+  return c.off;
+}
+
+size_t empose_update_workspace_bytes(const empose_model_t* m, int T) {
+  Carver c(nullptr);
+  carve_upd(c, m, T);
+  return c.off;
+}
+
+size_t empose_lgd_workspace_bytes(const empose_model_t* m, int B, int F) {
+  if (!m || B <= 0 || F <= 0) return 0;
+  Carver c(nullptr);
+  carve_lgd(c, m, B, F);
+  return c.off;
+}
+
+int empose_lgd_forward(const empose_model_t* m, const empose_lgd_io* io, void* workspace, size_t workspace_bytes,
+                       empose_stream_t stream_) {
+  return empose_lgd_forward_phase(m, io, workspace, workspace_bytes, stream_, EMPOSE_LGD_PHASE_INIT | EMPOSE_LGD_PHASE_ITER);
+}
+
+int empose_lgd_forward_phase(const empose_model_t* m, const empose_lgd_io* io, void* workspace, size_t workspace_bytes,
+                             empose_stream_t stream_, int phases) {
+  if (!m || !io || !workspace) return fail(EMPOSE_EINVAL, "null argument");
+  if (phases < 1 || phases > 3) return fail(EMPOSE_EINVAL, "phases: EMPOSE_LGD_PHASE_INIT, _ITER or both");
+  if (m->smpl_only) return fail(EMPOSE_EINVAL, "this handle holds the body model only (no networks)");
+  const int B = io->B, F = io->F;
+  if (B <= 0 || F <= 0) return fail(EMPOSE_EINVAL, "B and F must be positive");
+  if (!io->marker_pos || !io->marker_oris || !io->offset_t || !io->offset_r || !io->pose_hat || !io->shape_hat ||
+      !io->joints_hat)
+    return fail(EMPOSE_EINVAL, "null input/output tensor");
+  if (workspace_bytes < empose_lgd_workspace_bytes(m, B, F)) return fail(EMPOSE_ENOMEM, "workspace too small");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const int T = B * F;
+  Carver c(workspace);
+  LgdWs w = carve_lgd(c, m, B, F);
+  const int dx = m->d_x, din = m->d_in;
+  float* x_theta = w.x + din;
+  float* x_beta = w.x + din + 66;
+  float* x_gtheta = w.x + din + 76;
+  float* x_gbeta = w.x + din + 142;
+
+  if (phases & EMPOSE_LGD_PHASE_INIT) {
+  PackArgs pa;
+  pa.marker_pos = io->marker_pos; pa.marker_oris = io->marker_oris; pa.marker_masks = io->marker_masks;
+  pa.seq_lengths = io->seq_lengths; pa.x = w.x; pa.ldx = dx; pa.frame_scale = w.scale;
+  pa.B = B; pa.F = F; pa.n_markers = m->n_markers;
+  pa.rows_as_unpadded = (m->shape_avg == 2) ? 1 : 0;
+  pa.suppress_missing = io->suppress_missing; pa.mask_value = io->mask_value;
+  for (int i = 0; i < 12; ++i) pa.marker_idx[i] = m->marker_idx[i];
+  prof_mark(P_PACK, stream);
+  HIP_CHECK(launch_pack_inputs(pa, stream), "pack kernel");
+  if (m->use_gradient && m->N > 0 && use_tile_path(m, T)) {   // the targets of the frame-per-lane kernel, once per forward
+    HIP_CHECK(launch_rows_to_tile(w.x, dx, m->d_in, w.x_t, T, stream), "tile transpose");
+  }
+
+  // ---- initial estimate (reference models.py:511-526)
+  if (m->rnn_init) {
+    TRY(run_lstm(m->rnn, B, F, w.x, dx, io->seq_lengths, io->h0, io->c0, w.y, io->h_n, io->c_n, w.lstm, stream));
+    GemmBatch b;
+    b.count = 2;
+    b.p[0] = linear_prob(w.y, m->rnn.H, m->pose_head, x_theta, dx, T);
+    b.p[1] = linear_prob(w.y, m->rnn.H, m->shape_head, w.d_shape, 10, T);
+    prof_mark(P_HEADS, stream);
+    const bool rows = m->heads_frag && options().heads_rows != 0 && heads_rows_applicable(T, m->rnn.H);
+    const bool rx3 = options().rows_x3 != 0 && m->heads_frag3;
+    HIP_CHECK(rows ? launch_heads_rows(w.y, m->rnn.H, rx3 ? m->heads_frag3 : m->heads_frag, m->heads_bias, x_theta, dx,
+                                       w.d_shape, 10, T, m->rnn.H, 66, 10, rx3, stream)
+                   : launch_gemm(b, stream), "head gemm");
+  } else {
+    const Mlp* nets[2] = {&m->pose_init, &m->shape_init};
+    float* outs[2] = {x_theta, w.d_shape};
+    const int lds[2] = {dx, 10};
+    TRY(run_mlps(nets, 2, outs, lds, w.x, dx, T, w.upd, m->hidden_max, stream, true));
+  }
+  }   // EMPOSE_LGD_PHASE_INIT
+  if (!(phases & EMPOSE_LGD_PHASE_ITER)) return EMPOSE_OK;
+
+  const int N = m->N;
+  auto hist = [&](float* base, int i, size_t width) -> float* { return base ? base + (size_t)i * T * width : nullptr; };
+  for (int i = 0; i <= N; ++i) {
+    FeatArgs fa;
+    fa.theta = x_theta; fa.ld_theta = dx; fa.beta = x_beta; fa.ld_beta = dx;
+    fa.shape_avg = m->shape_avg;
+    fa.seq_lengths = io->seq_lengths;
+    if (i == 0) {
+      fa.d_theta = nullptr; fa.theta_step = 0.f;
+      fa.d_beta = w.d_shape; fa.beta_keep = 0.f; fa.beta_step = 1.f;
+    } else {
+      fa.d_theta = w.d_pose; fa.theta_step = m->step;
+      fa.d_beta = w.d_shape; fa.beta_keep = 1.f; fa.beta_step = m->step;
+    }
+    const bool tile = use_tile_path(m, T);
+    fa.out_theta = hist(io->hist_pose, i, 66); fa.out_beta = hist(io->hist_shape, i, 10);
+    fa.out_theta2 = (i == N) ? io->pose_hat : nullptr;
+    fa.out_beta2 = (i == N) ? io->shape_hat : nullptr;
+
+    const bool need_grad = (i < N) && m->use_gradient;
+    float* hm = hist(io->hist_markers, i, 36);
+    float* ho = hist(io->hist_markers_ori, i, 108);
+    float* hj = hist(io->hist_joints, i, 66);
+    if ((hm == nullptr) != (ho == nullptr)) return fail(EMPOSE_EINVAL, "hist_markers and hist_markers_ori go together");
+    GradOut go{x_gtheta, dx, x_gbeta, dx, hist(io->trace_g_pose, i, 66), hist(io->trace_g_shape, i, 10)};
+    // (the frame-per-lane kernel skips outputs nobody asked for; the general kernel always writes its scratch copies)
+    TRY(run_smpl_eval(m, T, F, w.smpl, fa, io->offset_r, io->offset_t, need_grad ? w.x : nullptr, dx, w.scale,
+                      hm ? hm : (tile ? nullptr : w.pos), ho ? ho : (tile ? nullptr : w.ori),
+                      (i == N) ? io->joints_hat : (hj ? hj : (tile ? nullptr : w.joints)),
+                      nullptr, nullptr, (i == N) ? hj : nullptr, stream, nullptr, nullptr, nullptr, w.x_t,
+                      need_grad ? &go : nullptr));
+    if (i == N) break;
+    const Mlp* nets[2] = {&m->pose_iter, &m->shape_iter};
+    float* outs[2] = {w.d_pose, w.d_shape};
+    const int lds[2] = {66, 10};
+    TRY(run_mlps(nets, 2, outs, lds, w.x, dx, T, w.upd, m->hidden_max, stream));
+  }
+  prof_end_forward(stream);
+  return EMPOSE_OK;
+}
+
+int empose_smpl_sensors_fwd_bwd(const empose_model_t* m, int T, int F, const float* theta, int ld_theta,
+                                const float* beta, int ld_beta, const float* offset_r, const float* offset_t,
+                                const float* tgt, int ld_tgt, const float* frame_scale, float* pos, float* ori,
+                                float* joints, float* g_theta, int ld_g, float* g_beta, int ld_gb, void* workspace,
+                                size_t workspace_bytes, empose_stream_t stream_) {
+  if (!m || !theta || !beta || !offset_r || !offset_t || !pos || !ori || !joints || !workspace)
+    return fail(EMPOSE_EINVAL, "null argument");
+  if (T <= 0 || F <= 0 || T % F != 0) return fail(EMPOSE_EINVAL, "T must be a positive multiple of F");
+  if (tgt && (!frame_scale || !g_theta || !g_beta)) return fail(EMPOSE_EINVAL, "gradient outputs missing");
+  if (workspace_bytes < empose_smpl_workspace_bytes(m, T)) return fail(EMPOSE_ENOMEM, "workspace too small");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  Carver c(workspace);
+  SmplWs ws = carve_smpl(c, m, T);
+  FeatArgs fa;   // the caller's rows are read in place (no update: the kernel does not write them back)
+  fa.theta = const_cast<float*>(theta); fa.ld_theta = ld_theta; fa.beta = const_cast<float*>(beta); fa.ld_beta = ld_beta;
+  fa.d_theta = nullptr; fa.d_beta = nullptr; fa.theta_step = 0.f; fa.beta_keep = 1.f; fa.beta_step = 0.f;
+  const bool tile = use_tile_path(m, T);
+  fa.shape_avg = 0;
+  fa.out_theta = fa.out_beta = fa.out_theta2 = fa.out_beta2 = nullptr;
+  if (tgt && tile) {
+    HIP_CHECK(launch_rows_to_tile(tgt, ld_tgt, 12 * m->n_markers, ws.tgt_t, T, stream), "tile transpose");
+  }
+  GradOut go{g_theta, ld_g, g_beta, ld_gb, nullptr, nullptr};
+  TRY(run_smpl_eval(m, T, F, ws, fa, offset_r, offset_t, tgt, ld_tgt, frame_scale, pos, ori, joints, nullptr, nullptr,
+                    nullptr, stream, nullptr, nullptr, nullptr, tile ? ws.tgt_t : nullptr, tgt ? &go : nullptr));
+  return EMPOSE_OK;
+}
+
+int empose_smpl_sensors_vjp(const empose_model_t* m, int T, int F, const float* theta, int ld_theta, const float* beta,
+                            int ld_beta, const float* offset_r, const float* offset_t, const float* d_pos,
+                            const float* d_ori, const float* d_joints, float* g_theta, float* g_beta, void* workspace,
+                            size_t workspace_bytes, empose_stream_t stream_) {
+  if (!m || !theta || !beta || !offset_r || !offset_t || !d_pos || !d_ori || !g_theta || !g_beta || !workspace)
+    return fail(EMPOSE_EINVAL, "null argument");
+  if (T <= 0 || F <= 0 || T % F != 0) return fail(EMPOSE_EINVAL, "T must be a positive multiple of F");
+  if (workspace_bytes < empose_smpl_workspace_bytes(m, T) + (size_t)T * (36 + 108 + 66) * sizeof(float) + 1024)
+    return fail(EMPOSE_ENOMEM, "workspace too small (need empose_smpl_vjp_workspace_bytes)");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  Carver c(workspace);
+  SmplWs ws = carve_smpl(c, m, T);
+  float* pos = c.f((size_t)T * 36);
+  float* ori = c.f((size_t)T * 108);
+  float* joints = c.f((size_t)T * 66);
+  FeatArgs fa;   // the caller's rows are read in place (no update: the kernel does not write them back)
+  fa.theta = const_cast<float*>(theta); fa.ld_theta = ld_theta; fa.beta = const_cast<float*>(beta); fa.ld_beta = ld_beta;
+  fa.d_theta = nullptr; fa.d_beta = nullptr; fa.theta_step = 0.f; fa.beta_keep = 1.f; fa.beta_step = 0.f;
+  const bool tile = use_tile_path(m, T, d_joints);
+  fa.shape_avg = 0;
+  fa.out_theta = fa.out_beta = fa.out_theta2 = fa.out_beta2 = nullptr;
+  GradOut go{g_theta, 66, g_beta, 10, nullptr, nullptr};
+  TRY(run_smpl_eval(m, T, F, ws, fa, offset_r, offset_t, nullptr, 0, nullptr, tile ? nullptr : pos, tile ? nullptr : ori,
+                    tile ? nullptr : joints, nullptr, nullptr, nullptr, stream, d_pos, d_ori, d_joints, nullptr, &go));
+  return EMPOSE_OK;
+}
+
+size_t empose_smpl_vjp_workspace_bytes(const empose_model_t* m, int T) {
+  return empose_smpl_workspace_bytes(m, T) + (size_t)T * (36 + 108 + 66) * sizeof(float) + 1024;
+}
+
+int empose_update_nets_fwd(const empose_model_t* m, int T, const float* x, int ldx, float* d_pose, float* d_shape,
+                           void* workspace, size_t workspace_bytes, empose_stream_t stream_) {
+  if (!m || !x || !d_pose || !d_shape || !workspace) return fail(EMPOSE_EINVAL, "null argument");
+  if (m->pose_iter.n_layers == 0) return fail(EMPOSE_EINVAL, "model has no update nets");
+  if (ldx < m->d_x || ldx % 4 != 0) return fail(EMPOSE_EINVAL, "ldx must be >= %d and a multiple of 4", m->d_x);
+  if (workspace_bytes < empose_update_workspace_bytes(m, T)) return fail(EMPOSE_ENOMEM, "workspace too small");
+  Carver c(workspace);
+  UpdWs ws = carve_upd(c, m, T);
+  const Mlp* nets[2] = {&m->pose_iter, &m->shape_iter};
+  float* outs[2] = {d_pose, d_shape};
+  const int lds[2] = {66, 10};
+  return run_mlps(nets, 2, outs, lds, x, ldx, T, ws, m->hidden_max, static_cast<hipStream_t>(stream_));
+}
+
+}  // extern "C"

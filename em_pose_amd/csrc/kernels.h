@@ -11,59 +11,65 @@
 namespace empose {
 
 // Kernel-variant selection for A/B and bit-identity tests (empose_set_option in the C ABI).  Plain process-wide ints set
-// by an explicit call -- the library never reads the environment.  Defaults as initialised below (empose_reset_options
-// restores them).
+// by an explicit call -- the library never reads the environment.  X(name, default) per option: this one list makes the
+// fields of Options and the names empose_set_option / empose_get_option take (api.hip); empose_reset_options restores
+// the defaults.
+#define EMPOSE_OPTIONS(X) \
+  X(mlp_fused, 1)      /* one-launch LDS-resident update MLPs (0: layer by layer) */ \
+  X(lstm_persist, 1)   /* whole-sequence small-batch LSTM kernel (0: step launches) */ \
+  X(gemm_splitk, 1)    /* split-K tile for problems of few output tiles (0: generic tiles) */ \
+  X(heads_rows, 1)     /* large batches: both init heads as one row-block product (0: two problems on the generic tile) */ \
+  X(lstm_seq, 0)       /* large batches: the whole sequence in one cooperative launch (measured slower: 0 = a launch per wavefront step) */ \
+  X(bptt_wave, 1)      /* training: the reverse recurrences of a 2-layer LSTM as a wavefront (0: layer after layer) */ \
+  X(gemm_wide, 1)      /* 256 x 256 four-wave tile (0: generic tiles) */ \
+  X(smpl_tile, 1)      /* frame-per-lane SMPL sub-mesh kernel: 0 never, 1 from 16384 frames on, 2 always */ \
+  X(smpl_fuse, 1)      /* on that path: update + feature row / Rodrigues reverse inside the blend GEMMs (0: own kernels) */ \
+  X(train_fused, 0)    /* train-mode BatchNorm / PReLU folded into the GEMMs: 0 never (default: measured no faster, \
+                             DESIGN.md), 1 above 1024 rows, 2 always */ \
+  X(atb_target, 0)     /* workgroups the A^T B weight-gradient GEMM aims for when it splits its reduction (0: by size) */ \
+  X(atb_fast, 1)       /* A^T B: whole-tile / whole-chunk problems on the branch-free interior kernel (0: the general kernel) */ \
+  X(atb_chunk, 0)      /* rows per staged chunk of that kernel, 16 or 32 (0: by size) */ \
+  X(mesh_skin_mfma, 0) /* split-bf16 full-mesh variant: the bone blend as a second matrix-core contraction (mesh_rows_bf16s_kernel; \
+                             measured 9 % SLOWER than vector skinning: 15.6 against 17.1 M frames/s, so off by default) */ \
+  X(train_epi, 1)      /* train-mode MLP layer: BatchNorm statistics in the GEMM epilogues + ONE combine-and-apply launch per \
+                             layer and direction (train_fused.hip, finish kernels): 0 never, 1 above BN_SINGLE_PASS_ROWS rows, 2 always */ \
+  X(spin_limit, 0)     /* polls of the cooperative LSTM kernels give up after this many spins (0: their own limits) */ \
+  X(rows_x3, 1)        /* the row-block products with fused prologue / epilogue (blend GEMMs of the frame-per-lane SMPL path, init \
+                             heads) on the same three-piece bf16 arithmetic; 0: the fp32 MFMA instruction */ \
+  X(lstm_x3, 1)        /* large-batch LSTM steps (inference, uni-directional): fp32 products as six bf16-MFMA products of three \
+                             bf16 pieces per operand; 1: lstm_x3.hip (K-split waves); 2: lstm_rows_x3.hip (row-split waves, weights \
+                             through LDS, cell update in registers -- round 6, measured 10 % SLOWER: 47.5 against 42.9 us per \
+                             launch, profiles/r06_lstm_rows_lab.txt, so opt-in); 0: the fp32 MFMA instruction (lstm_chain_kernel) */ \
+  X(train_cols, 1)     /* training at <= 512 rows: a layer's product + BatchNorm + PReLU as one launch, both update networks \
+                             side by side (train_cols.hip); 0: a product and a BatchNorm launch per layer and network */ \
+  X(cols_coop, 1)      /* those one-launch layers, eager: launched with hipLaunchCooperativeKernel (all workgroups resident by \
+                             the runtime's guarantee); 0: the ordinary launch (residency argued from the occupancy query) */ \
+  X(mesh_x3, 1)        /* full-mesh vertices: blend shapes as six bf16-MFMA products of three bf16 pieces per operand \
+                             (mesh_x3.hip): 1 stores staggered into the next tile's products, 2 stores at the end of the tile, \
+                             3 skinning software-pipelined under the next tile's products; 0: the fp32 MFMA instruction \
+                             (mesh_rows_kernel) */ \
+  X(train_x3, 1)       /* training at more than 1024 rows: the layer products y = a W^T and dA = dY W of the update networks on \
+                             three bf16 pieces (gemm_train_x3_kernel) when the caller supplies the packed weights \
+                             (empose_mlp_params::weight_x3 / weight_t_x3); 0: the fp32 MFMA tile */ \
+  X(lstm_midseq, 0)    /* 1: medium batches (4 .. 64 rows, inference): the whole sequence in one cooperative launch with the \
+                             weight pieces in registers (lstm_midseq_x3.hip) -- built, same bits, measured SLOWER than a launch \
+                             per wavefront step (10.5 against 8.2 us per step at 32 rows: a hand-over between XCDs costs more \
+                             than a kernel boundary; profiles/r06i_lstm_midseq_lab.txt), so opt-in */ \
+  X(lstm_mid16, 1)     /* LSTM steps of 17 .. 64 rows: 64 rows x 4-unit tiles on all 256 CUs (lstm_mid16_x3.hip); 0: the 8-unit \
+                             tiles of lstm_mid_x3.hip (128 workgroups) */ \
+  X(lstm_mid_x3, 1)    /* LSTM steps of 17 .. 256 rows (inference, uni-directional) on three bf16 pieces, 64 x 8-unit tiles \
+                             (lstm_mid_x3.hip); 0: lstm_mid_kernel (fp32 MFMA, operands through LDS) */ \
+  X(lstm_fewrows, 1)   /* LSTM steps of 4 .. 16 rows: all threads of a workgroup split K, lane reduce-scatter (lstm_fewrows_kernel), \
+                             instead of the whole-sequence kernel / lstm_small_kernel (0: those; they share their bits) */ \
+  X(mlp_x3, 1)         /* fused update MLPs: fp32 products as six bf16-MFMA products of three bf16 pieces per operand \
+                             (mlp_fused_x3.hip: fp32-equivalent accuracy, measured equal to the fp32 instruction's against \
+                             float64); 0: the fp32 MFMA instruction (mlp_fused.hip); 2: the variant whose waves share the \
+                             A-side split through LDS (a barrier per k-step; measured 9 % slower) */
+
 struct Options {
-  int mlp_fused = 1;      // one-launch LDS-resident update MLPs (0: layer by layer)
-  int lstm_persist = 1;   // whole-sequence small-batch LSTM kernel (0: step launches)
-  int gemm_splitk = 1;    // split-K tile for problems of few output tiles (0: generic tiles)
-  int heads_rows = 1;     // large batches: both init heads as one row-block product (0: two problems on the generic tile)
-  int lstm_seq = 0;       // large batches: the whole sequence in one cooperative launch (measured slower: 0 = a launch per wavefront step)
-  int bptt_wave = 1;      // training: the reverse recurrences of a 2-layer LSTM as a wavefront (0: layer after layer)
-  int gemm_wide = 1;      // 256 x 256 four-wave tile (0: generic tiles)
-  int smpl_tile = 1;      // frame-per-lane SMPL sub-mesh kernel: 0 never, 1 from 16384 frames on, 2 always
-  int smpl_fuse = 1;      // on that path: update + feature row / Rodrigues reverse inside the blend GEMMs (0: own kernels)
-  int train_fused = 0;    // train-mode BatchNorm / PReLU folded into the GEMMs: 0 never (default: measured no faster,
-                          // DESIGN.md), 1 above 1024 rows, 2 always
-  int atb_target = 0;     // workgroups the A^T B weight-gradient GEMM aims for when it splits its reduction (0: by size)
-  int atb_fast = 1;       // A^T B: whole-tile / whole-chunk problems on the branch-free interior kernel (0: the general kernel)
-  int atb_chunk = 0;      // rows per staged chunk of that kernel, 16 or 32 (0: by size)
-  int mesh_skin_mfma = 0; // split-bf16 full-mesh variant: the bone blend as a second matrix-core contraction (mesh_rows_bf16s_kernel;
-                          // measured 9 % SLOWER than vector skinning: 15.6 against 17.1 M frames/s, so off by default)
-  int train_epi = 1;      // train-mode MLP layer: BatchNorm statistics in the GEMM epilogues + ONE combine-and-apply launch per
-                          // layer and direction (train_fused.hip, finish kernels): 0 never, 1 above BN_SINGLE_PASS_ROWS rows, 2 always
-  int spin_limit = 0;     // polls of the cooperative LSTM kernels give up after this many spins (0: their own limits)
-  int rows_x3 = 1;        // the row-block products with fused prologue / epilogue (blend GEMMs of the frame-per-lane SMPL path, init
-                          // heads) on the same three-piece bf16 arithmetic; 0: the fp32 MFMA instruction
-  int lstm_x3 = 1;        // large-batch LSTM steps (inference, uni-directional): fp32 products as six bf16-MFMA products of three
-                          // bf16 pieces per operand; 1: lstm_x3.hip (K-split waves); 2: lstm_rows_x3.hip (row-split waves, weights
-                          // through LDS, cell update in registers -- round 6, measured 10 % SLOWER: 47.5 against 42.9 us per
-                          // launch, profiles/r06_lstm_rows_lab.txt, so opt-in); 0: the fp32 MFMA instruction (lstm_chain_kernel)
-  int train_cols = 1;     // training at <= 512 rows: a layer's product + BatchNorm + PReLU as one launch, both update networks
-                          // side by side (train_cols.hip); 0: a product and a BatchNorm launch per layer and network
-  int cols_coop = 1;      // those one-launch layers, eager: launched with hipLaunchCooperativeKernel (all workgroups resident by
-                          // the runtime's guarantee); 0: the ordinary launch (residency argued from the occupancy query)
-  int mesh_x3 = 1;        // full-mesh vertices: blend shapes as six bf16-MFMA products of three bf16 pieces per operand
-                          // (mesh_x3.hip): 1 stores staggered into the next tile's products, 2 stores at the end of the tile,
-                          // 3 skinning software-pipelined under the next tile's products; 0: the fp32 MFMA instruction
-                          // (mesh_rows_kernel)
-  int train_x3 = 1;       // training at more than 1024 rows: the layer products y = a W^T and dA = dY W of the update networks on
-                          // three bf16 pieces (gemm_train_x3_kernel) when the caller supplies the packed weights
-                          // (empose_mlp_params::weight_x3 / weight_t_x3); 0: the fp32 MFMA tile
-  int lstm_midseq = 0;    // 1: medium batches (4 .. 64 rows, inference): the whole sequence in one cooperative launch with the
-                          // weight pieces in registers (lstm_midseq_x3.hip) -- built, same bits, measured SLOWER than a launch
-                          // per wavefront step (10.5 against 8.2 us per step at 32 rows: a hand-over between XCDs costs more
-                          // than a kernel boundary; profiles/r06i_lstm_midseq_lab.txt), so opt-in
-  int lstm_mid16 = 1;     // LSTM steps of 17 .. 64 rows: 64 rows x 4-unit tiles on all 256 CUs (lstm_mid16_x3.hip); 0: the 8-unit
-                          // tiles of lstm_mid_x3.hip (128 workgroups)
-  int lstm_mid_x3 = 1;    // LSTM steps of 17 .. 256 rows (inference, uni-directional) on three bf16 pieces, 64 x 8-unit tiles
-                          // (lstm_mid_x3.hip); 0: lstm_mid_kernel (fp32 MFMA, operands through LDS)
-  int lstm_fewrows = 1;   // LSTM steps of 4 .. 16 rows: all threads of a workgroup split K, lane reduce-scatter (lstm_fewrows_kernel),
-                          // instead of the whole-sequence kernel / lstm_small_kernel (0: those; they share their bits)
-  int mlp_x3 = 1;         // fused update MLPs: fp32 products as six bf16-MFMA products of three bf16 pieces per operand
-                          // (mlp_fused_x3.hip: fp32-equivalent accuracy, measured equal to the fp32 instruction's against
-                          // float64); 0: the fp32 MFMA instruction (mlp_fused.hip); 2: the variant whose waves share the
-                          // A-side split through LDS (a barrier per k-step; measured 9 % slower)
+#define EMPOSE_OPTION_FIELD(name, default_value) int name = default_value;
+  EMPOSE_OPTIONS(EMPOSE_OPTION_FIELD)
+#undef EMPOSE_OPTION_FIELD
 };
 Options& options();
 
@@ -269,7 +275,7 @@ const char* gemm_kernel_name(int M, int N, int K, int count, int role);
 constexpr int FUSED_MAX_LAYERS = 8;
 constexpr int FUSED_MAX_WIDTH = 512;     // widest layer output the four 128-column waves cover
 struct FusedLayer {
-  const float* W; int K, N;              // weights in fragment order (api.hip pack_fragments), K % 4 == 0, N <= FUSED_MAX_WIDTH
+  const float* W; int K, N;              // weights in fragment order (api_model.hip pack_fragments), K % 4 == 0, N <= FUSED_MAX_WIDTH
   const float* scale; const float* shift;
   float slope; int act;                  // 0 none, 1 PReLU
 };
@@ -281,7 +287,7 @@ struct FusedNet {
 };
 struct FusedMlpArgs { FusedNet net[2]; int count; int M; };
 hipError_t launch_mlp_fused(const FusedMlpArgs& args, hipStream_t stream);
-// The same launch with FusedLayer::W = three bf16 pieces per weight in bf16-MFMA fragment order (api.hip
+// The same launch with FusedLayer::W = three bf16 pieces per weight in bf16-MFMA fragment order (api_model.hip
 // pack_fragments_x3_raw): mlp_fused_x3.hip.  Hidden widths must be multiples of 64.
 hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, hipStream_t stream);
 // One linear layer C = A . W^T with A's row block resident in LDS and W (fragment order) streamed from L2.
@@ -345,7 +351,7 @@ struct LstmSeqArgs {
   unsigned* timeouts;   // poll_timeout_word(): counts the polls that gave up (the outputs are NaN from there on)
 };
 // The wavefront step of large batches on the bf16 matrix path, three bf16 pieces per fp32 operand (lstm_x3.hip).  All
-// operands arrive in fragment order: weights packed at model creation (api.hip pack_lstm_x3: [k-step][32-unit block][gate]
+// operands arrive in fragment order: weights packed at model creation (api_lstm.hip pack_lstm_x3: [k-step][32-unit block][gate]
 // [piece][512 bf16]), activations as A planes [32-row tile][k-step][piece][512 bf16] written by the producing step (hidden
 // states) or by launch_lstm_split_rows (stored input, initial state).
 struct LstmX3Unit {
@@ -370,9 +376,9 @@ hipError_t launch_lstm_chain_x3(const LstmX3Args& a, hipStream_t stream);
 // registers (lstm_rows_x3.hip; option lstm_x3 = 2): one unit per workgroup, `units_per_block` unused
 hipError_t launch_lstm_rows_x3(const LstmX3Args& a, hipStream_t stream);
 // the step of MEDIUM batches (17 .. 256 rows): 64 rows x 8 units per workgroup, weights in the 8-unit-block order
-// (api.hip pack_lstm_x3 with mid = true), K split over the waves (lstm_mid_x3.hip; option lstm_mid_x3)
+// (api_lstm.hip pack_lstm_x3 with mid = true), K split over the waves (lstm_mid_x3.hip; option lstm_mid_x3)
 hipError_t launch_lstm_mid_x3(const LstmX3Args& a, hipStream_t stream);
-// ... at most 64 rows: 4-unit tiles (16 columns, v_mfma_f32_16x16x32_bf16), weights in the order of api.hip
+// ... at most 64 rows: 4-unit tiles (16 columns, v_mfma_f32_16x16x32_bf16), weights in the order of api_lstm.hip
 // pack_lstm_x3_mid16, twice the workgroups (lstm_mid16_x3.hip; option lstm_mid16)
 bool lstm_mid16_shape_ok(int B, int H);
 hipError_t launch_lstm_mid16_x3(const LstmX3Args& a, hipStream_t stream);
@@ -723,11 +729,11 @@ struct MeshSkinArgs {
   const float* trans;
   float* vertices;             // [T][V][3]
   int T, V;
-  const float* wc_frag;        // [tiles][25][3][64][4]: wc in fragment order per 32-vertex tile (api.hip pack_mesh_tiles)
+  const float* wc_frag;        // [tiles][25][3][64][4]: wc in fragment order per 32-vertex tile (api_mesh.hip pack_mesh_tiles)
   const int* skin_idx4; const float* skin_w4;   // [tiles * 32][4]
-  const void* wc_bf16 = nullptr;   // bf16 pieces of wc in fragment order per tile (api.hip pack_mesh_tiles_bf16), or nullptr
+  const void* wc_bf16 = nullptr;   // bf16 pieces of wc in fragment order per tile (api_mesh.hip pack_mesh_tiles_bf16), or nullptr
   const void* skin_bf16 = nullptr; // dense skin weights per 32-vertex tile as bf16 pieces in fragment order (pack_mesh_skin_bf16)
-  const void* wc_x3 = nullptr;     // THREE bf16 pieces of wc in fragment order per tile (api.hip pack_mesh_tiles_x3)
+  const void* wc_x3 = nullptr;     // THREE bf16 pieces of wc in fragment order per tile (api_mesh.hip pack_mesh_tiles_x3)
   int stagger = 1;                 // mesh_rows_x3_kernel: a tile's stores ride in the next tile's K loop, at a per-wave k-step
 };
 hipError_t launch_mesh_rows(const MeshSkinArgs& a, hipStream_t stream);

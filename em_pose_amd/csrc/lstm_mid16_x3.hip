@@ -6,7 +6,7 @@
 // twice the workgroups and half the K each the same launch takes 7.2 instead of 8.2 us at 32 rows and 8.2 instead of 10.1
 // at 36 (lab build LM3_LAB_TWICE_WGS, profiles/r06i_lstm_mid_ring_lab.txt).  Hence this form:
 //   * a workgroup owns 4 hidden units x 4 gates = 16 columns (column n = gate * 4 + unit) of up to 64 rows: 128 workgroups
-//     per layer, 256 per step; weights packed [k-step of 32][4-unit block][piece] (api.hip pack_lstm_x3_mid16);
+//     per layer, 256 per step; weights packed [k-step of 32][4-unit block][piece] (api_lstm.hip pack_lstm_x3_mid16);
 //   * the products are v_mfma_f32_16x16x32_bf16: 16 rows x 16 columns x 32 k.  The A planes stay as every other kernel
 //     writes them ([32-row tile][k-step of 16][piece][lane (row, k half)][8]): lane (row r, k quarter q) of a 16 x 32
 //     fragment reads the 16 bytes of row r, half q & 1 of k-step 2 K + (q >> 1) -- 16 lanes a contiguous 256 bytes;

@@ -7,7 +7,7 @@
 //     no pipelining) takes 17 us per step whatever the row count -- 55 % of the GPU time of the configs[3] stand-in
 //     (profiles/r06_evaluate_real_kernel_stats.csv);
 //   * here a workgroup owns up to 64 rows x 8 hidden units x 4 gates = ONE 32-column tile of one unit (the four gates of a
-//     unit sit in the same tile: weights packed [k-step][8-unit block][piece], column = gate * 8 + unit; api.hip
+//     unit sit in the same tile: weights packed [k-step][8-unit block][piece], column = gate * 8 + unit; api_lstm.hip
 //     pack_lstm_x3_mid), its four waves split K (wave w takes k-steps w, w + 4, ...: 16 steps of 6 or 12 MFMAs for K = 1024),
 //     fragments straight from L2 into a three-deep register ring, no LDS and no barrier in the loop; the partial sums meet
 //     in LDS (34 KB), then thread (row, 2 units) applies the cell non-linearities and the first 64 threads write the new

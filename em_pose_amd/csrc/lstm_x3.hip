@@ -6,7 +6,7 @@
 // of matrix work, and staging both operands through LDS (global -> registers -> LDS -> fragments) no longer hides under
 // it.  So nothing is staged:
 //   * W_ih / W_hh are split ONCE when the model is created and stored in fragment order, the four gates of a 32-unit block
-//     side by side: [k-step][unit block][gate][piece] -> one 1 KB wave fragment (api.hip pack_lstm_x3);
+//     side by side: [k-step][unit block][gate][piece] -> one 1 KB wave fragment (api_lstm.hip pack_lstm_x3);
 //   * the hidden states are split by the workgroup that PRODUCES them: besides h (fp32, for the state hand-over and rows
 //     past their length) a step writes h's three pieces in A-fragment order [32-row tile][k-step][piece] -> 1 KB, so that
 //     the next step (and the layer above) loads fragments, not rows;

@@ -272,7 +272,7 @@ constexpr int TILE_BYTES = KS * 3 * 2 * 1024;   // packed coefficients of one 32
 #define MB_RING 4
 #endif
 constexpr int RING = MB_RING;             // B fragments: steps s+1 .. s+RING-1 in flight while step s is consumed
-static_assert(TILE_BYTES == MESH_BF16_TILE_BYTES, "api.hip packs what this kernel reads");
+static_assert(TILE_BYTES == MESH_BF16_TILE_BYTES, "api_mesh.hip packs what this kernel reads");
 }  // namespace mb
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -492,7 +492,7 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16_kernel(MeshSkinArg
 // so, its C/D fragments line up with the blend-shape accumulators (lane = vertex, register = frame), and what is left for
 // the vector unit is  out = T^R v + T^t  on registers: 9 FMAs per vertex and frame, no LDS access.
 //   * W as a dense 32 (bones, 22 used) x 32 (vertices) block per tile, split hi + lo in bf16, in B-fragment order
-//     (api.hip pack_mesh_skin_bf16): 4 KB per tile, prefetched with the coefficient ring;
+//     (api_mesh.hip pack_mesh_tiles_bf16): 4 KB per tile, prefetched with the coefficient ring;
 //   * G of the workgroup's 64 frames staged ONCE as bf16 hi + lo pieces [piece][entry c][frame][24 bones] (48-byte rows:
 //     conflict-free 16-byte fragment reads; the k-slots 24..31 of a fragment read into the next row -- finite values --
 //     and meet zero weights), 72 KB next to the 58 KB feature block;
@@ -514,7 +514,7 @@ constexpr int G_PIECE_BYTES = 12 * BM * G_ROW_BYTES;              // [entry][fra
 constexpr int G_BYTES = 2 * G_PIECE_BYTES + 64;                   // + what the last row's k-slots 24..31 read
 constexpr size_t LDS_BYTES = (size_t)A_BYTES + G_BYTES + (size_t)TR_FLOATS * sizeof(float) + 64;
 constexpr int SKIN_TILE_BYTES = 2 * 2 * 1024;                     // [k-step][piece][lane][8 bf16]
-static_assert(SKIN_TILE_BYTES == MESH_SKIN_BF16_TILE_BYTES, "api.hip packs what this kernel reads");
+static_assert(SKIN_TILE_BYTES == MESH_SKIN_BF16_TILE_BYTES, "api_mesh.hip packs what this kernel reads");
 static_assert(NB <= 24, "the bones of a row fit its 24 slots");
 static_assert(LDS_BYTES <= 160 * 1024, "one workgroup per CU");
 }  // namespace ms

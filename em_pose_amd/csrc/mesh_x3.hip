@@ -8,7 +8,7 @@
 // Blocking as mesh_rows_kernel: a workgroup owns 64 frames; their features -- split once into three piece planes, 81 KB --
 // and their 22 relative bone transforms (66 KB, fp32) stay in LDS; its four waves (ONE per SIMD: bf16_hazard_repro.md) walk
 // the 32-vertex tiles.  A tile is 13 k-steps x 6 products x 6 accumulators (2 frame tiles x 3 coordinate planes) = 468
-// MFMAs; the coefficients arrive from L2 in fragment order ([tile][k-step][plane][piece] -> 1 KB, api.hip
+// MFMAs; the coefficients arrive from L2 in fragment order ([tile][k-step][plane][piece] -> 1 KB, api_mesh.hip
 // pack_mesh_tiles_x3; 117 KB per tile) through a register ring RING - 1 k-steps ahead.
 //
 // The skinning of a tile (4 bones x 3 rows x 16 bytes of LDS per (frame, vertex): 393 KB per tile and wave, LDS-bound,
@@ -36,7 +36,7 @@ constexpr int TR_FLOATS = BM * 4;
 constexpr size_t LDS_BYTES = (size_t)A_BYTES + (size_t)(XF_FLOATS + TR_FLOATS) * sizeof(float) + 64;
 constexpr int TILE_BYTES = KS * 9 * 1024;       // packed coefficients of one 32-vertex tile: [k-step][plane][piece]
 constexpr int RING = 3;                         // B fragments: steps s + 1, s + 2 in flight while step s is consumed
-static_assert(TILE_BYTES == MESH_X3_TILE_BYTES, "api.hip packs what this kernel reads");
+static_assert(TILE_BYTES == MESH_X3_TILE_BYTES, "api_mesh.hip packs what this kernel reads");
 static_assert(LDS_BYTES <= 160 * 1024 && LDS_BYTES > 80 * 1024, "one workgroup per CU");
 }  // namespace mx
 

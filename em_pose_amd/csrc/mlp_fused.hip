@@ -6,7 +6,7 @@
 // operand straight out of that buffer for the whole K loop and, once every wave has finished the loop, its epilogue
 // (bias, folded BatchNorm, PReLU) overwrites the buffer in place with the next layer's input.  Between the network
 // input x and the 66- / 10-column outputs nothing is stored to or loaded from global memory except the weights:
-//   * weights never touch LDS: they are packed once (api.hip pack_fragments) in MFMA fragment order, so a wave's B
+//   * weights never touch LDS: they are packed once (api_model.hip pack_fragments) in MFMA fragment order, so a wave's B
 //     fragment of a k-group of 8 is one coalesced 1 KB global load straight into registers, prefetched three k-groups
 //     ahead in a four-slot register ring (the weights of both nets are L2-resident);
 //   * no barrier inside a layer's K loop (its A operand is static): two workgroup barriers per layer in total.
@@ -293,7 +293,7 @@ __device__ __forceinline__ void fused_layer_t(const FusedNet& net, const FusedLa
 // The single-layer row-block product on the bf16 matrix path, every fp32 product from three bf16 pieces per operand
 // (bf16x3.h; round 5).  Same operands and output modes as fused_layer_t<WM, WN, OUT_T, A_KMAJOR> with `last` set -- the A
 // block in LDS as fp32 (row-major or K-major), split in registers as it is read; the weights as three bf16 pieces in
-// fragment order (api.hip pack_fragments_x3_raw: [k-step of 16][32-column tile][piece] -> 1 KB) --, the K loop of
+// fragment order (api_model.hip pack_fragments_x3_raw: [k-step of 16][32-column tile][piece] -> 1 KB) --, the K loop of
 // mlp_fused_x3.hip's x3_layer (k-steps as fenced chunks, weights ahead in a register ring), plus plain steps for what is
 // left behind the whole periods of the pipeline (K = 200: 12 pipelined steps + 1).
 // ---------------------------------------------------------------------------------------------------------------------
@@ -809,7 +809,7 @@ static hipError_t launch_rows_t_fused(Kern kern, size_t lds, const FusedMlpArgs&
   return hipGetLastError();
 }
 
-// `x3`: Wp holds three bf16 pieces per weight (api.hip pack_fragments_x3_raw) and the product runs on the bf16 matrix path
+// `x3`: Wp holds three bf16 pieces per weight (api_model.hip pack_fragments_x3_raw) and the product runs on the bf16 matrix path
 hipError_t launch_blend_feat_gemm(const FeatArgs& fa, const float* Wp, float* C_t, int ldc_t, int N, bool x3,
                                   hipStream_t stream) {
   if (N > 320 || ldc_t != ((N + 31) / 32) * 32) return hipErrorInvalidValue;

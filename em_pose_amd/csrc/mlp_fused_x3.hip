@@ -18,7 +18,7 @@
 //     registers (v_cvt_pk_bf16_f32 + shift/mask + subtract: 11 VALU per pair, 88 per k-step for the two row tiles,
 //     hidden under the 48 MFMAs of the step).  Every wave splits the same A block: redundant, but free in the MFMA shadow,
 //     whereas split planes in LDS would cost 64 more KB.
-//   * B side: the weights are split ONCE at model creation (api.hip pack_fragments_x3) and stored in fragment order, per
+//   * B side: the weights are split ONCE at model creation (api_model.hip pack_fragments_x3_raw) and stored in fragment order, per
 //     (k-step, 32-column tile, piece) one 1 KB wave fragment: lane (n = lane & 31, half = lane >> 5) owns
 //     W_piece[tile * 32 + n][ks * 16 + half * 8 .. + 7].  They stream from L2 straight into a register ring, three
 //     k-steps deep; 12 KB per wave and k-step.

@@ -53,7 +53,7 @@ int main(int argc, char** argv) {
       for (auto& v : h.sc) v = 0.75f + 0.5f * (float)(rng() & 0xffff) / 65536.f;
       for (auto& v : h.sh) v = 0.1f * nd(rng);
       flops += 2.0 * T * h.N * h.K;
-      // fp32 fragment order (api.hip pack_fragments_raw)
+      // fp32 fragment order (api_model.hip pack_fragments_raw)
       const int KG = (h.K + 7) / 8, NT = (h.N + 31) / 32, KG4 = (KG + 3) & ~3;
       std::vector<float> p32((size_t)KG4 * NT * 256, 0.f);
       for (int kg = 0; kg < KG; ++kg) for (int nt = 0; nt < NT; ++nt) for (int lane = 0; lane < 64; ++lane) {

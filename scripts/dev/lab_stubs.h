@@ -1,4 +1,5 @@
-// What the stand-alone labs need from api.hip when they #include a production kernel file directly.
+// What the stand-alone labs need from api.hip (options, dynamic LDS, co-residency, the poll-timeout word) when they
+// #include a production kernel file directly.
 #pragma once
 namespace empose {
 #ifndef EMPOSE_LAB_HAS_OPTIONS

@@ -84,3 +84,37 @@ def test_cpu_tensors_raise_instead_of_falling_back():
          'offset_t': np.zeros((1, 12, 3), np.float32), 'offset_r': np.tile(np.eye(3, dtype=np.float32), (1, 12, 1, 1))}
     with pytest.raises(_lib.EmposeError):  # ... and the training path refuses CPU tensors as well
         net(SyntheticBatch(w))
+
+
+EMPOSE_EINVAL = -1   # include/empose_hip.h
+
+# The 27 kernel-variant options and their defaults (EMPOSE_OPTIONS, csrc/kernels.h).
+OPTION_DEFAULTS = {
+    'mlp_fused': 1, 'lstm_persist': 1, 'gemm_splitk': 1, 'heads_rows': 1, 'lstm_seq': 0, 'bptt_wave': 1, 'gemm_wide': 1,
+    'smpl_tile': 1, 'smpl_fuse': 1, 'train_fused': 0, 'atb_target': 0, 'atb_fast': 1, 'atb_chunk': 0,
+    'mesh_skin_mfma': 0, 'train_epi': 1, 'spin_limit': 0, 'rows_x3': 1, 'lstm_x3': 1, 'train_cols': 1, 'cols_coop': 1,
+    'mesh_x3': 1, 'train_x3': 1, 'lstm_midseq': 0, 'lstm_mid16': 1, 'lstm_mid_x3': 1, 'lstm_fewrows': 1, 'mlp_x3': 1,
+}
+
+
+def test_options_round_trip_reset_and_refuse_unknown_names():
+    lib = _lib.lib()
+    assert len(OPTION_DEFAULTS) == 27
+    lib.empose_reset_options()
+    try:
+        for name, default in OPTION_DEFAULTS.items():
+            assert lib.empose_get_option(name.encode()) == default, name
+        for i, name in enumerate(OPTION_DEFAULTS):   # every name writes its own field: distinct values, read back after all
+            assert lib.empose_set_option(name.encode(), 100 + i) == 0, name
+        for i, name in enumerate(OPTION_DEFAULTS):
+            assert lib.empose_get_option(name.encode()) == 100 + i, name
+        assert lib.empose_reset_options() == 0
+        for name, default in OPTION_DEFAULTS.items():
+            assert lib.empose_get_option(name.encode()) == default, name
+        assert lib.empose_set_option(b'no_such_option', 1) == EMPOSE_EINVAL
+        assert lib.empose_last_error() == b"unknown option 'no_such_option'"
+        assert lib.empose_get_option(b'no_such_option') == -1
+        assert lib.empose_set_option(None, 1) == EMPOSE_EINVAL
+        assert lib.empose_get_option(None) == -1
+    finally:
+        lib.empose_reset_options()

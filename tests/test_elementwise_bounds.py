@@ -196,7 +196,7 @@ def test_check_message_names_the_hazard_footprint():
 
 
 def test_lstm_grid_reaches_every_three_piece_kernel_at_its_smallest_and_largest_batch():
-    """The pruned grid of tests/test_x3_elementwise.py against the ranges of the dispatcher (api.hip)."""
+    """The pruned grid of tests/test_x3_elementwise.py against the ranges of the dispatcher (api_lstm.hip)."""
     ranges = {'x3 mid16': (9, 64), 'x3 mid': (17, 256), 'x3 chain': (257, 1024), 'x3 rows': (257, 1024),
               'x3 midseq': (4, 64)}
     reached = {}

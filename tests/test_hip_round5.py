@@ -164,7 +164,7 @@ def _randomize_bn(net, seed):
 def test_config1_launch_shape_sampled_windows_vs_oracle(big_model, B):
     """BASELINE configs[1] at its own launch shape: LGD-12 WITHOUT the RNN (MLP init networks, reference models.py:517-526),
     N = 4, 2 x 512 MLPs, B = 256 windows x 32 frames = 8192 rows, V = 6890: fused update-network kernel + the general SMPL
-    kernels + MLP init.  B = 512 crosses the T >= 16384 switch to the frame-per-lane SMPL kernels (api.hip) with MLP init.
+    kernels + MLP init.  B = 512 crosses the T >= 16384 switch to the frame-per-lane SMPL kernels (api_model.hip) with MLP init.
     Eight windows sampled across workgroup boundaries against the oracle run on those windows alone."""
     torch.manual_seed(1614785570)
     net = create_model(lgd_config(12, False, 4), SMPLLayer(big_model))

@@ -18,7 +18,7 @@ what gamma alone would need), fp32-instruction control next to the three-piece k
 
 Pruning of the LSTM grid (all of B x H x In x options would take an hour): every batch size of the issue runs once, with
 H and In rotated over {64, 256, 512} x {72, 144, 296}; options run per case only where they select a different kernel
-(`_lstm_kernel` mirrors the dispatcher of api.hip), and tests/test_elementwise_bounds.py checks that the grid reaches every
+(`_lstm_kernel` mirrors the dispatcher of api_lstm.hip), and tests/test_elementwise_bounds.py checks that the grid reaches every
 three-piece kernel at its smallest and largest batch.
 """
 import numpy as np
@@ -109,7 +109,7 @@ _LSTM_OPTIONS = [dict(lstm_x3=0), dict(), dict(lstm_x3=2), dict(lstm_mid16=0), d
 
 
 def _lstm_kernel(B, F, opts):
-    """The kernel the dispatcher of api.hip (empose_rnn_fwd, uni-directional, H % 32 == 0, In % 4 == 0) picks."""
+    """The kernel the dispatcher of api_lstm.hip (empose_rnn_fwd, uni-directional, H % 32 == 0, In % 4 == 0) picks."""
     o = dict(_LSTM_DEFAULTS, **opts)
     if F >= 4 and B <= 16 and o['lstm_persist']:
         return 'fp32 persist'
