@@ -241,6 +241,9 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'empose_mesh_vertices_fwd_bf16x3': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                                    C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'empose_mesh_vjp_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int]),
+    'empose_mesh_vjp': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

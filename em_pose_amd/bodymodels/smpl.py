@@ -3,7 +3,11 @@ SMPL-H layer (mirror of reference empose/bodymodels/smpl.py:24-165) backed by th
 
 `SMPLLayer(...)(poses_body, betas, poses_root=None, trans=None, normalize_root=False, window_size=None)` returns
 `(vertices (N,V,3), joints (N,52,3))` exactly as the reference (`body.v`, `body.Jtr`, smpl.py:121-122): the 30 hand
-joints have zero pose (smpl.py:99) and ride rigidly on the wrists.  Differences to the reference, on purpose:
+joints have zero pose (smpl.py:99) and ride rigidly on the wrists.  Like the reference's, the layer is differentiable:
+when grad is enabled and one of `poses_body`, `betas`, `poses_root`, `trans` requires grad, the outputs carry a
+`grad_fn` whose backward is empose_mesh_vjp (the full-mesh vector-Jacobian product in HIP, recomputing the forward from
+the saved poses and betas; single backward only).  Otherwise the call is the plain forward, no autograd node.
+`fk_joints` stays forward-only.  Differences to the reference, on purpose:
   * `normalize_root=True` is not implemented (never used on this path, reference smpl.py:112-119).
   * the LGD loop itself never calls this layer: `IterativeErrorFeedback` evaluates only the sensor sub-mesh.
   * `rodrigues_convention` ('smplx' | 'so3') selects how the axis-angle map guards the angle at zero; the fork that
@@ -17,6 +21,7 @@ import os
 import numpy as np
 import torch
 import torch.nn as nn
+from torch.autograd.function import once_differentiable
 
 from em_pose_amd import _lib
 from em_pose_amd.bodymodels import tables as TB
@@ -161,6 +166,14 @@ class SMPLLayer(nn.Module):
             raise NotImplementedError('normalize_root is not available on the HIP path')
         if not poses_body.is_cuda:
             raise _lib.EmposeError('SMPLLayer needs GPU tensors; there is no CPU fallback')
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad
+                                           for t in (poses_body, betas, poses_root, trans)):
+            return _MeshFK.apply(self, poses_body, betas, poses_root, trans)
+        poses, betas, trans = self._pack(poses_body, betas, poses_root, trans)
+        return self._fk_packed(poses, betas, trans)
+
+    def _pack(self, poses_body, betas, poses_root, trans):
+        """The kernel's inputs: poses [N][66] (root first), betas [N][10], trans [N][3] or None."""
         n, dev = poses_body.shape[0], poses_body.device
         if poses_root is None:
             poses_root = torch.zeros(n, 3, dtype=torch.float32, device=dev)
@@ -169,6 +182,10 @@ class SMPLLayer(nn.Module):
         betas = betas[:, :self.num_betas].contiguous().float()
         poses = torch.cat([poses_root.float(), poses_body[:, :C.N_JOINTS * 3].float()], dim=1).contiguous()
         trans = trans.contiguous().float() if trans is not None else None
+        return poses, betas, trans
+
+    def _fk_packed(self, poses, betas, trans):
+        n, dev = poses.shape[0], poses.device
         lib = _lib.lib()
         with torch.cuda.device(dev):
             handle = self._mesh_handle(dev)
@@ -181,6 +198,23 @@ class SMPLLayer(nn.Module):
                                                     _lib.dptr(vertices), _lib.dptr(joints), _lib.dptr(ws), ws_bytes,
                                                     _lib.current_stream()))
         return vertices, joints
+
+    def _vjp_packed(self, poses, betas, d_vertices, d_joints, want_trans):
+        """empose_mesh_vjp: (g_poses [N][66], g_betas [N][10], g_trans [N][3] or None) for the cotangents (either may
+        be None)."""
+        n, dev = poses.shape[0], poses.device
+        lib = _lib.lib()
+        with torch.cuda.device(dev):
+            handle = self._mesh_handle(dev)
+            g_poses = torch.empty(n, 66, dtype=torch.float32, device=dev)
+            g_betas = torch.empty(n, self.num_betas, dtype=torch.float32, device=dev)
+            g_trans = torch.empty(n, 3, dtype=torch.float32, device=dev) if want_trans else None
+            ws_bytes = lib.empose_mesh_vjp_workspace_bytes(handle, n)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.empose_mesh_vjp(handle, n, _lib.dptr(poses), _lib.dptr(betas), _lib.dptr(d_vertices),
+                                           _lib.dptr(d_joints), _lib.dptr(g_poses), _lib.dptr(g_betas),
+                                           _lib.dptr(g_trans), _lib.dptr(ws), ws_bytes, _lib.current_stream()))
+        return g_poses, g_betas, g_trans
 
     def fk_joints(self, poses_body, betas, poses_root=None, trans=None):
         """The 22 posed body joints only (no vertices): forward kinematics for the metrics, (N,22,3) contiguous
@@ -214,6 +248,51 @@ class SMPLLayer(nn.Module):
 
     def forward(self, *args, **kwargs):
         return self.fk(*args, **kwargs)
+
+
+class _MeshFK(torch.autograd.Function):
+    """`SMPLLayer._fk` under autograd: the forward runs the HIP kernels as without grad; the backward is
+    empose_mesh_vjp, which recomputes what it needs from the packed poses and betas (the only saved tensors)."""
+
+    @staticmethod
+    def forward(ctx, layer, poses_body, betas, poses_root, trans):
+        poses, betas_p, trans_p = layer._pack(poses_body, betas, poses_root, trans)
+        ctx.layer = layer
+        ctx.save_for_backward(poses, betas_p)
+        ctx.body_shape, ctx.body_dtype = tuple(poses_body.shape), poses_body.dtype
+        ctx.betas_shape, ctx.betas_dtype = tuple(betas.shape), betas.dtype
+        ctx.betas_broadcast = betas.dim() == 1 or betas.shape[0] == 1
+        ctx.has_root, ctx.has_trans = poses_root is not None, trans is not None
+        ctx.root_dtype = poses_root.dtype if poses_root is not None else None
+        ctx.trans_dtype = trans.dtype if trans is not None else None
+        ctx.set_materialize_grads(False)
+        return layer._fk_packed(poses, betas_p, trans_p)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_vertices, d_joints):
+        if d_vertices is None and d_joints is None:
+            return None, None, None, None, None
+        poses, betas = ctx.saved_tensors
+        dv = d_vertices.contiguous().float() if d_vertices is not None else None
+        dj = d_joints.contiguous().float() if d_joints is not None else None
+        g_poses, g_betas, g_trans = ctx.layer._vjp_packed(poses, betas, dv, dj, ctx.has_trans)
+        nb = g_betas.shape[1]
+        g_body = g_root = g_b = g_t = None
+        if ctx.needs_input_grad[1]:
+            g_body = torch.zeros(ctx.body_shape, dtype=ctx.body_dtype, device=poses.device)
+            g_body[:, :C.N_JOINTS * 3] = g_poses[:, 3:]
+        if ctx.needs_input_grad[2]:
+            g_b = torch.zeros(ctx.betas_shape, dtype=ctx.betas_dtype, device=poses.device)
+            if ctx.betas_broadcast:   # `_pack` repeated one row for every frame
+                g_b.view(-1)[:nb] = g_betas.sum(dim=0)
+            else:
+                g_b[:, :nb] = g_betas
+        if ctx.needs_input_grad[3] and ctx.has_root:
+            g_root = g_poses[:, :3].to(ctx.root_dtype)
+        if ctx.needs_input_grad[4] and ctx.has_trans:
+            g_t = g_trans.to(ctx.trans_dtype)
+        return None, g_body, g_b, g_root, g_t
 
 
 def create_default_smpl_model(device=None, vposer_path=None):

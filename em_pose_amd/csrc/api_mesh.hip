@@ -22,6 +22,10 @@ struct empose_mesh {
   unsigned short* wc_bf16 = nullptr;   // split-bf16 pieces of wc in fragment order (only when the handle asked for them)
   unsigned short* wc_x3 = nullptr;     // three bf16 pieces of wc in fragment order (mesh_x3.hip), kb <= 4
   unsigned short* skin_bf16 = nullptr; // dense skin weights per 32-vertex tile, bf16 hi + lo, B-fragment order (ditto)
+  float* wc_vjp = nullptr;      // vertex rows of wc in the VJP feat sweep's B-fragment order (mesh_vjp.hip)
+  float* skin_dense = nullptr;  // dense skin weights per tile in the VJP bone sweep's B-fragment order (ditto)
+  float* wj_t = nullptr;        // rest-joint rows of wc transposed: [200][jw4], the reverse of the rest-joint gemm
+  int jw4 = 0;                  // ncp - j_off rounded up to 4
 };
 
 namespace {
@@ -142,6 +146,52 @@ int pack_mesh_tiles_bf16(empose_mesh* m, const empose_mesh_desc* d) {
   return EMPOSE_OK;
 }
 
+// Tables of the vector-Jacobian product (mesh_vjp.hip, api: empose_mesh_vjp), packed with the handle:
+//   wc_vjp     per tile, vertex pair p (vertices p and 16 + p), q < 6, lane (j = lane & 31, h = lane >> 5), e < 4: the
+//              entry q * 4 + e = c * 8 + ct is wc[(tile * 32 + 16 h + p) * 3 + c][ct * 32 + j] (ct = 7, features past 200
+//              and vertices past V: zero)
+//   skin_dense per tile, q < 4, lane (j, h), e < 4: the summed weight of bone j at vertex tile * 32 + e + 8 q + 4 h; slots
+//              past the 22 bones zero
+//   wj_t       [200][jw4]: wj_t[k][i] = wc[j_off + i][k], zero for i >= ncp - j_off
+int pack_mesh_vjp(empose_mesh* m, const empose_mesh_desc* d) {
+  const int V = d->n_vertices, NT = (V + 31) / 32, K = 200;
+  std::vector<float> wv((size_t)NT * MESH_VJP_WC_TILE_FLOATS, 0.f);
+  for (int t = 0; t < NT; ++t)
+    for (int p = 0; p < 16; ++p)
+      for (int q = 0; q < 6; ++q)
+        for (int lane = 0; lane < 64; ++lane)
+          for (int e = 0; e < 4; ++e) {
+            const int idx = q * 4 + e, c = idx / 8, ct = idx % 8, col = ct * 32 + (lane & 31);
+            const int v = t * 32 + 16 * (lane >> 5) + p;
+            if (ct == 7 || col >= K || v >= V) continue;
+            wv[(size_t)t * MESH_VJP_WC_TILE_FLOATS + (((size_t)p * 6 + q) * 64 + lane) * 4 + e] =
+                d->wc[((size_t)v * 3 + c) * K + col];
+          }
+  TRY(upload(m->allocs, wv.data(), wv.size(), &m->wc_vjp));
+  std::vector<float> sd((size_t)NT * MESH_VJP_SKIN_TILE_FLOATS, 0.f);
+  for (int t = 0; t < NT; ++t)
+    for (int q = 0; q < 4; ++q)
+      for (int lane = 0; lane < 64; ++lane)
+        for (int e = 0; e < 4; ++e) {
+          const int v = t * 32 + e + 8 * q + 4 * (lane >> 5), j = lane & 31;
+          if (v >= V) continue;
+          float w = 0.f;
+          for (int k = 0; k < d->kb && j < NB; ++k) {
+            const int b = d->skin_idx[(size_t)v * d->kb + k];
+            if (b < 0 || b >= NB) return fail(EMPOSE_EINVAL, "skin index %d of vertex %d outside the %d body bones", b, v, NB);
+            if (b == j) w += d->skin_w[(size_t)v * d->kb + k];
+          }
+          sd[(size_t)t * MESH_VJP_SKIN_TILE_FLOATS + ((size_t)q * 64 + lane) * 4 + e] = w;
+        }
+  TRY(upload(m->allocs, sd.data(), sd.size(), &m->skin_dense));
+  const int jw = d->ncp - d->j_off;
+  m->jw4 = (jw + 3) / 4 * 4;
+  std::vector<float> wj((size_t)K * m->jw4, 0.f);
+  for (int k = 0; k < K; ++k)
+    for (int i = 0; i < jw; ++i) wj[(size_t)k * m->jw4 + i] = d->wc[((size_t)d->j_off + i) * K + k];
+  return upload(m->allocs, wj.data(), wj.size(), &m->wj_t);
+}
+
 const int MESH_SLAB = 16384;  // frames per pass: bounds the scratch (rot, feat, rest joints, transforms)
 
 struct MeshWs { float *rot, *feat, *jrest, *xf; };
@@ -201,6 +251,31 @@ int run_mesh(const empose_mesh_t* mesh, int T, const float* poses, const float* 
     if (e != hipSuccess) return fail(EMPOSE_EHIP, "fused mesh kernel: %s", hipGetErrorString(e));
   }
   return EMPOSE_OK;
+}
+
+// Scratch of empose_mesh_vjp for a slab of S frames: the forward's, then the reverse's cotangents; `part` holds the
+// per-slice partial sums of a vertex sweep split over grid.y (small slabs only).
+struct MeshVjpWs { MeshWs f; float *dfeat_v, *dA, *part, *drot, *djrest, *dfeat; double* dtrans; };
+size_t vjp_part_floats(const empose_mesh* mesh, int n) {
+  if (n <= 0) return 0;
+  const int sf = mesh_vjp_feat_split(n, mesh->V), sb = mesh_vjp_bone_split(n, mesh->V);
+  return std::max(sf > 1 ? (size_t)sf * 200 : 0, sb > 1 ? (size_t)sb * MESH_VJP_DA : 0) * n;
+}
+MeshVjpWs carve_mesh_vjp(Carver& c, const empose_mesh* mesh, int T) {
+  const int S = T < MESH_SLAB ? T : MESH_SLAB;
+  MeshVjpWs w;
+  w.f = carve_mesh(c, mesh, (size_t)S);
+  w.dfeat_v = c.f((size_t)S * 200);
+  w.dA = c.f((size_t)S * MESH_VJP_DA);
+  // sized for the full slabs and for the last, shorter one (a smaller slab may split its sweeps further)
+  const size_t part = std::max(vjp_part_floats(mesh, S), vjp_part_floats(mesh, T % S));
+  w.part = part ? c.f(part) : nullptr;
+  const int ns = std::max(mesh_vjp_feat_split(S, mesh->V), T % S ? mesh_vjp_feat_split(T % S, mesh->V) : 1);
+  w.dtrans = reinterpret_cast<double*>(c.f((size_t)ns * S * 3 * 2));
+  w.drot = c.f((size_t)S * NB * 9);
+  w.djrest = c.f((size_t)S * mesh->jw4);
+  w.dfeat = c.f((size_t)S * 200);
+  return w;
 }
 
 }  // namespace
@@ -263,7 +338,7 @@ int empose_mesh_create(const empose_mesh_desc* d, empose_mesh_t** out) {
       (rc = upload(m->allocs, d->skin_w, (size_t)d->n_vertices * d->kb, &m->skin_w)) ||
       (rc = upload(m->allocs, d->parents, (size_t)nj, &m->parents)) || (rc = pack_mesh_tiles(m, d)) ||
       (d->kb <= 4 && (rc = pack_mesh_tiles_x3(m, d))) ||
-      (d->with_bf16x3 && (rc = pack_mesh_tiles_bf16(m, d)))) {
+      (d->with_bf16x3 && (rc = pack_mesh_tiles_bf16(m, d))) || (rc = pack_mesh_vjp(m, d))) {
     empose_mesh_destroy(m);
     return rc;
   }
@@ -306,6 +381,89 @@ int empose_mesh_joints_fwd(const empose_mesh_t* mesh, int T, const float* poses,
   if (T <= 0) return fail(EMPOSE_EINVAL, "T must be positive");
   if (workspace_bytes < empose_mesh_workspace_bytes(mesh, T)) return fail(EMPOSE_ENOMEM, "workspace too small");
   return run_mesh(mesh, T, poses, betas, trans, nullptr, joints, workspace, static_cast<hipStream_t>(stream_));
+}
+
+// ---- full-mesh vector-Jacobian product -------------------------------------------------------------------------
+size_t empose_mesh_vjp_workspace_bytes(const empose_mesh_t* mesh, int T) {
+  if (!mesh || T <= 0) return 0;
+  Carver c(nullptr);
+  carve_mesh_vjp(c, mesh, T);
+  return c.off;
+}
+
+int empose_mesh_vjp(const empose_mesh_t* mesh, int T, const float* poses, const float* betas, const float* d_vertices,
+                    const float* d_joints, float* g_poses, float* g_betas, float* g_trans, void* workspace,
+                    size_t workspace_bytes, empose_stream_t stream_) {
+  if (!mesh || !poses || !betas || !g_poses || !g_betas) return fail(EMPOSE_EINVAL, "null argument");
+  if (T <= 0) return fail(EMPOSE_EINVAL, "T must be positive");
+  if (!d_vertices && !d_joints) return fail(EMPOSE_EINVAL, "d_vertices and d_joints are both NULL");
+  if (!workspace || workspace_bytes < empose_mesh_vjp_workspace_bytes(mesh, T))
+    return fail(EMPOSE_EINVAL, "workspace too small (empose_mesh_vjp_workspace_bytes)");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const int S = T < MESH_SLAB ? T : MESH_SLAB;
+  const int jw = mesh->ncp - mesh->j_off, nj = mesh->n_joints;
+  Carver c(workspace);
+  const MeshVjpWs w = carve_mesh_vjp(c, mesh, T);
+  for (int t0 = 0; t0 < T; t0 += S) {
+    const int n = (T - t0) < S ? (T - t0) : S;
+    // the forward's rotations, features, rest joints and transforms (as run_mesh)
+    FeatArgs fa;
+    fa.theta = const_cast<float*>(poses) + (size_t)t0 * 66; fa.ld_theta = 66;
+    fa.beta = const_cast<float*>(betas) + (size_t)t0 * 10; fa.ld_beta = 10;
+    fa.d_theta = nullptr; fa.d_beta = nullptr; fa.theta_step = 0.f; fa.beta_keep = 1.f; fa.beta_step = 0.f;
+    fa.shape_avg = 0; fa.rot = w.f.rot; fa.feat = w.f.feat;
+    fa.out_theta = fa.out_beta = fa.out_theta2 = fa.out_beta2 = nullptr;
+    fa.T = n; fa.F = 1; fa.rod_conv = mesh->rod_conv;
+    HIP_CHECK(launch_update_feat(fa, stream), "update_feat kernel");
+    GemmBatch b;
+    b.count = 1;
+    GemmProb& p = b.p[0];
+    p.A = w.f.feat; p.lda = 200; p.W = mesh->wc + (size_t)mesh->j_off * 200; p.ldw = 200; p.C = w.f.jrest; p.ldc = jw;
+    p.M = n; p.N = jw; p.K = 200;
+    p.scale = nullptr; p.shift = nullptr; p.resid = nullptr; p.ldr = 0; p.act = 0; p.slope = 0.f;
+    HIP_CHECK(launch_gemm(b, stream), "rest-joint gemm");
+    const float* dv = d_vertices ? d_vertices + (size_t)t0 * mesh->V * 3 : nullptr;
+    if (dv) {
+      // the transforms; the posed joints are not needed and land in the reverse's scratch, which is written later
+      MeshChainArgs ca;
+      ca.rot = w.f.rot; ca.out = w.f.jrest; ca.ncp = jw; ca.j_off = 0; ca.parents = mesh->parents;
+      ca.trans = nullptr; ca.xf = w.f.xf; ca.joints = w.dfeat; ca.T = n; ca.n_joints = nj;
+      static_assert(MESH_MAX_JOINTS * 3 <= 200, "posed joints fit a feature row");
+      HIP_CHECK(launch_mesh_chain(ca, stream), "mesh chain");
+      MeshVjpArgs va;
+      va.feat = w.f.feat; va.xf = w.f.xf; va.dv = dv;
+      va.wc_frag = mesh->wc_frag; va.wc_vjp = mesh->wc_vjp; va.skin_dense = mesh->skin_dense;
+      va.skin_idx4 = mesh->skin_idx4; va.skin_w4 = mesh->skin_w4; va.skin_idx = mesh->skin_idx; va.skin_w = mesh->skin_w;
+      va.kb = mesh->kb; va.part = w.part; va.dtrans = w.dtrans; va.T = n; va.V = mesh->V;
+      va.out = w.dfeat_v;
+      HIP_CHECK(launch_mesh_vjp_feat(va, stream), "mesh VJP feat sweep");
+      va.out = w.dA;
+      HIP_CHECK(launch_mesh_vjp_bone(va, stream), "mesh VJP bone sweep");
+    }
+    MeshChainBwdArgs cb;
+    cb.rot = w.f.rot; cb.jrest = w.f.jrest; cb.ld_j = jw; cb.parents = mesh->parents;
+    cb.dA = dv ? w.dA : nullptr;
+    cb.dtrans = dv ? w.dtrans : nullptr; cb.n_slices = mesh_vjp_feat_split(n, mesh->V);
+    cb.dJ = d_joints ? d_joints + (size_t)t0 * nj * 3 : nullptr;
+    cb.d_rot = w.drot; cb.d_jrest = w.djrest; cb.ld_dj = mesh->jw4;
+    cb.g_trans = g_trans ? g_trans + (size_t)t0 * 3 : nullptr;
+    cb.T = n; cb.n_joints = nj;
+    HIP_CHECK(launch_mesh_chain_bwd(cb, stream), "mesh chain reverse");
+    // d_feat = (vertex sweep) + d_jrest . wc[j_off:]
+    GemmBatch g;
+    g.count = 1;
+    GemmProb& q = g.p[0];
+    q.A = w.djrest; q.lda = mesh->jw4; q.W = mesh->wj_t; q.ldw = mesh->jw4; q.C = w.dfeat; q.ldc = 200;
+    q.M = n; q.N = 200; q.K = mesh->jw4;
+    q.scale = nullptr; q.shift = nullptr; q.resid = dv ? w.dfeat_v : nullptr; q.ldr = 200; q.act = 0; q.slope = 0.f;
+    HIP_CHECK(launch_gemm(g, stream), "rest-joint reverse gemm");
+    RodBwdArgs ra;
+    ra.theta = poses + (size_t)t0 * 66; ra.ld_theta = 66; ra.d_rot = w.drot; ra.d_feat = w.dfeat;
+    ra.g_theta = g_poses + (size_t)t0 * 66; ra.ld_g = 66; ra.g_beta = g_betas + (size_t)t0 * 10; ra.ld_gb = 10;
+    ra.trace_g_theta = ra.trace_g_beta = nullptr; ra.T = n; ra.rod_conv = mesh->rod_conv;
+    HIP_CHECK(launch_rodrigues_bwd(ra, stream), "rodrigues_bwd kernel");
+  }
+  return EMPOSE_OK;
 }
 
 }  // extern "C"

@@ -751,6 +751,50 @@ constexpr int MESH_SKIN_BF16_TILE_BYTES = 2 * 2 * 1024;
 hipError_t launch_mesh_rows_x3(const MeshSkinArgs& a, bool overlap, hipStream_t stream);
 constexpr int MESH_X3_TILE_BYTES = 13 * 9 * 1024;
 
+// Full-mesh vector-Jacobian product (mesh_vjp.hip): the two vertex sweeps of the reverse for a cotangent dV [T][V][3].
+//   feat sweep: d_feat[t][k] = sum_v,c dvp[t][v][c] wc[3v+c][k], dvp_v = sum_b w_vb (A_b^R)^T dV_v   -> out [T][200]
+//   bone sweep: dA_b[t][r][c] = sum_v w_vb dV_v[r] [vp_v; 1][c]                                       -> out [T][22][12]
+//   the feat sweep also sums dV over the vertices in double precision (the translation's cotangent)   -> dtrans
+// Deterministic: fixed-order sums only.  With mesh_vjp_split(..) > 1 the vertex tiles are split over grid.y and the
+// partials ([split][T][cols] in `part`) are summed in slot order by a second launch.
+constexpr int MESH_VJP_BM = 32;            // frames per workgroup of both sweeps
+constexpr int MESH_VJP_DA = NB * 12;       // bone-sweep output columns per frame
+constexpr int MESH_VJP_WC_TILE_FLOATS = 16 * 6 * 64 * 4;   // wc_vjp per 32-vertex tile: [16 vertex pairs][6][64 lanes][4]
+constexpr int MESH_VJP_SKIN_TILE_FLOATS = 4 * 64 * 4;      // skin_dense per tile: [4][64 lanes][4]
+struct MeshVjpArgs {
+  const float* feat;           // [T][200]
+  const float* xf;             // [T][22][3][4] (mesh_chain_kernel)
+  const float* dv;             // [T][V][3]
+  const float* wc_frag;        // forward fragment order (MeshSkinArgs::wc_frag), bone sweep
+  const float* wc_vjp;         // vertex rows of wc in the feat sweep's B-fragment order (api_mesh.hip pack_mesh_vjp)
+  const float* skin_dense;     // dense bone weights per tile in the bone sweep's B-fragment order (ditto)
+  const int* skin_idx4; const float* skin_w4;   // [tiles * 32][4]
+  const int* skin_idx; const float* skin_w; int kb;
+  float* out;                  // [T][200] (feat sweep) or [T][MESH_VJP_DA] (bone sweep)
+  float* part;                 // [split][T][cols] scratch when the sweep is split over grid.y
+  double* dtrans;              // feat sweep: [split][T][3], sum_v dV_v over the slice's vertices
+  int T, V;
+};
+int mesh_vjp_feat_split(int T, int V);
+int mesh_vjp_bone_split(int T, int V);
+hipError_t launch_mesh_vjp_feat(const MeshVjpArgs& a, hipStream_t stream);
+hipError_t launch_mesh_vjp_bone(const MeshVjpArgs& a, hipStream_t stream);
+// Reverse kinematic chain (smpl.hip, beside mesh_chain_kernel): one thread per frame recomputes the 22 global rotations
+// and takes dA (bone sweep) and the joint cotangents back to d_rot, the rest-joint cotangents and d_trans.
+struct MeshChainBwdArgs {
+  const float* rot;            // [T][22][9]
+  const float* jrest; int ld_j;    // rest joints [T][ld_j], n_joints * 3 used
+  const int* parents;          // [n_joints]
+  const float* dA;             // [T][MESH_VJP_DA] or nullptr
+  const float* dJ;             // [T][n_joints][3] or nullptr
+  const double* dtrans; int n_slices;   // [n_slices][T][3] (feat sweep) or nullptr
+  float* d_rot;                // [T][22][9]
+  float* d_jrest; int ld_dj;   // [T][ld_dj]; columns past n_joints * 3 are written as zeros
+  float* g_trans;              // [T][3] or nullptr
+  int T, n_joints;
+};
+hipError_t launch_mesh_chain_bwd(const MeshChainBwdArgs& a, hipStream_t stream);
+
 struct VirtualSensorArgs {
   const float* vertices;   // [T][V][3]
   const int* center; const int* helper; const int* deg; const int* faces;  // [M], [M], [M], [M][max_deg][3] (mesh ids)

@@ -637,6 +637,25 @@ int empose_mesh_joints_fwd(const empose_mesh_t* mesh, int T, const float* poses,
                            const float* trans, float* joints, void* workspace, size_t workspace_bytes,
                            empose_stream_t stream);
 
+/* Vector-Jacobian product of empose_mesh_vertices_fwd (what autograd of the reference's SMPLLayer computes): for the
+ * cotangents d_vertices [T][V][3] and/or d_joints [T][n_joints][3] (either may be NULL, not both) it writes
+ * g_poses [T][66] and g_betas [T][10], and g_trans [T][3] unless NULL (the gradient with respect to trans, which the
+ * forward adds to every vertex and joint).  It recomputes the forward's rotations, features, rest joints and transforms
+ * from poses and betas; nothing is saved from the forward.  The gradient is that of the exact function, fp32 throughout
+ * (csrc/mesh_vjp.hip: the two vertex sweeps on the fp32 MFMA instruction; smpl.hip: the reverse kinematic chain), whatever
+ * arithmetic the forward of the handle uses.  Deterministic: repeated calls give the same bits.
+ * Workspace: empose_mesh_vjp_workspace_bytes(mesh, T) -- about 8.2 KB per frame of a slab of min(T, 16384) frames for
+ * SMPL-H (the forward's scratch, the sweeps' outputs and the reverse's cotangents); below 8192 frames the vertex sweeps
+ * split the mesh over more workgroups and add per-slice partial sums (at most about 4.5 MB more).
+ * Every handle carries the reverse's tables (packed by empose_mesh_create): per 32-vertex tile 96 KB of coefficients in
+ * the feat sweep's fragment order and 4 KB of dense skin weights, plus the rest-joint rows transposed, 200 x (ncp - j_off)
+ * floats: 22 MB for SMPL-H (V = 6890).  Returns EMPOSE_EINVAL for a NULL handle, poses, betas, g_poses or g_betas, T <= 0,
+ * both cotangents NULL or a workspace that is too small, before any GPU work. */
+size_t empose_mesh_vjp_workspace_bytes(const empose_mesh_t* mesh, int T);
+int empose_mesh_vjp(const empose_mesh_t* mesh, int T, const float* poses, const float* betas, const float* d_vertices,
+                    const float* d_joints, float* g_poses, float* g_betas, float* g_trans, void* workspace,
+                    size_t workspace_bytes, empose_stream_t stream);
+
 /* ---- evaluation metrics ------------------------------------------------------------------------ */
 /* Per frame: 22 Euclidean joint distances, 22 distances after similarity-Procrustes alignment of the prediction onto
  * the ground truth, and 21 geodesic angles (degrees) between global joint orientations with the root fixed to the
