@@ -223,6 +223,10 @@ SIGNATURES = {
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'empose_virtual_sensors_fwd': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    'empose_virtual_sensors_vjp_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'empose_virtual_sensors_vjp': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 +
+                                            [C.c_int] + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 6 +
+                                            [C.c_size_t, C.c_void_p]),
     'empose_profile_enable': (C.c_int, [C.c_int]),
     'empose_profile_enable_only': (C.c_int, [C.c_char_p]),
     'empose_profile_ntags': (C.c_int, []),

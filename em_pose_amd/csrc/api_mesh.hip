@@ -278,6 +278,14 @@ MeshVjpWs carve_mesh_vjp(Carver& c, const empose_mesh* mesh, int T) {
   return w;
 }
 
+// Frames per pass of empose_virtual_sensors_vjp: the scratch (nine floats per frame and sensor) stays below 128 MB
+// whatever T and M, and a slab never exceeds MESH_SLAB frames.
+int sensors_vjp_slab(int T, int M) {
+  const size_t cap = ((size_t)128 << 20) / (sizeof(float) * SENSOR_VJP_ROW * (size_t)M);
+  const size_t s = std::min<size_t>({(size_t)T, (size_t)MESH_SLAB, std::max<size_t>(cap, 1)});
+  return (int)s;
+}
+
 }  // namespace
 
 extern "C" {
@@ -291,6 +299,50 @@ int empose_virtual_sensors_fwd(int T, int V, const float* vertices, int M, int m
   a.vertices = vertices; a.center = center; a.helper = helper; a.deg = deg; a.faces = faces;
   a.pos = pos; a.ori = ori; a.normals = normals; a.T = T; a.V = V; a.M = M; a.max_deg = max_deg;
   HIP_CHECK(launch_virtual_sensors(a, static_cast<hipStream_t>(stream_)), "virtual sensors kernel");
+  return EMPOSE_OK;
+}
+
+// ---- virtual sensors: vector-Jacobian product --------------------------------------------------------------------
+size_t empose_virtual_sensors_vjp_workspace_bytes(int T, int M) {
+  if (T <= 0 || M <= 0) return 0;
+  Carver c(nullptr);
+  c.f((size_t)sensors_vjp_slab(T, M) * M * SENSOR_VJP_ROW);
+  return c.off;
+}
+
+int empose_virtual_sensors_vjp(int T, int V, const float* vertices, int M, int max_deg, const int* center,
+                               const int* helper, const int* deg, const int* faces, int n_sub_faces,
+                               const int* sub_faces, const int* face_ptr, const int* face_sensors, const int* vf_ptr,
+                               const int* vf_corner, const int* vs_ptr, const int* vs_role, int n_touched,
+                               const int* touched, const float* d_pos, const float* d_ori, const float* d_normals,
+                               float* d_vertices, void* workspace, size_t workspace_bytes, empose_stream_t stream_) {
+  if (!vertices || !center || !helper || !deg || !faces || !sub_faces || !face_ptr || !face_sensors || !vf_ptr ||
+      !vf_corner || !vs_ptr || !vs_role || !touched || !d_vertices)
+    return fail(EMPOSE_EINVAL, "null argument");
+  if (T <= 0 || V <= 0 || M <= 0 || max_deg <= 0 || n_sub_faces <= 0 || n_touched <= 0)
+    return fail(EMPOSE_EINVAL, "sizes must be positive");
+  if (!d_pos && !d_ori && !d_normals) return fail(EMPOSE_EINVAL, "d_pos, d_ori and d_normals are all NULL");
+  if (!workspace || workspace_bytes < empose_virtual_sensors_vjp_workspace_bytes(T, M))
+    return fail(EMPOSE_EINVAL, "workspace too small (empose_virtual_sensors_vjp_workspace_bytes)");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const int S = sensors_vjp_slab(T, M);
+  SensorVjpArgs a;
+  a.center = center; a.helper = helper; a.deg = deg; a.faces = faces;
+  a.sub_faces = sub_faces; a.face_ptr = face_ptr; a.face_sensors = face_sensors;
+  a.vf_ptr = vf_ptr; a.vf_corner = vf_corner; a.vs_ptr = vs_ptr; a.vs_role = vs_role;
+  a.touched = touched; a.n_touched = n_touched;
+  a.scratch = static_cast<float*>(workspace);
+  a.V = V; a.M = M; a.max_deg = max_deg;
+  for (int t0 = 0; t0 < T; t0 += S) {
+    const size_t r = (size_t)t0 * M;
+    a.T = (T - t0) < S ? (T - t0) : S;
+    a.vertices = vertices + (size_t)t0 * V * 3;
+    a.d_vertices = d_vertices + (size_t)t0 * V * 3;
+    a.d_pos = d_pos ? d_pos + r * 3 : nullptr;
+    a.d_ori = d_ori ? d_ori + r * 9 : nullptr;
+    a.d_normals = d_normals ? d_normals + r * 3 : nullptr;
+    HIP_CHECK(launch_sensors_vjp(a, stream), "virtual sensors VJP kernels");
+  }
   return EMPOSE_OK;
 }
 

@@ -802,6 +802,24 @@ struct VirtualSensorArgs {
   int T, V, M, max_deg;
 };
 hipError_t launch_virtual_sensors(const VirtualSensorArgs& a, hipStream_t stream);
+// Vector-Jacobian product of virtual_sensors_kernel (sensors_vjp.hip) for one slab of T frames: a sensor pass writes
+// SENSOR_VJP_ROW floats per (frame, sensor) to `scratch` (dn / deg, the center's and the helper's cotangents), a vertex
+// pass writes every element of d_vertices.  Reverse tables (api: empose_virtual_sensors_vjp): sub_faces [Fs][3],
+// face_ptr [Fs + 1] / face_sensors (ascending), vf_ptr [V + 1] / vf_corner (f * 3 + k, ascending f), vs_ptr [V + 1] /
+// vs_role (m * 2 + role, role 0 center, 1 helper, ascending), touched [n_touched].
+constexpr int SENSOR_VJP_ROW = 9;
+struct SensorVjpArgs {
+  const float* vertices;   // [T][V][3]
+  const int* center; const int* helper; const int* deg; const int* faces;   // the forward's tables
+  const int* sub_faces; const int* face_ptr; const int* face_sensors;
+  const int* vf_ptr; const int* vf_corner; const int* vs_ptr; const int* vs_role;
+  const int* touched; int n_touched;   // the vertices with entries in vf / vs, ascending
+  const float* d_pos; const float* d_ori; const float* d_normals;   // [T][M][3], [T][M][9], [T][M][3], each or nullptr
+  float* scratch;          // [T][M][SENSOR_VJP_ROW]
+  float* d_vertices;       // [T][V][3]
+  int T, V, M, max_deg;
+};
+hipError_t launch_sensors_vjp(const SensorVjpArgs& a, hipStream_t stream);
 
 struct MetricsArgs {
   const float* joints_gt; const float* joints_hat;   // [T][22][3]

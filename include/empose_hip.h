@@ -575,6 +575,35 @@ int empose_virtual_sensors_fwd(int T, int V, const float* vertices, int M, int m
                                const int* helper, const int* deg, const int* faces, float* pos, float* ori,
                                float* normals, empose_stream_t stream);
 
+/* Vector-Jacobian product of empose_virtual_sensors_fwd (what autograd of the reference's VirtualMarkerHelper and
+ * vertex normals computes): for the cotangents d_pos [T][M][3], d_ori [T][M][3][3] and d_normals [T][M][3] (any may be
+ * NULL, not all three) it writes d_vertices [T][V][3], every element: vertices no sensor touches get 0.  It recomputes
+ * the forward from `vertices`; nothing is saved from the forward.  fp32 throughout (csrc/sensors_vjp.hip: one pass per
+ * (frame, sensor), one per (frame, mesh vertex)); deterministic: every destination sums its terms in the fixed order of
+ * the tables below, no atomics, so repeated calls give the same bits.  No limit on max_deg.
+ * Tables: the forward's center/helper/deg [M] and faces [M][max_deg][3], and the reverse's, all DEVICE int32:
+ *   sub_faces     [n_sub_faces][3]   the distinct faces incident to the sensor vertices, mesh vertex ids, corners in
+ *                                    the mesh's order (every face of `faces` is one of them)
+ *   face_ptr      [n_sub_faces + 1]  CSR over sub-faces: face_sensors[face_ptr[f] .. face_ptr[f + 1]) are the sensors m
+ *   face_sensors                     whose `faces` rows hold sub-face f, ascending m
+ *   vf_ptr        [V + 1]            CSR over mesh vertices: vf_corner[vf_ptr[u] .. vf_ptr[u + 1]) = f * 3 + k for every
+ *   vf_corner                        sub-face f whose corner k is u, ascending f
+ *   vs_ptr        [V + 1]            CSR over mesh vertices: vs_role[vs_ptr[u] .. vs_ptr[u + 1]) = m * 2 + role for every
+ *   vs_role                          sensor m with center[m] == u (role 0) or helper[m] == u (role 1), ascending
+ *   touched       [n_touched]        the vertices u with entries in either CSR, ascending.  When they are at most a
+ *                                    quarter of the mesh, d_vertices is cleared and only their rows are computed
+ * Workspace: empose_virtual_sensors_vjp_workspace_bytes(T, M) -- 36 bytes per (frame, sensor) for a slab of frames
+ * capped at 16384 and at 128 MB (0 for T or M <= 0).  Returns EMPOSE_EINVAL for a NULL vertex, table or d_vertices
+ * pointer, T, V, M, max_deg, n_sub_faces or n_touched <= 0, all three cotangents NULL or a workspace that is too
+ * small, before any GPU work.  Indices are not checked: the tables must be consistent with V and M. */
+size_t empose_virtual_sensors_vjp_workspace_bytes(int T, int M);
+int empose_virtual_sensors_vjp(int T, int V, const float* vertices, int M, int max_deg, const int* center,
+                               const int* helper, const int* deg, const int* faces, int n_sub_faces,
+                               const int* sub_faces, const int* face_ptr, const int* face_sensors, const int* vf_ptr,
+                               const int* vf_corner, const int* vs_ptr, const int* vs_role, int n_touched,
+                               const int* touched, const float* d_pos, const float* d_ori, const float* d_normals,
+                               float* d_vertices, void* workspace, size_t workspace_bytes, empose_stream_t stream);
+
 /* ---- optional per-launch timing ------------------------------------------------------------------------------- */
 /* While enabled, every kernel launch issued by the entry points above is bracketed by HIP events on the launch stream
  * and attributed to one of empose_profile_ntags() categories (GEMMs by role, LSTM step, chain kernel, ...).
