@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get('EMPOSE_LIB_PATH') or os.path.join(_HERE, 'csrc', 'lib
 
 MAX_DENSE = 8
 RODRIGUES = {'smplx': 0, 'so3': 1}   # EMPOSE_RODRIGUES_* (include/empose_hip.h)
+ROOT_FRAME_ROTATE, ROOT_FRAME_SUBTRACT = 1, 2   # EMPOSE_ROOT_FRAME_*
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
 
@@ -248,6 +249,11 @@ SIGNATURES = {
     'empose_mesh_vjp_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int]),
     'empose_mesh_vjp': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    'empose_root_frame_fwd': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                        C.c_int, C.c_void_p]),
+    'empose_root_frame_vjp_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'empose_root_frame_vjp': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 +
+                                       [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

@@ -7,8 +7,14 @@ joints have zero pose (smpl.py:99) and ride rigidly on the wrists.  Like the ref
 when grad is enabled and one of `poses_body`, `betas`, `poses_root`, `trans` requires grad, the outputs carry a
 `grad_fn` whose backward is empose_mesh_vjp (the full-mesh vector-Jacobian product in HIP, recomputing the forward from
 the saved poses and betas; single backward only).  Otherwise the call is the plain forward, no autograd node.
-`fk_joints` stays forward-only.  Differences to the reference, on purpose:
-  * `normalize_root=True` is not implemented (never used on this path, reference smpl.py:112-119).
+`fk_joints` stays forward-only.  `normalize_root=True` re-expresses the sequence in the frame of its first root
+orientation and position (reference smpl.py:112-119) with the root-frame kernel (csrc/root_frame.hip) in front of the mesh
+kernels; under autograd it is a node of its own in front of the mesh node, with empose_root_frame_vjp as its backward.
+Differences to the reference, on purpose:
+  * `normalize_root=True`: the exponential map follows `rodrigues_convention`, the logarithm is accurate up to pi, and
+    the backward is the derivative of the exact maps, finite at the first frame, where the reference's acos-based
+    `so3_log_map` yields 0 * inf.  The translation keeps the shape (N, 3) for N = 1 too, where
+    the reference's `.squeeze()` collapses it.
   * the LGD loop itself never calls this layer: `IterativeErrorFeedback` evaluates only the sensor sub-mesh.
   * `rodrigues_convention` ('smplx' | 'so3') selects how the axis-angle map guards the angle at zero; the fork that
     holds the reference's arithmetic is not available, so the choice is explicit (include/empose_hip.h).
@@ -162,14 +168,20 @@ class SMPLLayer(nn.Module):
 
     def _fk(self, poses_body, betas, poses_root=None, trans=None, normalize_root=False):
         assert poses_body.shape[1] >= C.N_JOINTS * 3
-        if normalize_root:
-            raise NotImplementedError('normalize_root is not available on the HIP path')
         if not poses_body.is_cuda:
             raise _lib.EmposeError('SMPLLayer needs GPU tensors; there is no CPU fallback')
         if torch.is_grad_enabled() and any(t is not None and t.requires_grad
                                            for t in (poses_body, betas, poses_root, trans)):
+            if normalize_root:
+                if poses_root is None:
+                    poses_root = torch.zeros(poses_body.shape[0], 3, dtype=torch.float32, device=poses_body.device)
+                poses_root, trans = _RootFrame.apply(_lib.RODRIGUES[self.rodrigues_convention], poses_root, trans)
             return _MeshFK.apply(self, poses_body, betas, poses_root, trans)
         poses, betas, trans = self._pack(poses_body, betas, poses_root, trans)
+        if normalize_root:
+            # one segment of N frames, on the packed rows in place of their first three columns
+            root, trans = root_frame_fwd(poses, trans, poses.shape[0], _lib.RODRIGUES[self.rodrigues_convention])
+            poses[:, :3] = root
         return self._fk_packed(poses, betas, trans)
 
     def _pack(self, poses_body, betas, poses_root, trans):
@@ -248,6 +260,66 @@ class SMPLLayer(nn.Module):
 
     def forward(self, *args, **kwargs):
         return self.fk(*args, **kwargs)
+
+
+def root_frame_fwd(rows, trans, seg_len, rodrigues, flags=None):
+    """empose_root_frame_fwd on `rows` (T, ld) float32 whose first three columns are the root axis-angle, in segments of
+    `seg_len` frames: (root_out (T, 3), trans_out (T, 3) or None).  `trans` (T, 3) or None is rotated into the first
+    frame and the first translation subtracted, unless `flags` says otherwise."""
+    if flags is None:
+        flags = (_lib.ROOT_FRAME_ROTATE | _lib.ROOT_FRAME_SUBTRACT) if trans is not None else 0
+    n, dev = rows.shape[0], rows.device
+    with torch.cuda.device(dev):
+        root_out = torch.empty(n, 3, dtype=torch.float32, device=dev)
+        trans_out = torch.empty(n, 3, dtype=torch.float32, device=dev) if flags else None
+        _lib.check(_lib.lib().empose_root_frame_fwd(n, seg_len, rodrigues, _lib.dptr(rows), rows.shape[1],
+                                                    _lib.dptr(trans) if flags else None, _lib.dptr(root_out),
+                                                    _lib.dptr(trans_out), flags, _lib.current_stream()))
+    return root_out, trans_out
+
+
+class _RootFrame(torch.autograd.Function):
+    """`normalize_root=True` under autograd, one segment of N frames: (poses_root, trans) -> their normalised versions;
+    the backward is empose_root_frame_vjp on the saved inputs (single backward only)."""
+
+    @staticmethod
+    def forward(ctx, rodrigues, poses_root, trans):
+        root = poses_root.contiguous().float()
+        tr = trans.contiguous().float() if trans is not None else None
+        ctx.rodrigues = rodrigues
+        ctx.root_dtype = poses_root.dtype
+        ctx.trans_dtype = trans.dtype if trans is not None else None
+        ctx.save_for_backward(root, tr)
+        ctx.set_materialize_grads(False)
+        root_out, trans_out = root_frame_fwd(root, tr, root.shape[0], rodrigues)
+        return root_out, trans_out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, d_root, d_trans):
+        if d_root is None and d_trans is None:
+            return None, None, None
+        root, tr = ctx.saved_tensors
+        n, dev = root.shape[0], root.device
+        flags = (_lib.ROOT_FRAME_ROTATE | _lib.ROOT_FRAME_SUBTRACT) if tr is not None else 0
+        d_root = d_root.contiguous().float() if d_root is not None else None
+        d_trans = d_trans.contiguous().float() if d_trans is not None and tr is not None else None
+        lib = _lib.lib()
+        with torch.cuda.device(dev):
+            g_root = torch.empty(n, 3, dtype=torch.float32, device=dev)
+            g_trans = torch.empty(n, 3, dtype=torch.float32, device=dev) if d_trans is not None else None
+            ws_bytes = lib.empose_root_frame_vjp_workspace_bytes(n, n)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.empose_root_frame_vjp(n, n, ctx.rodrigues, _lib.dptr(root), 3, _lib.dptr(tr),
+                                                 _lib.dptr(d_root), _lib.dptr(d_trans), _lib.dptr(g_root),
+                                                 _lib.dptr(g_trans), flags, _lib.dptr(ws), ws_bytes,
+                                                 _lib.current_stream()))
+        g_root = g_root.to(ctx.root_dtype) if ctx.needs_input_grad[1] else None
+        if tr is not None and ctx.needs_input_grad[2]:
+            g_trans = g_trans.to(ctx.trans_dtype) if g_trans is not None else torch.zeros_like(tr, dtype=ctx.trans_dtype)
+        else:
+            g_trans = None
+        return None, g_root, g_trans
 
 
 class _MeshFK(torch.autograd.Function):

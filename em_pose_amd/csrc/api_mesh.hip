@@ -1,5 +1,5 @@
-// C ABI (include/empose_hip.h), full mesh: packing and evaluation of the posed vertices and joints, the metrics rows
-// and the virtual sensors.
+// C ABI (include/empose_hip.h), full mesh: packing and evaluation of the posed vertices and joints, the metrics rows,
+// the virtual sensors and the root normalisation.
 #include "api_internal.h"
 
 #include <algorithm>
@@ -515,6 +515,53 @@ int empose_mesh_vjp(const empose_mesh_t* mesh, int T, const float* poses, const 
     ra.trace_g_theta = ra.trace_g_beta = nullptr; ra.T = n; ra.rod_conv = mesh->rod_conv;
     HIP_CHECK(launch_rodrigues_bwd(ra, stream), "rodrigues_bwd kernel");
   }
+  return EMPOSE_OK;
+}
+
+// ---- root normalisation -----------------------------------------------------------------------------------------
+static int root_frame_args_ok(int T, int seg_len, int rodrigues, int ld_root, int flags) {
+  if (T <= 0 || seg_len <= 0) return fail(EMPOSE_EINVAL, "T and seg_len must be positive");
+  if (T % seg_len != 0) return fail(EMPOSE_EINVAL, "T = %d is not a multiple of seg_len = %d", T, seg_len);
+  if (ld_root < 3) return fail(EMPOSE_EINVAL, "ld_root must be at least 3");
+  if (rodrigues != EMPOSE_RODRIGUES_SMPLX && rodrigues != EMPOSE_RODRIGUES_SO3)
+    return fail(EMPOSE_EINVAL, "unknown Rodrigues convention %d", rodrigues);
+  if (flags & ~(EMPOSE_ROOT_FRAME_ROTATE | EMPOSE_ROOT_FRAME_SUBTRACT)) return fail(EMPOSE_EINVAL, "unknown flags %d", flags);
+  return EMPOSE_OK;
+}
+
+int empose_root_frame_fwd(int T, int seg_len, int rodrigues, const float* root, int ld_root, const float* trans,
+                          float* root_out, float* trans_out, int flags, empose_stream_t stream_) {
+  if (!root || !root_out || (flags && (!trans || !trans_out))) return fail(EMPOSE_EINVAL, "null argument");
+  TRY(root_frame_args_ok(T, seg_len, rodrigues, ld_root, flags));
+  static_assert(EMPOSE_ROOT_FRAME_ROTATE == ROOT_FRAME_ROTATE && EMPOSE_ROOT_FRAME_SUBTRACT == ROOT_FRAME_SUBTRACT, "flags");
+  RootFrameArgs a = {};
+  a.root = root; a.ld_root = ld_root; a.trans = trans; a.root_out = root_out; a.trans_out = trans_out;
+  a.T = T; a.seg_len = seg_len; a.rod_conv = rodrigues; a.flags = flags;
+  HIP_CHECK(launch_root_frame_fwd(a, static_cast<hipStream_t>(stream_)), "root frame kernel");
+  return EMPOSE_OK;
+}
+
+size_t empose_root_frame_vjp_workspace_bytes(int T, int seg_len) {
+  if (T <= 0 || seg_len <= 0 || T % seg_len != 0) return 0;
+  Carver c(nullptr);
+  c.f((size_t)root_frame_vjp_waves(T, seg_len) * ROOT_FRAME_SUMS);
+  return c.off;
+}
+
+int empose_root_frame_vjp(int T, int seg_len, int rodrigues, const float* root, int ld_root, const float* trans,
+                          const float* d_root_out, const float* d_trans_out, float* g_root, float* g_trans, int flags,
+                          void* workspace, size_t workspace_bytes, empose_stream_t stream_) {
+  if (!root || !g_root || (flags && !trans) || (d_trans_out && !g_trans)) return fail(EMPOSE_EINVAL, "null argument");
+  TRY(root_frame_args_ok(T, seg_len, rodrigues, ld_root, flags));
+  if (!d_root_out && !d_trans_out) return fail(EMPOSE_EINVAL, "d_root_out and d_trans_out are both NULL");
+  if (d_trans_out && !flags) return fail(EMPOSE_EINVAL, "d_trans_out needs flags != 0");
+  if (!workspace || workspace_bytes < empose_root_frame_vjp_workspace_bytes(T, seg_len))
+    return fail(EMPOSE_EINVAL, "workspace too small (empose_root_frame_vjp_workspace_bytes)");
+  RootFrameArgs a = {};
+  a.root = root; a.ld_root = ld_root; a.trans = trans; a.d_root_out = d_root_out; a.d_trans_out = d_trans_out;
+  a.g_root = g_root; a.g_trans = g_trans; a.part = static_cast<float*>(workspace);
+  a.T = T; a.seg_len = seg_len; a.rod_conv = rodrigues; a.flags = flags;
+  HIP_CHECK(launch_root_frame_vjp(a, static_cast<hipStream_t>(stream_)), "root frame VJP kernels");
   return EMPOSE_OK;
 }
 

@@ -821,6 +821,24 @@ struct SensorVjpArgs {
 };
 hipError_t launch_sensors_vjp(const SensorVjpArgs& a, hipStream_t stream);
 
+// Root normalisation and its vector-Jacobian product (root_frame.hip).  T frames in segments of seg_len rows; the root
+// axis-angles are the first three columns of rows of ld_root floats.  `flags`: what happens to the translation.
+constexpr int ROOT_FRAME_ROTATE = 1;     // trans_out = R_0^T trans
+constexpr int ROOT_FRAME_SUBTRACT = 2;   // ... minus the first frame's (rotated) translation
+constexpr int ROOT_FRAME_SUMS = 9;       // floats per wave of the reverse in `part`
+struct RootFrameArgs {
+  const float* root; int ld_root;
+  const float* trans;                              // [T][3], read when flags != 0
+  float* root_out; float* trans_out;               // forward: [T][3], [T][3] (flags != 0)
+  const float* d_root_out; const float* d_trans_out;   // reverse: [T][3] each or nullptr
+  float* g_root; float* g_trans;                   // reverse: [T][3]; g_trans is written when d_trans_out is given
+  float* part;                                     // reverse: [root_frame_vjp_waves(T, seg_len)][ROOT_FRAME_SUMS]
+  int T, seg_len, rod_conv, flags;
+};
+long root_frame_vjp_waves(int T, int seg_len);
+hipError_t launch_root_frame_fwd(const RootFrameArgs& a, hipStream_t stream);
+hipError_t launch_root_frame_vjp(const RootFrameArgs& a, hipStream_t stream);
+
 struct MetricsArgs {
   const float* joints_gt; const float* joints_hat;   // [T][22][3]
   const float* pose_gt; const float* pose_hat;       // [T][63] body axis-angles (no root) or nullptr

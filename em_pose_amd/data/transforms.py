@@ -88,9 +88,15 @@ class ExtractWindow(object):
 
 
 class NormalizeRoot(object):
-    def __init__(self, normalize_root_ori=True, remove_root_trans=True):
+    """`on_device=True` (CUDA batches only): the root orientations are normalised by one launch of the root-frame kernel
+    (empose_root_frame_fwd over N * F frames in segments of F) instead of the float64 host round trip: no `.cpu()`, no
+    synchronisation.  The default is the host path."""
+
+    def __init__(self, normalize_root_ori=True, remove_root_trans=True, on_device=False, rodrigues_convention='smplx'):
         self.normalize_root_ori = normalize_root_ori
         self.remove_root_trans = remove_root_trans
+        self.on_device = on_device
+        self.rodrigues_convention = rodrigues_convention
 
     def __call__(self, batch):
         with torch.no_grad():
@@ -98,7 +104,15 @@ class NormalizeRoot(object):
             batch.root_pose_source = batch.poses[:, :, :3].clone()
             if self.remove_root_trans:
                 batch.trans = torch.zeros_like(batch.trans)
-            if self.normalize_root_ori:
+            if self.normalize_root_ori and self.on_device:
+                from em_pose_amd import _lib
+                from em_pose_amd.bodymodels.smpl import root_frame_fwd
+                n, f, ld = batch.poses.shape
+                rows = batch.poses.detach().reshape(n * f, ld).contiguous().float()
+                root, _ = root_frame_fwd(rows, None, f, _lib.RODRIGUES[self.rodrigues_convention])
+                batch.poses = batch.poses.clone()
+                batch.poses[:, :, :3] = root.reshape(n, f, 3).to(batch.poses.dtype)
+            elif self.normalize_root_ori:
                 root = batch.poses[:, :, :3].detach().cpu().numpy().astype(np.float64)
                 R = rotvec_to_matrix(root)  # (N,F,3,3)
                 Rn = np.swapaxes(R[:, :1], -1, -2) @ R
@@ -207,12 +221,13 @@ class SampleMarkersWithOffsets(object):
         return batch
 
 
-def get_end_to_end_preprocess_fn(config, smpl_model, offset_files, randomize_if_configured=False):
+def get_end_to_end_preprocess_fn(config, smpl_model, offset_files, randomize_if_configured=False,
+                                 device_normalize=False):
     """
     The reference's preprocessing factory (transforms.py:23-48): NormalizeRoot -> SMPLFK -> SampleMarkersWithOffsets,
     with the configured offset noise level when `randomize_if_configured`.  `offset_files`: the `*_offsets.npz` files
     (the reference takes them from its data directory).  The reference's additional sensor-noise function
-    (`get_noise_fn`) is not part of this build.
+    (`get_noise_fn`) is not part of this build.  `device_normalize`: NormalizeRoot(on_device=True).
     """
     if not getattr(config, 'use_real_offsets', True):
         raise ValueError('We expect to use the real offsets.')
@@ -222,7 +237,7 @@ def get_end_to_end_preprocess_fn(config, smpl_model, offset_files, randomize_if_
         # marker suppression).  It is not part of this build: refuse instead of silently training without it.
         raise NotImplementedError('sensor-noise augmentation (spherical_noise_length / suppression_noise_length > 0) '
                                   'is not implemented in this build')
-    normalize_root, fk = NormalizeRoot(), SMPLFK(smpl_model)
+    normalize_root, fk = NormalizeRoot(on_device=device_normalize), SMPLFK(smpl_model)
     noise_level = getattr(config, 'offset_noise_level', -1) if randomize_if_configured else -1
     sample_markers = SampleMarkersWithOffsets(smpl_model, list(offset_files), noise_level=noise_level)
 

@@ -685,6 +685,37 @@ int empose_mesh_vjp(const empose_mesh_t* mesh, int T, const float* poses, const 
                     const float* d_joints, float* g_poses, float* g_betas, float* g_trans, void* workspace,
                     size_t workspace_bytes, empose_stream_t stream);
 
+/* ---- root normalisation (reference bodymodels/smpl.py:112-119, data/transforms.py:247-254) ----------------------- */
+/* T frames in segments of seg_len consecutive rows (T % seg_len == 0): a sequence is re-expressed in the frame of the
+ * first root orientation of its segment, R_0 = exp(root[first]):
+ *   root_out[t]  = log(R_0^T exp(root[t]))                                   [T][3]
+ *   trans_out[t] = R_0^T trans[t] - R_0^T trans[first]                       [T][3], by `flags`
+ * `root` points at rows of ld_root >= 3 floats whose first three columns are the root axis-angle (poses [T][66] in
+ * place: ld_root = 66); `rodrigues` is the EMPOSE_RODRIGUES_* convention of the exponential map.  flags = 0 leaves the
+ * translation alone (trans and trans_out may be NULL); EMPOSE_ROOT_FRAME_ROTATE rotates it, EMPOSE_ROOT_FRAME_SUBTRACT
+ * subtracts the segment's first (rotated, if also ROTATE) translation; the reference's layer does both.  The first
+ * frame of every segment gets exact zeros for the orientation and, with SUBTRACT, for the translation.  The logarithm is
+ * accurate over the whole range [0, pi] (csrc/root_frame.hip); outputs must not alias inputs.  No workspace.
+ *
+ * empose_root_frame_vjp: for cotangents d_root_out and/or d_trans_out [T][3] (either may be NULL, not both; d_trans_out
+ * needs flags != 0) it writes g_root [T][3] and, when d_trans_out is given, g_trans [T][3].  The first frame's rows
+ * collect what every frame of the segment sends back through R_0 and trans[first], summed in one fixed order: repeated
+ * calls give the same bits.  The derivative is that of the exact maps (left and right Jacobians of SO(3), series at small
+ * angles), finite everywhere including Rn = I -- not that of the reference's acos-based logarithm, which is 0 * inf at
+ * the first frame of every sequence.  Workspace: empose_root_frame_vjp_workspace_bytes(T, seg_len), 36 bytes per 64
+ * frames of a segment (0 for bad sizes).
+ * Both return EMPOSE_EINVAL, before any GPU work, for a NULL required pointer, T <= 0, seg_len <= 0, T % seg_len != 0,
+ * ld_root < 3, an unknown `rodrigues` or unknown flag bits; the reverse also for both cotangents NULL, d_trans_out with
+ * flags == 0 and a workspace that is too small. */
+#define EMPOSE_ROOT_FRAME_ROTATE 1
+#define EMPOSE_ROOT_FRAME_SUBTRACT 2
+int empose_root_frame_fwd(int T, int seg_len, int rodrigues, const float* root, int ld_root, const float* trans,
+                          float* root_out, float* trans_out, int flags, empose_stream_t stream);
+size_t empose_root_frame_vjp_workspace_bytes(int T, int seg_len);
+int empose_root_frame_vjp(int T, int seg_len, int rodrigues, const float* root, int ld_root, const float* trans,
+                          const float* d_root_out, const float* d_trans_out, float* g_root, float* g_trans, int flags,
+                          void* workspace, size_t workspace_bytes, empose_stream_t stream);
+
 /* ---- evaluation metrics ------------------------------------------------------------------------ */
 /* Per frame: 22 Euclidean joint distances, 22 distances after similarity-Procrustes alignment of the prediction onto
  * the ground truth, and 21 geodesic angles (degrees) between global joint orientations with the root fixed to the

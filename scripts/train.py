@@ -87,8 +87,10 @@ def train_on_amass(args, dev, rank, world):
     if not offsets:
         raise SystemExit('no *_offsets.npz files: pass --offset_files or set EM_DATA_REAL')
     buckets = make_buckets(net, params, world, args)
-    fn_train = get_end_to_end_preprocess_fn(cfg, smpl, offsets, randomize_if_configured=True)
-    fn_valid = get_end_to_end_preprocess_fn(cfg, smpl, offsets, randomize_if_configured=False)
+    fn_train = get_end_to_end_preprocess_fn(cfg, smpl, offsets, randomize_if_configured=True,
+                                            device_normalize=args.device_normalize)
+    fn_valid = get_end_to_end_preprocess_fn(cfg, smpl, offsets, randomize_if_configured=False,
+                                            device_normalize=args.device_normalize)
 
     # The sequences: AMASS npz files under --amass_dir, or the records of an LMDB database in the reference's key schema
     # (--amass_lmdb, + optionally a separate --valid_lmdb as the reference trains on AMASS and validates on 3DPW).
@@ -256,6 +258,8 @@ def main():
     p.add_argument('--valid_fraction', type=float, default=0.1)
     p.add_argument('--offset_noise_level', type=int, default=0)
     p.add_argument('--data_workers', type=int, default=0)
+    p.add_argument('--device_normalize', action='store_true', help='normalise the root orientations of a batch with the '
+                   'root-frame kernel on the GPU instead of the float64 host round trip (NormalizeRoot(on_device=True))')
     args = p.parse_args()
     # `--gpus N` as a plain command spawns its own N ranks (helpers/distributed.py); under torch.distributed.run the ranks
     # exist already.  --force_dist sends one rank through the same spawn + RCCL path (single-GPU self-test).
