@@ -254,6 +254,12 @@ SIGNATURES = {
     'empose_root_frame_vjp_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int]),
     'empose_root_frame_vjp': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int] + [C.c_void_p] * 5 +
                                        [C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # (the sequence tables: numpy records of data/resample.py SEQ_DTYPE, host and device copy)
+    'empose_resample_rotations': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    'empose_resample_positions_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    'empose_resample_positions': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                            C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

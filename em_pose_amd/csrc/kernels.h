@@ -839,6 +839,23 @@ long root_frame_vjp_waves(int T, int seg_len);
 hipError_t launch_root_frame_fwd(const RootFrameArgs& a, hipStream_t stream);
 hipError_t launch_root_frame_vjp(const RootFrameArgs& a, hipStream_t stream);
 
+// Resampling of a ragged batch of sequences to another frame rate (resample.hip).  One entry per sequence; the layout is
+// that of empose_resample_seq (include/empose_hip.h).  Output rows are packed: out_row[s + 1] = out_row[s] + f_out[s].
+struct ResampleSeq {
+  int in_row, f_in, out_row, f_out;
+  double fps_in, fps_out;
+};
+struct ResampleArgs {
+  const ResampleSeq* seqs; int S;   // device table
+  const float* in; int ld_in;       // rows of ld_in floats; the first 3 * n (rotations) or n (positions) columns are read
+  float* out; int ld_out;
+  int n;                            // joints per row (rotations) or channels (positions)
+  long out_rows;                    // sum of f_out
+  double* ws;                       // positions: [input rows][n] spline derivatives
+};
+hipError_t launch_resample_rotations(const ResampleArgs& a, hipStream_t stream);
+hipError_t launch_resample_positions(const ResampleArgs& a, hipStream_t stream);
+
 struct MetricsArgs {
   const float* joints_gt; const float* joints_hat;   // [T][22][3]
   const float* pose_gt; const float* pose_hat;       // [T][63] body axis-angles (no root) or nullptr

@@ -10,6 +10,7 @@ Datasets over the on-disk formats of the path.
                        importable (it is not in this image), a dict, a shelve ... so the schema is tested without it.
 * `AMASSNpzDataset` -- the AMASS release's own `*.npz` sequences, for a user without the LMDB conversion.
 """
+import copy
 import glob
 import os
 
@@ -35,18 +36,46 @@ class RealDataset(Dataset):
 
 
 class AMASSNpzDataset(Dataset):
-    """AMASS sequences (`poses`, `betas`, `trans`, `mocap_framerate` per npz) found under `base_path`, recursively."""
+    """AMASS sequences (`poses`, `betas`, `trans`, `mocap_framerate` per npz) found under `base_path`, recursively.
 
-    def __init__(self, base_path, transform=None, files=None):
+    `resample_fps` (default None: the sequences at their recorded rate, `fps` only recorded): every sequence is resampled
+    to that rate on the GPU when it is first loaded (data/resample.py) and kept, so windows are cut from the resampled
+    sequence and nothing is resampled twice; `transform` sees a shallow copy.  `preload()` resamples all files at once, in
+    ragged batches of one launch each -- do that before handing the dataset to worker processes."""
+
+    def __init__(self, base_path, transform=None, files=None, resample_fps=None, device=None):
         self.files = sorted(glob.glob(os.path.join(base_path, '**', '*.npz'), recursive=True)) if files is None else files
         self.transform = transform
+        self.resample_fps, self.device = resample_fps, device
+        self._resampled = {}
 
     def __len__(self):
         return len(self.files)
 
-    def __getitem__(self, item):
+    def _load(self, item):
         path = self.files[item]
-        sample = AMASSSample.from_disk(path, os.path.splitext(os.path.basename(path))[0])
+        return AMASSSample.from_disk(path, os.path.splitext(os.path.basename(path))[0])
+
+    def preload(self, batch_size=64):
+        """Loads and resamples every sequence not yet kept, `batch_size` sequences per launch."""
+        if self.resample_fps is None:
+            return self
+        from em_pose_amd.data.resample import resample_samples
+        missing = [i for i in range(len(self.files)) if i not in self._resampled]
+        for at in range(0, len(missing), batch_size):
+            items = missing[at:at + batch_size]
+            samples = resample_samples([self._load(i) for i in items], self.resample_fps, device=self.device)
+            self._resampled.update(zip(items, samples))
+        return self
+
+    def __getitem__(self, item):
+        if self.resample_fps is None:
+            sample = self._load(item)
+        else:
+            if item not in self._resampled:
+                from em_pose_amd.data.resample import resample_samples
+                self._resampled[item] = resample_samples([self._load(item)], self.resample_fps, device=self.device)[0]
+            sample = copy.copy(self._resampled[item])   # transforms assign fields of the sample they are given
         return sample if self.transform is None else self.transform(sample)
 
 

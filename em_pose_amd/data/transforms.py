@@ -4,6 +4,7 @@ The few transforms `evaluate_real` needs before the model sees a recording (refe
   NormalizeRealMarkers   reference transforms.py:99-129  sensor readings into the frame of the first SMPL root pose
   ToTensor               reference transforms.py:51-56
   NormalizeRoot          reference transforms.py:229-256 first root orientation := identity, translation := 0
+  ResampleSequence       reference scripts/preprocess_amass_3dpw.py:146-148 a sequence to 60 Hz, on the GPU
 
   SMPLFK, SampleMarkersWithOffsets, get_end_to_end_preprocess_fn   reference transforms.py:259-282,132-226,23-48 on the
                          HIP full-mesh kernel (pinned by tests/golden/preprocess.npz)
@@ -85,6 +86,22 @@ class ExtractWindow(object):
         else:
             sf = self.rng.randint(0, n - ws + 1)
         return sample.extract_window(sf, sf + ws)
+
+
+class ResampleSequence(object):
+    """An `AMASSSample` resampled to `fps` by the resampling kernels (data/resample.py): poses[:, :66] as 22 rotations by
+    SQUAD, trans by the not-a-knot cubic spline, `fps` set to the target (`n_frames` follows the arrays).  `joints`, when
+    the sample has them, are recomputed from the resampled poses through `smpl_model.fk_joints`, which must then be
+    given.  A sample already at `fps` is returned untouched.  Needs a GPU: there is no host path."""
+
+    def __init__(self, fps=None, smpl_model=None, device=None):
+        from em_pose_amd.helpers.configuration import CONSTANTS as C
+        self.fps = float(C.FPS if fps is None else fps)
+        self.smpl_model, self.device = smpl_model, device
+
+    def __call__(self, sample):
+        from em_pose_amd.data.resample import resample_samples
+        return resample_samples([sample], self.fps, self.smpl_model, self.device)[0]
 
 
 class NormalizeRoot(object):

@@ -716,6 +716,46 @@ int empose_root_frame_vjp(int T, int seg_len, int rodrigues, const float* root, 
                           const float* d_root_out, const float* d_trans_out, float* g_root, float* g_trans, int flags,
                           void* workspace, size_t workspace_bytes, empose_stream_t stream);
 
+/* ---- resampling to another frame rate (reference scripts/preprocess_amass_3dpw.py:63-123) ----------------------- */
+/* One launch resamples a ragged batch of S sequences.  Sequence s reads f_in input rows from row in_row (knots at
+ * k / fps_in) and writes f_out output rows from row out_row (times k / fps_out).  f_out is the caller's: the reference's
+ * len(np.arange(0, f_in / fps_in, 1 / fps_out)), which the kernels trust.  Output rows are packed in table order
+ * (out_row[0] = 0, out_row[s + 1] = out_row[s] + f_out[s]); input rows may lie anywhere inside [0, in_rows). */
+typedef struct {
+  int in_row, f_in, out_row, f_out;
+  double fps_in, fps_out;
+} empose_resample_seq;
+
+/* The table is passed twice: `seqs_host` is validated (no GPU work), `seqs_dev` is the same S entries in device memory,
+ * which the kernels read.  `in` points at in_rows rows of ld_in floats, `out` at out_rows rows of ld_out floats (float32,
+ * device); arithmetic inside a thread is double precision.  Outputs must not alias inputs.
+ *
+ * empose_resample_rotations replaces resample_rotations / interpolate_rotations: the first 3 * J columns of a row are J
+ * rotation vectors.  Shoemake's SQUAD on uniform knots over a hemisphere-consistent four-knot stencil, constant-velocity
+ * phantom knots at both ends (so the end control points are the end knots, and f_in = 2 is plain slerp), the last
+ * segment's formula past the last knot; the result is the rotation vector with |r| <= pi (csrc/resample.hip).  The
+ * reference takes SQUAD from the numpy-quaternion package: interior segments follow the same published formula, its
+ * treatment of the first and last segment and of times past the last knot is not verified against this one.
+ *
+ * empose_resample_positions replaces resample_positions / interpolate_positions: the first C columns of a row are C
+ * channels; the not-a-knot cubic spline scipy.interpolate.CubicSpline computes by default (f_in = 2: the line, f_in = 3:
+ * the parabola), extrapolated with the last polynomial.  The tridiagonal first-derivative system is solved in double by
+ * one serial sweep per (sequence, channel), in one fixed order, in a workspace of
+ * empose_resample_positions_workspace_bytes(in_rows, C) = one double per input row and channel (0 for bad sizes).
+ *
+ * Both are deterministic, and a sequence's result does not depend on the rest of the batch.  Both return EMPOSE_EINVAL,
+ * before any GPU work, for a NULL pointer, S, J or C <= 0, a leading dimension smaller than the columns read or written,
+ * f_in < 2 (one frame cannot be resampled), f_out < 1, a rate that is not positive and finite, input rows outside
+ * [0, in_rows), output rows that are not packed or do not sum to out_rows; the positions also for a workspace that is too
+ * small. */
+int empose_resample_rotations(int S, const empose_resample_seq* seqs_host, const empose_resample_seq* seqs_dev, int J,
+                              const float* in, int ld_in, int in_rows, float* out, int ld_out, int out_rows,
+                              empose_stream_t stream);
+size_t empose_resample_positions_workspace_bytes(int in_rows, int C);
+int empose_resample_positions(int S, const empose_resample_seq* seqs_host, const empose_resample_seq* seqs_dev, int C,
+                              const float* in, int ld_in, int in_rows, float* out, int ld_out, int out_rows,
+                              void* workspace, size_t workspace_bytes, empose_stream_t stream);
+
 /* ---- evaluation metrics ------------------------------------------------------------------------ */
 /* Per frame: 22 Euclidean joint distances, 22 distances after similarity-Procrustes alignment of the prediction onto
  * the ground truth, and 21 geodesic angles (degrees) between global joint orientations with the root fixed to the

@@ -96,7 +96,9 @@ def train_on_amass(args, dev, rank, world):
     # (--amass_lmdb, + optionally a separate --valid_lmdb as the reference trains on AMASS and validates on 3DPW).
     def ex_seqs(transform, items, lmdb_path=None):
         if lmdb_path is None:
-            return AMASSNpzDataset(None, transform, files=items)
+            data = AMASSNpzDataset(None, transform, files=items, resample_fps=args.resample_fps, device=dev)
+            # worker processes must not touch the GPU: resample everything here, in ragged batches
+            return data.preload() if args.data_workers > 0 else data
         return Subset(LMDBDataset(lmdb_path, transform), items)
     valid_src = train_src = args.amass_lmdb
     if args.amass_lmdb:
@@ -260,6 +262,9 @@ def main():
     p.add_argument('--data_workers', type=int, default=0)
     p.add_argument('--device_normalize', action='store_true', help='normalise the root orientations of a batch with the '
                    'root-frame kernel on the GPU instead of the float64 host round trip (NormalizeRoot(on_device=True))')
+    p.add_argument('--resample_fps', type=float, default=None,
+                   help='--amass_dir only: resample every sequence to this rate (the reference trains on 60 Hz) with the '
+                        'resampling kernels when it is first loaded; default: the recorded rate, as it is')
     args = p.parse_args()
     # `--gpus N` as a plain command spawns its own N ranks (helpers/distributed.py); under torch.distributed.run the ranks
     # exist already.  --force_dist sends one rank through the same spawn + RCCL path (single-GPU self-test).
