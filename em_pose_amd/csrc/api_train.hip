@@ -503,6 +503,7 @@ int empose_lgd_losses(const empose_loss_io* io, void* workspace, size_t workspac
       !io->pose_gt || !io->shape_gt || !io->inputs || !io->d_pose || !io->d_shape || !io->d_markers ||
       !io->d_markers_ori || !io->d_joints || !io->loss_vals)
     return fail(EMPOSE_EINVAL, "null tensor");
+  if (io->ld_inputs < 12 * io->n_markers) return fail(EMPOSE_EINVAL, "ld_inputs below 12 * n_markers");
   if (workspace_bytes < empose_lgd_losses_workspace_bytes(io->B, io->F, io->n_hist)) return fail(EMPOSE_ENOMEM, "workspace too small");
   LossArgs a;
   a.B = io->B; a.F = io->F; a.N1 = io->n_hist; a.n_markers = io->n_markers;

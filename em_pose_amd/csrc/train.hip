@@ -762,11 +762,12 @@ __global__ __launch_bounds__(256) void lgd_losses_kernel(LossArgs a) {
     const float* g = a.pose_gt + (size_t)t * 66;
     float* d = a.d_pose + row * 66;
     const float k = live ? a.w_pose * inv_n1 * inv / 66.f : 0.f;
+    const float kn = live ? -k : 0.f;   // a padding frame gets +0 whatever it holds (not -0 where df < 0, +0 where df is NaN)
     float s = 0.f;
     for (int c = 0; c < 66; ++c) {
       const float df = h[c] - g[c];
       s += fabsf(df);
-      d[c] = df > 0.f ? k : (df < 0.f ? -k : 0.f);
+      d[c] = df > 0.f ? k : (df < 0.f ? kn : 0.f);
     }
     l_pose = live ? s / 66.f * inv : 0.f;
   } else if (in_range && part == 1) {
@@ -774,11 +775,12 @@ __global__ __launch_bounds__(256) void lgd_losses_kernel(LossArgs a) {
     const float* g = a.shape_gt + (size_t)b * 10;
     float* d = a.d_shape + row * 10;
     const float k = live ? a.w_shape * inv_n1 * inv / 10.f : 0.f;
+    const float kn = live ? -k : 0.f;
     float s = 0.f;
     for (int c = 0; c < 10; ++c) {
       const float df = h[c] - g[c];
       s += fabsf(df);
-      d[c] = df > 0.f ? k : (df < 0.f ? -k : 0.f);
+      d[c] = df > 0.f ? k : (df < 0.f ? kn : 0.f);
     }
     l_shape = live ? s / 10.f * inv : 0.f;
   } else if (in_range && part >= 2 && part < 14) {

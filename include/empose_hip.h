@@ -494,7 +494,8 @@ typedef struct {
   const float* pose_gt;         /* [T][66] */
   const float* shape_gt;        /* [B][10] */
   const float* joints_gt;       /* [T][66] or NULL (no FK loss) */
-  const float* inputs; int ld_inputs;   /* network input rows: n_markers*3 positions then n_markers*9 orientations */
+  const float* inputs; int ld_inputs;   /* network input rows: n_markers*3 positions then n_markers*9 orientations;
+                                         * ld_inputs >= 12 * n_markers */
   const int* seq_lengths;       /* [B] or NULL */
   const float* marker_masks;    /* [T][12] or NULL */
   float w_pose, w_shape, w_fk, w_rec;

@@ -64,6 +64,68 @@ def test_bad_descriptors_are_rejected_without_a_gpu():
     assert lib.empose_lgd_workspace_bytes(None, 4, 4) == 0
 
 
+def test_training_bookkeeping_calls_refuse_bad_arguments_without_a_gpu():
+    """Every check of the loss and bookkeeping entry points (csrc/api_train.hip) precedes its launch: the calls below
+    return an error before any GPU work, so the pointers only have to be non-NULL."""
+    from em_pose_amd.helpers.configuration import CONSTANTS
+    lib = _lib.lib()
+    buf = np.zeros(64, np.float32)          # never read: every call below is refused
+    p = ctypes.c_void_p(buf.ctypes.data)
+
+    def loss_io(**change):
+        io = _lib.LossIO()
+        io.B, io.F, io.n_hist, io.n_markers = 2, 4, 3, 6
+        for k, v in enumerate(CONSTANTS.S_CONFIG_6):
+            io.marker_idx[k] = v
+        for name, kind in _lib.LossIO._fields_:
+            if kind is ctypes.c_void_p:
+                setattr(io, name, p)
+        io.ld_inputs = 72
+        for k, v in change.items():
+            if k == 'marker_idx':
+                io.marker_idx[v[0]] = v[1]
+            else:
+                setattr(io, k, v)
+        return io
+    nbytes = lib.empose_lgd_losses_workspace_bytes(2, 4, 3)
+    assert nbytes == 4 * 3 * 2 * 4 * 4 + 256
+    for B, F, n in ((0, 4, 3), (2, 0, 3), (2, 4, 0), (-1, 4, 3)):
+        assert lib.empose_lgd_losses_workspace_bytes(B, F, n) == 0
+
+    def losses(io, ws=p, size=nbytes):
+        return lib.empose_lgd_losses(ctypes.byref(io) if io is not None else None, ws, ctypes.c_size_t(size), None)
+    assert losses(None) != 0 and losses(loss_io(), ws=None) != 0
+    for name in ('pose_hist', 'shape_hist', 'markers_hist', 'markers_ori_hist', 'joints_final', 'pose_gt', 'shape_gt',
+                 'inputs', 'd_pose', 'd_shape', 'd_markers', 'd_markers_ori', 'd_joints', 'loss_vals'):
+        assert losses(loss_io(**{name: None})) == EMPOSE_EINVAL, name
+    assert losses(loss_io(n_markers=5)) == EMPOSE_EINVAL
+    assert losses(loss_io(marker_idx=(2, 12))) == EMPOSE_EINVAL and losses(loss_io(marker_idx=(0, -1))) == EMPOSE_EINVAL
+    assert losses(loss_io(), size=nbytes - 1) != 0
+    assert b'workspace' in lib.empose_last_error()
+    assert losses(loss_io(ld_inputs=71)) == EMPOSE_EINVAL         # a short row would be read past its end
+    assert b'ld_inputs' in lib.empose_last_error()
+    assert losses(loss_io(n_markers=12, ld_inputs=143)) == EMPOSE_EINVAL
+
+    def cotangent(F=4, d_pose=p, ld_g=66, ld_gb=10, dpad=p, dspad=p, Dp=p):
+        return lib.empose_lgd_cotangent_step(2, F, 1, d_pose, p, p, p, p, ld_g, p, ld_gb, Dp, p, 0.1, 1, dpad, dspad, None)
+    assert cotangent(F=1229) == EMPOSE_EINVAL      # 10 floats per frame above the 48 KB of dynamic shared memory
+    assert cotangent(F=0) == EMPOSE_EINVAL and cotangent(d_pose=None) == EMPOSE_EINVAL and cotangent(Dp=None) == EMPOSE_EINVAL
+    assert cotangent(ld_g=65) == EMPOSE_EINVAL and cotangent(ld_gb=9) == EMPOSE_EINVAL
+    assert cotangent(dspad=None) == EMPOSE_EINVAL and cotangent(dpad=None) == EMPOSE_EINVAL
+    assert lib.empose_lgd_additive_update(2, 4, 0.1, 1, p, p, p, None, p, p, None) == EMPOSE_EINVAL
+    assert lib.empose_lgd_additive_update(0, 4, 0.1, 1, p, p, p, p, p, p, None) == EMPOSE_EINVAL
+    assert lib.empose_window_mean(9, 4, 10, p, 10, p, 10, None) == EMPOSE_EINVAL       # T % F != 0
+    assert lib.empose_window_mean(8, 4, 10, p, 9, p, 10, None) == EMPOSE_EINVAL
+    assert lib.empose_window_mean(8, 4, 10, p, 10, p, 9, None) == EMPOSE_EINVAL
+    assert lib.empose_window_mean(8, 4, 10, None, 10, p, 10, None) == EMPOSE_EINVAL
+    assert lib.empose_axpby2d(3, 5, 1.0, p, 5, 1.0, p, 5, p, 4, None) == EMPOSE_EINVAL  # ldo < cols
+    assert lib.empose_axpby2d(3, 5, 1.0, p, 4, 1.0, p, 5, p, 5, None) == EMPOSE_EINVAL
+    assert lib.empose_axpby2d(3, 5, 1.0, p, 5, 1.0, p, 5, None, 5, None) == EMPOSE_EINVAL
+    assert lib.empose_lgd_assemble_inputs(4, 72, p, 72, p, p, p, 72 + 75, None) == EMPOSE_EINVAL
+    assert lib.empose_lgd_assemble_inputs(4, 72, p, 71, p, p, p, 224, None) == EMPOSE_EINVAL
+    assert lib.empose_lgd_assemble_inputs(4, 72, p, 72, None, p, p, 224, None) == EMPOSE_EINVAL
+
+
 def test_cpu_tensors_raise_instead_of_falling_back():
     from em_pose_amd.bodymodels.smpl import SMPLLayer
     from em_pose_amd.helpers.configuration import lgd_config
