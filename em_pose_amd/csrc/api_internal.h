@@ -93,6 +93,28 @@ inline void split3(float w, unsigned short p[3]) {
   p[1] = bf16_round(r);
   p[2] = bf16_round(r - bf16_value(p[1]));
 }
+// B operands of the three-piece kernels on the host: `n_frag` fragments of 3 x 512 bf16 -- piece 0, 1, 2 of the same 64 lanes x
+// 8 consecutive k, 1 KB each -- in the order the caller's layout gives them.  `src(frag, lane, &row, &k0)` names what a lane
+// of a fragment owns: row[k0 .. k0 + 7] (k0 = k-step * 16 + (lane >> 5) * 8 for the 32x32x16 instruction,
+// k-step * 32 + (lane >> 4) * 8 for the 16x16x32 one); it returns false for a lane that owns nothing.  What is not
+// written -- those lanes and k >= K -- is zero.
+template <typename Src>
+std::vector<unsigned short> pack_fragments_x3(size_t n_frag, int K, Src src) {
+  std::vector<unsigned short> buf(n_frag * 3 * 512, 0);
+  for (size_t f = 0; f < n_frag; ++f)
+    for (int lane = 0; lane < 64; ++lane) {
+      const float* row = nullptr;
+      int k0 = 0;
+      if (!src(f, lane, &row, &k0)) continue;
+      for (int e = 0; e < 8 && k0 + e < K; ++e) {
+        unsigned short p[3];
+        split3(row[k0 + e], p);
+        const size_t at = f * 3 * 512 + (size_t)lane * 8 + e;
+        buf[at] = p[0]; buf[at + 512] = p[1]; buf[at + 1024] = p[2];
+      }
+    }
+  return buf;
+}
 // A table of bf16 pieces goes to the device as it is; `out` is typed as the kernels that read it take it.
 template <typename T>
 int upload_bf16(std::vector<void*>& allocs, const std::vector<unsigned short>& buf, T** out) {

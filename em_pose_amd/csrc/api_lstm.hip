@@ -73,46 +73,24 @@ void fill_unit(LstmUnitArgs& ua, const Lstm& r, const LstmWs& ws, int u) {
 // n = lane & 31 is gate n >> 3 of unit block * 8 + (n & 7).
 int pack_lstm_x3(std::vector<void*>& allocs, const float* w, int H, int K, unsigned short** out, bool mid = false) {
   const int KS = (K + 15) / 16, JB = mid ? H / 8 : H / 32, NQ = mid ? 1 : 4;
-  std::vector<unsigned short> buf((size_t)KS * JB * NQ * 3 * 512, 0);
-  for (int ks = 0; ks < KS; ++ks)
-    for (int jb = 0; jb < JB; ++jb)
-      for (int q = 0; q < NQ; ++q)
-        for (int lane = 0; lane < 64; ++lane) {
-          const int n = lane & 31;
-          const float* row = mid ? w + (size_t)((n >> 3) * H + jb * 8 + (n & 7)) * K
-                                 : w + (size_t)(q * H + jb * 32 + n) * K;
-          for (int e = 0; e < 8; ++e) {
-            const int k = ks * 16 + (lane >> 5) * 8 + e;
-            if (k >= K) continue;
-            unsigned short p[3];
-            split3(row[k], p);
-            const size_t at = ((((size_t)ks * JB + jb) * NQ + q) * 3) * 512 + (size_t)lane * 8 + e;
-            buf[at] = p[0]; buf[at + 512] = p[1]; buf[at + 1024] = p[2];
-          }
-        }
-  return upload_bf16(allocs, buf, out);
+  return upload_bf16(allocs, pack_fragments_x3((size_t)KS * JB * NQ, K, [&](size_t f, int lane, const float** row, int* k0) {
+    const int q = (int)(f % NQ), jb = (int)(f / NQ % JB), ks = (int)(f / NQ / JB), n = lane & 31;
+    *row = mid ? w + (size_t)((n >> 3) * H + jb * 8 + (n & 7)) * K : w + (size_t)(q * H + jb * 32 + n) * K;
+    *k0 = ks * 16 + (lane >> 5) * 8;
+    return true;
+  }), out);
 }
 
 // ... and in the order of lstm_mid16_x3.hip: [k-step of 32][4-unit block][piece] -> one fragment of the 16x16x32 instruction,
 // lane (n = lane & 15, q = lane >> 4) owns W[gate (n >> 2) * H + block * 4 + (n & 3)][ks * 32 + q * 8 .. + 7]; k past K is zero.
 int pack_lstm_x3_mid16(std::vector<void*>& allocs, const float* w, int H, int K, unsigned short** out) {
   const int K2 = (K + 31) / 32, JB = H / 4;
-  std::vector<unsigned short> buf((size_t)K2 * JB * 3 * 512, 0);
-  for (int ks = 0; ks < K2; ++ks)
-    for (int jb = 0; jb < JB; ++jb)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int n = lane & 15, q = lane >> 4;
-        const float* row = w + (size_t)((n >> 2) * H + jb * 4 + (n & 3)) * K;
-        for (int e = 0; e < 8; ++e) {
-          const int k = ks * 32 + q * 8 + e;
-          if (k >= K) continue;
-          unsigned short p[3];
-          split3(row[k], p);
-          const size_t at = (((size_t)ks * JB + jb) * 3) * 512 + (size_t)lane * 8 + e;
-          buf[at] = p[0]; buf[at + 512] = p[1]; buf[at + 1024] = p[2];
-        }
-      }
-  return upload_bf16(allocs, buf, out);
+  return upload_bf16(allocs, pack_fragments_x3((size_t)K2 * JB, K, [&](size_t f, int lane, const float** row, int* k0) {
+    const int jb = (int)(f % JB), ks = (int)(f / JB), n = lane & 15;
+    *row = w + (size_t)((n >> 2) * H + jb * 4 + (n & 3)) * K;
+    *k0 = ks * 32 + (lane >> 4) * 8;
+    return true;
+  }), out);
 }
 
 struct TrainLstmWs {

@@ -65,26 +65,14 @@ int pack_mesh_tiles(empose_mesh* m, const empose_mesh_desc* d) {
 // row (tile * 32 + v) * 3 + c, as piece p of their three-piece bf16 split (bf16x3.h); k >= 200 and vertices past V are zero.
 int pack_mesh_tiles_x3(empose_mesh* m, const empose_mesh_desc* d) {
   const int V = d->n_vertices, NT = (V + 31) / 32, K = 200, KS = 13;
-  const size_t tile_shorts = MESH_X3_TILE_BYTES / 2;
-  std::vector<unsigned short> buf((size_t)NT * tile_shorts, 0);
-  for (int t = 0; t < NT; ++t)
-    for (int lane = 0; lane < 64; ++lane) {
-      const int v = t * 32 + (lane & 31), half = lane >> 5;
-      if (v >= V) continue;
-      for (int c = 0; c < 3; ++c) {
-        const float* row = d->wc + ((size_t)v * 3 + c) * K;
-        for (int ks = 0; ks < KS; ++ks)
-          for (int e = 0; e < 8; ++e) {
-            const int k = ks * 16 + half * 8 + e;
-            if (k >= K) continue;
-            unsigned short p[3];
-            split3(row[k], p);
-            unsigned short* dst = &buf[(size_t)t * tile_shorts + ((size_t)((ks * 3 + c) * 3) * 64 + lane) * 8 + e];
-            dst[0] = p[0]; dst[64 * 8] = p[1]; dst[2 * 64 * 8] = p[2];
-          }
-      }
-    }
-  return upload_bf16(m->allocs, buf, &m->wc_x3);
+  static_assert(MESH_X3_TILE_BYTES == KS * 3 * 3 * 1024, "a tile is [k-step][plane] fragments of three pieces");
+  return upload_bf16(m->allocs, pack_fragments_x3((size_t)NT * KS * 3, K, [&](size_t f, int lane, const float** row, int* k0) {
+    const int c = (int)(f % 3), ks = (int)(f / 3 % KS), v = (int)(f / 3 / KS) * 32 + (lane & 31);
+    if (v >= V) return false;
+    *row = d->wc + ((size_t)v * 3 + c) * K;
+    *k0 = ks * 16 + (lane >> 5) * 8;
+    return true;
+  }), &m->wc_x3);
 }
 
 // Tables of mesh_rows_bf16_kernel: per 32-vertex tile, k-step of 16, coordinate plane and (hi, lo) piece, lane

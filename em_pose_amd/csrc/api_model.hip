@@ -159,22 +159,13 @@ int pack_fragments_raw(std::vector<void*>& allocs, const float* weight, int N, i
 int pack_fragments_x3_raw(std::vector<void*>& allocs, const float* weight, int N, int K, float** out) {
   const int KS = (K + 15) / 16, NT = (N + 31) / 32;
   const int KS4 = (KS + 3) & ~3;
-  std::vector<unsigned short> buf((size_t)KS4 * NT * 3 * 512, 0);
-  for (int ks = 0; ks < KS; ++ks)
-    for (int nt = 0; nt < NT; ++nt)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int n = nt * 32 + (lane & 31);
-        if (n >= N) continue;
-        for (int e = 0; e < 8; ++e) {
-          const int k = ks * 16 + (lane >> 5) * 8 + e;
-          if (k >= K) continue;
-          unsigned short p[3];
-          split3(weight[(size_t)n * K + k], p);
-          const size_t at = (((size_t)ks * NT + nt) * 3) * 512 + (size_t)lane * 8 + e;
-          buf[at] = p[0]; buf[at + 512] = p[1]; buf[at + 1024] = p[2];
-        }
-      }
-  return upload_bf16(allocs, buf, out);
+  return upload_bf16(allocs, pack_fragments_x3((size_t)KS4 * NT, K, [&](size_t f, int lane, const float** row, int* k0) {
+    const int ks = (int)(f / NT), n = (int)(f % NT) * 32 + (lane & 31);
+    if (n >= N) return false;
+    *row = weight + (size_t)n * K;
+    *k0 = ks * 16 + (lane >> 5) * 8;      // (the padding k-steps start past K: nothing written)
+    return true;
+  }), out);
 }
 
 int pack_fragments(std::vector<void*>& allocs, const empose_dense_desc& d, Dense* out) {

@@ -4,6 +4,7 @@
 //   x w ~= x_h w_h + (x_h w_m + x_m w_h) + (x_h w_l + x_m w_m + x_l w_h)        six v_mfma_f32_32x32x16_bf16 products;
 // what is dropped (x_m w_l, x_l w_m, x_l w_l) is below 2^-23 of the product.  Internal, gfx950 only.
 #pragma once
+#include "device_common.h"
 #include "kernels.h"
 
 namespace empose {
@@ -12,6 +13,11 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
+
+constexpr int FRAG = 512;   // bf16 elements of one piece's wave fragment (64 lanes x 8 = 1 KB), the unit of every packed layout
+// a fragment / its bf16 elements in global memory (the address space spelled out: global_load, not flat_load)
+typedef const __attribute__((address_space(1))) u32x4_t* x3_gvec_t;
+typedef const __attribute__((address_space(1))) unsigned short* x3_gptr_t;
 
 // two fp32 -> their three bf16 pieces, packed (element 0 in the low half): v_cvt_pk_bf16_f32 + shift / mask + subtract
 __device__ __forceinline__ void split_pair(float x0, float x1, unsigned& h, unsigned& m, unsigned& l) {
@@ -45,11 +51,7 @@ __device__ __forceinline__ Pieces split8(float x0, float x1, float x2, float x3,
 // needs no LDS (the training engine's side streams, the streaming evaluation driver, another process).  Touching the last
 // architectural and the last accumulation register makes the wave allocate all 512 registers of its SIMD lane: no other
 // wave fits beside it, whatever it is -- exclusivity by construction (round 6).  First statement of every such kernel.
-#ifdef X3_LAB_SHARED_SIMD      // (scripts/dev/x3_shared_simd_lab.sh: the library WITHOUT the guarantee, to show what it is for)
-#define X3_EXCLUSIVE_SIMD() do { } while (0)
-#else
 #define X3_EXCLUSIVE_SIMD() asm volatile("v_mov_b32 v255, 0\n\tv_accvgpr_write_b32 a255, 0" ::: "v255", "a255")
-#endif
 
 // The six piece products of a k-step in the order they are issued: the small ones first, so that they meet in the
 // accumulator before the large one rounds.

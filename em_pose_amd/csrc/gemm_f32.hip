@@ -345,9 +345,7 @@ static hipError_t launch_cfg(const GemmBatch& batch, hipStream_t stream) {
   }
   if (blocks == 0) return hipSuccess;
   constexpr size_t lds = (size_t)C::LDS_FLOATS * sizeof(float);
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(gemm_tn_f32_kernel<C, ROLE>), lds)) return e;
-  hipLaunchKernelGGL((gemm_tn_f32_kernel<C, ROLE>), dim3(blocks, batch.count), dim3(C::NT), lds, stream, batch);
-  return hipGetLastError();
+  return launch_lds(gemm_tn_f32_kernel<C, ROLE>, dim3(blocks, batch.count), dim3(C::NT), lds, stream, batch);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -367,11 +365,7 @@ namespace wide {
 constexpr int BM = 256, BN = 256, BK = 32, LDT = BK + 4, NT = 256;
 constexpr int STAGE = (BM + BN) * LDT;
 constexpr size_t LDS_BYTES = 2 * (size_t)STAGE * sizeof(float);
-constexpr int SG_MFMA = 0x008, SG_VMEM_RD = 0x020, SG_DS_RD = 0x100, SG_DS_WR = 0x200;
 }  // namespace wide
-
-
-#define EMPOSE_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 
 #ifdef EMPOSE_GEMM_TRACE   // dev lab only: per-phase shader-clock stamps of two blocks
 __device__ long long g_gemm_trace[2][64];
@@ -494,16 +488,16 @@ __global__ __launch_bounds__(wide::NT) void gemm_wide_f32_kernel(GemmBatch batch
     gload(kill ? -lc : k_next);
     mma(fa[0], fb[0]);
 #pragma unroll
-    for (int s = 0; s < 8; ++s) { EMPOSE_SGB(SG_MFMA, 2); EMPOSE_SGB(SG_DS_RD, 1); }
+    for (int s = 0; s < 8; ++s) { SGB(SG_MFMA, 2); SGB(SG_DS_RD, 1); }
 #pragma unroll
-    for (int s = 0; s < 16; ++s) { EMPOSE_SGB(SG_MFMA, 2); EMPOSE_SGB(SG_VMEM_RD, 1); }
-    EMPOSE_SGB(SG_MFMA, 16);
+    for (int s = 0; s < 16; ++s) { SGB(SG_MFMA, 2); SGB(SG_VMEM_RD, 1); }
+    SGB(SG_MFMA, 16);
     // ---- k-group 1
     fread(cur, 2, fa[0], fb[0]);
     mma(fa[1], fb[1]);
 #pragma unroll
-    for (int s = 0; s < 8; ++s) { EMPOSE_SGB(SG_MFMA, 4); EMPOSE_SGB(SG_DS_RD, 1); }
-    EMPOSE_SGB(SG_MFMA, 32);
+    for (int s = 0; s < 8; ++s) { SGB(SG_MFMA, 4); SGB(SG_DS_RD, 1); }
+    SGB(SG_MFMA, 32);
     if (ragged && last_fetch) {   // uniform branch, taken once per block at most
 #pragma unroll
       for (int i = 0; i < 16; ++i)
@@ -515,17 +509,17 @@ __global__ __launch_bounds__(wide::NT) void gemm_wide_f32_kernel(GemmBatch batch
     lwrite(nxt);
     mma(fa[0], fb[0]);
 #pragma unroll
-    for (int s = 0; s < 8; ++s) { EMPOSE_SGB(SG_MFMA, 2); EMPOSE_SGB(SG_DS_RD, 1); }
+    for (int s = 0; s < 8; ++s) { SGB(SG_MFMA, 2); SGB(SG_DS_RD, 1); }
 #pragma unroll
-    for (int s = 0; s < 16; ++s) { EMPOSE_SGB(SG_MFMA, 2); EMPOSE_SGB(SG_DS_WR, 1); }
-    EMPOSE_SGB(SG_MFMA, 16);
+    for (int s = 0; s < 16; ++s) { SGB(SG_MFMA, 2); SGB(SG_DS_WR, 1); }
+    SGB(SG_MFMA, 16);
     __syncthreads();
     // ---- k-group 3
     fread(nxt, 0, fa[0], fb[0]);
     mma(fa[1], fb[1]);
 #pragma unroll
-    for (int s = 0; s < 8; ++s) { EMPOSE_SGB(SG_MFMA, 4); EMPOSE_SGB(SG_DS_RD, 1); }
-    EMPOSE_SGB(SG_MFMA, 32);
+    for (int s = 0; s < 8; ++s) { SGB(SG_MFMA, 4); SGB(SG_DS_RD, 1); }
+    SGB(SG_MFMA, 32);
     EMPOSE_STAMP(2 + kt)
   }
 
@@ -542,10 +536,7 @@ static hipError_t launch_wide(const GemmBatch& batch, hipStream_t stream) {
     blocks = t > blocks ? t : blocks;
   }
   if (blocks == 0) return hipSuccess;
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(gemm_wide_f32_kernel<ROLE>), wide::LDS_BYTES)) return e;
-  hipLaunchKernelGGL((gemm_wide_f32_kernel<ROLE>), dim3(blocks, batch.count), dim3(wide::NT), wide::LDS_BYTES, stream,
-                     batch);
-  return hipGetLastError();
+  return launch_lds(gemm_wide_f32_kernel<ROLE>, dim3(blocks, batch.count), dim3(wide::NT), wide::LDS_BYTES, stream, batch);
 }
 
 using CfgS11 = Cfg<2, 2, 1, 1, 32, false>;   //  64 x  64
@@ -841,8 +832,7 @@ size_t gemm_ksplit_workspace_floats(int M, int N, int K) {
 hipError_t launch_gemm_ksplit(const GemmProb& p, float* workspace, hipStream_t stream, const LstmCellBwdArgs* cell) {
   const int tiles = ((p.M + ks::BT - 1) / ks::BT) * ((p.N + ks::BT - 1) / ks::BT);
   const int S = (p.K + ks::KS - 1) / ks::KS;
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(gemm_ksplit_kernel), ks::LDS_BYTES)) return e;
-  hipLaunchKernelGGL(gemm_ksplit_kernel, dim3(tiles, S), dim3(256), ks::LDS_BYTES, stream, p, workspace);
+  if (hipError_t e = launch_lds(gemm_ksplit_kernel, dim3(tiles, S), dim3(256), ks::LDS_BYTES, stream, p, workspace)) return e;
   hipLaunchKernelGGL(gemm_ksplit_reduce_kernel, dim3(tiles * 16), dim3(256), 0, stream, p, (const float*)workspace, S, tiles,
                      cell ? *cell : LstmCellBwdArgs{}, cell ? 1 : 0);
   return hipGetLastError();
@@ -950,11 +940,9 @@ static hipError_t launch_fewrows_cfg(const GemmBatch& batch, int maxN, int maxK,
                                      const LstmCellBwdArgs* cell = nullptr) {
   const size_t lds = (size_t)MB * maxK * sizeof(float);   // arow[MB][K of the widest problem]
   if (lds > FEWROWS_MAX_LDS) return hipErrorInvalidValue;
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(gemm_fewrows_kernel<MB>), lds)) return e;
   dim3 grid((maxN + 3) / 4, batch.count);
-  hipLaunchKernelGGL(gemm_fewrows_kernel<MB>, grid, dim3(256), lds, stream, batch, cell ? *cell : LstmCellBwdArgs{},
-                     cell ? 1 : 0);
-  return hipGetLastError();
+  return launch_lds(gemm_fewrows_kernel<MB>, grid, dim3(256), lds, stream, batch, cell ? *cell : LstmCellBwdArgs{},
+                    cell ? 1 : 0);
 }
 
 static hipError_t launch_fewrows(const GemmBatch& batch, hipStream_t stream, const LstmCellBwdArgs* cell = nullptr) {
@@ -1089,9 +1077,9 @@ hipError_t launch_rec_ksplit(const RecBatch& b, const LstmCellBwdArgs* cells, fl
     if (i > 0 && t != tiles) return hipErrorInvalidValue;   // the problems of a wavefront step share M and N
     tiles = t;
   }
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(rec_ksplit_kernel), ks::LDS_BYTES)) return e;
-  hipLaunchKernelGGL(rec_ksplit_kernel, dim3(tiles, s_max, b.count), dim3(256), ks::LDS_BYTES, stream, b, workspace, tiles,
-                     s_max);
+  if (hipError_t e = launch_lds(rec_ksplit_kernel, dim3(tiles, s_max, b.count), dim3(256), ks::LDS_BYTES, stream, b, workspace,
+                                tiles, s_max))
+    return e;
   hipLaunchKernelGGL(rec_ksplit_reduce_kernel, dim3(tiles * 16, b.count), dim3(256), 0, stream, b, (const float*)workspace,
                      tiles, s_max, cells[0], cells[b.count > 1 ? 1 : 0]);
   return hipGetLastError();
@@ -1264,10 +1252,8 @@ static hipError_t launch_rec_fewrows_cfg(const RecBatch& b, const LstmCellBwdArg
                        cells[b.count > 1 ? 1 : 0]);
     return hipGetLastError();
   }
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(rec_fewrows_kernel<MB>), lds)) return e;
-  hipLaunchKernelGGL(rec_fewrows_kernel<MB>, dim3((maxN + 3) / 4, b.count), dim3(256), lds, stream, b, cells[0],
-                     cells[b.count > 1 ? 1 : 0]);
-  return hipGetLastError();
+  return launch_lds(rec_fewrows_kernel<MB>, dim3((maxN + 3) / 4, b.count), dim3(256), lds, stream, b, cells[0],
+                    cells[b.count > 1 ? 1 : 0]);
 }
 
 hipError_t launch_rec_fewrows(const RecBatch& b, const LstmCellBwdArgs* cells, hipStream_t stream) {
@@ -1375,9 +1361,6 @@ constexpr size_t LDS_BYTES = (size_t)BM * LDA * sizeof(float) + 64;
 constexpr int RING = 3;
 }  // namespace gx
 
-typedef const __attribute__((address_space(1))) u32x4_t* gx_gvec_t;
-typedef const __attribute__((address_space(1))) unsigned short* gx_gptr_t;
-
 // W [N][ldw] (K columns used) -> pieces in fragment order: [k-step of 16][32-column tile][piece][lane][8], lane
 // (n = lane & 31, half = lane >> 5) owns W[tile * 32 + n][ks * 16 + half * 8 .. + 7]; rows >= N and columns >= K are zero.
 __global__ __launch_bounds__(256) void pack_x3_kernel(const float* __restrict__ W, int ldw, int N, int K,
@@ -1430,7 +1413,7 @@ __global__ __launch_bounds__(gx::NT) void gemm_train_x3_kernel(GemmProb p, const
   int ct[2];
 #pragma unroll
   for (int j = 0; j < 2; ++j) { const int t = n0 / 32 + wave * 2 + j; ct[j] = t < NT32 ? t : NT32 - 1; }
-  gx_gptr_t wb = (gx_gptr_t)wfrag + lane * 8;
+  x3_gptr_t wb = (x3_gptr_t)wfrag + lane * 8;
   const float* a_rd = act + l31 * LDA + lh * 8;
 
   f32x16 acc[2][2];
@@ -1448,7 +1431,7 @@ __global__ __launch_bounds__(gx::NT) void gemm_train_x3_kernel(GemmProb p, const
 #pragma unroll
     for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int pc = 0; pc < 3; ++pc) b[j][pc] = *(gx_gvec_t)(wb + (((size_t)kc * NT32 + ct[j]) * 3 + pc) * 512);
+      for (int pc = 0; pc < 3; ++pc) b[j][pc] = *(x3_gvec_t)(wb + (((size_t)kc * NT32 + ct[j]) * 3 + pc) * 512);
   };
   auto asplit = [&](Pieces (&a)[2], int ks) {
     const int kc = ks < KS ? ks : KS - 1;
@@ -1507,14 +1490,8 @@ hipError_t launch_gemm_train_x3(const TrainGemmArgs& t, const unsigned short* wf
     g.e_slope = t.e_slope;
   }
   const dim3 grid((unsigned)(((t.M + gx::BM - 1) / gx::BM) * ((t.N + gx::BN - 1) / gx::BN)));
-  if (emode == 2) {
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(gemm_train_x3_kernel<true>), gx::LDS_BYTES)) return e;
-    hipLaunchKernelGGL(gemm_train_x3_kernel<true>, grid, dim3(gx::NT), gx::LDS_BYTES, stream, g, wfrag);
-  } else {
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(gemm_train_x3_kernel<false>), gx::LDS_BYTES)) return e;
-    hipLaunchKernelGGL(gemm_train_x3_kernel<false>, grid, dim3(gx::NT), gx::LDS_BYTES, stream, g, wfrag);
-  }
-  return hipGetLastError();
+  return emode == 2 ? launch_lds(gemm_train_x3_kernel<true>, grid, dim3(gx::NT), gx::LDS_BYTES, stream, g, wfrag)
+                    : launch_lds(gemm_train_x3_kernel<false>, grid, dim3(gx::NT), gx::LDS_BYTES, stream, g, wfrag);
 }
 
 // Name (as a profiler prints it) of the kernel `launch_gemm` runs for `count` problems of this shape.

@@ -86,6 +86,15 @@ unsigned poll_timeouts_take();          // host: read and clear
 unsigned poll_timeouts_peek();          // host: read
 constexpr size_t LDS_BYTES_PER_CU = 160 * 1024;
 hipError_t allow_dynamic_lds(const void* fn, size_t bytes);
+// A launch of a kernel with a large dynamic-LDS request: raises the limit of `fn` (above), launches, returns the launch's
+// error.  `args` convert to the kernel's parameter types here, as they would at a direct launch.
+template <typename... Params, typename... Args>
+inline hipError_t launch_lds(void (*fn)(Params...), dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream,
+                             const Args&... args) {
+  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(fn), lds_bytes)) return e;
+  hipLaunchKernelGGL(fn, grid, block, lds_bytes, stream, static_cast<Params>(args)...);
+  return hipGetLastError();
+}
 // Workgroups of `fn` (block size `threads`, `lds_bytes` of dynamic LDS) that can be resident at once on the CURRENT device:
 // what a cooperative launch may ask for.  Cached per (device, kernel); the attribute above is set on the way.
 hipError_t coresident_blocks(const void* fn, int threads, size_t lds_bytes, int* blocks);

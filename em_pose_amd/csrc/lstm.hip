@@ -20,6 +20,7 @@
 // so that one ds_read_b128 feeds four MFMAs.
 #include <type_traits>
 
+#include "device_common.h"
 #include "kernels.h"
 #include "lane_reduce.h"
 
@@ -49,10 +50,7 @@ constexpr int BM = 64, BU = 32, BK = 64;
 constexpr int ROWS = BM + 4 * BU;
 constexpr int STAGE = ROWS * BK;
 constexpr size_t LDS_BYTES = 2 * (size_t)STAGE * sizeof(float);
-constexpr int SG_MFMA = 0x008, SG_VMEM_RD = 0x020, SG_DS_RD = 0x100, SG_DS_WR = 0x200;
 }  // namespace lc
-
-#define LSTM_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 
 #ifdef EMPOSE_LSTM_TRACE   // dev lab only: per-phase shader-clock stamps of block (0,0,0)
 __device__ long long g_lstm_trace[128];
@@ -61,11 +59,6 @@ __device__ long long g_lstm_trace[128];
 #else
 #define LSTM_STAMP(i)
 #endif
-
-// Fast cell non-linearities: v_exp_f32 / v_rcp_f32 (about 1 ulp each); absolute error ~1e-7, far inside the 1e-4 parity
-// budget, and the unit finish is no longer a visible fraction of the launch.
-__device__ __forceinline__ float fsigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float ftanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
 
 typedef const __attribute__((address_space(1))) f32x4* gvec_t;
 typedef const __attribute__((address_space(1))) char* gbyte_t;
@@ -212,10 +205,10 @@ __global__ __launch_bounds__(256) void lstm_chain_kernel(LstmWaveArgs a) {
       const size_t hc = (size_t)row * H + e_unit;
       const bool live = t < e_len[e];
       const int t_out = (rev && live) ? e_len[e] - 1 - t : t;   // a finished reverse row zero-fills the padded slot t
-      const float g_i = fsigmoid(acc[i][0][r] + e_bias[0]), g_f = fsigmoid(acc[i][1][r] + e_bias[1]);
-      const float g_g = ftanh(acc[i][2][r] + e_bias[2]), g_o = fsigmoid(acc[i][3][r] + e_bias[3]);
+      const float g_i = fast_sigmoid(acc[i][0][r] + e_bias[0]), g_f = fast_sigmoid(acc[i][1][r] + e_bias[1]);
+      const float g_g = fast_tanh(acc[i][2][r] + e_bias[2]), g_o = fast_sigmoid(acc[i][3][r] + e_bias[3]);
       const float c_new = g_f * e_c[e] + g_i * g_g;
-      const float h_new = g_o * ftanh(c_new);
+      const float h_new = g_o * fast_tanh(c_new);
       if (live) cst[hc] = c_new;
       h_next[hc] = live ? h_new : e_hp[e];
       if (yout) yout[((size_t)row * F + t_out) * y_ld + y_col + e_unit] = live ? h_new : 0.f;
@@ -258,41 +251,35 @@ __global__ __launch_bounds__(256) void lstm_chain_kernel(LstmWaveArgs a) {
       if (ragged) gzero();     // uniform branch; the registers hold the next tile of the stream
       // ---- chunk 0
       fread(cur, 1, fa[1], fb[1]);
-#ifndef LSTM_EXP_NOWRITE
       lwrite(nxt);
-#endif
       mma(fa[0], fb[0]);
 #pragma unroll
-      for (int q = 0; q < 6; ++q) { LSTM_SGB(SG_MFMA, 1); LSTM_SGB(SG_DS_RD, 1); }
+      for (int q = 0; q < 6; ++q) { SGB(SG_MFMA, 1); SGB(SG_DS_RD, 1); }
 #pragma unroll
-      for (int q = 0; q < 12; ++q) { LSTM_SGB(SG_MFMA, 2); LSTM_SGB(SG_DS_WR, 1); }
-      LSTM_SGB(SG_MFMA, 2);
+      for (int q = 0; q < 12; ++q) { SGB(SG_MFMA, 2); SGB(SG_DS_WR, 1); }
+      SGB(SG_MFMA, 2);
       // ---- chunk 1
       fread(cur, 2, fa[0], fb[0]);
-#ifndef LSTM_EXP_NOLOAD
       ragged = gload();
-#endif
       mma(fa[1], fb[1]);
 #pragma unroll
-      for (int q = 0; q < 6; ++q) { LSTM_SGB(SG_MFMA, 1); LSTM_SGB(SG_DS_RD, 1); }
+      for (int q = 0; q < 6; ++q) { SGB(SG_MFMA, 1); SGB(SG_DS_RD, 1); }
 #pragma unroll
-      for (int q = 0; q < 12; ++q) { LSTM_SGB(SG_MFMA, 2); LSTM_SGB(SG_VMEM_RD, 1); }
-      LSTM_SGB(SG_MFMA, 2);
+      for (int q = 0; q < 12; ++q) { SGB(SG_MFMA, 2); SGB(SG_VMEM_RD, 1); }
+      SGB(SG_MFMA, 2);
       // ---- chunk 2
       fread(cur, 3, fa[1], fb[1]);
       mma(fa[0], fb[0]);
 #pragma unroll
-      for (int q = 0; q < 6; ++q) { LSTM_SGB(SG_MFMA, 2); LSTM_SGB(SG_DS_RD, 1); }
-      LSTM_SGB(SG_MFMA, 20);
-#ifndef LSTM_EXP_NOBARRIER
+      for (int q = 0; q < 6; ++q) { SGB(SG_MFMA, 2); SGB(SG_DS_RD, 1); }
+      SGB(SG_MFMA, 20);
       __syncthreads();
-#endif
       // ---- chunk 3
       fread(nxt, 0, fa[0], fb[0]);
       mma(fa[1], fb[1]);
 #pragma unroll
-      for (int q = 0; q < 6; ++q) { LSTM_SGB(SG_MFMA, 2); LSTM_SGB(SG_DS_RD, 1); }
-      LSTM_SGB(SG_MFMA, 20);
+      for (int q = 0; q < 6; ++q) { SGB(SG_MFMA, 2); SGB(SG_DS_RD, 1); }
+      SGB(SG_MFMA, 20);
       ld_advance();
       LSTM_STAMP(stamp++)
     }
@@ -527,10 +514,10 @@ __global__ __launch_bounds__(256) void lstm_seq_kernel(LstmSeqArgs a) {
       const size_t hc = (size_t)row * H + e_unit;
       const bool live = t < e_len[e];
       const int t_out = (rev && live) ? e_len[e] - 1 - t : t;   // a finished reverse row zero-fills the padded slot t
-      const float g_i = fsigmoid(acc[i][0][r] + e_bias[0]), g_f = fsigmoid(acc[i][1][r] + e_bias[1]);
-      const float g_g = ftanh(acc[i][2][r] + e_bias[2]), g_o = fsigmoid(acc[i][3][r] + e_bias[3]);
+      const float g_i = fast_sigmoid(acc[i][0][r] + e_bias[0]), g_f = fast_sigmoid(acc[i][1][r] + e_bias[1]);
+      const float g_g = fast_tanh(acc[i][2][r] + e_bias[2]), g_o = fast_sigmoid(acc[i][3][r] + e_bias[3]);
       const float c_new = g_f * e_c[e] + g_i * g_g;
-      const float h_new = g_o * ftanh(c_new);
+      const float h_new = g_o * fast_tanh(c_new);
       if (live) cst[hc] = failed ? poison : c_new;
       const float h_out = failed ? poison : (live ? h_new : e_hp[e]);
       // other workgroups (on other XCDs) read this row in the next step: a store that reaches the memory side
@@ -586,10 +573,10 @@ __global__ __launch_bounds__(256) void lstm_seq_kernel(LstmSeqArgs a) {
       lwrite(nxt);
       mma(fa[0], fb[0]);
 #pragma unroll
-      for (int q = 0; q < 6; ++q) { LSTM_SGB(SG_MFMA, 1); LSTM_SGB(SG_DS_RD, 1); }
+      for (int q = 0; q < 6; ++q) { SGB(SG_MFMA, 1); SGB(SG_DS_RD, 1); }
 #pragma unroll
-      for (int q = 0; q < 12; ++q) { LSTM_SGB(SG_MFMA, 2); LSTM_SGB(SG_DS_WR, 1); }
-      LSTM_SGB(SG_MFMA, 2);
+      for (int q = 0; q < 12; ++q) { SGB(SG_MFMA, 2); SGB(SG_DS_WR, 1); }
+      SGB(SG_MFMA, 2);
       // ---- chunk 1
       fread(cur, 2, fa[0], fb[0]);
       if (pub_unit >= 0 && (--pub_wait == 0 || ld_wait)) {   // (early when this wave is about to wait for the others)
@@ -615,23 +602,23 @@ __global__ __launch_bounds__(256) void lstm_seq_kernel(LstmSeqArgs a) {
       ragged = gload();
       mma(fa[1], fb[1]);
 #pragma unroll
-      for (int q = 0; q < 6; ++q) { LSTM_SGB(SG_MFMA, 1); LSTM_SGB(SG_DS_RD, 1); }
+      for (int q = 0; q < 6; ++q) { SGB(SG_MFMA, 1); SGB(SG_DS_RD, 1); }
 #pragma unroll
-      for (int q = 0; q < 12; ++q) { LSTM_SGB(SG_MFMA, 2); LSTM_SGB(SG_VMEM_RD, 1); }
-      LSTM_SGB(SG_MFMA, 2);
+      for (int q = 0; q < 12; ++q) { SGB(SG_MFMA, 2); SGB(SG_VMEM_RD, 1); }
+      SGB(SG_MFMA, 2);
       // ---- chunk 2
       fread(cur, 3, fa[1], fb[1]);
       mma(fa[0], fb[0]);
 #pragma unroll
-      for (int q = 0; q < 6; ++q) { LSTM_SGB(SG_MFMA, 2); LSTM_SGB(SG_DS_RD, 1); }
-      LSTM_SGB(SG_MFMA, 20);
+      for (int q = 0; q < 6; ++q) { SGB(SG_MFMA, 2); SGB(SG_DS_RD, 1); }
+      SGB(SG_MFMA, 20);
       __syncthreads();
       // ---- chunk 3
       fread(nxt, 0, fa[0], fb[0]);
       mma(fa[1], fb[1]);
 #pragma unroll
-      for (int q = 0; q < 6; ++q) { LSTM_SGB(SG_MFMA, 2); LSTM_SGB(SG_DS_RD, 1); }
-      LSTM_SGB(SG_MFMA, 20);
+      for (int q = 0; q < 6; ++q) { SGB(SG_MFMA, 2); SGB(SG_DS_RD, 1); }
+      SGB(SG_MFMA, 20);
       ld_advance();
       LSTM_STAMP(stamp++)
     }
@@ -822,10 +809,10 @@ __global__ __launch_bounds__(256) void lstm_mid_kernel(LstmWaveArgs a) {
     const size_t hc = (size_t)row * H + e_unit;
     const bool live = t < e_len[x];
     const int t_out = (rev && live) ? e_len[x] - 1 - t : t;
-    const float g_i = fsigmoid(gs[0] + e_bias[0]), g_f = fsigmoid(gs[1] + e_bias[1]);
-    const float g_g = ftanh(gs[2] + e_bias[2]), g_o = fsigmoid(gs[3] + e_bias[3]);
+    const float g_i = fast_sigmoid(gs[0] + e_bias[0]), g_f = fast_sigmoid(gs[1] + e_bias[1]);
+    const float g_g = fast_tanh(gs[2] + e_bias[2]), g_o = fast_sigmoid(gs[3] + e_bias[3]);
     const float c_new = g_f * e_c[x] + g_i * g_g;
-    const float h_new = g_o * ftanh(c_new);
+    const float h_new = g_o * fast_tanh(c_new);
     if (live) L.c[hc] = c_new;
     L.h[(t + 1) & 1][hc] = live ? h_new : e_hp[x];
     if (L.y) L.y[((size_t)row * F + t_out) * L.y_ld + L.y_col + e_unit] = live ? h_new : 0.f;
@@ -921,8 +908,8 @@ __global__ __launch_bounds__(256) void lstm_small_kernel(LstmWaveArgs a) {
     float h_new = 0.f, c_old = 0.f, c_keep = 0.f, h_carry;
     if (live) {   // (these expressions are kept as they are: lstm_persist_kernel must give the same bits)
       c_old = cst[hc];
-      const float c_new = fsigmoid(gf + bias[H + unit]) * c_old + fsigmoid(gi + bias[unit]) * ftanh(gg + bias[2 * H + unit]);
-      h_new = fsigmoid(go + bias[3 * H + unit]) * ftanh(c_new);
+      const float c_new = fast_sigmoid(gf + bias[H + unit]) * c_old + fast_sigmoid(gi + bias[unit]) * fast_tanh(gg + bias[2 * H + unit]);
+      h_new = fast_sigmoid(go + bias[3 * H + unit]) * fast_tanh(c_new);
       cst[hc] = c_new;
       h_next[hc] = h_carry = h_new;
       c_keep = c_new;
@@ -934,8 +921,8 @@ __global__ __launch_bounds__(256) void lstm_small_kernel(LstmWaveArgs a) {
     if (L.sv_gates) {   // training forward: what back-propagation through time reads
       const size_t rt = (size_t)row * F + t;
       float* sg = L.sv_gates + rt * 4 * H + unit;
-      sg[0] = fsigmoid(gi + bias[unit]); sg[H] = fsigmoid(gf + bias[H + unit]);
-      sg[2 * H] = ftanh(gg + bias[2 * H + unit]); sg[3 * H] = fsigmoid(go + bias[3 * H + unit]);
+      sg[0] = fast_sigmoid(gi + bias[unit]); sg[H] = fast_sigmoid(gf + bias[H + unit]);
+      sg[2 * H] = fast_tanh(gg + bias[2 * H + unit]); sg[3 * H] = fast_sigmoid(go + bias[3 * H + unit]);
       L.sv_c[rt * H + unit] = c_keep;
       if (t + 1 < F) L.sv_hprev[(rt + 1) * H + unit] = h_carry;
     }
@@ -1031,10 +1018,10 @@ __global__ __launch_bounds__(256) void lstm_fewrows_kernel(LstmWaveArgs a) {
   const size_t hc = (size_t)row * H + unit;
   const bool live = t < e_len;
   const int t_out = (rev && live) ? e_len - 1 - t : t;   // a finished reverse row zero-fills the padded slot t
-  const float g_i = fsigmoid(gs[0] + e_bias[0]), g_f = fsigmoid(gs[1] + e_bias[1]);
-  const float g_g = ftanh(gs[2] + e_bias[2]), g_o = fsigmoid(gs[3] + e_bias[3]);
+  const float g_i = fast_sigmoid(gs[0] + e_bias[0]), g_f = fast_sigmoid(gs[1] + e_bias[1]);
+  const float g_g = fast_tanh(gs[2] + e_bias[2]), g_o = fast_sigmoid(gs[3] + e_bias[3]);
   const float c_new = g_f * e_c + g_i * g_g;
-  const float h_new = g_o * ftanh(c_new);
+  const float h_new = g_o * fast_tanh(c_new);
   if (live) L.c[hc] = c_new;
   L.h[(t + 1) & 1][hc] = live ? h_new : e_hp;
   if (L.y) L.y[((size_t)row * F + t_out) * L.y_ld + L.y_col + unit] = live ? h_new : 0.f;
@@ -1273,8 +1260,8 @@ __global__ __launch_bounds__(256) void lstm_persist_kernel(LstmPersistArgs a) {
           const bool live = k < len;
           float h_new = 0.f;
           if (live) {
-            const float c_new = fsigmoid(gf + bias[1]) * c_reg + fsigmoid(gi + bias[0]) * ftanh(gg + bias[2]);
-            h_new = fsigmoid(go + bias[3]) * ftanh(c_new);
+            const float c_new = fast_sigmoid(gf + bias[1]) * c_reg + fast_sigmoid(gi + bias[0]) * fast_tanh(gg + bias[2]);
+            h_new = fast_sigmoid(go + bias[3]) * fast_tanh(c_new);
             c_reg = c_new;
             h_reg = h_new;
           }
@@ -1285,8 +1272,8 @@ __global__ __launch_bounds__(256) void lstm_persist_kernel(LstmPersistArgs a) {
           if (U.sv_gates) {   // training forward: what back-propagation through time reads (as lstm_small_kernel)
             const size_t rt = (size_t)lane * F + k;
             float* sg = U.sv_gates + rt * 4 * H + unit;
-            sg[0] = fsigmoid(gi + bias[0]); sg[H] = fsigmoid(gf + bias[1]);
-            sg[2 * H] = ftanh(gg + bias[2]); sg[3 * H] = fsigmoid(go + bias[3]);
+            sg[0] = fast_sigmoid(gi + bias[0]); sg[H] = fast_sigmoid(gf + bias[1]);
+            sg[2 * H] = fast_tanh(gg + bias[2]); sg[3 * H] = fast_sigmoid(go + bias[3]);
             U.sv_c[rt * H + unit] = failed ? poison : c_reg;
             if (k + 1 < F) U.sv_hprev[(rt + 1) * H + unit] = failed ? poison : h_reg;
           }
@@ -1383,20 +1370,16 @@ hipError_t launch_lstm_wave(const LstmWaveArgs& a_in, hipStream_t stream) {
   }
   if (a.B <= LSTM_MID_B) {   // K split over the waves of 32 x 16 tiles, one z slice per unit
     lstm_build_chain(a, 1);
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(lstm_mid_kernel), lm::LDS_BYTES)) return e;
     dim3 grid((a.H + lm::BU - 1) / lm::BU, (a.B + lm::BM - 1) / lm::BM, a.n_units);
-    hipLaunchKernelGGL(lstm_mid_kernel, grid, dim3(256), lm::LDS_BYTES, stream, a);
-    return hipGetLastError();
+    return launch_lds(lstm_mid_kernel, grid, dim3(256), lm::LDS_BYTES, stream, a);
   }
   const int tiles = ((a.H + lc::BU - 1) / lc::BU) * ((a.B + lc::BM - 1) / lc::BM);
   // Chain all units in one block (equal work per block) once the tiles alone fill the CUs; spread them otherwise.
   const int units_per_block = tiles >= 192 ? a.n_units : 1;
   lstm_build_chain(a, units_per_block);
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(lstm_chain_kernel), lc::LDS_BYTES)) return e;
   dim3 grid((a.H + lc::BU - 1) / lc::BU, (a.B + lc::BM - 1) / lc::BM,
             (a.n_units + units_per_block - 1) / units_per_block);
-  hipLaunchKernelGGL(lstm_chain_kernel, grid, dim3(256), lc::LDS_BYTES, stream, a);
-  return hipGetLastError();
+  return launch_lds(lstm_chain_kernel, grid, dim3(256), lc::LDS_BYTES, stream, a);
 }
 
 size_t lstm_seq_counter_uints(int B) { return (size_t)((B + lc::BM - 1) / lc::BM) * 4; }

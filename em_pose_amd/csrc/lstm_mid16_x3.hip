@@ -4,7 +4,7 @@
 // two layers of a wavefront step -- half of the chip -- and each streams 196 KB of weight pieces per step, which is what ONE
 // CU can pull from the memory side in the 3.6 us its K loop takes (the L2 does not keep weights across launches).  With
 // twice the workgroups and half the K each the same launch takes 7.2 instead of 8.2 us at 32 rows and 8.2 instead of 10.1
-// at 36 (lab build LM3_LAB_TWICE_WGS, profiles/r06i_lstm_mid_ring_lab.txt).  Hence this form:
+// at 36 (a lab build of lstm_mid_x3.hip with twice the workgroups, profiles/r06i_lstm_mid_ring_lab.txt).  Hence this form:
 //   * a workgroup owns 4 hidden units x 4 gates = 16 columns (column n = gate * 4 + unit) of up to 64 rows: 128 workgroups
 //     per layer, 256 per step; weights packed [k-step of 32][4-unit block][piece] (api_lstm.hip pack_lstm_x3_mid16);
 //   * the products are v_mfma_f32_16x16x32_bf16: 16 rows x 16 columns x 32 k.  The A planes stay as every other kernel
@@ -31,16 +31,10 @@ constexpr int PART_FLOATS = 4 * NC * PLD;                     // [wave][column][
 constexpr int HX_FLOATS = BM * (BU + 1);
 constexpr size_t LDS_BYTES = 84 * 1024;                       // > half a CU: one workgroup per CU
 static_assert((PART_FLOATS + HX_FLOATS) * 4 <= (int)LDS_BYTES, "LDS layout");
-constexpr int FRAG = 512;                                     // bf16 elements of one fragment (1 KB)
 }  // namespace lh3
 
-typedef const __attribute__((address_space(1))) u32x4_t* lh3_gvec_t;
-typedef const __attribute__((address_space(1))) unsigned short* lh3_gptr_t;
 typedef float lh3_f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned lh3_u32x2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float lh3_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float lh3_tanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
 
 template <int RT, int D>   // row tiles of 16 a workgroup multiplies (2: at most 32 rows, 4: at most 64); ring depth
 __global__ __launch_bounds__(lh3::NT) void lstm_mid16_x3_kernel(LstmX3Args a) {
@@ -92,18 +86,18 @@ __global__ __launch_bounds__(lh3::NT) void lstm_mid16_x3_kernel(LstmX3Args a) {
     // the second k-step of 16 of this step; an odd input ends on a half step: its lanes read the first half again (finite
     // values against weights that are zero there)
     const int ks = 2 * k2 + ((2 * k2 + 1 < ksn) ? (lq >> 1) : 0);
-    lh3_gptr_t ab = (lh3_gptr_t)(in ? p_in : p_rec) + ((size_t)ks * 3) * FRAG + lane_off;
-    lh3_gptr_t wb = (lh3_gptr_t)(in ? p_wih : p_whh) + (((size_t)k2 * JB + jb) * 3) * FRAG + lane * 8;
+    x3_gptr_t ab = (x3_gptr_t)(in ? p_in : p_rec) + ((size_t)ks * 3) * FRAG + lane_off;
+    x3_gptr_t wb = (x3_gptr_t)(in ? p_wih : p_whh) + (((size_t)k2 * JB + jb) * 3) * FRAG + lane * 8;
 #pragma unroll
     for (int r = 0; r < RT; ++r) {
       // row tile of 16 r: 32-row tile r >> 1 (a tile past the batch reads the last one: rows never stored), rows (r & 1) * 16 ..
       const int rt32 = (r >> 1) < RT32 ? (r >> 1) : RT32 - 1;
-      lh3_gptr_t ar = ab + (size_t)rt32 * ksn * 3 * FRAG + (r & 1) * 16 * 8;
+      x3_gptr_t ar = ab + (size_t)rt32 * ksn * 3 * FRAG + (r & 1) * 16 * 8;
 #pragma unroll
-      for (int pc = 0; pc < 3; ++pc) A[r][pc] = *(lh3_gvec_t)(ar + pc * FRAG);
+      for (int pc = 0; pc < 3; ++pc) A[r][pc] = *(x3_gvec_t)(ar + pc * FRAG);
     }
 #pragma unroll
-    for (int pc = 0; pc < 3; ++pc) W[pc] = *(lh3_gvec_t)(wb + pc * FRAG);
+    for (int pc = 0; pc < 3; ++pc) W[pc] = *(x3_gvec_t)(wb + pc * FRAG);
   };
   auto mma = [&](const u32x4_t (&A)[RT][3], const u32x4_t (&W)[3]) {
 #pragma unroll
@@ -141,10 +135,10 @@ __global__ __launch_bounds__(lh3::NT) void lstm_mid16_x3_kernel(LstmX3Args a) {
     const float* ps = part + (q * BU + f_u) * PLD + f_row;
     gsum[q] = (RT == 4 || f_row < 32) ? ((ps[0] + ps[NC * PLD]) + ps[2 * NC * PLD]) + ps[3 * NC * PLD] : 0.f;
   }
-  const float g_i = lh3_sigmoid(gsum[0] + e_bias[0]), g_f = lh3_sigmoid(gsum[1] + e_bias[1]);
-  const float g_g = lh3_tanh(gsum[2] + e_bias[2]), g_o = lh3_sigmoid(gsum[3] + e_bias[3]);
+  const float g_i = fast_sigmoid(gsum[0] + e_bias[0]), g_f = fast_sigmoid(gsum[1] + e_bias[1]);
+  const float g_g = fast_tanh(gsum[2] + e_bias[2]), g_o = fast_sigmoid(gsum[3] + e_bias[3]);
   const float c_new = g_f * e_c + g_i * g_g;
-  const float h_new = g_o * lh3_tanh(c_new);
+  const float h_new = g_o * fast_tanh(c_new);
   const float hv = live ? h_new : (a.seq_lengths ? e_hp : 0.f);
   if (row_used) {
     const size_t o = (size_t)g_row * H + g_unit;
@@ -181,16 +175,8 @@ hipError_t launch_lstm_mid16_x3(const LstmX3Args& a, hipStream_t stream) {
   if (a.n_units == 0) return hipSuccess;
   if (!lstm_mid16_shape_ok(a.B, a.H)) return hipErrorInvalidValue;
   dim3 grid(a.H / lh3::BU, 1, a.n_units);
-  if (a.B <= 32) {
-    auto* fn = lstm_mid16_x3_kernel<2, LH3_RING2>;
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(fn), lh3::LDS_BYTES)) return e;
-    hipLaunchKernelGGL(fn, grid, dim3(lh3::NT), lh3::LDS_BYTES, stream, a);
-  } else {
-    auto* fn = lstm_mid16_x3_kernel<4, LH3_RING4>;
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(fn), lh3::LDS_BYTES)) return e;
-    hipLaunchKernelGGL(fn, grid, dim3(lh3::NT), lh3::LDS_BYTES, stream, a);
-  }
-  return hipGetLastError();
+  return a.B <= 32 ? launch_lds(lstm_mid16_x3_kernel<2, LH3_RING2>, grid, dim3(lh3::NT), lh3::LDS_BYTES, stream, a)
+                   : launch_lds(lstm_mid16_x3_kernel<4, LH3_RING4>, grid, dim3(lh3::NT), lh3::LDS_BYTES, stream, a);
 }
 
 }  // namespace empose

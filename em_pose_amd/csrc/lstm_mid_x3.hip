@@ -28,15 +28,7 @@ constexpr int PART_FLOATS = 4 * 32 * PLD;                     // [wave][column][
 constexpr int HX_FLOATS = BM * (BU + 1);                      // the new hidden values [row][unit] for the piece split
 constexpr size_t LDS_BYTES = 84 * 1024;                       // > half a CU: one workgroup per CU
 static_assert((PART_FLOATS + HX_FLOATS) * 4 <= (int)LDS_BYTES, "LDS layout");
-constexpr int FRAG = 512;
-constexpr int SG_MFMA = 0x008, SG_VMEM_RD = 0x020;
 }  // namespace lm3
-
-typedef const __attribute__((address_space(1))) u32x4_t* lm3_gvec_t;
-typedef const __attribute__((address_space(1))) unsigned short* lm3_gptr_t;
-
-__device__ __forceinline__ float lm3_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float lm3_tanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
 
 template <int RTS, int D>   // row tiles of 32 a workgroup multiplies: 1 (launches of at most 32 rows) or 2; ring depth
 __global__ __launch_bounds__(lm3::NT) void lstm_mid_x3_kernel(LstmX3Args a) {
@@ -45,11 +37,7 @@ __global__ __launch_bounds__(lm3::NT) void lstm_mid_x3_kernel(LstmX3Args a) {
   extern __shared__ __attribute__((aligned(16))) float part[];
   float* hx = part + PART_FLOATS;
   const int H = a.H, B = a.B, F = a.F;
-#ifdef LM3_LAB_TWICE_WGS   // (dev: twice the workgroups, each with every other k-step of its waves -- results are wrong)
-  const int JB = H / BU, jb = blockIdx.x % JB, j0 = jb * BU, lab_half = blockIdx.x / JB;
-#else
   const int jb = blockIdx.x, JB = H / BU, j0 = jb * BU;
-#endif
   const int m0 = blockIdx.y * BM, rt0 = blockIdx.y * 2, RT = (B + 31) / 32;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -83,34 +71,24 @@ __global__ __launch_bounds__(lm3::NT) void lstm_mid_x3_kernel(LstmX3Args a) {
 
   // ---- the wave's k-steps: g = wave + 4 i
   u32x4_t fa[D][RTS][3], fw[D][3];
-#ifdef LM3_LAB_TWICE_WGS
-  const int n_w = ((KS - wave + 3) / 4 + 1 - lab_half) / 2;
-#elif defined(LM3_LAB_NOK)      // (dev, scripts/dev/lstm_mid_lab.sh: one k-step per wave -- what a launch costs without its K loop)
-  const int n_w = 1;
-#else
   const int n_w = (KS - wave + 3) / 4;
-#endif
   const unsigned short* const p_in = U.a3_in; const unsigned short* const p_rec = U.a3_rec;
   const unsigned short* const p_wih = U.w3_ih; const unsigned short* const p_whh = U.w3_hh;
   auto load = [&, p_in, p_rec, p_wih, p_whh](u32x4_t (&A)[RTS][3], u32x4_t (&W)[3], int i) {
-#ifdef LM3_LAB_TWICE_WGS
-    int g = wave + 4 * (i + (lab_half ? ((KS - wave + 3) / 4 + 1) / 2 : 0));   // the other half of the wave's k-steps
-#else
     int g = wave + 4 * i;
-#endif
     g = g < KS ? g : KS - 1;                      // (past the wave's last step: fetched, never multiplied)
     const bool in = g < KS_in;
     const int ks = in ? g : g - KS_in, ksn = in ? KS_in : KS_h;
-    lm3_gptr_t ab = (lm3_gptr_t)(in ? p_in : p_rec) + (((size_t)rt0 * ksn + ks) * 3) * FRAG + lane * 8;
-    lm3_gptr_t wb = (lm3_gptr_t)(in ? p_wih : p_whh) + (((size_t)ks * JB + jb) * 3) * FRAG + lane * 8;
+    x3_gptr_t ab = (x3_gptr_t)(in ? p_in : p_rec) + (((size_t)rt0 * ksn + ks) * 3) * FRAG + lane * 8;
+    x3_gptr_t wb = (x3_gptr_t)(in ? p_wih : p_whh) + (((size_t)ks * JB + jb) * 3) * FRAG + lane * 8;
     // (a second row tile that does not exist reads the first again; its rows are >= B and never stored)
     const size_t rt_stride = rt0 + 1 < RT ? (size_t)ksn * 3 * FRAG : 0;
 #pragma unroll
     for (int r = 0; r < RTS; ++r)
 #pragma unroll
-      for (int pc = 0; pc < 3; ++pc) A[r][pc] = *(lm3_gvec_t)(ab + r * rt_stride + pc * FRAG);
+      for (int pc = 0; pc < 3; ++pc) A[r][pc] = *(x3_gvec_t)(ab + r * rt_stride + pc * FRAG);
 #pragma unroll
-    for (int pc = 0; pc < 3; ++pc) W[pc] = *(lm3_gvec_t)(wb + pc * FRAG);
+    for (int pc = 0; pc < 3; ++pc) W[pc] = *(x3_gvec_t)(wb + pc * FRAG);
   };
   auto mma = [&](const u32x4_t (&A)[RTS][3], const u32x4_t (&W)[3]) {
 #pragma unroll
@@ -159,10 +137,10 @@ __global__ __launch_bounds__(lm3::NT) void lstm_mid_x3_kernel(LstmX3Args a) {
       const float* ps = part + (q * BU + 2 * f_up + e) * PLD + f_row;
       gsum[q] = row_used ? ((ps[0] + ps[32 * PLD]) + ps[2 * 32 * PLD]) + ps[3 * 32 * PLD] : 0.f;
     }
-    const float g_i = lm3_sigmoid(gsum[0] + e_bias[0][e]), g_f = lm3_sigmoid(gsum[1] + e_bias[1][e]);
-    const float g_g = lm3_tanh(gsum[2] + e_bias[2][e]), g_o = lm3_sigmoid(gsum[3] + e_bias[3][e]);
+    const float g_i = fast_sigmoid(gsum[0] + e_bias[0][e]), g_f = fast_sigmoid(gsum[1] + e_bias[1][e]);
+    const float g_g = fast_tanh(gsum[2] + e_bias[2][e]), g_o = fast_sigmoid(gsum[3] + e_bias[3][e]);
     const float c_new = g_f * e_c[e] + g_i * g_g;
-    const float h_new = g_o * lm3_tanh(c_new);
+    const float h_new = g_o * fast_tanh(c_new);
     hv[e] = live ? h_new : (a.seq_lengths ? e_hp[e] : 0.f);
     if (g_row < B && row_used) {
       const size_t hc = (size_t)g_row * H + g_unit + e;
@@ -193,21 +171,9 @@ __global__ __launch_bounds__(lm3::NT) void lstm_mid_x3_kernel(LstmX3Args a) {
 
 hipError_t launch_lstm_mid_x3(const LstmX3Args& a, hipStream_t stream) {
   if (a.n_units == 0) return hipSuccess;
-#ifdef LM3_LAB_TWICE_WGS
-  dim3 grid(2 * a.H / lm3::BU, (a.B + lm3::BM - 1) / lm3::BM, a.n_units);
-#else
   dim3 grid(a.H / lm3::BU, (a.B + lm3::BM - 1) / lm3::BM, a.n_units);
-#endif
-  if (a.B <= 32) {
-    auto* fn = lstm_mid_x3_kernel<1, LM3_RING1>;
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(fn), lm3::LDS_BYTES)) return e;
-    hipLaunchKernelGGL(fn, grid, dim3(lm3::NT), lm3::LDS_BYTES, stream, a);
-  } else {
-    auto* fn = lstm_mid_x3_kernel<2, LM3_RING2>;
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(fn), lm3::LDS_BYTES)) return e;
-    hipLaunchKernelGGL(fn, grid, dim3(lm3::NT), lm3::LDS_BYTES, stream, a);
-  }
-  return hipGetLastError();
+  return a.B <= 32 ? launch_lds(lstm_mid_x3_kernel<1, LM3_RING1>, grid, dim3(lm3::NT), lm3::LDS_BYTES, stream, a)
+                   : launch_lds(lstm_mid_x3_kernel<2, LM3_RING2>, grid, dim3(lm3::NT), lm3::LDS_BYTES, stream, a);
 }
 
 }  // namespace empose

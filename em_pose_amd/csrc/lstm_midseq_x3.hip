@@ -39,15 +39,8 @@ constexpr int PART_FLOATS = 4 * 32 * PLD;
 constexpr int HX_FLOATS = BM * (BU + 1);
 constexpr size_t LDS_BYTES = 84 * 1024;                       // > half a CU: one workgroup per CU
 static_assert((PART_FLOATS + HX_FLOATS + 4) * 4 <= (int)LDS_BYTES, "LDS layout");
-constexpr int FRAG = 512;
 constexpr int MAXW = 16;                                      // k-steps a wave keeps in registers: K <= 4 * 16 * 16
 }  // namespace lq3
-
-typedef const __attribute__((address_space(1))) u32x4_t* lq3_gvec_t;
-typedef const __attribute__((address_space(1))) unsigned short* lq3_gptr_t;
-
-__device__ __forceinline__ float lq3_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float lq3_tanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
 
 // 16 bytes to the memory side (agent scope: what `__hip_atomic_store(..., __HIP_MEMORY_SCOPE_AGENT)` emits for 8)
 __device__ __forceinline__ void lq3_store_through(unsigned short* p, u32x4_t v) {
@@ -82,9 +75,9 @@ __global__ __launch_bounds__(lq3::NT) void lstm_midseq_x3_kernel(LstmMidSeqArgs 
     if (i < n_w) {
       const bool in = g < KS_in;
       const int ks = in ? g : g - KS_in;
-      lq3_gptr_t wb = (lq3_gptr_t)(in ? U.w3_ih : U.w3_hh) + (((size_t)ks * JB + jb) * 3) * FRAG + lane * 8;
+      x3_gptr_t wb = (x3_gptr_t)(in ? U.w3_ih : U.w3_hh) + (((size_t)ks * JB + jb) * 3) * FRAG + lane * 8;
 #pragma unroll
-      for (int pc = 0; pc < 3; ++pc) W[i][pc] = *(lq3_gvec_t)(wb + pc * FRAG);
+      for (int pc = 0; pc < 3; ++pc) W[i][pc] = *(x3_gvec_t)(wb + pc * FRAG);
     } else {
 #pragma unroll
       for (int pc = 0; pc < 3; ++pc) W[i][pc] = u32x4_t{0u, 0u, 0u, 0u};
@@ -117,7 +110,6 @@ __global__ __launch_bounds__(lq3::NT) void lstm_midseq_x3_kernel(LstmMidSeqArgs 
     const bool active = t >= 0 && t < F;       // (uniform)
     if (active) {
       // ---- every workgroup of this layer and of the layer below has finished wavefront step s - 1
-#ifndef LQ3_LAB_NOPOLL   // (dev, scripts/dev/lstm_midseq_lab.sh: parts of a step compiled out -- results are then wrong)
       if (s > 0 && !failed) {       // (a workgroup that gave up once does not wait again: it only poisons and counts on)
         int spins = 0;
         for (;;) {
@@ -132,16 +124,10 @@ __global__ __launch_bounds__(lq3::NT) void lstm_midseq_x3_kernel(LstmMidSeqArgs 
         }
         asm volatile("" ::: "memory");       // (the planes are read after the counters, in program order)
       }
-#endif
       // ---- the step's A planes: input = the stored sequence (layer 0) or slot t + 1 of the layer below; recurrent = slot t
-#ifdef LQ3_LAB_SAMEPLANES   // every step reads slot 0 / time 0 again: the loads hit the caches
-      const unsigned short* const p_in = l == 0 ? U.in3 : a.unit[l - 1].xa;
-      const unsigned short* const p_rec = U.xa;
-#else
       const unsigned short* const p_in = l == 0 ? U.in3 + (size_t)t * U.in_t_stride
                                                 : a.unit[l - 1].xa + (size_t)(t + 1) * plane;
       const unsigned short* const p_rec = U.xa + (size_t)t * plane;
-#endif
       f32x16 acc[RTS][2];
 #pragma unroll
       for (int r = 0; r < RTS; ++r)
@@ -154,12 +140,12 @@ __global__ __launch_bounds__(lq3::NT) void lstm_midseq_x3_kernel(LstmMidSeqArgs 
         const int g = wave + 4 * i;
         const bool in = g < KS_in;
         const int ks = in ? g : g - KS_in, ksn = in ? KS_in : KS_h;
-        lq3_gptr_t ab = (lq3_gptr_t)(in ? p_in : p_rec) + ((size_t)ks * 3) * FRAG + lane * 8;
+        x3_gptr_t ab = (x3_gptr_t)(in ? p_in : p_rec) + ((size_t)ks * 3) * FRAG + lane * 8;
         const size_t rt_stride = RT > 1 ? (size_t)ksn * 3 * FRAG : 0;
 #pragma unroll
         for (int r = 0; r < RTS; ++r)
 #pragma unroll
-          for (int pc = 0; pc < 3; ++pc) A[r][pc] = *(lq3_gvec_t)(ab + r * rt_stride + pc * FRAG);
+          for (int pc = 0; pc < 3; ++pc) A[r][pc] = *(x3_gvec_t)(ab + r * rt_stride + pc * FRAG);
       };
       auto mma = [&](const u32x4_t (&A)[RTS][3], const u32x4_t (&Wf)[3]) {
 #pragma unroll
@@ -204,10 +190,10 @@ __global__ __launch_bounds__(lq3::NT) void lstm_midseq_x3_kernel(LstmMidSeqArgs 
           const float* ps = part + (q * BU + 2 * f_up + e) * PLD + f_row;
           gsum[q] = (RTS == 2 || f_row < 32) ? ((ps[0] + ps[32 * PLD]) + ps[2 * 32 * PLD]) + ps[3 * 32 * PLD] : 0.f;
         }
-        const float g_i = lq3_sigmoid(gsum[0] + e_bias[0][e]), g_f = lq3_sigmoid(gsum[1] + e_bias[1][e]);
-        const float g_g = lq3_tanh(gsum[2] + e_bias[2][e]), g_o = lq3_sigmoid(gsum[3] + e_bias[3][e]);
+        const float g_i = fast_sigmoid(gsum[0] + e_bias[0][e]), g_f = fast_sigmoid(gsum[1] + e_bias[1][e]);
+        const float g_g = fast_tanh(gsum[2] + e_bias[2][e]), g_o = fast_sigmoid(gsum[3] + e_bias[3][e]);
         const float c_new = g_f * c_reg[e] + g_i * g_g;
-        const float h_new = g_o * lq3_tanh(c_new);
+        const float h_new = g_o * fast_tanh(c_new);
         if (live) { c_reg[e] = c_new; h_reg[e] = h_new; }
         else if (!a.seq_lengths) h_reg[e] = 0.f;
         if (failed) { c_reg[e] = poison; h_reg[e] = poison; }
@@ -225,9 +211,7 @@ __global__ __launch_bounds__(lq3::NT) void lstm_midseq_x3_kernel(LstmMidSeqArgs 
 #pragma unroll
         for (int pc = 0; pc < 3; ++pc) lq3_store_through(o + pc * FRAG, q.p[pc]);
       }
-#ifndef LQ3_LAB_NOACK
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // the stores have been acknowledged by the memory side
-#endif
       __syncthreads();
     }
     // ---- progress: wavefront step s of this workgroup is done (raised on idle steps too: counters only go up)

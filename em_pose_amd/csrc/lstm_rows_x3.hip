@@ -27,25 +27,15 @@ namespace empose {
 
 namespace lr {
 constexpr int BM = 128, BU = 32, NT = 256;
-constexpr int FRAG = 512;                                // bf16 elements of one wave fragment (1 KB)
 constexpr int WBLK = 12 * FRAG;                          // elements of one k-step's weight block (4 gates x 3 pieces)
 constexpr int WBUF_BYTES = WBLK * 2;                     // 12,288
 constexpr int TP = 33;                                   // row stride of the transpose tile (floats)
 constexpr int NBUF = 8;                                   // LDS stage buffers (a k-step's weight block each)
 constexpr size_t LDS_BYTES = NBUF * WBUF_BYTES;           // 96 KB > half of a CU's 160 KB: never two workgroups on a CU
-constexpr int SG_MFMA = 0x008, SG_VMEM_RD = 0x020, SG_DS_RD = 0x100, SG_DS_WR = 0x200;
 static_assert(LDS_BYTES > 80 * 1024 && 4 * 32 * TP * 4 <= 2 * WBUF_BYTES, "LDS layout");
 }  // namespace lr
 
-typedef const __attribute__((address_space(1))) u32x4_t* lr_gvec_t;
-typedef const __attribute__((address_space(1))) unsigned short* lr_gptr_t;
-
-#define LR_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
-
-__device__ __forceinline__ float lr_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float lr_tanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
-
-__device__ unsigned short lr_zero_frags[3 * lr::FRAG];   // zero-initialised: the A fragments of the padding k-steps
+__device__ unsigned short lr_zero_frags[3 * FRAG];   // zero-initialised: the A fragments of the padding k-steps
 
 __global__ __launch_bounds__(lr::NT) void lstm_rows_x3_kernel(LstmX3Args a) {
   X3_EXCLUSIVE_SIMD();
@@ -54,7 +44,6 @@ __global__ __launch_bounds__(lr::NT) void lstm_rows_x3_kernel(LstmX3Args a) {
   const int H = a.H, B = a.B, F = a.F;
   const int JB = H / BU;
   int jb = blockIdx.x, rb = blockIdx.y, uz = blockIdx.z;
-#ifndef LR_LAB_NOXCD
   // Workgroups go to the 8 XCDs round-robin by their linear index.  When the grid is 16 unit blocks x 8 row blocks (the
   // headline shape) the 32 workgroups of an XCD are remapped to 4 unit blocks x 4 row blocks x both units: its L2 then
   // streams 5.2 + 5.2 MB of weights and A planes per launch instead of 2.6 + 10.3 MB.
@@ -63,7 +52,6 @@ __global__ __launch_bounds__(lr::NT) void lstm_rows_x3_kernel(LstmX3Args a) {
     const int xcd = lin & 7, s = lin >> 3;
     if ((int)gridDim.z == 2) { jb = 4 * (xcd & 3) + (s & 3); rb = 4 * (xcd >> 2) + ((s >> 2) & 3); uz = s >> 4; }
   }
-#endif
   const int j0 = jb * BU;
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -109,9 +97,9 @@ __global__ __launch_bounds__(lr::NT) void lstm_rows_x3_kernel(LstmX3Args a) {
     g = g < KS ? g : KS - 1;                          // (past the last step: fetched, never multiplied)
     const bool in = g < KS_in;
     const int ks = in ? g : g - KS_in;
-    lr_gptr_t wb = (lr_gptr_t)(in ? p_wih : p_whh) + ((size_t)ks * JB + jb) * WBLK + tid * 8;
+    x3_gptr_t wb = (x3_gptr_t)(in ? p_wih : p_whh) + ((size_t)ks * JB + jb) * WBLK + tid * 8;
 #pragma unroll
-    for (int p = 0; p < 3; ++p) S[p] = *(lr_gvec_t)(wb + p * (NT * 8));
+    for (int p = 0; p < 3; ++p) S[p] = *(x3_gvec_t)(wb + p * (NT * 8));
   };
   auto gload_a = [&, p_in, p_rec](u32x4_t (&A)[3], int g) {
     // The K loop runs whole groups of six steps (its register sets rotate with periods 3, 3 and 2; exits in mid-group cost
@@ -122,10 +110,10 @@ __global__ __launch_bounds__(lr::NT) void lstm_rows_x3_kernel(LstmX3Args a) {
     g = dead ? KS - 1 : g;
     const bool in = g < KS_in;
     const int ks = in ? g : g - KS_in, ksn = in ? KS_in : KS_h;
-    lr_gptr_t ab = dead ? (lr_gptr_t)lr_zero_frags + lane * 8
-                        : (lr_gptr_t)(in ? p_in : p_rec) + (((size_t)rt * ksn + ks) * 3) * FRAG + lane * 8;
+    x3_gptr_t ab = dead ? (x3_gptr_t)lr_zero_frags + lane * 8
+                        : (x3_gptr_t)(in ? p_in : p_rec) + (((size_t)rt * ksn + ks) * 3) * FRAG + lane * 8;
 #pragma unroll
-    for (int pc = 0; pc < 3; ++pc) A[pc] = *(lr_gvec_t)(ab + pc * FRAG);
+    for (int pc = 0; pc < 3; ++pc) A[pc] = *(x3_gvec_t)(ab + pc * FRAG);
   };
   auto lds_write = [&](const u32x4_t (&S)[3], int g) {
     unsigned char* b = smem + (g & (NBUF - 1)) * WBUF_BYTES + tid * 16;
@@ -146,10 +134,8 @@ __global__ __launch_bounds__(lr::NT) void lstm_rows_x3_kernel(LstmX3Args a) {
                                                          __builtin_bit_cast(bf16x8_t, W[q * 3 + X3_PB[p]]), acc[q], 0, 0, 0);
   };
   auto handover = [&]() {
-#ifndef LR_LAB_NOBARRIER   // (scripts/dev/lstm_rows_lab.sh: timing ablations, results are then wrong)
     __builtin_amdgcn_s_waitcnt(0xc07f);               // lgkmcnt(0): this wave's LDS writes and reads of the stage are done
     __builtin_amdgcn_s_barrier();
-#endif
   };
   // One k-step i: the products of step i (operands in registers) with, spread between them, the global loads of the weight
   // pieces of step i + 6 and the A fragments of step i + 2, the LDS write of the pieces of step i + 4 (loaded two steps ago)
@@ -157,21 +143,17 @@ __global__ __launch_bounds__(lr::NT) void lstm_rows_x3_kernel(LstmX3Args a) {
   // step k - 4 and read at step k - 1 (a hand-over lies between), its buffer is rewritten at step k + 4 (eight buffers).
   auto step = [&](int i, bool sync, u32x4_t (&S_new)[3], const u32x4_t (&S_ready)[3], u32x4_t (&A_new)[3],
                   const u32x4_t (&A_cur)[3], u32x4_t (&W_next)[12], const u32x4_t (&W_cur)[12]) {
-#ifndef LR_LAB_NOGLOAD
     gload_w(S_new, i + 6);
     gload_a(A_new, i + 2);
-#endif
-#ifndef LR_LAB_NOLDS
     lds_write(S_ready, i + 4);
     lds_read(W_next, i + 1);
-#endif
     mma(A_cur, W_cur);
 #pragma unroll
     for (int q = 0; q < 24; ++q) {
-      LR_SGB(SG_MFMA, 1);
-      if (q < 6) LR_SGB(SG_VMEM_RD, 1);
-      else if (q < 9) LR_SGB(SG_DS_WR, 1);
-      else if (q < 21) LR_SGB(SG_DS_RD, 1);
+      SGB(SG_MFMA, 1);
+      if (q < 6) SGB(SG_VMEM_RD, 1);
+      else if (q < 9) SGB(SG_DS_WR, 1);
+      else if (q < 21) SGB(SG_DS_RD, 1);
     }
     if (sync) handover();
   };
@@ -192,15 +174,8 @@ __global__ __launch_bounds__(lr::NT) void lstm_rows_x3_kernel(LstmX3Args a) {
   handover();
   lds_read(wreg[0], 0);
 
-#if defined(LR_LAB_KS)      // (lab: a fixed number of k-steps: what a launch costs besides its K loop)
-  const int KS_loop = LR_LAB_KS;
-#elif defined(LR_LAB_BALANCED)   // (lab: every workgroup runs the mean of the two units' k-steps: the floor a balanced split would have)
-  const int KS_loop = 54;
-#else
-  const int KS_loop = KS;
-#endif
   // (sets rotate with periods 3, 3 and 2: six steps per trip)
-  for (int i = 0; i < KS_loop; i += 6) {
+  for (int i = 0; i < KS; i += 6) {
     step(i, false, sreg[0], sreg[1], areg[2], areg[0], wreg[1], wreg[0]);
     step(i + 1, true, sreg[1], sreg[2], areg[0], areg[1], wreg[0], wreg[1]);
     step(i + 2, false, sreg[2], sreg[0], areg[1], areg[2], wreg[1], wreg[0]);
@@ -215,10 +190,10 @@ __global__ __launch_bounds__(lr::NT) void lstm_rows_x3_kernel(LstmX3Args a) {
   const bool carry = a.seq_lengths != nullptr;
 #pragma unroll
   for (int r = 0; r < 16; ++r) {
-    const float g_i = lr_sigmoid(acc[0][r] + e_bias[0]), g_f = lr_sigmoid(acc[1][r] + e_bias[1]);
-    const float g_g = lr_tanh(acc[2][r] + e_bias[2]), g_o = lr_sigmoid(acc[3][r] + e_bias[3]);
+    const float g_i = fast_sigmoid(acc[0][r] + e_bias[0]), g_f = fast_sigmoid(acc[1][r] + e_bias[1]);
+    const float g_g = fast_tanh(acc[2][r] + e_bias[2]), g_o = fast_sigmoid(acc[3][r] + e_bias[3]);
     const float c_new = g_f * c_old[r] + g_i * g_g;
-    hv[r] = g_o * lr_tanh(c_new);
+    hv[r] = g_o * fast_tanh(c_new);
     c_old[r] = c_new;                                   // (rows past their length keep the old state: not stored below)
   }
   float* tile = reinterpret_cast<float*>(smem) + wave * (32 * TP);
@@ -258,10 +233,8 @@ bool lstm_rows_x3_covers(int H) { return H % 32 == 0; }
 
 hipError_t launch_lstm_rows_x3(const LstmX3Args& a, hipStream_t stream) {
   if (a.n_units == 0) return hipSuccess;
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(lstm_rows_x3_kernel), lr::LDS_BYTES)) return e;
   dim3 grid(a.H / lr::BU, (a.B + lr::BM - 1) / lr::BM, a.n_units);
-  hipLaunchKernelGGL(lstm_rows_x3_kernel, grid, dim3(lr::NT), lr::LDS_BYTES, stream, a);
-  return hipGetLastError();
+  return launch_lds(lstm_rows_x3_kernel, grid, dim3(lr::NT), lr::LDS_BYTES, stream, a);
 }
 
 }  // namespace empose

@@ -27,17 +27,7 @@ namespace lx {
 constexpr int BM = 64, BU = 32, NT = 256;
 constexpr int PLD = BM + 4;                                          // row stride of a partial-sum column (floats)
 constexpr size_t LDS_BYTES = (size_t)4 * 4 * BU * PLD * sizeof(float);   // [wave][gate][unit][row]: 139,264 bytes
-constexpr int FRAG = 512;                                            // bf16 elements of one wave fragment (1 KB)
-constexpr int SG_MFMA = 0x008, SG_VMEM_RD = 0x020;
 }  // namespace lx
-
-typedef const __attribute__((address_space(1))) u32x4_t* lx_gvec_t;
-typedef const __attribute__((address_space(1))) unsigned short* lx_gptr_t;
-
-#define LX_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
-
-__device__ __forceinline__ float lx_sigmoid(float x) { return __builtin_amdgcn_rcpf(1.f + __expf(-x)); }
-__device__ __forceinline__ float lx_tanh(float x) { return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __expf(2.f * x)); }
 
 // Row-major fp32 matrices -> A-fragment-order pieces.  Matrix z: rows src + z * z_stride + row * row_stride, K columns
 // (K % 4 == 0); output z: dst + z * dst_z_stride as [32-row tile][k-step of 16][piece][lane][8] with
@@ -61,9 +51,9 @@ __global__ __launch_bounds__(256) void lstm_split_rows_kernel(const float* __res
   }
   const Pieces q = split8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
   const int rt = row >> 5, ks = kg >> 1, lane = (row & 31) + 32 * (kg & 1);
-  unsigned short* o = dst + (long)z * dst_z_stride + (((long)rt * KS + ks) * 3) * lx::FRAG + lane * 8;
+  unsigned short* o = dst + (long)z * dst_z_stride + (((long)rt * KS + ks) * 3) * FRAG + lane * 8;
 #pragma unroll
-  for (int pc = 0; pc < 3; ++pc) *reinterpret_cast<u32x4_t*>(o + pc * lx::FRAG) = q.p[pc];
+  for (int pc = 0; pc < 3; ++pc) *reinterpret_cast<u32x4_t*>(o + pc * FRAG) = q.p[pc];
 }
 
 #ifdef LX_LAB_TIMES      // (scripts/dev/lstm_x3_lab.hip: shader-clock stamps of thread 0 of every workgroup)
@@ -138,19 +128,19 @@ __global__ __launch_bounds__(lx::NT) void lstm_chain_x3_kernel(LstmX3Args a) {
       g = g < KS ? g : KS - 1;                      // (past the wave's last step: fetched, never multiplied)
       const bool in = g < KS_in;
       const int ks = in ? g : g - KS_in, ksn = in ? KS_in : KS_h;
-      lx_gptr_t ab = (lx_gptr_t)(in ? p_in : p_rec) + (((size_t)rt0 * ksn + ks) * 3) * FRAG + lane * 8;
-      lx_gptr_t wb = (lx_gptr_t)(in ? p_wih : p_whh) + ((((size_t)ks * JB + jb) * 4) * 3) * FRAG + lane * 8;
+      x3_gptr_t ab = (x3_gptr_t)(in ? p_in : p_rec) + (((size_t)rt0 * ksn + ks) * 3) * FRAG + lane * 8;
+      x3_gptr_t wb = (x3_gptr_t)(in ? p_wih : p_whh) + ((((size_t)ks * JB + jb) * 4) * 3) * FRAG + lane * 8;
       // (an odd number of 32-row tiles: the last workgroup's second tile does not exist in the piece planes -- it reads its
       // first tile again instead of one tile past the plane; those rows are >= B and never stored)
       const size_t rt_stride = rt0 + 1 < (B + 31) / 32 ? (size_t)ksn * 3 * FRAG : 0;
 #pragma unroll
       for (int r = 0; r < 2; ++r)
 #pragma unroll
-        for (int pc = 0; pc < 3; ++pc) A[r][pc] = *(lx_gvec_t)(ab + r * rt_stride + pc * FRAG);
+        for (int pc = 0; pc < 3; ++pc) A[r][pc] = *(x3_gvec_t)(ab + r * rt_stride + pc * FRAG);
 #pragma unroll
       for (int q = 0; q < 4; ++q)
 #pragma unroll
-        for (int pc = 0; pc < 3; ++pc) W[q][pc] = *(lx_gvec_t)(wb + (q * 3 + pc) * FRAG);
+        for (int pc = 0; pc < 3; ++pc) W[q][pc] = *(x3_gvec_t)(wb + (q * 3 + pc) * FRAG);
     };
     auto mma = [&](const u32x4_t (&A)[2][3], const u32x4_t (&W)[4][3]) {
 #pragma unroll
@@ -164,16 +154,12 @@ __global__ __launch_bounds__(lx::NT) void lstm_chain_x3_kernel(LstmX3Args a) {
     };
     auto pattern = [&]() {   // 48 MFMAs with the 18 fragment loads of the step after next between them
 #pragma unroll
-      for (int q = 0; q < 18; ++q) { LX_SGB(SG_MFMA, 2); LX_SGB(SG_VMEM_RD, 1); }
-      LX_SGB(SG_MFMA, 12);
+      for (int q = 0; q < 18; ++q) { SGB(SG_MFMA, 2); SGB(SG_VMEM_RD, 1); }
+      SGB(SG_MFMA, 12);
     };
     load(fa[0], fw[0], 0);
     load(fa[1], fw[1], 1);
     int i = 0;
-#ifdef LX_LAB_NOLOAD      // (lab ablation, scripts/dev/lstm_x3_lab.hip: the K loop on the first fragments only)
-    load(fa[2], fw[2], 2);
-    for (; i + 3 <= n_w; i += 3) { mma(fa[0], fw[0]); mma(fa[1], fw[1]); mma(fa[2], fw[2]); }
-#else
     for (; i + 3 <= n_w; i += 3) {
       load(fa[2], fw[2], i + 2);
       mma(fa[0], fw[0]);
@@ -185,26 +171,12 @@ __global__ __launch_bounds__(lx::NT) void lstm_chain_x3_kernel(LstmX3Args a) {
       mma(fa[2], fw[2]);
       pattern();
     }
-#endif
     if (i < n_w) mma(fa[0], fw[0]);
     if (i + 1 < n_w) mma(fa[1], fw[1]);
     LX_STAMP(1 + 5 * (u - u_beg));
 
     // ---- partial sums -> LDS as [wave][gate][unit][row]: 16-byte pieces of four consecutive rows (the C/D layout has rows
     // 8 q + 4 lh .. + 3 of a column in one lane); the row stride of 68 floats spreads the 32 units of a store over the banks
-#ifdef LX_LAB_NOPART     // (lab ablation: no exchange, no finish -- the sums leave through one predicated store)
-    {
-      float sacc = 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int r = 0; r < 2; ++r)
-#pragma unroll
-          for (int v = 0; v < 16; ++v) sacc += acc[r][q][v];
-      if (sacc == 123.456f) U.c[tid] = sacc + e_c[0][0] + e_hp[0][0] + e_bias[0][0];
-      continue;
-    }
-#endif
     if (u > u_beg) __syncthreads();   // the previous unit's finish has read its sums
     {
       float* pw = part + (size_t)wave * 4 * BU * PLD;
@@ -221,10 +193,6 @@ __global__ __launch_bounds__(lx::NT) void lstm_chain_x3_kernel(LstmX3Args a) {
     __syncthreads();
     LX_STAMP(3 + 5 * (u - u_beg));
 
-#ifdef LX_LAB_NOFINISH   // (lab ablation: the exchange, but no cell arithmetic and no stores)
-    if (part[tid] == 123.456f) U.c[tid] = part[tid + 1] + e_c[0][0] + e_hp[0][0] + e_bias[0][0];
-    continue;
-#endif
     // ---- finish: thread (row, 8 units)
     float hv[8], cv[8], yv[8];
     const bool live = t < e_len;
@@ -236,11 +204,11 @@ __global__ __launch_bounds__(lx::NT) void lstm_chain_x3_kernel(LstmX3Args a) {
         const float* ps = part + (q * BU + f_ug * 8 + e) * PLD + f_row;
         gsum[q] = ((ps[0] + ps[4 * BU * PLD]) + ps[2 * 4 * BU * PLD]) + ps[3 * 4 * BU * PLD];
       }
-      const float g_i = lx_sigmoid(gsum[0] + e_bias[0][e]), g_f = lx_sigmoid(gsum[1] + e_bias[1][e]);
-      const float g_g = lx_tanh(gsum[2] + e_bias[2][e]), g_o = lx_sigmoid(gsum[3] + e_bias[3][e]);
+      const float g_i = fast_sigmoid(gsum[0] + e_bias[0][e]), g_f = fast_sigmoid(gsum[1] + e_bias[1][e]);
+      const float g_g = fast_tanh(gsum[2] + e_bias[2][e]), g_o = fast_sigmoid(gsum[3] + e_bias[3][e]);
       const float c_old = e_c[e >> 2][e & 3], h_old = e_hp[e >> 2][e & 3];
       const float c_new = g_f * c_old + g_i * g_g;
-      const float h_new = g_o * lx_tanh(c_new);
+      const float h_new = g_o * fast_tanh(c_new);
       cv[e] = live ? c_new : c_old;
       hv[e] = live ? h_new : (a.seq_lengths ? h_old : 0.f);
       yv[e] = live ? h_new : 0.f;
@@ -279,10 +247,8 @@ hipError_t launch_lstm_split_rows(const float* src, long row_stride, long z_stri
 
 hipError_t launch_lstm_chain_x3(const LstmX3Args& a, hipStream_t stream) {
   if (a.n_units == 0) return hipSuccess;
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(lstm_chain_x3_kernel), lx::LDS_BYTES)) return e;
   dim3 grid(a.H / lx::BU, (a.B + lx::BM - 1) / lx::BM, (a.n_units + a.units_per_block - 1) / a.units_per_block);
-  hipLaunchKernelGGL(lstm_chain_x3_kernel, grid, dim3(lx::NT), lx::LDS_BYTES, stream, a);
-  return hipGetLastError();
+  return launch_lds(lstm_chain_x3_kernel, grid, dim3(lx::NT), lx::LDS_BYTES, stream, a);
 }
 
 }  // namespace empose

@@ -742,45 +742,33 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16s_kernel(MeshSkinAr
 
 hipError_t launch_mesh_rows_bf16s(const MeshSkinArgs& a, hipStream_t stream) {
   if (!a.skin_bf16 || !a.wc_bf16) return hipErrorInvalidValue;
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(mesh_rows_bf16s_kernel), ms::LDS_BYTES)) return e;
   const int bx = (a.T + mb::BM - 1) / mb::BM;
   const int n_tiles = (a.V + 31) / 32;
   int by = bx >= 256 ? 1 : (256 + bx - 1) / bx;
   const int max_by = (n_tiles + mb::NW - 1) / mb::NW;
   if (by > max_by) by = max_by;
-  hipLaunchKernelGGL(mesh_rows_bf16s_kernel, dim3(bx, by), dim3(mb::NW * 64), ms::LDS_BYTES, stream, a);
-  return hipGetLastError();
+  return launch_lds(mesh_rows_bf16s_kernel, dim3(bx, by), dim3(mb::NW * 64), ms::LDS_BYTES, stream, a);
 }
 
 hipError_t launch_mesh_rows_bf16(const MeshSkinArgs& a, hipStream_t stream) {
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(mesh_rows_bf16_kernel<false>), mb::LDS_BYTES)) return e;
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(mesh_rows_bf16_kernel<true>), mb::LDS_BYTES)) return e;
   const int bx = (a.T + mb::BM - 1) / mb::BM;
   const int n_tiles = (a.V + 31) / 32;
   int by = bx >= 256 ? 1 : (256 + bx - 1) / bx;
   const int max_by = (n_tiles + mb::NW - 1) / mb::NW;
   if (by > max_by) by = max_by;
-  if (a.kb > 4)
-    hipLaunchKernelGGL(mesh_rows_bf16_kernel<true>, dim3(bx, by), dim3(mb::NW * 64), mb::LDS_BYTES, stream, a);
-  else
-    hipLaunchKernelGGL(mesh_rows_bf16_kernel<false>, dim3(bx, by), dim3(mb::NW * 64), mb::LDS_BYTES, stream, a);
-  return hipGetLastError();
+  return a.kb <= 4 ? launch_lds(mesh_rows_bf16_kernel<false>, dim3(bx, by), dim3(mb::NW * 64), mb::LDS_BYTES, stream, a)
+                   : launch_lds(mesh_rows_bf16_kernel<true>, dim3(bx, by), dim3(mb::NW * 64), mb::LDS_BYTES, stream, a);
 }
 
 hipError_t launch_mesh_rows(const MeshSkinArgs& a, hipStream_t stream) {
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(mesh_rows_kernel<false>), mr::LDS_BYTES)) return e;
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(mesh_rows_kernel<true>), mr::LDS_BYTES)) return e;
   const int bx = (a.T + mr::BM - 1) / mr::BM;
   const int n_tiles = (a.V + 31) / 32;
   // fewer than one workgroup per CU: split the mesh's tiles over grid.y (at least one tile per wave)
   int by = bx >= 256 ? 1 : (256 + bx - 1) / bx;
   const int max_by = (n_tiles + mr::NW - 1) / mr::NW;
   if (by > max_by) by = max_by;
-  if (a.kb > 4)
-    hipLaunchKernelGGL(mesh_rows_kernel<true>, dim3(bx, by), dim3(mr::NW * 64), mr::LDS_BYTES, stream, a);
-  else
-    hipLaunchKernelGGL(mesh_rows_kernel<false>, dim3(bx, by), dim3(mr::NW * 64), mr::LDS_BYTES, stream, a);
-  return hipGetLastError();
+  return a.kb <= 4 ? launch_lds(mesh_rows_kernel<false>, dim3(bx, by), dim3(mr::NW * 64), mr::LDS_BYTES, stream, a)
+                   : launch_lds(mesh_rows_kernel<true>, dim3(bx, by), dim3(mr::NW * 64), mr::LDS_BYTES, stream, a);
 }
 
 }  // namespace empose

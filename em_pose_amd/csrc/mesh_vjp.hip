@@ -333,24 +333,19 @@ int mesh_vjp_feat_split(int T, int V) { return vjp_split(T, V, mv::FNW); }
 int mesh_vjp_bone_split(int T, int V) { return vjp_split(T, V, mv::BNW); }
 
 hipError_t launch_mesh_vjp_feat(const MeshVjpArgs& a, hipStream_t stream) {
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(mesh_vjp_feat_kernel<false>), mv::F_LDS_BYTES)) return e;
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(mesh_vjp_feat_kernel<true>), mv::F_LDS_BYTES)) return e;
   const int bx = (a.T + mv::BM - 1) / mv::BM, by = mesh_vjp_feat_split(a.T, a.V);
   if (by > 1 && !a.part) return hipErrorInvalidValue;
-  if (a.kb > 4)
-    hipLaunchKernelGGL(mesh_vjp_feat_kernel<true>, dim3(bx, by), dim3(mv::FNW * 64), mv::F_LDS_BYTES, stream, a);
-  else
-    hipLaunchKernelGGL(mesh_vjp_feat_kernel<false>, dim3(bx, by), dim3(mv::FNW * 64), mv::F_LDS_BYTES, stream, a);
-  if (hipError_t e = hipGetLastError()) return e;
+  if (hipError_t e = a.kb <= 4
+          ? launch_lds(mesh_vjp_feat_kernel<false>, dim3(bx, by), dim3(mv::FNW * 64), mv::F_LDS_BYTES, stream, a)
+          : launch_lds(mesh_vjp_feat_kernel<true>, dim3(bx, by), dim3(mv::FNW * 64), mv::F_LDS_BYTES, stream, a))
+    return e;
   return by > 1 ? sum_slices(a, by, 200, stream) : hipSuccess;
 }
 
 hipError_t launch_mesh_vjp_bone(const MeshVjpArgs& a, hipStream_t stream) {
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(mesh_vjp_bone_kernel), mv::B_LDS_BYTES)) return e;
   const int bx = (a.T + mv::BM - 1) / mv::BM, by = mesh_vjp_bone_split(a.T, a.V);
   if (by > 1 && !a.part) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(mesh_vjp_bone_kernel, dim3(bx, by), dim3(mv::BNW * 64), mv::B_LDS_BYTES, stream, a);
-  if (hipError_t e = hipGetLastError()) return e;
+  if (hipError_t e = launch_lds(mesh_vjp_bone_kernel, dim3(bx, by), dim3(mv::BNW * 64), mv::B_LDS_BYTES, stream, a)) return e;
   return by > 1 ? sum_slices(a, by, MESH_VJP_DA, stream) : hipSuccess;
 }
 

@@ -132,45 +132,32 @@ __global__ __launch_bounds__(mx::NW * 64) void mesh_rows_x3_kernel(MeshSkinArgs 
   };
   // One (frame, vertex) pair e = frame tile * 16 + accumulator index: blended 3 x 4 transform of the vertex's four bones
   // (reference order: T = sum_k w_k G_k, v = T . [v_posed, 1] + trans), one mat-vec, one 12-byte store.
-  float lab_sink = 0.f;   // (lab builds only: what a dummy skinning pass leaves)
   // The result goes to registers (outv): nothing is stored here.  A global store issued while this
   // SIMD has v_mfma_f32_32x32x16_bf16 in flight corrupts one accumulator element of the running products -- element r = 1,
   // lanes 48..63 of the first accumulator of a group, the very footprint scripts/dev/bf16_hazard_repro.md records for two
-  // waves per SIMD (there the OTHER wave's skinning stores met this wave's MFMAs); found with scripts/dev/mesh_x3_lab.sh:
-  // the same vector work and LDS reads between the MFMAs WITHOUT the stores is clean.  So the vertices of a tile leave in
-  // `flush`, after the pass, when the wave has no MFMA in flight.
+  // waves per SIMD (there the OTHER wave's skinning stores met this wave's MFMAs); found with an ablation build
+  // (profiles/r06_mesh_x3_lab.txt): the same vector work and LDS reads between the MFMAs WITHOUT the stores is clean.
+  // So the vertices of a tile leave in `flush`, after the pass, when the wave has no MFMA in flight.
   float outv[32][3];      // the skinned vertices of the tile being skinned, until `flush`
-  auto skin_one = [&](const f32x16 (&acc)[2][3], const SkinTile& st, int e, bool dummy = false) {
+  auto skin_one = [&](const f32x16 (&acc)[2][3], const SkinTile& st, int e) {
     const int i = e >> 4, r = e & 15;
     const int dm = i * 32 + (r & 3) + 8 * (r >> 2);   // frame within the block, less 4 * lh
     const float vx = acc[i][0][r], vy = acc[i][1][r], vz = acc[i][2][r];
-#if defined(MX_LAB_DUMMY) && defined(MX_LAB_NOLDS)
-    const f32x4 tr = dummy ? f32x4{vx, vy, vz, vx} : *reinterpret_cast<const f32x4*>(trl + dm * 16);
-#else
     const f32x4 tr = *reinterpret_cast<const f32x4*>(trl + dm * 16);
-#endif
     const char* xk[4] = {xfl + st.bone4.x * 48, xfl + st.bone4.y * 48, xfl + st.bone4.z * 48, xfl + st.bone4.w * 48};
     float out[3];
 #pragma unroll
     for (int row = 0; row < 3; ++row) {
-#if defined(MX_LAB_DUMMY) && defined(MX_LAB_NOLDS)
-#define MX_GK(k) (dummy ? f32x4{vx + (float)(k), vy, vz, st.w4[k]} : *reinterpret_cast<const f32x4*>(xk[k] + dm * (NB * 48) + row * 16))
-#else
-#define MX_GK(k) (*reinterpret_cast<const f32x4*>(xk[k] + dm * (NB * 48) + row * 16))
-#endif
-      f32x4 gk = MX_GK(0);
+      f32x4 gk = *reinterpret_cast<const f32x4*>(xk[0] + dm * (NB * 48) + row * 16);
       mx_f32x2 Ta = mx_f32x2{st.w4[0], st.w4[0]} * mx_f32x2{gk[0], gk[1]}, Tb = mx_f32x2{st.w4[0], st.w4[0]} * mx_f32x2{gk[2], gk[3]};
 #pragma unroll
       for (int k = 1; k < 4; ++k) {
-        gk = MX_GK(k);
+        gk = *reinterpret_cast<const f32x4*>(xk[k] + dm * (NB * 48) + row * 16);
         Ta = __builtin_elementwise_fma(mx_f32x2{st.w4[k], st.w4[k]}, mx_f32x2{gk[0], gk[1]}, Ta);
         Tb = __builtin_elementwise_fma(mx_f32x2{st.w4[k], st.w4[k]}, mx_f32x2{gk[2], gk[3]}, Tb);
       }
       out[row] = __builtin_fmaf(Ta[0], vx, __builtin_fmaf(Ta[1], vy, __builtin_fmaf(Tb[0], vz, Tb[1]))) + tr[row];
     }
-#ifdef MX_LAB_DUMMY
-    if (dummy) { lab_sink += out[0] + out[1] + out[2]; return; }
-#endif
     // (pinned: with the stores gone nothing anchors an element -- the compiler sank the arithmetic of all 32 of them down
     // to the flush and kept their 384 fetched transform rows alive until then, 1500 spilled registers; an empty asm that
     // "uses" the three results and clobbers memory holds both the arithmetic and the LDS reads of an element in place)
@@ -206,7 +193,7 @@ __global__ __launch_bounds__(mx::NW * 64) void mesh_rows_x3_kernel(MeshSkinArgs 
   // `flush_at` (DO_K without DO_S): the k-step in front of which the vertices of the PREVIOUS tile (outv, st_flush) are
   // stored, -1 for none -- see the tile loop.
   auto pass = [&](auto do_k_tag, auto do_s_tag, f32x16 (&acc_k)[2][3], const f32x16 (&acc_s)[2][3],
-                  const SkinTile& st, int bt, int bnext, bool dummy = false, int flush_at = -1,
+                  const SkinTile& st, int bt, int bnext, int flush_at = -1,
                   const SkinTile* st_flush = nullptr) {
     constexpr bool DO_K = decltype(do_k_tag)::value, DO_S = decltype(do_s_tag)::value;
     if (DO_K) {
@@ -255,7 +242,7 @@ __global__ __launch_bounds__(mx::NW * 64) void mesh_rows_x3_kernel(MeshSkinArgs 
         }
         if (DO_S) {
 #pragma unroll
-          for (int e = (g * 32) / (KS * 6); e < ((g + 1) * 32) / (KS * 6); ++e) skin_one(acc_s, st, e, dummy);
+          for (int e = (g * 32) / (KS * 6); e < ((g + 1) * 32) / (KS * 6); ++e) skin_one(acc_s, st, e);
         }
         if (DO_K) __builtin_amdgcn_sched_barrier(0x6);   // only VALU / SALU may move across: the MFMA order stands
         else __builtin_amdgcn_sched_barrier(0);           // (skinning alone: keep the elements apart, or the scheduler
@@ -295,15 +282,8 @@ __global__ __launch_bounds__(mx::NW * 64) void mesh_rows_x3_kernel(MeshSkinArgs 
         const int bt = tile_off_of(vt);
         const int bnext = vt + NW < end ? tile_off_of(vt + NW) : bt;
         const SkinTile st_next = skin_params(vt);
-#ifdef MX_LAB_DUMMY   // (lab: the real skinning one after the other, a DUMMY one -- results dropped -- under the K loop)
-        pass(yes, yes, accB, accA, st, bt, bnext, true);
-        pass(no, yes, accB, accA, st, 0, 0);
-#else
         pass(yes, yes, accB, accA, st, bt, bnext);
-#endif
-#ifndef MX_LAB_NOFLUSH
         flush(no, st);
-#endif
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -312,9 +292,6 @@ __global__ __launch_bounds__(mx::NW * 64) void mesh_rows_x3_kernel(MeshSkinArgs 
       }
       pass(no, yes, accB, accA, st, 0, 0);
       flush(no, st);
-#ifdef MX_LAB_DUMMY
-      if (lab_sink == 12345.678f) a.vertices[0] = lab_sink;
-#endif
     } else {
       // K loop, skinning, stores, one after the other -- but the stores of a tile wait until the NEXT tile's K loop has
       // reached k-step `flush_at`, a different one for every wave and workgroup (a.stagger): every wave of the chip
@@ -328,16 +305,10 @@ __global__ __launch_bounds__(mx::NW * 64) void mesh_rows_x3_kernel(MeshSkinArgs 
         const int bt = tile_off_of(vt);
         const int bnext = vt + NW < end ? tile_off_of(vt + NW) : bt;
         const SkinTile st = skin_params(vt);
-#ifndef MX_LAB_NOK        // (lab, scripts/dev/mesh_x3_lab.sh: what each phase of a tile costs; results are then wrong)
-        pass(yes, no, accA, accA, st, bt, bnext, false, pending ? flush_at : -1, &st_prev);
-#endif
-#ifndef MX_LAB_NOSKIN
+        pass(yes, no, accA, accA, st, bt, bnext, pending ? flush_at : -1, &st_prev);
         pass(no, yes, accB, accA, st, 0, 0);
-#endif
-#ifndef MX_LAB_NOFLUSH
         if (flush_at < 0) flush(no, st);
         else { st_prev = st; pending = true; }
-#endif
       }
       if (pending) flush(no, st_prev);
     }
@@ -360,14 +331,8 @@ hipError_t launch_mesh_rows_x3(const MeshSkinArgs& a, bool overlap, hipStream_t 
   int by = bx >= 256 ? 1 : (256 + bx - 1) / bx;
   const int max_by = (n_tiles + mx::NW - 1) / mx::NW;
   if (by > max_by) by = max_by;
-  if (overlap) {
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(mesh_rows_x3_kernel<true>), mx::LDS_BYTES)) return e;
-    hipLaunchKernelGGL(mesh_rows_x3_kernel<true>, dim3(bx, by), dim3(mx::NW * 64), mx::LDS_BYTES, stream, a);
-  } else {
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(mesh_rows_x3_kernel<false>), mx::LDS_BYTES)) return e;
-    hipLaunchKernelGGL(mesh_rows_x3_kernel<false>, dim3(bx, by), dim3(mx::NW * 64), mx::LDS_BYTES, stream, a);
-  }
-  return hipGetLastError();
+  return overlap ? launch_lds(mesh_rows_x3_kernel<true>, dim3(bx, by), dim3(mx::NW * 64), mx::LDS_BYTES, stream, a)
+                 : launch_lds(mesh_rows_x3_kernel<false>, dim3(bx, by), dim3(mx::NW * 64), mx::LDS_BYTES, stream, a);
 }
 
 }  // namespace empose

@@ -27,7 +27,6 @@ namespace fm {
 constexpr int BM = 64, NT = 256;
 constexpr int LDA = FUSED_MAX_WIDTH + 4;                     // activation row stride in LDS (floats)
 constexpr size_t LDS_BYTES = (size_t)BM * LDA * sizeof(float) + 64;   // + the look-ahead of the last fragment read
-constexpr int SG_MFMA = 0x008, SG_VMEM_RD = 0x020, SG_DS_RD = 0x100;
 }  // namespace fm
 
 // LDS layout of the single-layer row-block kernels below -- ONE definition: the kernels take their strides and region
@@ -52,8 +51,6 @@ __host__ __device__ constexpr RowsLds rows_lds(int K, int rows, bool a_kmajor, i
   const int end = extra_off + extra;
   return RowsLds{kpad, lda, extra_off, end > a ? (end > ct ? end : ct) : (a > ct ? a : ct)};
 }
-
-#define FM_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 
 #ifdef EMPOSE_FUSED_TRACE   // dev lab only: shader-clock stamps of block (0,0): per layer start, loop start, loop end, end
 __device__ long long g_fused_trace[64];
@@ -154,10 +151,10 @@ __device__ __forceinline__ void fused_layer_t(const FusedNet& net, const FusedLa
     constexpr int step = NMMA >= 2 * (NDS + WN) + 2 ? 2 : 1;
     static_assert(NMMA >= step * (NDS + WN), "k-group too small for its memory operations");
 #pragma unroll
-    for (int q = 0; q < NDS; ++q) { FM_SGB(SG_MFMA, step); FM_SGB(SG_DS_RD, 1); }
+    for (int q = 0; q < NDS; ++q) { SGB(SG_MFMA, step); SGB(SG_DS_RD, 1); }
 #pragma unroll
-    for (int q = 0; q < WN; ++q) { FM_SGB(SG_MFMA, step); FM_SGB(SG_VMEM_RD, 1); }
-    FM_SGB(SG_MFMA, NMMA - step * (NDS + WN));
+    for (int q = 0; q < WN; ++q) { SGB(SG_MFMA, step); SGB(SG_VMEM_RD, 1); }
+    SGB(SG_MFMA, NMMA - step * (NDS + WN));
   };
 
 #pragma unroll
@@ -297,7 +294,6 @@ __device__ __forceinline__ void fused_layer_t(const FusedNet& net, const FusedLa
 // mlp_fused_x3.hip's x3_layer (k-steps as fenced chunks, weights ahead in a register ring), plus plain steps for what is
 // left behind the whole periods of the pipeline (K = 200: 12 pipelined steps + 1).
 // ---------------------------------------------------------------------------------------------------------------------
-typedef const __attribute__((address_space(1))) u32x4_t* fm_gvec3_t;
 
 template <int WM, int WN, int OUT_T, bool A_KMAJOR>
 __device__ __forceinline__ void x3_rows_layer(const FusedNet& net, const FusedLayer& L, int M, int m0, float* act, int lda,
@@ -347,7 +343,7 @@ __device__ __forceinline__ void x3_rows_layer(const FusedNet& net, const FusedLa
 #pragma unroll
     for (int j = 0; j < WN; ++j)
 #pragma unroll
-      for (int q = 0; q < 3; ++q) b[j][q] = *(fm_gvec3_t)(p + b_voff[j] + q * 1024);
+      for (int q = 0; q < 3; ++q) b[j][q] = *(x3_gvec_t)(p + b_voff[j] + q * 1024);
   };
   auto split = [&](const f32x4 (&a)[WM][2], Pieces (&q)[WM]) {
 #pragma unroll
@@ -372,7 +368,7 @@ __device__ __forceinline__ void x3_rows_layer(const FusedNet& net, const FusedLa
     for (int c = 0; c < NCH; ++c) {
 #pragma unroll
       for (int o = c * NMEM / NCH; o < (c + 1) * NMEM / NCH; ++o) {
-        if (o < 3 * WN) b_free[o / 3][o % 3] = *(fm_gvec3_t)(pb + b_voff[o / 3] + (o % 3) * 1024);
+        if (o < 3 * WN) b_free[o / 3][o % 3] = *(x3_gvec_t)(pb + b_voff[o / 3] + (o % 3) * 1024);
         else aread1(ka, ra_free, o - 3 * WN);
       }
       {
@@ -389,7 +385,7 @@ __device__ __forceinline__ void x3_rows_layer(const FusedNet& net, const FusedLa
                                                             __builtin_bit_cast(bf16x8_t, b_cur[j][X3_PB[t]]), acc[i][j], 0, 0, 0);
       }
 #pragma unroll
-      for (int mm = 0; mm < (NM + NCH - 1) / NCH; ++mm) { FM_SGB(SG_MFMA, 1); FM_SGB(0x002, 2); if (mm < 3) FM_SGB(SG_VMEM_RD | SG_DS_RD, 1); }
+      for (int mm = 0; mm < (NM + NCH - 1) / NCH; ++mm) { SGB(SG_MFMA, 1); SGB(SG_VALU, 2); if (mm < 3) SGB(SG_VMEM_RD | SG_DS_RD, 1); }
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -542,10 +538,7 @@ __global__ __launch_bounds__(fm::NT) void gemm_rows_kernel(FusedMlpArgs args) {
 template <int BM_, int WM, int WN, int WCOLS>
 static hipError_t launch_gemm_rows_cfg(const FusedMlpArgs& args, hipStream_t stream) {
   const size_t lds = rows_lds(args.net[0].layer[0].K, BM_, false).bytes();
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(gemm_rows_kernel<BM_, WM, WN, WCOLS>), lds)) return e;
-  hipLaunchKernelGGL((gemm_rows_kernel<BM_, WM, WN, WCOLS>), dim3((args.M + BM_ - 1) / BM_), dim3(fm::NT), lds, stream,
-                     args);
-  return hipGetLastError();
+  return launch_lds(gemm_rows_kernel<BM_, WM, WN, WCOLS>, dim3((args.M + BM_ - 1) / BM_), dim3(fm::NT), lds, stream, args);
 }
 
 // C[M][N] = A[M][K] . Wp^T with Wp in fragment order. Returns false when the row-block kernel does not pay (the caller
@@ -730,9 +723,7 @@ __global__ __launch_bounds__(fm::NT) void blend_t_gemm_rod_kernel(FusedMlpArgs a
 template <int WN, bool A_T>
 static hipError_t launch_gemm_rows_t_cfg(const FusedMlpArgs& args, hipStream_t stream) {
   const size_t lds = rows_lds(args.net[0].layer[0].K, 64, A_T).bytes();
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(gemm_rows_t_kernel<WN, A_T>), lds)) return e;
-  hipLaunchKernelGGL((gemm_rows_t_kernel<WN, A_T>), dim3((args.M + 63) / 64), dim3(fm::NT), lds, stream, args);
-  return hipGetLastError();
+  return launch_lds(gemm_rows_t_kernel<WN, A_T>, dim3((args.M + 63) / 64), dim3(fm::NT), lds, stream, args);
 }
 
 hipError_t launch_gemm_rows_t(const float* A, int lda, bool a_tile, const float* Wp, float* C_t, int ldc_t, int M, int N,
@@ -804,9 +795,7 @@ static size_t x3_exclusive_lds(size_t lds) {
 
 template <class Kern, class Extra>
 static hipError_t launch_rows_t_fused(Kern kern, size_t lds, const FusedMlpArgs& a, const Extra& x, hipStream_t stream) {
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(kern), lds)) return e;
-  hipLaunchKernelGGL(kern, dim3((a.M + 63) / 64), dim3(fm::NT), lds, stream, a, x);
-  return hipGetLastError();
+  return launch_lds(kern, dim3((a.M + 63) / 64), dim3(fm::NT), lds, stream, a, x);
 }
 
 // `x3`: Wp holds three bf16 pieces per weight (api_model.hip pack_fragments_x3_raw) and the product runs on the bf16 matrix path
@@ -841,22 +830,13 @@ hipError_t launch_heads_rows(const float* y, int ldy, const float* Wp, const flo
   // the staged rows of y, later the transposed result (whole 32-column tiles): whichever is larger (a narrow LSTM's
   // row block is smaller than the 96 x 64 result) -- rows_lds, the layout the kernel indexes with
   const size_t lds = rows_lds(K, 64, false, n_pose + n_shape).bytes();
-  if (x3) {
-    const size_t lds1 = x3_exclusive_lds(lds);
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(heads_rows_kernel<true>), lds1)) return e;
-    hipLaunchKernelGGL(heads_rows_kernel<true>, dim3((M + 63) / 64), dim3(fm::NT), lds1, stream, a, h);
-    return hipGetLastError();
-  }
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(heads_rows_kernel<false>), lds)) return e;
-  hipLaunchKernelGGL(heads_rows_kernel<false>, dim3((M + 63) / 64), dim3(fm::NT), lds, stream, a, h);
-  return hipGetLastError();
+  if (x3) return launch_lds(heads_rows_kernel<true>, dim3((M + 63) / 64), dim3(fm::NT), x3_exclusive_lds(lds), stream, a, h);
+  return launch_lds(heads_rows_kernel<false>, dim3((M + 63) / 64), dim3(fm::NT), lds, stream, a, h);
 }
 
 hipError_t launch_mlp_fused(const FusedMlpArgs& args, hipStream_t stream) {
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(mlp_fused_kernel), fm::LDS_BYTES)) return e;
   dim3 grid((args.M + fm::BM - 1) / fm::BM, args.count);
-  hipLaunchKernelGGL(mlp_fused_kernel, grid, dim3(fm::NT), fm::LDS_BYTES, stream, args);
-  return hipGetLastError();
+  return launch_lds(mlp_fused_kernel, grid, dim3(fm::NT), fm::LDS_BYTES, stream, args);
 }
 
 }  // namespace empose

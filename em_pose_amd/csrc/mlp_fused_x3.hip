@@ -34,21 +34,12 @@ constexpr int BM = 64, NT = 256;
 constexpr int LDA = FUSED_MAX_WIDTH + 4;
 constexpr size_t LDS_BYTES = (size_t)BM * LDA * sizeof(float) + 64;
 constexpr int RING = 4;                      // weight ring: three k-steps in flight + the one being multiplied
-constexpr int SG_MFMA = 0x008, SG_VALU = 0x002, SG_VMEM_RD = 0x020, SG_DS_RD = 0x100;
 }  // namespace fx
 
-typedef const __attribute__((address_space(1))) u32x4_t* fx_gvec_t;
 typedef const __attribute__((address_space(1))) char* fx_gbyte_t;
-
-#define FX_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0)
 
 // the pieces of a lane's 8 consecutive k
 __device__ __forceinline__ Pieces fx_split8(const f32x4& lo, const f32x4& hi) {
-#ifdef FX_LAB_NOSPLIT   // dev lab: no arithmetic on the A side (what the loop costs without the split)
-  Pieces z;
-  z.p[0] = __builtin_bit_cast(u32x4_t, lo); z.p[1] = __builtin_bit_cast(u32x4_t, hi); z.p[2] = z.p[0];
-  return z;
-#endif
   return split8(lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]);
 }
 
@@ -101,19 +92,12 @@ __device__ __forceinline__ void x3_layer(const FusedNet& net, const FusedLayer& 
     }
   };
   auto bload = [&](u32x4_t (&b)[WN][3], int ks) {
-#ifdef FX_LAB_NOB   // dev lab: only the prologue's weight loads (what the loop costs without its weight stream)
-    if (ks >= 3) return;
-#endif
-#ifdef FX_LAB_SAMEB   // dev lab: every k-step fetches the weights of step 0 (the loads' issue cost without their stream)
-    const int kc = 0 * ks;
-#else
     const int kc = ks < KS4 ? ks : KS4 - 1;   // (clamped: fetched, never used)
-#endif
     fx_gbyte_t p = wb + (size_t)kc * NT32 * 3072;
 #pragma unroll
     for (int j = 0; j < WN; ++j)
 #pragma unroll
-      for (int q = 0; q < 3; ++q) b[j][q] = *(fx_gvec_t)(p + b_voff[j] + q * 1024);
+      for (int q = 0; q < 3; ++q) b[j][q] = *(x3_gvec_t)(p + b_voff[j] + q * 1024);
   };
   auto split = [&](const f32x4 (&a)[WM][2], Pieces (&q)[WM]) {
 #pragma unroll
@@ -139,10 +123,10 @@ __device__ __forceinline__ void x3_layer(const FusedNet& net, const FusedLayer& 
     static_assert(NVM + NDS <= NM, "k-step too small for its memory operations");
 #pragma unroll
     for (int q = 0; q < NM; ++q) {
-      FX_SGB(SG_MFMA, 1);
-      if (q < NVM) FX_SGB(SG_VMEM_RD, 1);
-      else if (q < NVM + NDS) FX_SGB(SG_DS_RD, 1);
-      FX_SGB(SG_VALU, vper);
+      SGB(SG_MFMA, 1);
+      if (q < NVM) SGB(SG_VMEM_RD, 1);
+      else if (q < NVM + NDS) SGB(SG_DS_RD, 1);
+      SGB(SG_VALU, vper);
     }
   };
   // One k-step as NCH chunks, each fenced by a scheduling barrier: 48 / NCH of the step's MFMAs, the split of ONE pair of the
@@ -161,9 +145,7 @@ __device__ __forceinline__ void x3_layer(const FusedNet& net, const FusedLayer& 
 #pragma unroll
       for (int o = c * NMEM / NCH; o < (c + 1) * NMEM / NCH; ++o) {
         if (o < 3 * WN) {
-#ifndef FX_LAB_NOB
-          b_free[o / 3][o % 3] = *(fx_gvec_t)(pb + b_voff[o / 3] + (o % 3) * 1024);
-#endif
+          b_free[o / 3][o % 3] = *(x3_gvec_t)(pb + b_voff[o / 3] + (o % 3) * 1024);
         } else {
           const int r = o - 3 * WN;
           ra_free[r / 2][r % 2] = *reinterpret_cast<const f32x4*>(a_rd + (r / 2) * 32 * lda + ka * 16 + (r % 2) * 4);
@@ -174,11 +156,7 @@ __device__ __forceinline__ void x3_layer(const FusedNet& net, const FusedLayer& 
         const int i = c / 4, q = c % 4;
         const f32x4& v = ra_nxt[i][q / 2];
         unsigned h, m, l;
-#ifdef FX_LAB_NOSPLIT
-        h = __builtin_bit_cast(unsigned, v[(q % 2) * 2]); m = __builtin_bit_cast(unsigned, v[(q % 2) * 2 + 1]); l = h;
-#else
         split_pair(v[(q % 2) * 2], v[(q % 2) * 2 + 1], h, m, l);
-#endif
         ap_nxt[i].p[0][q] = h; ap_nxt[i].p[1][q] = m; ap_nxt[i].p[2][q] = l;
       }
       // ---- this chunk's share of the step's MFMAs, in (product, row tile, column tile) order
@@ -189,7 +167,7 @@ __device__ __forceinline__ void x3_layer(const FusedNet& net, const FusedLayer& 
                                                             __builtin_bit_cast(bf16x8_t, b_cur[j][X3_PB[t]]), acc[i][j], 0, 0, 0);
       }
 #pragma unroll
-      for (int mm = 0; mm < (NM + NCH - 1) / NCH; ++mm) { FX_SGB(SG_MFMA, 1); FX_SGB(SG_VALU, 2); if (mm < 2) FX_SGB(SG_VMEM_RD | SG_DS_RD, 1); }
+      for (int mm = 0; mm < (NM + NCH - 1) / NCH; ++mm) { SGB(SG_MFMA, 1); SGB(SG_VALU, 2); if (mm < 2) SGB(SG_VMEM_RD | SG_DS_RD, 1); }
       __builtin_amdgcn_sched_barrier(0);
     }
   };
@@ -342,7 +320,7 @@ __device__ __forceinline__ void x3c_layer(const FusedNet& net, const FusedLayer&
 #pragma unroll
     for (int j = 0; j < WN; ++j)
 #pragma unroll
-      for (int q = 0; q < 3; ++q) b[j][q] = *(fx_gvec_t)(p + b_voff[j] + q * 1024);
+      for (int q = 0; q < 3; ++q) b[j][q] = *(x3_gvec_t)(p + b_voff[j] + q * 1024);
   };
   auto mma = [&](const Pieces (&a)[WM], const u32x4_t (&b)[WN][3]) {
 #pragma unroll
@@ -360,14 +338,14 @@ __device__ __forceinline__ void x3c_layer(const FusedNet& net, const FusedLayer&
       // the split of step s + 2 and its three LDS writes FIRST (they must have landed long before the next barrier, which
       // waits for this wave's LDS operations), then the fragment reads, then the weight loads
 #pragma unroll
-      for (int q = 0; q < 12; ++q) { FX_SGB(SG_MFMA, 1); FX_SGB(SG_VALU, 2); }
+      for (int q = 0; q < 12; ++q) { SGB(SG_MFMA, 1); SGB(SG_VALU, 2); }
 #pragma unroll
-      for (int q = 0; q < 3; ++q) { FX_SGB(SG_MFMA, 1); FX_SGB(0x200, 1); }
+      for (int q = 0; q < 3; ++q) { SGB(SG_MFMA, 1); SGB(0x200, 1); }
 #pragma unroll
-      for (int q = 0; q < NDS; ++q) { FX_SGB(SG_MFMA, 1); FX_SGB(SG_DS_RD, 1); }
+      for (int q = 0; q < NDS; ++q) { SGB(SG_MFMA, 1); SGB(SG_DS_RD, 1); }
 #pragma unroll
-      for (int q = 0; q < NVM; ++q) { FX_SGB(SG_MFMA, 1); FX_SGB(SG_VMEM_RD, 1); }
-      FX_SGB(SG_MFMA, NM - 15 - NDS - NVM);
+      for (int q = 0; q < NVM; ++q) { SGB(SG_MFMA, 1); SGB(SG_VMEM_RD, 1); }
+      SGB(SG_MFMA, NM - 15 - NDS - NVM);
     }
   };
   // step s: barrier (stage (s + 1) & 1 is complete) | split + write of s + 2 | fragments of s + 1, raw of s + 3 | weights of
@@ -507,13 +485,9 @@ __global__ __launch_bounds__(fx::NT) void mlp_fused_x3_kernel(FusedMlpArgs args)
 hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, hipStream_t stream) {
   dim3 grid((args.M + fx::BM - 1) / fx::BM, args.count);
   if (options().mlp_x3 >= 2) {   // opt-in: the cooperative split (measured slower, see x3c_layer)
-    if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(mlp_fused_x3c_kernel), fx::LDS_BYTES_C)) return e;
-    hipLaunchKernelGGL(mlp_fused_x3c_kernel, grid, dim3(fx::NT), fx::LDS_BYTES_C, stream, args);
-    return hipGetLastError();
+    return launch_lds(mlp_fused_x3c_kernel, grid, dim3(fx::NT), fx::LDS_BYTES_C, stream, args);
   }
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(mlp_fused_x3_kernel), fx::LDS_BYTES)) return e;
-  hipLaunchKernelGGL(mlp_fused_x3_kernel, grid, dim3(fx::NT), fx::LDS_BYTES, stream, args);
-  return hipGetLastError();
+  return launch_lds(mlp_fused_x3_kernel, grid, dim3(fx::NT), fx::LDS_BYTES, stream, args);
 }
 
 }  // namespace empose

@@ -8,36 +8,6 @@ struct Rod {
   float ux, uy, uz, ang, dx, dy, dz, s, c;   // (ux, uy, uz) = ang * d(ang)/d(r)
 };
 
-// Axis-angle -> rotation, R = I + sin(a) K + (1 - cos a) K^2 with K = hat(r / a).  The un-vendored BodyModel's guard of
-// the angle at r = 0 is not pinned (SURVEY.md 8c), so both published conventions are kept (EMPOSE_RODRIGUES_*):
-//   smplx  a = ||r + 1e-8||                 (smplx lbs.batch_rodrigues)
-//   so3    a = sqrt(max(||r||^2, 1e-4))     (reference helpers/so3.py:116-121; below the clamp a is constant)
-__device__ __forceinline__ void rodrigues(float rx, float ry, float rz, int conv, Rod& q, float (&R)[9]) {
-  if (conv == 0) {
-    q.ux = rx + 1e-8f; q.uy = ry + 1e-8f; q.uz = rz + 1e-8f;
-    q.ang = sqrtf(q.ux * q.ux + q.uy * q.uy + q.uz * q.uz);
-  } else {
-    const float n2 = rx * rx + ry * ry + rz * rz;
-    const bool clamped = n2 < 1e-4f;
-    q.ux = clamped ? 0.f : rx; q.uy = clamped ? 0.f : ry; q.uz = clamped ? 0.f : rz;
-    q.ang = sqrtf(fmaxf(n2, 1e-4f));
-  }
-  q.dx = rx / q.ang; q.dy = ry / q.ang; q.dz = rz / q.ang;
-  sincosf(q.ang, &q.s, &q.c);
-  const float oc = 1.f - q.c;
-  // K = [[0,-dz,dy],[dz,0,-dx],[-dy,dx,0]];  R = I + s K + (1-c) K K
-  R[0] = 1.f + oc * (-q.dz * q.dz - q.dy * q.dy);
-  R[1] = -q.s * q.dz + oc * (q.dx * q.dy);
-  R[2] = q.s * q.dy + oc * (q.dx * q.dz);
-  R[3] = q.s * q.dz + oc * (q.dx * q.dy);
-  R[4] = 1.f + oc * (-q.dz * q.dz - q.dx * q.dx);
-  R[5] = -q.s * q.dx + oc * (q.dy * q.dz);
-  R[6] = -q.s * q.dy + oc * (q.dx * q.dz);
-  R[7] = q.s * q.dx + oc * (q.dy * q.dz);
-  R[8] = 1.f + oc * (-q.dy * q.dy - q.dx * q.dx);
-}
-
-
 // sin and cos of a non-negative angle of ordinary size (axis-angle magnitudes: a few radians): Cody-Waite reduction by
 // pi/2 in three pieces and the single-precision minimax polynomials on [-pi/4, pi/4] (errors below 1 ulp there).  The
 // library's sincosf carries its large-argument reduction along (~150 dependent instructions); a wave of the
@@ -56,8 +26,14 @@ __device__ __forceinline__ void sincos_small(float x, float* s, float* c) {
   *c = ((k + 1) & 2) ? -cv : cv;
 }
 
-// rodrigues() with sincos_small (the frame-per-lane kernels; same conventions, same outputs to ~1 ulp)
-__device__ __forceinline__ void rodrigues_fast(float rx, float ry, float rz, int conv, Rod& q, float (&R)[9]) {
+// Axis-angle -> rotation, R = I + sin(a) K + (1 - cos a) K^2 with K = hat(r / a).  The un-vendored BodyModel's guard of
+// the angle at r = 0 is not pinned (SURVEY.md 8c), so both published conventions are kept (EMPOSE_RODRIGUES_*):
+//   smplx  a = ||r + 1e-8||                 (smplx lbs.batch_rodrigues)
+//   so3    a = sqrt(max(||r||^2, 1e-4))     (reference helpers/so3.py:116-121; below the clamp a is constant)
+// FAST (the frame-per-lane kernels): one reciprocal and three products instead of three divisions, and sincos_small
+// instead of the library's sincosf; same conventions, same outputs to ~1 ulp.
+template <bool FAST>
+__device__ __forceinline__ void rodrigues_impl(float rx, float ry, float rz, int conv, Rod& q, float (&R)[9]) {
   if (conv == 0) {
     q.ux = rx + 1e-8f; q.uy = ry + 1e-8f; q.uz = rz + 1e-8f;
     q.ang = sqrtf(q.ux * q.ux + q.uy * q.uy + q.uz * q.uz);
@@ -67,10 +43,16 @@ __device__ __forceinline__ void rodrigues_fast(float rx, float ry, float rz, int
     q.ux = clamped ? 0.f : rx; q.uy = clamped ? 0.f : ry; q.uz = clamped ? 0.f : rz;
     q.ang = sqrtf(fmaxf(n2, 1e-4f));
   }
-  const float inv = 1.f / q.ang;
-  q.dx = rx * inv; q.dy = ry * inv; q.dz = rz * inv;
-  sincos_small(q.ang, &q.s, &q.c);
+  if (FAST) {
+    const float inv = 1.f / q.ang;
+    q.dx = rx * inv; q.dy = ry * inv; q.dz = rz * inv;
+    sincos_small(q.ang, &q.s, &q.c);
+  } else {
+    q.dx = rx / q.ang; q.dy = ry / q.ang; q.dz = rz / q.ang;
+    sincosf(q.ang, &q.s, &q.c);
+  }
   const float oc = 1.f - q.c;
+  // K = [[0,-dz,dy],[dz,0,-dx],[-dy,dx,0]];  R = I + s K + (1-c) K K
   R[0] = 1.f + oc * (-q.dz * q.dz - q.dy * q.dy);
   R[1] = -q.s * q.dz + oc * (q.dx * q.dy);
   R[2] = q.s * q.dy + oc * (q.dx * q.dz);
@@ -80,6 +62,12 @@ __device__ __forceinline__ void rodrigues_fast(float rx, float ry, float rz, int
   R[6] = -q.s * q.dy + oc * (q.dx * q.dz);
   R[7] = q.s * q.dx + oc * (q.dy * q.dz);
   R[8] = 1.f + oc * (-q.dy * q.dy - q.dx * q.dx);
+}
+__device__ __forceinline__ void rodrigues(float rx, float ry, float rz, int conv, Rod& q, float (&R)[9]) {
+  rodrigues_impl<false>(rx, ry, rz, conv, q, R);
+}
+__device__ __forceinline__ void rodrigues_fast(float rx, float ry, float rz, int conv, Rod& q, float (&R)[9]) {
+  rodrigues_impl<true>(rx, ry, rz, conv, q, R);
 }
 
 __device__ __forceinline__ void cross3(const float* a, const float* b, float* o) {

@@ -772,11 +772,8 @@ static hipError_t launch_tile_cfg(const TileArgs& a, hipStream_t stream) {
 #define TL_BWD_WAVES 4
 #endif
   constexpr int NWAVES = BWD ? TL_BWD_WAVES : 8;
-  if (hipError_t e = allow_dynamic_lds(reinterpret_cast<const void*>(smpl_tile_kernel<BWD, NLOC, NBL, NWAVES>), tl::LDS_BYTES))
-    return e;
   const int tiles = (a.T + TL_FR - 1) / TL_FR;
-  hipLaunchKernelGGL((smpl_tile_kernel<BWD, NLOC, NBL, NWAVES>), dim3(tiles), dim3(64 * NWAVES), tl::LDS_BYTES, stream, a);
-  return hipGetLastError();
+  return launch_lds(smpl_tile_kernel<BWD, NLOC, NBL, NWAVES>, dim3(tiles), dim3(64 * NWAVES), tl::LDS_BYTES, stream, a);
 }
 
 // `nloc`, `nbl`: the model's largest patch (TileTables::nloc / nbl, host copies).  Two unrolled sizes: the common

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Dev: ring depths of lstm_mid16_x3_kernel (LH3_RING2: launches of at most 32 rows, LH3_RING4: 33..64 rows), timed on the
 # stand-alone LSTM (2 x 512, input 60; scripts/dev/bench_lstm_mid.py).  Variants <ring 2>_<ring 4>.
-# usage (container): bash scripts/dev/lstm_mid_lab.sh build ; (GPU box): bash scripts/dev/lstm_mid_lab.sh run
+# usage (container): bash scripts/dev/lstm_mid16_lab.sh build ; (GPU box): bash scripts/dev/lstm_mid16_lab.sh run
 set -u
 R=$(cd "$(dirname "$0")/../.." && pwd)
 C=$R/em_pose_amd/csrc

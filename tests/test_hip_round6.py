@@ -263,7 +263,7 @@ def test_three_piece_kernels_keep_their_bits_beside_a_storing_kernel_on_another_
     pause while the headline-shaped forward (update MLPs, LSTM steps, heads, blend GEMMs on three pieces) and the full-mesh
     evaluation repeat on the first one: every repetition has the bits of the run alone on the device.  A guard, not the
     reproducer: found in round 6 when the three-piece training GEMMs met the engine's side streams -- two runs of the same
-    64-window step differed in the eighth digit; `scripts/dev/x3_shared_simd_lab.sh` shows five runs / five results without
+    64-window step differed in the eighth digit; `profiles/r06_x3_shared_simd_lab.txt` shows five runs / five results without
     the macro and five / one with it, and tests/test_bench_contract.py::test_training_with_buckets_rccl_and_side_streams_
     equals_the_plain_step holds the exact equality in the suite."""
     torch.manual_seed(3)
