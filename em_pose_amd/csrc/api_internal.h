@@ -222,7 +222,7 @@ struct empose_model {
   int smpl_only = 0;
   int rod_conv = 0;            // EMPOSE_RODRIGUES_*
   // frame-per-lane path (smpl_tile.hip): tables, the blend matrix with per-patch vertex copies in fragment order
-  int tile_ok = 0, ncp2 = 0, tile_nloc = 0, tile_nbl = 0;
+  int tile_ok = 0, ncp2 = 0, tile_nloc = 0, tile_nbl = 0, tile_j_off2 = 0;   // (host copies of TileTables fields)
   empose::TileTables* tile_tab = nullptr;
   float* wc2_frag = nullptr;   // [ncp2][200]
   float* wc2t_frag = nullptr;  // [200][ncp2]

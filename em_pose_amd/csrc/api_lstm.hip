@@ -218,6 +218,7 @@ int run_lstm(const Lstm& r, int B, int F, const float* x, int ldx, const int* se
   LstmWaveArgs a;
   a.seq_lengths = seq_lengths; a.B = B; a.F = F; a.H = H;
   bool seq_done = false;
+  bool state_direct = false;   // the step kernel has stored h_n / c_n itself
   if (D == 1) {
     // Stacked uni-directional layers: wavefront over (layer, time), launch s advances layer l by its step s - l.
     if (L > 4) return fail(EMPOSE_EINVAL, "at most 4 stacked layers per wavefront");
@@ -278,9 +279,28 @@ int run_lstm(const Lstm& r, int B, int F, const float* x, int ldx, const int* se
       prof_mark(P_COPY, stream);
       const int KS_in = (r.input_size + 15) / 16, KS_h = H / 16;
       hipError_t e = launch_lstm_split_rows(x, (long)F * ldx, ldx, F, B, r.input_size, KS_in, ws.x3, (long)ws.x3_t_stride, stream);
-      for (int l = 0; l < L && e == hipSuccess; ++l) {
-        e = launch_lstm_split_rows(ws.h[l][0], H, 0, 1, B, H, KS_h, ws.a3[l][0], 0, stream);
-        if (e == hipSuccess) e = hipMemsetAsync(ws.a3[l][1], 0, lstm_x3_plane_elems(B, H) * sizeof(unsigned short), stream);
+      // New sequences (option lstm_state_direct): the pieces of a zero state are zero planes, and the 2 L hidden-state
+      // planes are carved back to back (carve_lstm_of) -- one fill instead of a split launch and a fill per layer.  On
+      // the chain kernel the last step of each layer then stores h_n / c_n itself (rows past their length included: it
+      // rewrites their frozen state at every step), so the 2 L trailing copies go too.
+      const bool direct = options().lstm_state_direct != 0 && !h0 && !c0;
+      state_direct = direct && p.step == LstmStep::chain_x3;
+      const size_t plane_bytes = lstm_x3_plane_elems(B, H) * sizeof(unsigned short);
+      if (direct) {
+        // (checked, not assumed: the fill below covers [a3[0][0], a3[L-1][1] + plane) and must hit these planes only)
+        const char* lo = reinterpret_cast<const char*>(ws.a3[0][0]);
+        const size_t stride = align_up((lstm_x3_plane_elems(B, H) + 1) / 2 * sizeof(float));
+        for (int l = 0; l < L; ++l)
+          for (int k = 0; k < 2; ++k)
+            if (reinterpret_cast<const char*>(ws.a3[l][k]) != lo + (size_t)(2 * l + k) * stride)
+              return fail(EMPOSE_EINVAL, "internal: the LSTM hidden-state planes are not carved back to back");
+        const size_t span = (size_t)(2 * L - 1) * stride + plane_bytes;
+        if (e == hipSuccess) e = hipMemsetAsync(ws.a3[0][0], 0, span, stream);
+      } else {
+        for (int l = 0; l < L && e == hipSuccess; ++l) {
+          e = launch_lstm_split_rows(ws.h[l][0], H, 0, 1, B, H, KS_h, ws.a3[l][0], 0, stream);
+          if (e == hipSuccess) e = hipMemsetAsync(ws.a3[l][1], 0, plane_bytes, stream);
+        }
       }
       if (e != hipSuccess) return fail(EMPOSE_EHIP, "lstm operand split: %s", hipGetErrorString(e));
       const int tiles = (H / 32) * ((B + 63) / 64);
@@ -298,6 +318,9 @@ int run_lstm(const Lstm& r, int B, int F, const float* x, int ldx, const int* se
           xu.a3_rec = ws.a3[l][t & 1]; xu.a3_out = ws.a3[l][(t + 1) & 1];
           xu.h_prev = ws.h[l][t & 1]; xu.h_next = ws.h[l][(t + 1) & 1]; xu.c = ws.c[l];
           xu.y = l == L - 1 ? y : nullptr; xu.y_ld = H; xu.y_col = 0; xu.t = t;
+          const bool last_step = state_direct && t == F - 1;
+          xu.h_final = last_step && h_n ? h_n + l * bh : nullptr;
+          xu.c_final = last_step && c_n ? c_n + l * bh : nullptr;
         }
         xa.units_per_block = tiles >= 192 ? xa.n_units : 1;
         prof_mark(P_LSTM_STEP, stream);
@@ -335,6 +358,7 @@ int run_lstm(const Lstm& r, int B, int F, const float* x, int ldx, const int* se
       }
     }
   }
+  if (state_direct) return EMPOSE_OK;
   prof_mark(P_COPY, stream);
   for (int u = 0; u < U; ++u) {
     // the final hidden state: buffer F & 1 after step launches, F % 3 of (h[0], h[1], h3) after the large-batch sequence kernel

@@ -353,7 +353,14 @@ int run_smpl_eval(const empose_model* m, int T, int F, const SmplWs& ws, FeatArg
     // frame-per-lane path: blend GEMM -> tile layout -> smpl_tile_kernel -> tile layout -> transposed GEMM
     prof_mark(P_BLEND_GEMM, stream);
     const bool rx3 = options().rows_x3 != 0 && m->wc2_frag3 && m->wc2t_frag3;
-    HIP_CHECK(fuse ? launch_blend_feat_gemm(fa, rx3 ? m->wc2_frag3 : m->wc2_frag, ws.out, m->ncp2, m->ncp2, rx3, stream)
+    // Joints only (option last_pass_joints; the last pass of an LGD forward without histories): no gradient, no sensor
+    // output, so of the blend product only the 66 rest-joint columns are read -- the GEMM multiplies just their column
+    // tiles (same fragments, same order: same bits) and the tile kernel stops after the chain.
+    const bool joints_only = fuse && options().last_pass_joints != 0 && !bwd && !pos && !ori && !pos2 && !ori2 &&
+                             (joints || joints2);
+    const int j_off2 = m->tile_j_off2;
+    HIP_CHECK(fuse ? launch_blend_feat_gemm(fa, rx3 ? m->wc2_frag3 : m->wc2_frag, ws.out, m->ncp2, m->ncp2, rx3, stream,
+                                            joints_only ? j_off2 : 0, joints_only ? j_off2 + 66 : 0)
                    : launch_gemm_rows_t(ws.feat, 200, false, m->wc2_frag, ws.out, m->ncp2, T, m->ncp2, 200, stream),
               "blend gemm (tile)");
     TileArgs a;
@@ -366,7 +373,7 @@ int run_smpl_eval(const empose_model* m, int T, int F, const SmplWs& ws, FeatArg
     a.d_out_t = ws.d_out; a.d_rot_t = ws.d_rot; a.T = T; a.F = F; a.rod_conv = m->rod_conv;
     a.cot_pos = cot_pos; a.cot_ori = cot_ori;
     prof_mark(P_CHAIN, stream);
-    HIP_CHECK(launch_smpl_tile(a, bwd, m->tile_nloc, m->tile_nbl, stream), "smpl tile kernel");
+    HIP_CHECK(launch_smpl_tile(a, bwd, m->tile_nloc, m->tile_nbl, stream, joints_only), "smpl tile kernel");
     if (bwd) {
       RodBwdTArgs ra;
       ra.theta = fa.theta; ra.ld_theta = fa.ld_theta; ra.theta_t = ws.theta_t; ra.d_rot_t = ws.d_rot;
@@ -524,7 +531,7 @@ int empose_model_create(const empose_model_desc* d, empose_model_t** out) {
       MTRY(pack_fragments_raw(m->allocs, wc2t.data(), 200, tt.ncp2, &m->wc2t_frag));
       MTRY(pack_fragments_x3_raw(m->allocs, wc2.data(), tt.ncp2, 200, &m->wc2_frag3));
       MTRY(pack_fragments_x3_raw(m->allocs, wc2t.data(), 200, tt.ncp2, &m->wc2t_frag3));
-      m->ncp2 = tt.ncp2; m->tile_nloc = tt.nloc; m->tile_nbl = tt.nbl;
+      m->ncp2 = tt.ncp2; m->tile_nloc = tt.nloc; m->tile_nbl = tt.nbl; m->tile_j_off2 = tt.j_off2;
       m->tile_ok = tt.ncp2 <= 320;   // the widest tile gemm_rows_t_kernel covers
     }
   }

@@ -64,7 +64,13 @@ namespace empose {
   X(mlp_x3, 1)         /* fused update MLPs: fp32 products as six bf16-MFMA products of three bf16 pieces per operand \
                              (mlp_fused_x3.hip: fp32-equivalent accuracy, measured equal to the fp32 instruction's against \
                              float64); 0: the fp32 MFMA instruction (mlp_fused.hip); 2: the variant whose waves share the \
-                             A-side split through LDS (a barrier per k-step; measured 9 % slower) */
+                             A-side split through LDS (a barrier per k-step; measured 9 % slower) */ \
+  X(last_pass_joints, 1) /* LGD forward, frame-per-lane path: an SMPL evaluation nobody asks sensor outputs of (the last pass \
+                             without histories) multiplies only the rest-joint column tiles of the blend matrix and runs the \
+                             chain alone (smpl_tile_kernel, CHAIN_ONLY); 0: the whole sub-mesh, as for every other pass */ \
+  X(lstm_state_direct, 1) /* large-batch LSTM steps (lstm_x3.hip), new sequences: the piece planes of the zero initial state by \
+                             one fill, h_n / c_n stored by the last step of each layer; 0: a split launch and a fill per layer, \
+                             2 L trailing copies */
 
 struct Options {
 #define EMPOSE_OPTION_FIELD(name, default_value) int name = default_value;
@@ -373,6 +379,9 @@ struct LstmX3Unit {
   const float* h_prev; float* h_next; float* c;   // [B][H] fp32: state hand-over and rows past their length
   float* y; int y_ld, y_col;         // output sequence [B][F][y_ld] or nullptr
   int t;                             // the unit's time step in this launch
+  // the layer's slices of h_n / c_n ([B][H]) on the launch of its last step, else nullptr: a second copy of what goes to
+  // h_next / c (lstm_chain_x3_kernel only; the other step kernels ignore them and the caller copies the state out)
+  float* h_final = nullptr; float* c_final = nullptr;
 };
 struct LstmX3Args {
   LstmX3Unit unit[4];
@@ -686,7 +695,9 @@ struct TileArgs {
   const float* cot_pos = nullptr;     // [T][36], [T][108]: external cotangents instead of the residual
   const float* cot_ori = nullptr;
 };
-hipError_t launch_smpl_tile(const TileArgs& a, bool backward, int nloc, int nbl, hipStream_t stream);
+// `chain_only` (forward, no sensor outputs asked for): Rodrigues + chain and the joint stores alone; reads only the
+// rest-joint columns of out_t
+hipError_t launch_smpl_tile(const TileArgs& a, bool backward, int nloc, int nbl, hipStream_t stream, bool chain_only = false);
 struct RodBwdTArgs {
   const float* theta; int ld_theta;
   const float* theta_t = nullptr;     // optional: the same values in tile layout [tiles][66][64] (coalesced loads)
@@ -707,8 +718,10 @@ hipError_t launch_gemm_rows_t(const float* A, int lda, bool a_tile, const float*
 // feature row as the prologue of the first (the [T][200] feature matrix never reaches HBM), the Rodrigues reverse as
 // the epilogue of the second (neither do the feature cotangents).
 // x3: Wp = three bf16 pieces per weight in bf16-MFMA fragment order (pack_fragments_x3_raw), product on the bf16 matrix path
+// [col_lo, col_hi): compute and write only the 32-column tiles of C_t that cover these columns (same bits there as the
+// full product); the default is every column
 hipError_t launch_blend_feat_gemm(const FeatArgs& fa, const float* Wp, float* C_t, int ldc_t, int N, bool x3,
-                                  hipStream_t stream);
+                                  hipStream_t stream, int col_lo = 0, int col_hi = 0);
 hipError_t launch_blend_t_gemm_rod(const float* A_t, int lda_t, const float* Wp, int K, const RodBwdTArgs& ra, bool x3,
                                    hipStream_t stream);
 

@@ -220,6 +220,16 @@ __global__ __launch_bounds__(lx::NT) void lstm_chain_x3_kernel(LstmX3Args a) {
       *reinterpret_cast<f32x4*>(U.c + hc + 4) = f32x4{cv[4], cv[5], cv[6], cv[7]};
       *reinterpret_cast<f32x4*>(U.h_next + hc) = f32x4{hv[0], hv[1], hv[2], hv[3]};
       *reinterpret_cast<f32x4*>(U.h_next + hc + 4) = f32x4{hv[4], hv[5], hv[6], hv[7]};
+      // the layer's last step: the same values once more, where the caller wants h_n / c_n (rows past their length carry
+      // their frozen state through every step, so every row of the final state is written here)
+      if (U.h_final) {
+        *reinterpret_cast<f32x4*>(U.h_final + hc) = f32x4{hv[0], hv[1], hv[2], hv[3]};
+        *reinterpret_cast<f32x4*>(U.h_final + hc + 4) = f32x4{hv[4], hv[5], hv[6], hv[7]};
+      }
+      if (U.c_final) {
+        *reinterpret_cast<f32x4*>(U.c_final + hc) = f32x4{cv[0], cv[1], cv[2], cv[3]};
+        *reinterpret_cast<f32x4*>(U.c_final + hc + 4) = f32x4{cv[4], cv[5], cv[6], cv[7]};
+      }
       if (U.y) {
         float* yo = U.y + ((size_t)g_row * F + t) * U.y_ld + U.y_col + g_unit;
         *reinterpret_cast<f32x4*>(yo) = f32x4{yv[0], yv[1], yv[2], yv[3]};

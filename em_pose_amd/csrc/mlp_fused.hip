@@ -646,10 +646,13 @@ __global__ __launch_bounds__(fm::NT) void gemm_rows_t_kernel(FusedMlpArgs args) 
 // The blend-shape GEMM of the frame-per-lane path with the iteration's pose / shape update, Rodrigues and the feature
 // row as its PROLOGUE (feat_rows.h: the body of update_feat_kernel): the 64 x 200 feature block is built in LDS from
 // 76 floats per frame and never exists in HBM.  out_t = feat . Wc2^T in tile layout.
+// `ct0`: the first 32-column tile of the product; the 2 x 2 waves cover the tiles ct0 .. ct0 + 2 WN - 1 (0 and WN = 4 / 5:
+// every column).  A launch that wants a column range only (launch_blend_feat_gemm) runs the same prologue and, per column
+// tile, the same fragments in the same k and piece order as the full launch: those columns carry the same bits.
 constexpr int BLEND_FEAT_K = 200;   // feature columns (feat_rows.h); a tile of 64 frames touches at most 64 windows
 __host__ __device__ constexpr RowsLds blend_feat_lds() { return rows_lds(BLEND_FEAT_K, 64, false, 0, 64 * 10); }
 template <int WN, bool X3 = false>
-__global__ __launch_bounds__(fm::NT) void blend_feat_gemm_kernel(FusedMlpArgs args, FeatArgs fa) {
+__global__ __launch_bounds__(fm::NT) void blend_feat_gemm_kernel(FusedMlpArgs args, FeatArgs fa, int ct0) {
   if (X3) X3_EXCLUSIVE_SIMD();
   extern __shared__ __attribute__((aligned(16))) float act[];
   const FusedNet& net = args.net[0];
@@ -690,8 +693,8 @@ __global__ __launch_bounds__(fm::NT) void blend_feat_gemm_kernel(FusedMlpArgs ar
   }
   __syncthreads();
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  if (X3) x3_rows_layer<1, WN, 2, false>(net, L, M, m0, act, lda, wave >> 1, (wave & 1) * WN);
-  else fused_layer_t<1, WN, 2>(net, L, M, m0, act, lda, wave >> 1, (wave & 1) * WN, 0, true);
+  if (X3) x3_rows_layer<1, WN, 2, false>(net, L, M, m0, act, lda, wave >> 1, ct0 + (wave & 1) * WN);
+  else fused_layer_t<1, WN, 2>(net, L, M, m0, act, lda, wave >> 1, ct0 + (wave & 1) * WN, 0, true);
 }
 
 // The transposed blend-shape GEMM of the frame-per-lane path (d_feat = d_out . Wc2, both in tile layout) with the
@@ -793,31 +796,41 @@ static size_t x3_exclusive_lds(size_t lds) {
   return lds > half ? lds : half;
 }
 
-template <class Kern, class Extra>
-static hipError_t launch_rows_t_fused(Kern kern, size_t lds, const FusedMlpArgs& a, const Extra& x, hipStream_t stream) {
-  return launch_lds(kern, dim3((a.M + 63) / 64), dim3(fm::NT), lds, stream, a, x);
+template <class Kern, class... Extra>
+static hipError_t launch_rows_t_fused(Kern kern, size_t lds, const FusedMlpArgs& a, hipStream_t stream, const Extra&... x) {
+  return launch_lds(kern, dim3((a.M + 63) / 64), dim3(fm::NT), lds, stream, a, x...);
 }
 
 // `x3`: Wp holds three bf16 pieces per weight (api_model.hip pack_fragments_x3_raw) and the product runs on the bf16 matrix path
+// [col_lo, col_hi) (col_hi > col_lo): only the 32-column tiles that cover these columns of C_t are computed and written
+// -- at most four, on the narrow instantiation; the prologue (update, copies, feature rows) runs as ever.
 hipError_t launch_blend_feat_gemm(const FeatArgs& fa, const float* Wp, float* C_t, int ldc_t, int N, bool x3,
-                                  hipStream_t stream) {
+                                  hipStream_t stream, int col_lo, int col_hi) {
   if (N > 320 || ldc_t != ((N + 31) / 32) * 32) return hipErrorInvalidValue;
   const FusedMlpArgs a = rows_t_args(nullptr, 0, Wp, C_t, ldc_t, fa.T, N, BLEND_FEAT_K);
   const size_t lds = blend_feat_lds().bytes();   // the A block + the tile's window means
-  if (x3) {
-    if (N > 256) return launch_rows_t_fused(blend_feat_gemm_kernel<5, true>, x3_exclusive_lds(lds), a, fa, stream);
-    return launch_rows_t_fused(blend_feat_gemm_kernel<4, true>, x3_exclusive_lds(lds), a, fa, stream);
+  if (col_hi > col_lo) {
+    if (col_lo < 0 || col_hi > N) return hipErrorInvalidValue;
+    const int ct0 = col_lo / 32, ct1 = (col_hi + 31) / 32;
+    if (ct1 - ct0 <= 4) {   // (tiles past ct1 that the four waves reach are inside N or clamped and never stored)
+      if (x3) return launch_rows_t_fused(blend_feat_gemm_kernel<2, true>, x3_exclusive_lds(lds), a, stream, fa, ct0);
+      return launch_rows_t_fused(blend_feat_gemm_kernel<2>, lds, a, stream, fa, ct0);
+    }
   }
-  if (N > 256) return launch_rows_t_fused(blend_feat_gemm_kernel<5>, lds, a, fa, stream);
-  return launch_rows_t_fused(blend_feat_gemm_kernel<4>, lds, a, fa, stream);
+  if (x3) {
+    if (N > 256) return launch_rows_t_fused(blend_feat_gemm_kernel<5, true>, x3_exclusive_lds(lds), a, stream, fa, 0);
+    return launch_rows_t_fused(blend_feat_gemm_kernel<4, true>, x3_exclusive_lds(lds), a, stream, fa, 0);
+  }
+  if (N > 256) return launch_rows_t_fused(blend_feat_gemm_kernel<5>, lds, a, stream, fa, 0);
+  return launch_rows_t_fused(blend_feat_gemm_kernel<4>, lds, a, stream, fa, 0);
 }
 
 hipError_t launch_blend_t_gemm_rod(const float* A_t, int lda_t, const float* Wp, int K, const RodBwdTArgs& ra, bool x3,
                                    hipStream_t stream) {
   if (K % 4 != 0) return hipErrorInvalidValue;
   const FusedMlpArgs a = rows_t_args(A_t, lda_t, Wp, nullptr, 0, ra.T, BLEND_T_N, K);
-  if (x3) return launch_rows_t_fused(blend_t_gemm_rod_kernel<4, true>, x3_exclusive_lds(blend_t_rod_lds(K).bytes()), a, ra, stream);
-  return launch_rows_t_fused(blend_t_gemm_rod_kernel<4>, blend_t_rod_lds(K).bytes(), a, ra, stream);
+  if (x3) return launch_rows_t_fused(blend_t_gemm_rod_kernel<4, true>, x3_exclusive_lds(blend_t_rod_lds(K).bytes()), a, stream, ra);
+  return launch_rows_t_fused(blend_t_gemm_rod_kernel<4>, blend_t_rod_lds(K).bytes(), a, stream, ra);
 }
 
 bool heads_rows_applicable(int M, int K) { return M >= 4096 && K % 4 == 0 && K <= FUSED_MAX_WIDTH; }

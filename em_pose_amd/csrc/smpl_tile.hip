@@ -494,8 +494,12 @@ __device__ __forceinline__ void tile_sensor(const TileArgs& a, const TileTables&
 
 // NW waves per tile: the forward-only launch runs 8 (two per SIMD cover each other's latencies; 176 VGPRs), the launch
 // with the reverse pass 4 (its sensors need ~380 registers: with 8 waves they spill and the launch is slower).
-template <bool BWD, int NLOC, int NBL, int NW>
+// CHAIN_ONLY (forward only): a launch nobody asks sensor outputs of -- the last pass of an LGD forward without histories
+// wants the 22 joints and nothing else.  Rodrigues + chain and the joint stores, then the end: no transform goes to LDS
+// (nobody reads it), no barrier, no sensor loop, no LDS request.  Five waves, one per limb path.
+template <bool BWD, int NLOC, int NBL, int NW, bool CHAIN_ONLY = false>
 __global__ __launch_bounds__(64 * NW) void smpl_tile_kernel(TileArgs a) {
+  static_assert(!(BWD && CHAIN_ONLY), "the reverse pass needs the sensors");
   using namespace tl;
   constexpr int NT = 64 * NW;
   extern __shared__ __attribute__((aligned(16))) float lds[];
@@ -603,12 +607,14 @@ __global__ __launch_bounds__(64 * NW) void smpl_tile_kernel(TileArgs a) {
 #pragma unroll
       for (int c = 0; c < 3; ++c) Jp[c] = Jr[c];
       if (k >= own_from) {
-        float* g = sG + (size_t)j * GW * FR + lane;
+        if (!CHAIN_ONLY) {
+          float* g = sG + (size_t)j * GW * FR + lane;
 #pragma unroll
-        for (int e = 0; e < 12; ++e) g[e * FR] = G[e];
+          for (int e = 0; e < 12; ++e) g[e * FR] = G[e];
 #pragma unroll
-        for (int r = 0; r < 3; ++r)
-          g[(12 + r) * FR] = G[9 + r] - (G[r * 3 + 0] * Jr[0] + G[r * 3 + 1] * Jr[1] + G[r * 3 + 2] * Jr[2]);
+          for (int r = 0; r < 3; ++r)
+            g[(12 + r) * FR] = G[9 + r] - (G[r * 3 + 0] * Jr[0] + G[r * 3 + 1] * Jr[1] + G[r * 3 + 2] * Jr[2]);
+        }
         if (valid) {
           if (a.joints) { float* o = a.joints + (size_t)t * 66 + j * 3; o[0] = G[9]; o[1] = G[10]; o[2] = G[11]; }
           if (a.joints2) { float* o = a.joints2 + (size_t)t * 66 + j * 3; o[0] = G[9]; o[1] = G[10]; o[2] = G[11]; }
@@ -619,6 +625,7 @@ __global__ __launch_bounds__(64 * NW) void smpl_tile_kernel(TileArgs a) {
     }
   }
   TL_STAMP(1)
+  if (CHAIN_ONLY) return;
   __syncthreads();   // the chain's transforms are complete
   TL_STAMP(3)
   // ---- sensors: wave w takes sensors w, w + NW, ... (no barrier in between: the bone sums are ordered by the turn
@@ -778,7 +785,16 @@ static hipError_t launch_tile_cfg(const TileArgs& a, hipStream_t stream) {
 
 // `nloc`, `nbl`: the model's largest patch (TileTables::nloc / nbl, host copies).  Two unrolled sizes: the common
 // degree-6 patch over at most 6 bones, and the largest the tables admit.
-hipError_t launch_smpl_tile(const TileArgs& a, bool backward, int nloc, int nbl, hipStream_t stream) {
+hipError_t launch_smpl_tile(const TileArgs& a, bool backward, int nloc, int nbl, hipStream_t stream, bool chain_only) {
+  if (chain_only) {   // (the patch sizes the sensors are unrolled for do not matter: one instantiation)
+#ifndef TL_CHAIN_WAVES
+#define TL_CHAIN_WAVES 5
+#endif
+    if (backward || a.pos || a.ori || a.pos2 || a.ori2) return hipErrorInvalidValue;
+    hipLaunchKernelGGL((smpl_tile_kernel<false, 7, 6, TL_CHAIN_WAVES, true>), dim3((a.T + TL_FR - 1) / TL_FR),
+                       dim3(64 * TL_CHAIN_WAVES), 0, stream, a);
+    return hipGetLastError();
+  }
   const bool small = nloc <= 7 && nbl <= 6;
   if (backward) return small ? launch_tile_cfg<true, 7, 6>(a, stream) : launch_tile_cfg<true, TL_NLOC, TL_NBL>(a, stream);
   return small ? launch_tile_cfg<false, 7, 6>(a, stream) : launch_tile_cfg<false, TL_NLOC, TL_NBL>(a, stream);

@@ -77,7 +77,12 @@ const char* empose_arch(void);
  * 16 rows -- the reference's training batch, chunks of recordings -- as launches whose workgroups own two hidden units and
  * split K over all their threads; 0 = the whole-sequence kernel / the small-batch step kernel, which share their bits),
  * "mesh_skin_mfma" (split-bf16 full-mesh variant only: the bone blend as a second matrix-core contraction; 0 [default,
- * measured faster] = vector skinning), "spin_limit" (see empose_async_status).
+ * measured faster] = vector skinning), "spin_limit" (see empose_async_status), "last_pass_joints" (LGD forward on the
+ * frame-per-lane path: an SMPL evaluation that is asked for joints only -- the last pass when no marker histories are
+ * kept -- multiplies just the rest-joint column tiles of the blend matrix and runs the kinematic chain without the
+ * sensors, bit-identical; 0 = the whole sub-mesh as in every other pass), "lstm_state_direct" (LSTM steps of batches above
+ * 256 rows, new sequences [h0 = c0 = NULL]: the zero initial hidden-state planes by one fill and h_n / c_n stored by the
+ * last step of each layer, bit-identical; 0 = a split launch and a fill per layer and 2 x layers trailing copies).
  * empose_get_option returns -1 for an unknown name.  New in this library (no counterpart in the reference). */
 int empose_set_option(const char* name, int value);
 int empose_get_option(const char* name);
