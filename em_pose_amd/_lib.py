@@ -260,6 +260,10 @@ SIGNATURES = {
     'empose_resample_positions_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int]),
     'empose_resample_positions': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
                                             C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p]),
+    # (mode, N, F, M, K, window_len; the plan's start / sensor ids on the host and on the device; u_r, theta, phi; max_r,
+    # thigh_a, thigh_b, mask_value; pos, ori, normal and their outputs; stream)
+    'empose_sensor_noise': (C.c_int, [C.c_int] * 6 + [C.c_void_p] * 7 + [C.c_float, C.c_int, C.c_int, C.c_float] +
+                                     [C.c_void_p] * 7),
 }
 
 _lib = None

@@ -878,6 +878,21 @@ struct ResampleArgs {
 hipError_t launch_resample_rotations(const ResampleArgs& a, hipStream_t stream);
 hipError_t launch_resample_positions(const ResampleArgs& a, hipStream_t stream);
 
+// Sensor-noise augmentation (sensor_noise.hip): one launch writes the noisy copies of [N][F][M * 3] positions and, when
+// suppressing, [N][F][M * 9] orientations and [N][F][M * 3] normals, from a plan in device memory.
+constexpr int SENSOR_NOISE_SPHERICAL = 0;   // EMPOSE_SENSOR_NOISE_* (include/empose_hip.h)
+constexpr int SENSOR_NOISE_SUPPRESS = 1;
+struct SensorNoiseArgs {
+  const float* pos; const float* ori; const float* normal;   // ori, normal: suppression only
+  float* pos_out; float* ori_out; float* normal_out;
+  const int* start;                                // [N] first affected frame of a window
+  const int* sensor;                               // suppression: [N][K], spherical: [K]
+  const float* u_r; const float* theta; const float* phi;   // spherical: [N][window_len][K]
+  int N, F, M, K, window_len, mode, thigh_a, thigh_b;
+  float max_r, mask_value;
+};
+hipError_t launch_sensor_noise(const SensorNoiseArgs& a, hipStream_t stream);
+
 struct MetricsArgs {
   const float* joints_gt; const float* joints_hat;   // [T][22][3]
   const float* pose_gt; const float* pose_hat;       // [T][63] body axis-angles (no root) or nullptr

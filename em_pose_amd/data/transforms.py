@@ -9,8 +9,9 @@ The few transforms `evaluate_real` needs before the model sees a recording (refe
   SMPLFK, SampleMarkersWithOffsets, get_end_to_end_preprocess_fn   reference transforms.py:259-282,132-226,23-48 on the
                          HIP full-mesh kernel (pinned by tests/golden/preprocess.npz)
 
-The sensor-noise augmentation of the reference (noise_functions.py) is not part of this build; configurations that ask
-for it are refused.
+The sensor-noise augmentation of the reference (noise_functions.py: spherical noise, sensor suppression) is
+data/noise_functions.py on the sensor-noise kernel; `get_end_to_end_preprocess_fn` adds it with `device_noise=True` and
+refuses configurations that ask for it otherwise.
 """
 import numpy as np
 import torch
@@ -239,31 +240,41 @@ class SampleMarkersWithOffsets(object):
 
 
 def get_end_to_end_preprocess_fn(config, smpl_model, offset_files, randomize_if_configured=False,
-                                 device_normalize=False):
+                                 device_normalize=False, device_noise=False):
     """
-    The reference's preprocessing factory (transforms.py:23-48): NormalizeRoot -> SMPLFK -> SampleMarkersWithOffsets,
-    with the configured offset noise level when `randomize_if_configured`.  `offset_files`: the `*_offsets.npz` files
-    (the reference takes them from its data directory).  The reference's additional sensor-noise function
-    (`get_noise_fn`) is not part of this build.  `device_normalize`: NormalizeRoot(on_device=True).
+    The reference's preprocessing factory (transforms.py:23-48): NormalizeRoot -> SMPLFK -> SampleMarkersWithOffsets ->
+    sensor noise, with the configured offset noise level when `randomize_if_configured`.  `offset_files`: the
+    `*_offsets.npz` files (the reference takes them from its data directory).  `device_normalize`:
+    NormalizeRoot(on_device=True).  `device_noise`: the reference's sensor-noise function (`get_noise_fn`) on the
+    sensor-noise kernel (data/noise_functions.py; GPU batches only); it runs after the sensors are sampled and receives
+    the keyword arguments of the call, as in the reference.  Without the switch a configuration that asks for sensor noise
+    is refused.
     """
     if not getattr(config, 'use_real_offsets', True):
         raise ValueError('We expect to use the real offsets.')
-    if randomize_if_configured and (getattr(config, 'spherical_noise_length', 0.0) > 0.0 or
-                                    getattr(config, 'suppression_noise_length', 0.0) > 0.0):
+    noise_fn = None
+    if device_noise:
+        from em_pose_amd.data.noise_functions import get_noise_fn, no_noise
+        noise_fn = get_noise_fn(config, randomize_if_configured)
+        noise_fn = None if noise_fn is no_noise else noise_fn
+    elif randomize_if_configured and (getattr(config, 'spherical_noise_length', 0.0) > 0.0 or
+                                      getattr(config, 'suppression_noise_length', 0.0) > 0.0):
         # The reference would now add its sensor-noise augmentation (noise_functions.py:14-36: spherical marker noise or
-        # marker suppression).  It is not part of this build: refuse instead of silently training without it.
+        # marker suppression).  It runs on the GPU only and is opt-in: refuse instead of silently training without it.
         raise NotImplementedError('sensor-noise augmentation (spherical_noise_length / suppression_noise_length > 0) '
-                                  'is not implemented in this build')
+                                  'is not implemented in this build without device_noise=True (the sensor-noise kernel)')
     normalize_root, fk = NormalizeRoot(on_device=device_normalize), SMPLFK(smpl_model)
     noise_level = getattr(config, 'offset_noise_level', -1) if randomize_if_configured else -1
     sample_markers = SampleMarkersWithOffsets(smpl_model, list(offset_files), noise_level=noise_level)
 
-    def _preprocess_fn(sample, mode='all', **_):
+    def _preprocess_fn(sample, mode='all', **noise_kwargs):
+        noise = (lambda b: noise_fn(b, **noise_kwargs)) if noise_fn is not None else (lambda b: b)
         if mode == 'all':
-            return sample_markers(fk(normalize_root(sample)))
+            return noise(sample_markers(fk(normalize_root(sample))))
         if mode == 'normalize_only':
             return normalize_root(sample)
         if mode == 'after_normalize':
-            return sample_markers(fk(sample))
+            return noise(sample_markers(fk(sample)))
         raise ValueError("Mode '{}' unknown.".format(mode))
+    _preprocess_fn.noise_fn = noise_fn   # None: the plain pipeline
     return _preprocess_fn

@@ -4,6 +4,7 @@ Constants and run configuration for the LGD path.
 Mirrors the data (not the code) of the reference's `empose/helpers/configuration.py`:
   * VERTEX_IDS            reference configuration.py:32-34
   * S_CONFIG_6            reference configuration.py:89
+  * THIGH_*_IDX           reference configuration.py:43-55
   * N_JOINTS / N_JOINTS_HAND / N_SHAPE_PARAMS   reference configuration.py:104-107
   * SMPL_PARENTS          reference configuration.py:118
   * flag names/defaults   reference configuration.py:147-212
@@ -38,6 +39,10 @@ class _Constants(object):
         # The reduced 6-sensor configuration: back, head, both wrists, both lower legs.
         self.S_CONFIG_6 = [0, 1, 2, 6, 7, 11]
         self.N_TRACKERS_WO_ROOT = 12
+        # The two sensors between which the spherical sensor noise measures the thigh (reference configuration.py:43-55:
+        # T_TO_IDX_WO_ROOT[T_RUL], T_TO_IDX_WO_ROOT[T_RLL]): right upper leg, right lower leg.
+        self.THIGH_UPPER_IDX = 5
+        self.THIGH_LOWER_IDX = 6
 
         # SMPL-H constants.
         self.N_JOINTS = 21  # body joints, root not counted

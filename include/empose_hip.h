@@ -762,6 +762,36 @@ int empose_resample_positions(int S, const empose_resample_seq* seqs_host, const
                               const float* in, int ld_in, int in_rows, float* out, int ld_out, int out_rows,
                               void* workspace, size_t workspace_bytes, empose_stream_t stream);
 
+/* ---- sensor-noise augmentation (reference empose/data/noise_functions.py) -------------------------------------- */
+/* One launch writes the noisy copies of the synthetic sensor readings of N windows of F frames and M sensors: positions
+ * [N][F][M * 3], orientations [N][F][M * 9], normals [N][F][M * 3], float32, device.  The random draws are the caller's
+ * (the reference's seeded host generators); `window_len` consecutive frames of window i are affected, from frame
+ * start[i].  The plan's integers are passed twice: `start_host` / `sensor_host` are validated (no GPU work),
+ * `start_dev` / `sensor_dev` are the same values in device memory, which the kernel reads.
+ *
+ * EMPOSE_SENSOR_NOISE_SUPPRESS: sensors sensor[i][0..K) of window i (ids into the batch's own M sensors; [N][K]) read
+ *   `mask_value` in all 3 + 9 + 3 floats over the affected frames; every other float is a bit copy.  u_r, theta, phi,
+ *   max_r and the thigh indices are ignored.
+ * EMPOSE_SENSOR_NOISE_SPHERICAL: the K sensors sensor[0..K) ([K], shared by all windows) are displaced by
+ *   (r cos(theta) sin(phi), r sin(theta) cos(phi), r cos(phi)) -- the reference's formula as written -- with
+ *   r = u_r * max_r * thigh / 2 and thigh = |pos[0][F / 2][thigh_a] - pos[0][0][thigh_b]| read on the device; u_r, theta
+ *   and phi are [N][window_len][K] (may be NULL when window_len = 0).  Only positions are written: ori, normal, ori_out,
+ *   normal_out and mask_value are ignored.  Every product and sum is rounded on its own (no contraction).
+ *
+ * A sensor id named twice in a plan is harmless (spherical: its last entry counts), window_len = 0 copies, repeated calls
+ * give the same bits, and a window's result does not depend on the rest of the batch.  Returns EMPOSE_EINVAL, before any
+ * GPU work, for a NULL required pointer, N, F or M <= 0 (or N * F * M * 15 above 2^39: one launch), K < 1 or K > M,
+ * window_len < 0 or > F, an unknown mode, a thigh index outside [0, M) (spherical), an output pointer equal to its input,
+ * suppression without the orientation and normal buffers, a start outside [0, F - window_len] or a sensor id outside
+ * [0, M). */
+#define EMPOSE_SENSOR_NOISE_SPHERICAL 0
+#define EMPOSE_SENSOR_NOISE_SUPPRESS 1
+int empose_sensor_noise(int mode, int N, int F, int M, int K, int window_len, const int* start_host,
+                        const int* sensor_host, const int* start_dev, const int* sensor_dev, const float* u_r,
+                        const float* theta, const float* phi, float max_r, int thigh_a, int thigh_b, float mask_value,
+                        const float* pos, const float* ori, const float* normal, float* pos_out, float* ori_out,
+                        float* normal_out, empose_stream_t stream);
+
 /* ---- evaluation metrics ------------------------------------------------------------------------ */
 /* Per frame: 22 Euclidean joint distances, 22 distances after similarity-Procrustes alignment of the prediction onto
  * the ground truth, and 21 geodesic angles (degrees) between global joint orientations with the root fixed to the

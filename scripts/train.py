@@ -61,6 +61,27 @@ def average_gradients(buckets, params):
     return buckets.finish() if buckets is not None else allreduce_gradients(params)
 
 
+NOISE_FLAGS = ('noise_num_markers', 'spherical_noise_strength', 'spherical_noise_length', 'suppression_noise_length',
+               'suppression_noise_value')
+
+
+def noise_config(args):
+    """The five sensor-noise fields of the configuration (they land in the written config.json)."""
+    return {k: getattr(args, k) for k in NOISE_FLAGS}
+
+
+def with_sensor_noise(noise_fn, batch):
+    """A synthetic batch whose sensor readings are the noisy ones of this step (data/noise_functions.py: one launch, no
+    wait for the device); the batch itself keeps its clean readings for the next time it comes round."""
+    import copy
+    b = noise_fn(copy.copy(batch))
+    for x in ('pos', 'ori', 'normal'):
+        noisy = getattr(b, 'marker_%s_noisy' % x, None)
+        if noisy is not None:
+            setattr(b, 'marker_%s_synth' % x, noisy)
+    return b
+
+
 def train_on_amass(args, dev, rank, world):
     """Data-parallel training on AMASS npz sequences: random windows, offsets with the configured noise level, periodic
     validation on held-out sequences, best checkpoint + config.json in the reference's experiment layout (so that
@@ -79,7 +100,7 @@ def train_on_amass(args, dev, rank, world):
     smpl = SMPLLayer(args.smpl_model if args.smpl_model else synthetic.make_model()).to(dev)
     torch.manual_seed(args.seed)
     cfg = lgd_config(args.n_markers, not args.no_rnn, args.iterations, window_size=args.window_size, lr=args.lr,
-                     offset_noise_level=args.offset_noise_level)
+                     offset_noise_level=args.offset_noise_level, **noise_config(args))
     net = create_model(cfg, smpl).to(dev)
     params = [q for n, q in net.named_parameters() if not n.startswith('smpl.')]
     opt = torch.optim.Adam(params, lr=args.lr)
@@ -88,9 +109,9 @@ def train_on_amass(args, dev, rank, world):
         raise SystemExit('no *_offsets.npz files: pass --offset_files or set EM_DATA_REAL')
     buckets = make_buckets(net, params, world, args)
     fn_train = get_end_to_end_preprocess_fn(cfg, smpl, offsets, randomize_if_configured=True,
-                                            device_normalize=args.device_normalize)
+                                            device_normalize=args.device_normalize, device_noise=True)
     fn_valid = get_end_to_end_preprocess_fn(cfg, smpl, offsets, randomize_if_configured=False,
-                                            device_normalize=args.device_normalize)
+                                            device_normalize=args.device_normalize, device_noise=True)
 
     # The sequences: AMASS npz files under --amass_dir, or the records of an LMDB database in the reference's key schema
     # (--amass_lmdb, + optionally a separate --valid_lmdb as the reference trains on AMASS and validates on 3DPW).
@@ -259,6 +280,15 @@ def main():
     p.add_argument('--eval_every', type=int, default=200)
     p.add_argument('--valid_fraction', type=float, default=0.1)
     p.add_argument('--offset_noise_level', type=int, default=0)
+    # sensor-noise augmentation (reference configuration.py: the same five flags; data/noise_functions.py)
+    p.add_argument('--noise_num_markers', type=int, default=1, help='how many sensors the sensor noise affects')
+    p.add_argument('--spherical_noise_strength', type=float, default=0.0,
+                   help='diameter of the displacement sphere relative to the thigh, in [0, 1]')
+    p.add_argument('--spherical_noise_length', type=float, default=0.0,
+                   help='share of a window that spherical noise displaces, in [0, 1]; > 0 switches it on')
+    p.add_argument('--suppression_noise_length', type=float, default=0.0,
+                   help='share of a window over which sensors are suppressed, in [0, 1]; > 0 switches it on')
+    p.add_argument('--suppression_noise_value', type=float, default=0.0, help='what a suppressed sensor reads')
     p.add_argument('--data_workers', type=int, default=0)
     p.add_argument('--device_normalize', action='store_true', help='normalise the root orientations of a batch with the '
                    'root-frame kernel on the GPU instead of the float64 host round trip (NormalizeRoot(on_device=True))')
@@ -310,7 +340,10 @@ def main():
         return train_on_amass(args, dev, rank, world)
     model = synthetic.make_model()
     torch.manual_seed(args.seed)  # identical initial replicas on every rank
-    cfg = lgd_config(args.n_markers, not args.no_rnn, args.iterations, window_size=args.window_size, lr=args.lr)
+    cfg = lgd_config(args.n_markers, not args.no_rnn, args.iterations, window_size=args.window_size, lr=args.lr,
+                     **noise_config(args))
+    from em_pose_amd.data.noise_functions import get_noise_fn, no_noise
+    noise_fn = get_noise_fn(cfg, True)
     net = create_model(cfg, SMPLLayer(model)).to(dev)
     params = [q for n, q in net.named_parameters() if not n.startswith('smpl.')]
     from em_pose_amd.helpers.optim import HipAdam
@@ -336,6 +369,9 @@ def main():
                                                           b.offset_r_augmented, b.offset_t_augmented,
                                                           frames_per_window=F)
         b.joints_gt = joints.reshape(B, F, 66)
+        if noise_fn is not no_noise:   # (suppression also writes the normals: the z axes of the orientations)
+            M = b.marker_ori_synth.shape[-1] // 9
+            b.marker_normal_synth = b.marker_ori_synth.reshape(B, F, M, 3, 3)[..., 2].reshape(B, F, M * 3).contiguous()
         return b
     batches = [make_batch(s) for s in range(4)]  # data preparation is not part of the measured step
     net.train()
@@ -354,6 +390,8 @@ def main():
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         batch = batches[step % len(batches)]
+        if noise_fn is not no_noise:
+            batch = with_sensor_noise(noise_fn, batch)   # part of the step, as in training on real sequences
         if graphed is not None:
             vals = graphed(batch)            # forward + backward replayed; gradients in the static .grad tensors
             n_coll = average_gradients(buckets, params)
