@@ -21,6 +21,13 @@ int check_mlp_params(const empose_mlp_params* p) {
   }
   return EMPOSE_OK;
 }
+// HIP_CHECK with a message chosen at run time
+#define HIP_CHECK_AS(expr, what)                                                                 \
+  do {                                                                                           \
+    hipError_t e_ = (expr);                                                                      \
+    if (e_ != hipSuccess) return fail(EMPOSE_EHIP, "%s: %s", what, hipGetErrorString(e_));       \
+  } while (0)
+
 struct MlpTrainWs {
   float* d[2];       // [M][hidden] cotangent ping-pong
   float* wt;         // transposed weight [hidden][max(hidden, out_pad)]
@@ -52,278 +59,380 @@ MlpTrainWs carve_mlp_train(Carver& c, const empose_mlp_params* p, int M) {
   w.mbox = reinterpret_cast<unsigned long long*>(c.f(w.mbox_bytes / sizeof(float)));
   return w;
 }
-// The BatchNorm / PReLU passes folded into the GEMMs (train_fused.hip).  Opt-in: gradient parity with the reference is
-// tested, but at 256 windows the step is no faster (the operand transform and the statistics epilogue cost the GEMMs
-// about what the removed passes cost: 701-711 k against 705-720 k frames/s).  Option "train_fused": 0 never (default),
-// 1 from BN_SINGLE_PASS_ROWS rows on, 2 always (tests).
-// (empose_mlp_params::save_layout != 0: the layout chosen when the step's forward ran wins over the options of the moment)
-bool mlp_train_fused(const empose_mlp_params* p, int M) {
-  if (p->save_layout) return p->save_layout == 2;
-  const int opt = options().train_fused;
-  return opt != 0 && (opt == 2 || M > BN_SINGLE_PASS_ROWS) && p->hidden % 4 == 0 && p->in_dim % 4 == 0;
-}
-// Round 4, the default above BN_SINGLE_PASS_ROWS rows: the statistics still come out of the GEMM epilogues, but the
-// activations / cotangents are materialised by ONE combine-and-apply launch per layer and direction (train_fused.hip,
-// bn_finish_*): GEMM + 1 launch instead of GEMM + 3, and every consumer reads a ready operand.  Option "train_epi":
-// 0 never, 1 above BN_SINGLE_PASS_ROWS rows (default), 2 always (tests).  "train_fused" takes precedence when both apply.
-bool mlp_train_epi(const empose_mlp_params* p, int M) {
-  if (p->save_layout) return p->save_layout == 3;
-  const int opt = options().train_epi;
-  return !mlp_train_fused(p, M) && opt != 0 && (opt == 2 || M > BN_SINGLE_PASS_ROWS) && p->hidden % 4 == 0 &&
-         p->in_dim % 4 == 0;
-}
-// per hidden layer: passes  z [M][H] | a [M][H] | mean [H] | rstd [H];  fused  y [M][H] | mean | rstd | s | t;
-//                   epi     y [M][H] | a [M][H] | mean | rstd | s | t
-size_t mlp_layer_save(const empose_mlp_params* p, int M) {
-  if (mlp_train_fused(p, M)) return (size_t)M * p->hidden + 4 * (size_t)p->hidden;
-  if (mlp_train_epi(p, M)) return (size_t)2 * M * p->hidden + 4 * (size_t)p->hidden;
-  return (size_t)2 * M * p->hidden + 2 * (size_t)p->hidden;
-}
-// At the reference's training batch a layer is one launch: product, BatchNorm and PReLU of both update networks in
-// train_cols.hip (option "train_cols": 0 never, 1 up to COLS_MAX_ROWS rows).  Reads and writes save layout 1 (passes).
-bool mlp_train_cols(const empose_mlp_params* p, int M) {
-  if (options().train_cols == 0 || M > COLS_MAX_ROWS) return false;
-  if (mlp_train_fused(p, M) || mlp_train_epi(p, M)) return false;
-  return cols_launchable(p->hidden > p->out_dim ? p->hidden : p->out_dim, 2);
-}
-bool mlp_cols_pairable(const empose_mlp_params* a, const empose_mlp_params* b, int M) {
-  return a->n_layers == b->n_layers && a->hidden == b->hidden && a->bn_eps == b->bn_eps &&
-         a->bn_momentum == b->bn_momentum && mlp_train_cols(a, M) && mlp_train_cols(b, M) &&
-         b->out_dim <= (a->hidden > a->out_dim ? a->hidden : a->out_dim);
+
+// Layer l as the product out [M][N] = in [M][K] . W [N][K]^T: `lda` the leading dimension of its input (the network
+// input's for layer 0), `out_pad` that of its output cotangent in the stash (the last layer's padded to a multiple of 4).
+struct LayerDims { bool last; int N, K, lda, ldw, out_pad; };
+LayerDims layer_dims(const empose_mlp_params* p, int l, int ldx) {
+  LayerDims d;
+  d.last = l == p->n_layers - 1;
+  d.N = d.last ? p->out_dim : p->hidden;
+  d.K = l == 0 ? p->in_dim : p->hidden;
+  d.lda = l == 0 ? ldx : p->hidden;
+  d.ldw = d.K;
+  d.out_pad = d.last ? (p->out_dim + 3) & ~3 : p->hidden;
+  return d;
 }
 
-int mlp_fwd_cols(const empose_mlp_params* const* ps, int n, int M, const float* x, int ldx, float* const* outs,
-                 const int* ld_outs, float* const* saves, const MlpTrainWs& w, hipStream_t stream) {
-  const int L = ps[0]->n_layers;
+// How one MLP trains on M rows, decided once per entry point: which family of launches runs and, the one place that
+// knows it, where everything sits in the save buffer and the stash.  One record per hidden layer:
+//   layout 1, passes  z [M][H] | a [M][H] | mean [H] | rstd [H]        GEMM + BatchNorm / PReLU launches (round 2), and
+//                                                                      the one-launch layers of train_cols.hip (round 5)
+//   layout 2, fused   y [M][H] | mean | rstd | s | t                   the passes folded into the GEMMs (train_fused.hip):
+//                     the activations are not stored, consumers re-form a = PReLU(s y + t) while they stage the operand
+//   layout 3, epi     y [M][H] | a [M][H] | mean | rstd | s | t        statistics from the GEMM epilogues, ONE
+//                     combine-and-apply launch per layer and direction (bn_finish_*): GEMM + 1 launch instead of GEMM + 3
+// Options: "train_fused" 0 never (default; gradient parity is tested, but at 256 windows the step is no faster: 701-711 k
+// against 705-720 k frames/s), "train_epi" 1 (default); both: 1 above BN_SINGLE_PASS_ROWS rows, 2 always (tests);
+// "train_fused" takes precedence.  empose_mlp_params::save_layout != 0: the layout chosen when the step's forward ran wins
+// over the options of the moment.
+// Stash of one application: dZ of the hidden layers [M][H] each, then a copy of d_out [M][out_pad].
+struct MlpPlan {
+  const empose_mlp_params* p;
+  int M, H, L, op;
+  int layout;
+  // At the reference's training batch a layer is one launch: product, BatchNorm and PReLU of both update networks in
+  // train_cols.hip (option "train_cols": 0 never, 1 up to COLS_MAX_ROWS rows).  Reads and writes layout 1; not pinned by
+  // save_layout.  (Asks the device: only the entry points that launch, and empose_mlp_train_uses_weight_t, read it.)
+  bool cols() const {
+    if (options().train_cols == 0 || M > COLS_MAX_ROWS || layout != 1) return false;
+    return cols_launchable(H > p->out_dim ? H : p->out_dim, 2);
+  }
+  size_t planes() const { return layout == 2 ? 1 : 2; }
+  size_t layer_floats() const { return planes() * M * H + (size_t)(layout == 1 ? 2 : 4) * H; }
+  size_t save_floats() const { return (size_t)(L - 1) * layer_floats(); }
+  template <typename F> F* pre(F* save, int l) const { return save + (size_t)l * layer_floats(); }   // z / y
+  template <typename F> F* act(F* save, int l) const { return pre(save, l) + (size_t)M * H; }        // (not in layout 2)
+  template <typename F> F* mean(F* save, int l) const { return pre(save, l) + planes() * M * H; }
+  template <typename F> F* rstd(F* save, int l) const { return mean(save, l) + H; }
+  template <typename F> F* s(F* save, int l) const { return mean(save, l) + 2 * H; }                 // (layouts 2, 3)
+  template <typename F> F* t(F* save, int l) const { return mean(save, l) + 3 * H; }
+  size_t stash_floats() const { return (size_t)M * ((size_t)(L - 1) * H + op); }
+  template <typename F> F* stash_slot(F* stash, int l) const { return stash + (size_t)M * l * H; }   // l = L - 1: d_out
+};
+MlpPlan mlp_plan(const empose_mlp_params* p, int M) {
+  MlpPlan pl;
+  pl.p = p; pl.M = M; pl.H = p->hidden; pl.L = p->n_layers; pl.op = (p->out_dim + 3) & ~3;
+  auto on = [&](int opt) {
+    return opt != 0 && (opt == 2 || M > BN_SINGLE_PASS_ROWS) && p->hidden % 4 == 0 && p->in_dim % 4 == 0;
+  };
+  if (p->save_layout) pl.layout = p->save_layout == 2 ? 2 : (p->save_layout == 3 ? 3 : 1);
+  else pl.layout = on(options().train_fused) ? 2 : (on(options().train_epi) ? 3 : 1);
+  return pl;
+}
+bool mlp_cols_pairable(const MlpPlan& a, const MlpPlan& b) {
+  return a.L == b.L && a.H == b.H && a.p->bn_eps == b.p->bn_eps && a.p->bn_momentum == b.p->bn_momentum && a.cols() &&
+         b.cols() && b.p->out_dim <= (a.H > a.p->out_dim ? a.H : a.p->out_dim);
+}
+
+// ---- what the sweeps share ----------------------------------------------------------------------------------------
+hipError_t gemm_one(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
+                    const float* scale, const float* shift, const float* resid, int ldr, int act, float slope,
+                    hipStream_t stream) {
+  GemmBatch b;
+  b.count = 1;
+  GemmProb& g = b.p[0];
+  g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
+  g.scale = scale; g.shift = shift; g.resid = resid; g.ldr = ldr; g.act = act; g.slope = slope;
+  return launch_gemm(b, stream);
+}
+// Weight gradients deferred: keep d_out for empose_mlp_train_wgrad (no copy when the caller produced it in its stash slot
+// already, include/empose_hip.h)
+int stash_d_out(const MlpPlan& pl, const float* d_out, int ld_dout, float* stash, hipStream_t stream) {
+  float* slot = pl.stash_slot(stash, pl.L - 1);
+  if (d_out != slot || ld_dout != pl.op) {
+    HIP_CHECK(launch_axpby2d(pl.M, pl.op, 1.f, d_out, ld_dout, 0.f, nullptr, 0, slot, pl.op, stream), "stash");
+  }
+  return EMPOSE_OK;
+}
+// W_l^T [H][out_pad] for dA_{l-1} = dY_l W_l on the K-contiguous GEMM: the caller's copy (made once per step), else
+// transposed into the workspace (the last layer's padding columns zero)
+int weight_t_of(const MlpPlan& pl, int l, const MlpTrainWs& w, hipStream_t stream, const float** wt) {
+  const empose_mlp_params* p = pl.p;
+  *wt = p->weight_t[l];
+  if (*wt) return EMPOSE_OK;
+  const LayerDims d = layer_dims(p, l, 0);
+  const int H = pl.H, op = pl.op;
+  if (d.last) HIP_TRY(hipMemsetAsync(w.wt, 0, (size_t)H * op * sizeof(float), stream));
+  HIP_CHECK(launch_transpose(p->weight[l], H, w.wt, d.out_pad, d.N, H, stream), "transpose");
+  *wt = w.wt;
+  return EMPOSE_OK;
+}
+// dW_l, db_l over n applications of the network: dy[s]^T in[s], with dy[s] the cotangent of layer l's product (leading
+// dimension ld_dy) and in[s] the layer's input, x[s] or a_{l-1} in save[s].  Layout 2 stores y_{l-1} only: the product
+// re-forms a_{l-1} from it and its (s, t) while it stages its B operand.  `segmented`: one product over the n row
+// segments (M % 32 == 0, aligned operands); else one per application, added up.
+int layer_wgrad(const MlpPlan& pl, int l, int n, bool segmented, const float* const* dy, int ld_dy, const float* const* x,
+                int ldx, const float* const* save, const empose_mlp_grads* gr, int accumulate, float* ws, size_t ws_floats,
+                const char* what, hipStream_t stream) {
+  const LayerDims d = layer_dims(pl.p, l, ldx);
+  const bool reform = pl.layout == 2 && l > 0;
+  AtbArgs ab{};
+  ab.lda = ld_dy; ab.ldb = d.lda; ab.C = gr->weight[l]; ab.ldc = d.K; ab.bias = gr->bias[l]; ab.N = d.N; ab.K = d.K;
+  if (reform) { ab.b_mode = 1; ab.b_slope = pl.p->prelu[l - 1]; }
+  auto fill = [&](int slot, int s) {
+    ab.A_seg[slot] = dy[s];
+    ab.B_seg[slot] = l == 0 ? x[s] : (reform ? pl.pre(save[s], l - 1) : pl.act(save[s], l - 1));
+    ab.Bs_seg[slot] = reform ? pl.s(save[s], l - 1) : nullptr;
+  };
+  if (segmented) {
+    for (int s = 0; s < n; ++s) fill(s, s);
+    ab.n_seg = n; ab.seg_rows = pl.M;
+  }
+  for (int s = 0; s < (segmented ? 1 : n); ++s) {
+    if (!segmented) fill(0, s);
+    ab.A = ab.A_seg[0]; ab.B = ab.B_seg[0]; ab.M = segmented ? n * pl.M : pl.M; ab.accumulate = s > 0 ? 1 : accumulate;
+    HIP_CHECK_AS(launch_gemm_atb(ab, ws, ws_floats, stream), what);
+  }
+  return EMPOSE_OK;
+}
+
+// ---- the forward sweeps ---------------------------------------------------------------------------------------------
+// GEMM, then BatchNorm + PReLU as launches of their own (layout 1)
+int fwd_passes(const MlpPlan& pl, const float* x, int ldx, float* out, int ld_out, float* save, const MlpTrainWs& w,
+               hipStream_t stream) {
+  const empose_mlp_params* p = pl.p;
+  const int M = pl.M, H = pl.H;
+  for (int l = 0; l < pl.L; ++l) {
+    const LayerDims d = layer_dims(p, l, ldx);
+    float* z = d.last ? out : pl.pre(save, l);
+    HIP_CHECK(gemm_one(l == 0 ? x : pl.act(save, l - 1), d.lda, p->weight[l], d.ldw, z, d.last ? ld_out : H, M, d.N, d.K,
+                       nullptr, p->bias[l], nullptr, 0, 0, 0.f, stream), "mlp forward gemm");
+    if (d.last) break;
+    BnPreluArgs a{};
+    a.M = M; a.C = H; a.x = z; a.ldx = H; a.gamma = p->bn_weight[l]; a.beta = p->bn_bias[l]; a.slope = p->prelu[l];
+    a.eps = p->bn_eps; a.momentum = p->bn_momentum; a.running_mean = p->bn_running_mean[l];
+    a.running_var = p->bn_running_var[l]; a.num_batches_tracked = p->bn_num_batches[l];
+    a.z = pl.act(save, l); a.ldz = H; a.save_mean = pl.mean(save, l); a.save_rstd = pl.rstd(save, l);
+    a.workspace = w.bn;
+    HIP_CHECK(launch_bn_prelu(a, false, stream), "bn_prelu forward");
+  }
+  return EMPOSE_OK;
+}
+// y_l = a_{l-1} W_l^T + b_l, the epilogue leaving the column statistics of y_l per row block (layouts 2 and 3).
+// fused: a_{l-1} = PReLU(s y_{l-1} + t) is formed while the GEMM stages its A operand, and a small kernel turns the
+// statistics into (mean, rstd, s, t);  epi: the GEMM reads the materialised a_{l-1}, and ONE launch turns the statistics
+// into (mean, rstd, s, t), updates the running statistics and writes a_l = PReLU(s y_l + t).
+int fwd_stats(const MlpPlan& pl, const float* x, int ldx, float* out, int ld_out, float* save, const MlpTrainWs& w,
+              hipStream_t stream) {
+  const empose_mlp_params* p = pl.p;
+  const int M = pl.M, H = pl.H;
+  const bool epi = pl.layout == 3;
+  for (int l = 0; l < pl.L; ++l) {
+    const LayerDims d = layer_dims(p, l, ldx);
+    const bool transform = !epi && l > 0;
+    TrainGemmArgs g{};
+    g.A = l == 0 ? x : (epi ? pl.act(save, l - 1) : pl.pre(save, l - 1)); g.lda = d.lda; g.W = p->weight[l]; g.ldw = d.ldw;
+    g.C = d.last ? out : pl.pre(save, l); g.ldc = d.last ? ld_out : H;
+    g.M = M; g.N = d.N; g.K = d.K; g.bias = p->bias[l];
+    if (transform) { g.a_s = pl.s(save, l - 1); g.a_t = pl.t(save, l - 1); g.a_slope = p->prelu[l - 1]; }
+    g.part = w.part;
+    const bool x3 = epi && !d.last && options().train_x3 != 0 && p->weight_x3[l] && gemm_train_x3_applicable(g.M, g.N, g.K);
+    HIP_CHECK_AS(x3 ? launch_gemm_train_x3(g, p->weight_x3[l], 1, stream)
+                    : launch_gemm_train(g, transform ? 1 : 0, d.last ? 0 : 1, stream),
+                 epi ? "mlp forward gemm (statistics epilogue)" : "fused mlp forward gemm");
+    if (d.last) break;
+    auto statistics = [&](auto& c) {
+      c.M = M; c.C = H; c.part = w.part; c.gamma = p->bn_weight[l]; c.beta = p->bn_bias[l];
+      c.eps = p->bn_eps; c.momentum = p->bn_momentum; c.running_mean = p->bn_running_mean[l];
+      c.running_var = p->bn_running_var[l]; c.num_batches_tracked = p->bn_num_batches[l];
+      c.mean = pl.mean(save, l); c.rstd = pl.rstd(save, l); c.s = pl.s(save, l); c.t = pl.t(save, l);
+    };
+    if (epi) {
+      BnFinishFwdArgs c{};
+      statistics(c);
+      c.y = pl.pre(save, l); c.ldy = H; c.act = pl.act(save, l); c.ld_act = H; c.slope = p->prelu[l];
+      HIP_CHECK(launch_bn_finish_fwd(c, stream), "bn finish forward");
+    } else {
+      BnFusedFwdArgs c{};
+      statistics(c);
+      HIP_CHECK(launch_bn_fused_combine_fwd(c, stream), "fused bn combine");
+    }
+  }
+  return EMPOSE_OK;
+}
+// One launch per layer for one network or a pair (train_cols.hip)
+int mlp_fwd_cols(const MlpPlan* pls, int n, const float* x, int ldx, float* const* outs, const int* ld_outs,
+                 float* const* saves, const MlpTrainWs& w, hipStream_t stream) {
+  const int L = pls[0].L, M = pls[0].M;
   HIP_TRY(hipMemsetAsync(w.mbox, 0, w.mbox_bytes, stream));
   for (int l = 0; l < L; ++l) {
     const bool last = l == L - 1;
     ColsArgs a{};
-    a.n_nets = n; a.M = M; a.eps = ps[0]->bn_eps; a.momentum = ps[0]->bn_momentum; a.tag = (unsigned)l + 1;
+    a.n_nets = n; a.M = M; a.eps = pls[0].p->bn_eps; a.momentum = pls[0].p->bn_momentum; a.tag = (unsigned)l + 1;
     a.mailbox = w.mbox;
     for (int i = 0; i < n; ++i) {
-      const empose_mlp_params* p = ps[i];
-      const int H = p->hidden;
-      const size_t lsz = (size_t)2 * M * H + 2 * (size_t)H;
-      float* sv = saves[i] + (size_t)l * lsz;                                   // z | a | mean | rstd
+      const MlpPlan& pl = pls[i];
+      const empose_mlp_params* p = pl.p;
+      const LayerDims d = layer_dims(p, l, ldx);
       ColsNet& c = a.net[i];
-      c.A = l == 0 ? x : saves[i] + (size_t)(l - 1) * lsz + (size_t)M * H; c.lda = l == 0 ? ldx : H;
-      c.W = p->weight[l]; c.ldw = l == 0 ? p->in_dim : H; c.bias = p->bias[l];
-      c.N = last ? p->out_dim : H; c.K = l == 0 ? p->in_dim : H;
+      c.A = l == 0 ? x : pl.act(saves[i], l - 1); c.lda = d.lda;
+      c.W = p->weight[l]; c.ldw = d.ldw; c.bias = p->bias[l];
+      c.N = d.N; c.K = d.K;
       if (last) { c.out = outs[i]; c.ld_out = ld_outs[i]; continue; }
       c.gamma = p->bn_weight[l]; c.beta = p->bn_bias[l]; c.slope = p->prelu[l];
       c.running_mean = p->bn_running_mean[l]; c.running_var = p->bn_running_var[l]; c.num_batches = p->bn_num_batches[l];
-      c.z = sv; c.ldz = H; c.out = sv + (size_t)M * H; c.ld_out = H;
-      c.mean = sv + (size_t)2 * M * H; c.rstd = c.mean + H;
+      c.z = pl.pre(saves[i], l); c.ldz = pl.H; c.out = pl.act(saves[i], l); c.ld_out = pl.H;
+      c.mean = pl.mean(saves[i], l); c.rstd = pl.rstd(saves[i], l);
     }
     HIP_CHECK(launch_cols(a, last ? 1 : 0, stream), "one-launch layer forward");
   }
   return EMPOSE_OK;
 }
 
-// stash of one application: dZ of the hidden layers [M][hidden] each, then a copy of d_out [M][out_pad]
-size_t mlp_stash_floats(const empose_mlp_params* p, int M) {
-  return (size_t)M * ((size_t)(p->n_layers - 1) * p->hidden + ((p->out_dim + 3) & ~3));
+// ---- the reverse sweeps ---------------------------------------------------------------------------------------------
+// With a stash the weight gradients are deferred (empose_mlp_train_wgrad) and dZ_l of every layer stays in it; without,
+// they are formed here, layer by layer, and the dZ_l ping-pong in the workspace.
+struct MlpBwdIo {
+  const float* x; int ldx;
+  const float* d_out; int ld_dout;
+  const float* save;
+  const empose_mlp_grads* gr; int accumulate;
+  float* stash;   // or nullptr
+};
+int sweep_wgrad(const MlpPlan& pl, const MlpBwdIo& io, int l, const float* dy, int ld_dy, const MlpTrainWs& w,
+                const char* what, hipStream_t stream) {
+  return layer_wgrad(pl, l, 1, false, &dy, ld_dy, &io.x, io.ldx, &io.save, io.gr, io.accumulate, w.atb, w.atb_floats, what,
+                     stream);
 }
-// The reverse sweep of one or two MLPs on the one-launch layers: layer l's launch forms dA_{l-1} = dZ_l W_l and, in its
-// epilogue, the BatchNorm / PReLU reverse of layer l - 1 (whose column sums the row parts exchange) -> dZ_{l-1}.  With
-// stashes the weight gradients are deferred (empose_mlp_train_wgrad); without (one network only) they are formed here.
-int mlp_bwd_cols(const empose_mlp_params* const* ps, int n, int M, const float* x, int ldx, const float* const* d_outs,
-                 const int* ld_douts, const float* const* saves, const empose_mlp_grads* const* grs, int accumulate,
-                 float* const* stashes, const MlpTrainWs& w, hipStream_t stream) {
-  const int L = ps[0]->n_layers;
-  const bool deferred = stashes && stashes[0];
-  if (!deferred && n != 1) return fail(EMPOSE_EINVAL, "a pair of networks runs its reverse sweep with deferred weight gradients");
-  HIP_TRY(hipMemsetAsync(w.mbox, 0, w.mbox_bytes, stream));
-  auto layer_save = [&](int i, int l) { return saves[i] + (size_t)l * ((size_t)2 * M * ps[i]->hidden + 2 * (size_t)ps[i]->hidden); };
-  auto dz_of = [&](int i, int l) -> float* { return deferred ? stashes[i] + (size_t)M * l * ps[i]->hidden : w.d[l & 1]; };
-  auto atb = [&](int l) -> int {   // dW_l, db_l of the single network (not deferred)
-    const empose_mlp_params* p = ps[0];
-    const int H = p->hidden;
-    const bool last = l == L - 1;
-    AtbArgs ab{};
-    ab.A = last ? d_outs[0] : dz_of(0, l); ab.lda = last ? ld_douts[0] : H;
-    ab.B = l == 0 ? x : layer_save(0, l - 1) + (size_t)M * H; ab.ldb = l == 0 ? ldx : H;
-    ab.C = grs[0]->weight[l]; ab.ldc = l == 0 ? p->in_dim : H; ab.bias = grs[0]->bias[l];
-    ab.M = M; ab.N = last ? p->out_dim : H; ab.K = l == 0 ? p->in_dim : H; ab.accumulate = accumulate;
-    HIP_CHECK(launch_gemm_atb(ab, w.atb, w.atb_floats, stream), "dW");
-    return EMPOSE_OK;
-  };
-  for (int i = 0; i < n && deferred; ++i) {   // keep d_out for empose_mlp_train_wgrad (no copy when it was produced in its slot)
-    const int op = (ps[i]->out_dim + 3) & ~3;
-    float* slot = stashes[i] + (size_t)M * (L - 1) * ps[i]->hidden;
-    if (d_outs[i] != slot || ld_douts[i] != op) {
-      HIP_CHECK(launch_axpby2d(M, op, 1.f, d_outs[i], ld_douts[i], 0.f, nullptr, 0, slot, op, stream), "stash");
+// dA_{l-1} = dY_l W_l as a plain GEMM, then the BatchNorm / PReLU reverse of layer l - 1 as a launch of its own (layout 1)
+int bwd_passes(const MlpPlan& pl, const MlpBwdIo& io, const MlpTrainWs& w, hipStream_t stream) {
+  const empose_mlp_params* p = pl.p;
+  const int M = pl.M, H = pl.H;
+  if (io.stash) TRY(stash_d_out(pl, io.d_out, io.ld_dout, io.stash, stream));
+  // w.d[0]: cotangent of the current layer's activation (the one of the layer below overwrites the consumed one);
+  // w.d[1]: dZ_l when it is not stashed
+  const float* dy = io.d_out;
+  int ld_dy = io.ld_dout;
+  for (int l = pl.L - 1; l >= 0; --l) {
+    const LayerDims d = layer_dims(p, l, io.ldx);
+    if (!d.last) {
+      BnPreluArgs a{};
+      a.M = M; a.C = H; a.x = pl.pre(io.save, l); a.ldx = H; a.gamma = p->bn_weight[l]; a.beta = p->bn_bias[l];
+      a.slope = p->prelu[l];
+      a.save_mean = const_cast<float*>(pl.mean(io.save, l)); a.save_rstd = const_cast<float*>(pl.rstd(io.save, l));
+      float* dz = io.stash ? pl.stash_slot(io.stash, l) : w.d[1];
+      a.dz = w.d[0]; a.lddz = H; a.dx = dz; a.lddx = H;
+      a.dgamma = io.gr->bn_weight[l]; a.dbeta = io.gr->bn_bias[l]; a.dslope = io.gr->prelu[l];
+      a.dslope_partial = w.slope_partial; a.counter = w.counter; a.workspace = w.bn; a.accumulate = io.accumulate;
+      HIP_CHECK(launch_bn_prelu(a, true, stream), "bn_prelu backward");
+      dy = dz; ld_dy = H;
+    }
+    if (!io.stash) TRY(sweep_wgrad(pl, io, l, dy, ld_dy, w, "dW", stream));
+    if (l == 0) break;
+    const float* wt = nullptr;
+    TRY(weight_t_of(pl, l, w, stream, &wt));
+    HIP_CHECK(gemm_one(dy, ld_dy, wt, d.out_pad, w.d[0], H, M, H, d.out_pad, nullptr, nullptr, nullptr, 0, 0, 0.f, stream),
+              "dX gemm");
+  }
+  return EMPOSE_OK;
+}
+// Layouts 2 and 3: dA_{l-1} = dY_l W_l on the forward tile against W_l^T, its epilogue already in terms of layer l - 1: it
+// writes dyh = dA * PReLU'(yhat) and the column sums BatchNorm's reverse needs.  fused: a small kernel turns the sums into
+// dgamma / dbeta / dslope and three per-column coefficients, one pass forms dY = c1 dyh + c3 y + c0 in place;  epi: both
+// in ONE launch (bn_finish_bwd).
+int bwd_stats(const MlpPlan& pl, const MlpBwdIo& io, const MlpTrainWs& w, hipStream_t stream) {
+  const empose_mlp_params* p = pl.p;
+  const int M = pl.M, H = pl.H;
+  const bool epi = pl.layout == 3;
+  auto dz_of = [&](int l) -> float* { return io.stash ? pl.stash_slot(io.stash, l) : w.d[l & 1]; };
+  if (io.stash) TRY(stash_d_out(pl, io.d_out, io.ld_dout, io.stash, stream));
+  for (int l = pl.L - 1; l >= 0; --l) {
+    const LayerDims d = layer_dims(p, l, io.ldx);
+    const float* dy = d.last ? io.d_out : dz_of(l);
+    const int ld_dy = d.last ? io.ld_dout : H;
+    if (!io.stash) TRY(sweep_wgrad(pl, io, l, dy, ld_dy, w, "fused dW", stream));
+    if (l == 0) break;
+    const float* wt = nullptr;
+    TRY(weight_t_of(pl, l, w, stream, &wt));
+    TrainGemmArgs g{};
+    g.A = dy; g.lda = ld_dy; g.W = wt; g.ldw = d.out_pad;
+    g.C = dz_of(l - 1); g.ldc = H; g.M = M; g.N = H; g.K = d.out_pad; g.bias = nullptr;
+    g.part = w.part; g.e_y = pl.pre(io.save, l - 1); g.ld_ey = H;
+    g.e_mean = pl.mean(io.save, l - 1); g.e_rstd = pl.rstd(io.save, l - 1); g.e_s = pl.s(io.save, l - 1);
+    g.e_t = pl.t(io.save, l - 1); g.e_slope = p->prelu[l - 1];
+    const bool x3 = options().train_x3 != 0 && p->weight_t[l] && p->weight_t_x3[l] && gemm_train_x3_applicable(g.M, g.N, g.K);
+    HIP_CHECK(x3 ? launch_gemm_train_x3(g, p->weight_t_x3[l], 2, stream) : launch_gemm_train(g, 0, 2, stream), "fused dX gemm");
+    auto sums = [&](auto& c) {
+      c.M = M; c.C = H; c.part = w.part; c.gamma = p->bn_weight[l - 1];
+      c.mean = pl.mean(io.save, l - 1); c.rstd = pl.rstd(io.save, l - 1);
+      c.dgamma = io.gr->bn_weight[l - 1]; c.dbeta = io.gr->bn_bias[l - 1]; c.dslope = io.gr->prelu[l - 1];
+      c.dslope_partial = w.slope_partial; c.accumulate = io.accumulate;
+    };
+    if (epi) {
+      BnFinishBwdArgs f{};
+      sums(f);
+      f.counter = w.counter; f.dyh = dz_of(l - 1); f.ld = H; f.y = pl.pre(io.save, l - 1); f.ldy = H;
+      HIP_CHECK(launch_bn_finish_bwd(f, stream), "bn finish backward");
+    } else {
+      BnFusedBwdArgs c{};
+      sums(c);
+      c.coef = w.coef;
+      HIP_CHECK(launch_bn_fused_combine_bwd(c, stream), "fused bn reverse combine");
+      HIP_CHECK(launch_bn_fused_apply_bwd(dz_of(l - 1), pl.pre(io.save, l - 1), w.coef, M, H, stream), "fused bn reverse apply");
     }
   }
-  for (int l = L - 1; l >= 1; --l) {
+  return EMPOSE_OK;
+}
+// One or two MLPs on the one-launch layers: layer l's launch forms dA_{l-1} = dZ_l W_l and, in its epilogue, the
+// BatchNorm / PReLU reverse of layer l - 1 (whose column sums the row parts exchange) -> dZ_{l-1}.  A pair runs deferred.
+int mlp_bwd_cols(const MlpPlan* pls, int n, const MlpBwdIo* ios, const MlpTrainWs& w, hipStream_t stream) {
+  const int L = pls[0].L, M = pls[0].M;
+  const bool deferred = ios[0].stash != nullptr;
+  if (!deferred && n != 1) return fail(EMPOSE_EINVAL, "a pair of networks runs its reverse sweep with deferred weight gradients");
+  HIP_TRY(hipMemsetAsync(w.mbox, 0, w.mbox_bytes, stream));
+  auto dz_of = [&](int i, int l) -> float* { return deferred ? pls[i].stash_slot(ios[i].stash, l) : w.d[l & 1]; };
+  for (int i = 0; i < n && deferred; ++i) TRY(stash_d_out(pls[i], ios[i].d_out, ios[i].ld_dout, ios[i].stash, stream));
+  for (int l = L - 1; l >= 0; --l) {
     const bool last = l == L - 1;
-    if (!deferred) TRY(atb(l));
+    if (!deferred) TRY(sweep_wgrad(pls[0], ios[0], l, last ? ios[0].d_out : dz_of(0, l), last ? ios[0].ld_dout : pls[0].H, w, "dW", stream));
+    if (l == 0) break;
     ColsArgs a{};
-    a.n_nets = n; a.M = M; a.eps = ps[0]->bn_eps; a.momentum = ps[0]->bn_momentum; a.accumulate = accumulate;
+    a.n_nets = n; a.M = M; a.eps = pls[0].p->bn_eps; a.momentum = pls[0].p->bn_momentum; a.accumulate = ios[0].accumulate;
     a.tag = (unsigned)l; a.mailbox = w.mbox;
     for (int i = 0; i < n; ++i) {
-      const empose_mlp_params* p = ps[i];
-      const int H = p->hidden, op = (p->out_dim + 3) & ~3, kdim = last ? op : H;
-      const float* sv = layer_save(i, l - 1);
+      const MlpPlan& pl = pls[i];
+      const MlpBwdIo& io = ios[i];
+      const empose_mlp_params* p = pl.p;
+      const LayerDims d = layer_dims(p, l, io.ldx);
+      const int H = pl.H;
       ColsNet& c = a.net[i];
-      c.A = last ? d_outs[i] : dz_of(i, l); c.lda = last ? ld_douts[i] : H;
-      c.N = H; c.K = kdim;
-      if (p->weight_t[l]) { c.W = p->weight_t[l]; c.ldw = kdim; }
-      else { c.W = p->weight[l]; c.ldw = H; c.w_kmajor = 1; c.Kw = last ? p->out_dim : H; }   // the layer's own W, read by rows
+      c.A = last ? io.d_out : dz_of(i, l); c.lda = last ? io.ld_dout : H;
+      c.N = H; c.K = d.out_pad;
+      if (p->weight_t[l]) { c.W = p->weight_t[l]; c.ldw = d.out_pad; }
+      else { c.W = p->weight[l]; c.ldw = H; c.w_kmajor = 1; c.Kw = d.N; }   // the layer's own W, read by rows
       c.gamma = p->bn_weight[l - 1]; c.beta = p->bn_bias[l - 1]; c.slope = p->prelu[l - 1];
-      c.z_in = sv; c.ldz = H; c.mean = const_cast<float*>(sv + (size_t)2 * M * H); c.rstd = c.mean + H;
+      c.z_in = pl.pre(io.save, l - 1); c.ldz = H;
+      c.mean = const_cast<float*>(pl.mean(io.save, l - 1)); c.rstd = const_cast<float*>(pl.rstd(io.save, l - 1));
       c.out = dz_of(i, l - 1); c.ld_out = H;
-      c.dgamma = grs[i]->bn_weight[l - 1]; c.dbeta = grs[i]->bn_bias[l - 1]; c.dslope = grs[i]->prelu[l - 1];
+      c.dgamma = io.gr->bn_weight[l - 1]; c.dbeta = io.gr->bn_bias[l - 1]; c.dslope = io.gr->prelu[l - 1];
     }
     HIP_CHECK(launch_cols(a, 2, stream), "one-launch layer backward");
   }
-  if (!deferred) TRY(atb(0));
   return EMPOSE_OK;
 }
 
-int mlp_train_bwd_impl(const empose_mlp_params* p, int M, const float* x, int ldx, const float* d_out, int ld_dout,
-                       const float* save, const empose_mlp_grads* gr, int accumulate, float* stash, void* workspace,
-                       size_t workspace_bytes, empose_stream_t stream_) {
+// ---- in front of the reverse sweeps, immediate or deferred: the argument checks, once (the forward: empose_mlp_train_fwd)
+int mlp_train_bwd(const empose_mlp_params* p, int M, const MlpBwdIo& io, void* workspace, size_t workspace_bytes,
+                  empose_stream_t stream_) {
   TRY(check_mlp_params(p));
   TRY(earlier_poll_timeouts());
-  if (!x || !d_out || !save || !gr || !workspace) return fail(EMPOSE_EINVAL, "null argument");
-  const int H = p->hidden, L = p->n_layers, op = (p->out_dim + 3) & ~3;
-  if (M <= 0 || ldx < p->in_dim || ld_dout < op || ld_dout % 4 != 0) return fail(EMPOSE_EINVAL, "bad sizes");
+  if (!io.x || !io.d_out || !io.save || !io.gr || !workspace) return fail(EMPOSE_EINVAL, "null argument");
+  const int L = p->n_layers, op = (p->out_dim + 3) & ~3;
+  if (M <= 0 || io.ldx < p->in_dim || io.ld_dout < op || io.ld_dout % 4 != 0) return fail(EMPOSE_EINVAL, "bad sizes");
   if (workspace_bytes < empose_mlp_train_workspace_bytes(p, M)) return fail(EMPOSE_ENOMEM, "workspace too small");
   for (int l = 0; l < L; ++l) {
-    if (!gr->weight[l] || !gr->bias[l]) return fail(EMPOSE_EINVAL, "null gradient output");
-    if (l < L - 1 && (!gr->bn_weight[l] || !gr->bn_bias[l] || !gr->prelu[l])) return fail(EMPOSE_EINVAL, "null gradient output");
+    if (!io.gr->weight[l] || !io.gr->bias[l]) return fail(EMPOSE_EINVAL, "null gradient output");
+    if (l < L - 1 && (!io.gr->bn_weight[l] || !io.gr->bn_bias[l] || !io.gr->prelu[l])) return fail(EMPOSE_EINVAL, "null gradient output");
   }
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   Carver c(workspace);
-  MlpTrainWs w = carve_mlp_train(c, p, M);
-  if (mlp_train_cols(p, M))
-    return mlp_bwd_cols(&p, 1, M, x, ldx, &d_out, &ld_dout, &save, &gr, accumulate, &stash, w, stream);
+  const MlpTrainWs w = carve_mlp_train(c, p, M);
+  const MlpPlan pl = mlp_plan(p, M);
+  if (pl.cols()) return mlp_bwd_cols(&pl, 1, &io, w, stream);
   // the last-arriver counter of the single-pass BatchNorm reverse kernel (it re-arms itself; the workspace may be fresh)
-  const bool epi = mlp_train_epi(p, M);
-  if (M <= BN_SINGLE_PASS_ROWS || epi) HIP_TRY(hipMemsetAsync(w.counter, 0, sizeof(int), stream));
-  auto gemm = [&](const float* A, int lda, const float* W, int ldw, float* C, int ldc, int N, int K) -> hipError_t {
-    GemmBatch b;
-    b.count = 1;
-    GemmProb& g = b.p[0];
-    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.C = C; g.ldc = ldc; g.M = M; g.N = N; g.K = K;
-    g.scale = nullptr; g.shift = nullptr; g.resid = nullptr; g.ldr = 0; g.act = 0; g.slope = 0.f;
-    return launch_gemm(b, stream);
-  };
-  auto layer_save = [&](int l) { return save + (size_t)l * mlp_layer_save(p, M); };
-  if (mlp_train_fused(p, M) || epi) {
-    // The dX GEMM's epilogue writes dyh_l = dA_l * PReLU'(yhat_l) and the column sums BatchNorm's reverse needs; a
-    // small kernel turns the sums into dgamma / dbeta / dslope and three per-column coefficients, one pass forms
-    // dY_l = c1 dyh_l + c3 y_l + c0 in place (`epi`: both in ONE launch, bn_finish_bwd).  Fused: the layer inputs a_{l-1}
-    // are not stored, the A^T B product re-forms them from y_{l-1} while it stages its B operand; `epi`: they are.
-    auto stats_of = [&](int l) { return layer_save(l) + (size_t)(epi ? 2 : 1) * M * H; };   // mean | rstd | s | t
-    auto dz_of = [&](int l) -> float* { return stash ? stash + (size_t)M * l * H : w.d[l & 1]; };
-    auto atb = [&](int l) -> int {   // dW_l, db_l (not deferred)
-      const bool last = l == L - 1;
-      AtbArgs ab{};
-      ab.A = last ? d_out : dz_of(l); ab.lda = last ? ld_dout : H;
-      ab.B = l == 0 ? x : layer_save(l - 1) + (epi ? (size_t)M * H : 0); ab.ldb = l == 0 ? ldx : H;
-      ab.C = gr->weight[l]; ab.ldc = l == 0 ? p->in_dim : H; ab.bias = gr->bias[l];
-      ab.M = M; ab.N = last ? p->out_dim : H; ab.K = l == 0 ? p->in_dim : H; ab.accumulate = accumulate;
-      if (l > 0 && !epi) { ab.b_mode = 1; ab.Bs_seg[0] = stats_of(l - 1) + 2 * H; ab.b_slope = p->prelu[l - 1]; }
-      HIP_CHECK(launch_gemm_atb(ab, w.atb, w.atb_floats, stream), "fused dW");
-      return EMPOSE_OK;
-    };
-    for (int l = L - 1; l >= 0; --l) {
-      const bool last = l == L - 1;
-      if (last && stash) {   // keep d_out for empose_mlp_train_wgrad (no copy when the caller produced it in its slot)
-        float* slot = stash + (size_t)M * (L - 1) * H;
-        if (d_out != slot || ld_dout != op) {
-          HIP_CHECK(launch_axpby2d(M, op, 1.f, d_out, ld_dout, 0.f, nullptr, 0, slot, op, stream), "stash");
-        }
-      }
-      if (!stash) TRY(atb(l));
-      if (l == 0) break;
-      // dA_{l-1} = dY_l W_l on the forward tile against W_l^T, its epilogue already in terms of layer l - 1
-      const float* wt = p->weight_t[l];
-      const int kdim = last ? op : H;
-      if (!wt) {
-        if (last) HIP_TRY(hipMemsetAsync(w.wt, 0, (size_t)H * op * sizeof(float), stream));
-        HIP_CHECK(launch_transpose(p->weight[l], H, w.wt, kdim, last ? p->out_dim : H, H, stream), "transpose");
-        wt = w.wt;
-      }
-      TrainGemmArgs g{};
-      g.A = last ? d_out : dz_of(l); g.lda = last ? ld_dout : H; g.W = wt; g.ldw = kdim;
-      g.C = dz_of(l - 1); g.ldc = H; g.M = M; g.N = H; g.K = kdim; g.bias = nullptr;
-      g.part = w.part; g.e_y = layer_save(l - 1); g.ld_ey = H;
-      g.e_mean = stats_of(l - 1); g.e_rstd = g.e_mean + H; g.e_s = g.e_rstd + H; g.e_t = g.e_s + H; g.e_slope = p->prelu[l - 1];
-      const bool x3 = options().train_x3 != 0 && p->weight_t[l] && p->weight_t_x3[l] && gemm_train_x3_applicable(g.M, g.N, g.K);
-      HIP_CHECK(x3 ? launch_gemm_train_x3(g, p->weight_t_x3[l], 2, stream) : launch_gemm_train(g, 0, 2, stream), "fused dX gemm");
-      if (epi) {
-        BnFinishBwdArgs f{};
-        f.M = M; f.C = H; f.part = w.part; f.gamma = p->bn_weight[l - 1]; f.mean = stats_of(l - 1); f.rstd = f.mean + H;
-        f.dgamma = gr->bn_weight[l - 1]; f.dbeta = gr->bn_bias[l - 1]; f.dslope = gr->prelu[l - 1];
-        f.dslope_partial = w.slope_partial; f.counter = w.counter; f.accumulate = accumulate;
-        f.dyh = dz_of(l - 1); f.ld = H; f.y = layer_save(l - 1); f.ldy = H;
-        HIP_CHECK(launch_bn_finish_bwd(f, stream), "bn finish backward");
-        continue;
-      }
-      BnFusedBwdArgs c{};
-      c.M = M; c.C = H; c.part = w.part; c.gamma = p->bn_weight[l - 1]; c.mean = stats_of(l - 1); c.rstd = stats_of(l - 1) + H;
-      c.dgamma = gr->bn_weight[l - 1]; c.dbeta = gr->bn_bias[l - 1]; c.dslope = gr->prelu[l - 1];
-      c.dslope_partial = w.slope_partial; c.coef = w.coef; c.accumulate = accumulate;
-      HIP_CHECK(launch_bn_fused_combine_bwd(c, stream), "fused bn reverse combine");
-      HIP_CHECK(launch_bn_fused_apply_bwd(dz_of(l - 1), layer_save(l - 1), w.coef, M, H, stream), "fused bn reverse apply");
-    }
-    return EMPOSE_OK;
-  }
-  // output layer: dW = d_out^T a_{L-2}, db, dA = d_out . W
-  {
-    const int l = L - 1;
-    if (stash) {   // weight gradients deferred: keep d_out for empose_mlp_train_wgrad (no copy when the caller
-                   // produced it in its stash slot already, include/empose_hip.h)
-      float* slot = stash + (size_t)M * (L - 1) * H;
-      if (d_out != slot || ld_dout != op) {
-        HIP_CHECK(launch_axpby2d(M, op, 1.f, d_out, ld_dout, 0.f, nullptr, 0, slot, op, stream), "stash");
-      }
-    } else {
-      AtbArgs ab{};
-      ab.A = d_out; ab.lda = ld_dout; ab.B = layer_save(l - 1) + (size_t)M * H; ab.ldb = H; ab.C = gr->weight[l]; ab.ldc = H;
-      ab.bias = gr->bias[l]; ab.M = M; ab.N = p->out_dim; ab.K = H; ab.accumulate = accumulate;
-      HIP_CHECK(launch_gemm_atb(ab, w.atb, w.atb_floats, stream), "dW");
-    }
-    const float* wt = p->weight_t[l];
-    if (!wt) {
-      HIP_TRY(hipMemsetAsync(w.wt, 0, (size_t)H * op * sizeof(float), stream));
-      HIP_CHECK(launch_transpose(p->weight[l], H, w.wt, op, p->out_dim, H, stream), "transpose");
-      wt = w.wt;
-    }
-    HIP_CHECK(gemm(d_out, ld_dout, wt, op, w.d[0], H, H, op), "dX gemm");
-  }
-  const int cur = 0;   // w.d[0]: cotangent of the current layer's activation; w.d[1]: dZ when it is not stashed
-  for (int l = L - 2; l >= 0; --l) {
-    const float* sv = layer_save(l);
-    BnPreluArgs a{};
-    a.M = M; a.C = H; a.x = sv; a.ldx = H; a.gamma = p->bn_weight[l]; a.beta = p->bn_bias[l]; a.slope = p->prelu[l];
-    a.save_mean = const_cast<float*>(sv + (size_t)2 * M * H); a.save_rstd = a.save_mean + H;
-    float* dz = stash ? stash + (size_t)M * l * H : w.d[cur ^ 1];   // dZ_l: into the stash when the dW are deferred
-    a.dz = w.d[cur]; a.lddz = H; a.dx = dz; a.lddx = H;
-    a.dgamma = gr->bn_weight[l]; a.dbeta = gr->bn_bias[l]; a.dslope = gr->prelu[l];
-    a.dslope_partial = w.slope_partial; a.counter = w.counter; a.workspace = w.bn; a.accumulate = accumulate;
-    HIP_CHECK(launch_bn_prelu(a, true, stream), "bn_prelu backward");
-    const float* in = l == 0 ? x : layer_save(l - 1) + (size_t)M * H;
-    const int ld_in = l == 0 ? ldx : H, k_in = l == 0 ? p->in_dim : H;
-    if (!stash) {
-      AtbArgs ab{};
-      ab.A = dz; ab.lda = H; ab.B = in; ab.ldb = ld_in; ab.C = gr->weight[l]; ab.ldc = k_in;
-      ab.bias = gr->bias[l]; ab.M = M; ab.N = H; ab.K = k_in; ab.accumulate = accumulate;
-      HIP_CHECK(launch_gemm_atb(ab, w.atb, w.atb_floats, stream), "dW");
-    }
-    if (l == 0) break;
-    const float* wt = p->weight_t[l];
-    if (!wt) {
-      HIP_CHECK(launch_transpose(p->weight[l], H, w.wt, H, H, H, stream), "transpose");
-      wt = w.wt;
-    }
-    HIP_CHECK(gemm(dz, H, wt, H, w.d[cur], H, H, H), "dX gemm");   // the cotangent of the layer below overwrites the consumed one
-  }
-  return EMPOSE_OK;
+  if (M <= BN_SINGLE_PASS_ROWS || pl.layout == 3) HIP_TRY(hipMemsetAsync(w.counter, 0, sizeof(int), stream));
+  return pl.layout == 1 ? bwd_passes(pl, io, w, stream) : bwd_stats(pl, io, w, stream);
 }
 }  // namespace
 
@@ -336,12 +445,8 @@ int empose_linear_f32_ex(const float* A, int lda, const float* W, int ldw, float
   if (K % 4 != 0 || lda % 4 != 0 || ldw % 4 != 0) return fail(EMPOSE_EINVAL, "K, lda, ldw must be multiples of 4");
   if (((uintptr_t)A & 15) || ((uintptr_t)W & 15)) return fail(EMPOSE_EINVAL, "A and W must be 16-byte aligned");
   if (act < 0 || act > 2) return fail(EMPOSE_EINVAL, "act must be 0 (none), 1 (PReLU, residual added after) or 2 (residual, then ReLU)");
-  GemmBatch b;
-  b.count = 1;
-  GemmProb& p = b.p[0];
-  p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
-  p.scale = scale; p.shift = shift; p.resid = resid; p.ldr = ldr; p.act = act; p.slope = slope;
-  HIP_CHECK(launch_gemm(b, static_cast<hipStream_t>(stream_)), "gemm launch");
+  HIP_CHECK(gemm_one(A, lda, W, ldw, C, ldc, M, N, K, scale, shift, resid, ldr, act, slope, static_cast<hipStream_t>(stream_)),
+            "gemm launch");
   return EMPOSE_OK;
 }
 
@@ -543,18 +648,18 @@ int empose_adam_step(int n_chunks, const void* params, const void* grads, const 
 
 int empose_mlp_train_uses_weight_t(const empose_mlp_params* p, int M) {
   if (!p || M <= 0) return fail(EMPOSE_EINVAL, "null parameters / no rows");
-  return mlp_train_cols(p, M) ? 0 : 1;
+  return mlp_plan(p, M).cols() ? 0 : 1;
 }
 
 int empose_mlp_train_save_layout(const empose_mlp_params* p, int M) {
   if (!p || M <= 0) return fail(EMPOSE_EINVAL, "null parameters / no rows");
   if (p->save_layout < 0 || p->save_layout > 3) return fail(EMPOSE_EINVAL, "save_layout must be 0 .. 3");
-  return mlp_train_fused(p, M) ? 2 : (mlp_train_epi(p, M) ? 3 : 1);
+  return mlp_plan(p, M).layout;
 }
 
 size_t empose_mlp_train_save_floats(const empose_mlp_params* p, int M) {
   if (!p || M <= 0) return 0;
-  return (size_t)(p->n_layers - 1) * mlp_layer_save(p, M);
+  return mlp_plan(p, M).save_floats();
 }
 
 size_t empose_mlp_train_workspace_bytes(const empose_mlp_params* p, int M) {
@@ -573,103 +678,29 @@ int empose_mlp_train_fwd(const empose_mlp_params* p, int M, const float* x, int 
   if (workspace_bytes < empose_mlp_train_workspace_bytes(p, M)) return fail(EMPOSE_ENOMEM, "workspace too small");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   Carver c(workspace);
-  MlpTrainWs w = carve_mlp_train(c, p, M);
-  const int H = p->hidden, L = p->n_layers;
-  if (mlp_train_cols(p, M)) return mlp_fwd_cols(&p, 1, M, x, ldx, &out, &ld_out, &save, w, stream);
-  if (mlp_train_epi(p, M)) {
-    // y_l = a_{l-1} W_l^T + b_l on the materialised a_{l-1}; the epilogue leaves the column statistics of y_l per row
-    // block; ONE launch turns them into (mean, rstd, s, t), updates the running statistics and writes a_l = PReLU(s y_l + t)
-    const size_t lsz = mlp_layer_save(p, M);
-    for (int l = 0; l < L; ++l) {
-      const bool last = l == L - 1;
-      float* sv = save + (size_t)l * lsz;                      // this layer's y | a | mean | rstd | s | t
-      const float* pa = l > 0 ? save + (size_t)(l - 1) * lsz + (size_t)M * H : nullptr;
-      TrainGemmArgs g{};
-      g.A = l == 0 ? x : pa; g.lda = l == 0 ? ldx : H; g.W = p->weight[l]; g.ldw = l == 0 ? p->in_dim : H;
-      g.C = last ? out : sv; g.ldc = last ? ld_out : H;
-      g.M = M; g.N = last ? p->out_dim : H; g.K = l == 0 ? p->in_dim : H; g.bias = p->bias[l];
-      g.part = w.part;
-      const bool x3 = !last && options().train_x3 != 0 && p->weight_x3[l] && gemm_train_x3_applicable(g.M, g.N, g.K);
-      HIP_CHECK(x3 ? launch_gemm_train_x3(g, p->weight_x3[l], 1, stream) : launch_gemm_train(g, 0, last ? 0 : 1, stream), "mlp forward gemm (statistics epilogue)");
-      if (last) break;
-      BnFinishFwdArgs c{};
-      c.M = M; c.C = H; c.part = w.part; c.gamma = p->bn_weight[l]; c.beta = p->bn_bias[l];
-      c.eps = p->bn_eps; c.momentum = p->bn_momentum; c.running_mean = p->bn_running_mean[l];
-      c.running_var = p->bn_running_var[l]; c.num_batches_tracked = p->bn_num_batches[l];
-      c.mean = sv + (size_t)2 * M * H; c.rstd = c.mean + H; c.s = c.rstd + H; c.t = c.s + H;
-      c.y = sv; c.ldy = H; c.act = sv + (size_t)M * H; c.ld_act = H; c.slope = p->prelu[l];
-      HIP_CHECK(launch_bn_finish_fwd(c, stream), "bn finish forward");
-    }
-    return EMPOSE_OK;
-  }
-  if (mlp_train_fused(p, M)) {
-    // y_l = a_{l-1} W_l^T + b_l with a_{l-1} = PReLU(s y_{l-1} + t) formed while the GEMM stages its A operand; the
-    // epilogue leaves the column statistics of y_l per row block, a small kernel turns them into (mean, rstd, s, t)
-    const size_t lsz = mlp_layer_save(p, M);
-    for (int l = 0; l < L; ++l) {
-      const bool last = l == L - 1;
-      float* sv = save + (size_t)l * lsz;                      // this layer's y | mean | rstd | s | t
-      const float* pv = l > 0 ? save + (size_t)(l - 1) * lsz : nullptr;
-      TrainGemmArgs g{};
-      g.A = l == 0 ? x : pv; g.lda = l == 0 ? ldx : H; g.W = p->weight[l]; g.ldw = l == 0 ? p->in_dim : H;
-      g.C = last ? out : sv; g.ldc = last ? ld_out : H;
-      g.M = M; g.N = last ? p->out_dim : H; g.K = l == 0 ? p->in_dim : H; g.bias = p->bias[l];
-      if (l > 0) { g.a_s = pv + (size_t)M * H + 2 * H; g.a_t = g.a_s + H; g.a_slope = p->prelu[l - 1]; }
-      g.part = w.part;
-      HIP_CHECK(launch_gemm_train(g, l > 0 ? 1 : 0, last ? 0 : 1, stream), "fused mlp forward gemm");
-      if (last) break;
-      BnFusedFwdArgs c{};
-      c.M = M; c.C = H; c.part = w.part; c.gamma = p->bn_weight[l]; c.beta = p->bn_bias[l];
-      c.eps = p->bn_eps; c.momentum = p->bn_momentum; c.running_mean = p->bn_running_mean[l];
-      c.running_var = p->bn_running_var[l]; c.num_batches_tracked = p->bn_num_batches[l];
-      c.mean = sv + (size_t)M * H; c.rstd = c.mean + H; c.s = c.rstd + H; c.t = c.s + H;
-      HIP_CHECK(launch_bn_fused_combine_fwd(c, stream), "fused bn combine");
-    }
-    return EMPOSE_OK;
-  }
-  const float* in = x;
-  int ld_in = ldx, k_in = p->in_dim;
-  for (int l = 0; l < L; ++l) {
-    const bool last = l == L - 1;
-    float* sv = save + (size_t)l * mlp_layer_save(p, M);
-    float* z = last ? out : sv;
-    GemmBatch b;
-    b.count = 1;
-    GemmProb& g = b.p[0];
-    g.A = in; g.lda = ld_in; g.W = p->weight[l]; g.ldw = k_in; g.C = z; g.ldc = last ? ld_out : H;
-    g.M = M; g.N = last ? p->out_dim : H; g.K = k_in;
-    g.scale = nullptr; g.shift = p->bias[l]; g.resid = nullptr; g.ldr = 0; g.act = 0; g.slope = 0.f;
-    HIP_CHECK(launch_gemm(b, stream), "mlp forward gemm");
-    if (last) break;
-    float* act = sv + (size_t)M * H;
-    BnPreluArgs a{};
-    a.M = M; a.C = H; a.x = z; a.ldx = H; a.gamma = p->bn_weight[l]; a.beta = p->bn_bias[l]; a.slope = p->prelu[l];
-    a.eps = p->bn_eps; a.momentum = p->bn_momentum; a.running_mean = p->bn_running_mean[l];
-    a.running_var = p->bn_running_var[l]; a.num_batches_tracked = p->bn_num_batches[l];
-    a.z = act; a.ldz = H; a.save_mean = sv + (size_t)2 * M * H; a.save_rstd = a.save_mean + H;
-    a.workspace = w.bn;
-    HIP_CHECK(launch_bn_prelu(a, false, stream), "bn_prelu forward");
-    in = act; ld_in = H; k_in = H;
-  }
-  return EMPOSE_OK;
+  const MlpTrainWs w = carve_mlp_train(c, p, M);
+  const MlpPlan pl = mlp_plan(p, M);
+  if (pl.cols()) return mlp_fwd_cols(&pl, 1, x, ldx, &out, &ld_out, &save, w, stream);
+  return pl.layout == 1 ? fwd_passes(pl, x, ldx, out, ld_out, save, w, stream)
+                        : fwd_stats(pl, x, ldx, out, ld_out, save, w, stream);
 }
 
 int empose_mlp_train_bwd(const empose_mlp_params* p, int M, const float* x, int ldx, const float* d_out, int ld_dout,
                          const float* save, const empose_mlp_grads* gr, int accumulate, void* workspace,
                          size_t workspace_bytes, empose_stream_t stream) {
-  return mlp_train_bwd_impl(p, M, x, ldx, d_out, ld_dout, save, gr, accumulate, nullptr, workspace, workspace_bytes, stream);
+  return mlp_train_bwd(p, M, {x, ldx, d_out, ld_dout, save, gr, accumulate, nullptr}, workspace, workspace_bytes, stream);
 }
 
 size_t empose_mlp_train_stash_floats(const empose_mlp_params* p, int M) {
   if (!p || M <= 0 || check_mlp_params(p) != EMPOSE_OK) return 0;
-  return mlp_stash_floats(p, M);
+  return mlp_plan(p, M).stash_floats();
 }
 
 int empose_mlp_train_bwd_deferred(const empose_mlp_params* p, int M, const float* x, int ldx, const float* d_out,
                                   int ld_dout, const float* save, const empose_mlp_grads* gr, int accumulate,
                                   float* dz_stash, void* workspace, size_t workspace_bytes, empose_stream_t stream) {
   if (!dz_stash) return fail(EMPOSE_EINVAL, "null stash");
-  return mlp_train_bwd_impl(p, M, x, ldx, d_out, ld_dout, save, gr, accumulate, dz_stash, workspace, workspace_bytes, stream);
+  return mlp_train_bwd(p, M, {x, ldx, d_out, ld_dout, save, gr, accumulate, dz_stash}, workspace, workspace_bytes, stream);
 }
 
 // ---- both update networks of an iteration in one call: paired launches on the one-launch layers, else one after the other
@@ -685,15 +716,15 @@ int empose_mlp_train_fwd_pair(const empose_mlp_params* p0, const empose_mlp_para
   TRY(check_mlp_params(p1));
   TRY(earlier_poll_timeouts());
   if (workspace_bytes < empose_mlp_train_pair_workspace_bytes(p0, p1, M)) return fail(EMPOSE_ENOMEM, "workspace too small");
+  const MlpPlan pls[2] = {mlp_plan(p0, M), mlp_plan(p1, M)};
   if (M > 0 && x && out0 && out1 && save0 && save1 && workspace && ldx % 4 == 0 && ldx >= p0->in_dim && ldx >= p1->in_dim &&
-      ld_out0 >= p0->out_dim && ld_out1 >= p1->out_dim && mlp_cols_pairable(p0, p1, M)) {
+      ld_out0 >= p0->out_dim && ld_out1 >= p1->out_dim && mlp_cols_pairable(pls[0], pls[1])) {
     Carver c(workspace);
-    MlpTrainWs w = carve_mlp_train(c, p0, M);
-    const empose_mlp_params* ps[2] = {p0, p1};
+    const MlpTrainWs w = carve_mlp_train(c, p0, M);
     float* outs[2] = {out0, out1};
     const int lds[2] = {ld_out0, ld_out1};
     float* saves[2] = {save0, save1};
-    return mlp_fwd_cols(ps, 2, M, x, ldx, outs, lds, saves, w, static_cast<hipStream_t>(stream_));
+    return mlp_fwd_cols(pls, 2, x, ldx, outs, lds, saves, w, static_cast<hipStream_t>(stream_));
   }
   TRY(empose_mlp_train_fwd(p0, M, x, ldx, out0, ld_out0, save0, workspace, workspace_bytes, stream_));
   return empose_mlp_train_fwd(p1, M, x, ldx, out1, ld_out1, save1, workspace, workspace_bytes, stream_);
@@ -709,26 +740,21 @@ int empose_mlp_train_bwd_deferred_pair(const empose_mlp_params* p0, const empose
   TRY(earlier_poll_timeouts());
   if (!dz_stash0 || !dz_stash1) return fail(EMPOSE_EINVAL, "null stash");
   if (workspace_bytes < empose_mlp_train_pair_workspace_bytes(p0, p1, M)) return fail(EMPOSE_ENOMEM, "workspace too small");
-  bool pair = M > 0 && x && d_out0 && d_out1 && save0 && save1 && gr0 && gr1 && workspace && mlp_cols_pairable(p0, p1, M) &&
-              ld_dout0 % 4 == 0 && ld_dout1 % 4 == 0 && ld_dout0 >= ((p0->out_dim + 3) & ~3) && ld_dout1 >= ((p1->out_dim + 3) & ~3);
+  const MlpPlan pls[2] = {mlp_plan(p0, M), mlp_plan(p1, M)};
+  const MlpBwdIo ios[2] = {{x, ldx, d_out0, ld_dout0, save0, gr0, accumulate, dz_stash0},
+                           {x, ldx, d_out1, ld_dout1, save1, gr1, accumulate, dz_stash1}};
+  bool pair = M > 0 && x && d_out0 && d_out1 && save0 && save1 && gr0 && gr1 && workspace && mlp_cols_pairable(pls[0], pls[1]) &&
+              ld_dout0 % 4 == 0 && ld_dout1 % 4 == 0 && ld_dout0 >= pls[0].op && ld_dout1 >= pls[1].op;
   for (int l = 0; l < p0->n_layers - 1 && pair; ++l)
     if (!gr0->bn_weight[l] || !gr0->bn_bias[l] || !gr0->prelu[l] || !gr1->bn_weight[l] || !gr1->bn_bias[l] || !gr1->prelu[l])
       pair = false;
   if (pair) {
     Carver c(workspace);
-    MlpTrainWs w = carve_mlp_train(c, p0, M);
-    const empose_mlp_params* ps[2] = {p0, p1};
-    const float* d_outs[2] = {d_out0, d_out1};
-    const int lds[2] = {ld_dout0, ld_dout1};
-    const float* saves[2] = {save0, save1};
-    const empose_mlp_grads* grs[2] = {gr0, gr1};
-    float* stashes[2] = {dz_stash0, dz_stash1};
-    return mlp_bwd_cols(ps, 2, M, x, ldx, d_outs, lds, saves, grs, accumulate, stashes, w, static_cast<hipStream_t>(stream_));
+    const MlpTrainWs w = carve_mlp_train(c, p0, M);
+    return mlp_bwd_cols(pls, 2, ios, w, static_cast<hipStream_t>(stream_));
   }
-  TRY(empose_mlp_train_bwd_deferred(p0, M, x, ldx, d_out0, ld_dout0, save0, gr0, accumulate, dz_stash0, workspace,
-                                    workspace_bytes, stream_));
-  return empose_mlp_train_bwd_deferred(p1, M, x, ldx, d_out1, ld_dout1, save1, gr1, accumulate, dz_stash1, workspace,
-                                       workspace_bytes, stream_);
+  TRY(mlp_train_bwd(p0, M, ios[0], workspace, workspace_bytes, stream_));
+  return mlp_train_bwd(p1, M, ios[1], workspace, workspace_bytes, stream_);
 }
 
 size_t empose_mlp_train_wgrad_workspace_bytes(const empose_mlp_params* p, int n_app, int M) {
@@ -746,10 +772,6 @@ int empose_mlp_train_wgrad(const empose_mlp_params* p, int n_app, int M, const f
   if (!x || !save || !dz_stash || !gr || !workspace) return fail(EMPOSE_EINVAL, "null argument");
   if (n_app < 1 || n_app > ATB_MAX_SEG || M <= 0 || ldx < p->in_dim) return fail(EMPOSE_EINVAL, "bad sizes");
   if (workspace_bytes < empose_mlp_train_wgrad_workspace_bytes(p, n_app, M)) return fail(EMPOSE_ENOMEM, "workspace too small");
-  const int H = p->hidden, L = p->n_layers, op = (p->out_dim + 3) & ~3;
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  float* ws = static_cast<float*>(workspace);
-  const size_t ws_floats = workspace_bytes / sizeof(float);
   // one product over all applications when their rows can be addressed as 32-row aligned segments, else one per application
   bool batched = M % 32 == 0 && ldx % 4 == 0;
   for (int s = 0; s < n_app && batched; ++s)
@@ -757,68 +779,22 @@ int empose_mlp_train_wgrad(const empose_mlp_params* p, int n_app, int M, const f
               ((uintptr_t)dz_stash[s] & 15) == 0;
   for (int s = 0; s < n_app; ++s)
     if (!x[s] || !save[s] || !dz_stash[s]) return fail(EMPOSE_EINVAL, "null argument");
-  const bool fused = mlp_train_fused(p, M);
-  for (int l = 0; l < L; ++l) {
+  const MlpPlan pl = mlp_plan(p, M);
+  for (int l = 0; l < pl.L; ++l) {
     if (!gr->weight[l] || !gr->bias[l]) return fail(EMPOSE_EINVAL, "null gradient output");
-    const bool last = l == L - 1;
-    const int ld_a = last ? op : H, n_out = last ? p->out_dim : H;
-    const int ld_b = l == 0 ? ldx : H, k_in = l == 0 ? p->in_dim : H;
-    if (fused) {
-      // operands as the fused sweeps left them: dY_l (stash), y_{l-1} and its (s, t) (save)
-      const size_t lsz = mlp_layer_save(p, M);
-      AtbArgs ab{};
-      ab.lda = ld_a; ab.ldb = ld_b; ab.C = gr->weight[l]; ab.ldc = k_in; ab.bias = gr->bias[l]; ab.N = n_out; ab.K = k_in;
-      ab.b_mode = l > 0 ? 1 : 0; ab.b_slope = l > 0 ? p->prelu[l - 1] : nullptr;
-      auto fill = [&](int slot, int s) {
-        ab.A_seg[slot] = dz_stash[s] + (size_t)M * l * H;
-        ab.B_seg[slot] = l == 0 ? x[s] : save[s] + (size_t)(l - 1) * lsz;
-        ab.Bs_seg[slot] = l > 0 ? save[s] + (size_t)(l - 1) * lsz + (size_t)M * H + 2 * H : nullptr;
-      };
-      if (batched) {
-        for (int s = 0; s < n_app; ++s) fill(s, s);
-        ab.A = ab.A_seg[0]; ab.B = ab.B_seg[0]; ab.M = n_app * M; ab.accumulate = accumulate;
-        ab.n_seg = n_app; ab.seg_rows = M;
-        HIP_CHECK(launch_gemm_atb(ab, ws, ws_floats, stream), "fused dW");
-      } else {
-        for (int s = 0; s < n_app; ++s) {
-          fill(0, s);
-          ab.A = ab.A_seg[0]; ab.B = ab.B_seg[0]; ab.M = M; ab.accumulate = accumulate || s > 0;
-          HIP_CHECK(launch_gemm_atb(ab, ws, ws_floats, stream), "fused dW");
-        }
-      }
-      continue;
-    }
-    auto a_of = [&](int s) { return dz_stash[s] + (size_t)M * l * H; };
-    auto b_of = [&](int s) { return l == 0 ? x[s] : save[s] + (size_t)(l - 1) * mlp_layer_save(p, M) + (size_t)M * H; };
-    AtbArgs ab{};
-    ab.lda = ld_a; ab.ldb = ld_b; ab.C = gr->weight[l]; ab.ldc = k_in; ab.bias = gr->bias[l]; ab.N = n_out; ab.K = k_in;
-    if (batched) {
-      ab.A = a_of(0); ab.B = b_of(0); ab.M = n_app * M; ab.accumulate = accumulate;
-      ab.n_seg = n_app; ab.seg_rows = M;
-      for (int s = 0; s < n_app; ++s) { ab.A_seg[s] = a_of(s); ab.B_seg[s] = b_of(s); }
-      HIP_CHECK(launch_gemm_atb(ab, ws, ws_floats, stream), "dW");
-    } else {
-      for (int s = 0; s < n_app; ++s) {
-        ab.A = a_of(s); ab.B = b_of(s); ab.M = M; ab.accumulate = accumulate || s > 0;
-        HIP_CHECK(launch_gemm_atb(ab, ws, ws_floats, stream), "dW");
-      }
-    }
+    // operands as the reverse sweeps left them: dY_l (stash) and the layer's input (x, save)
+    const float* dy[ATB_MAX_SEG];
+    for (int s = 0; s < n_app; ++s) dy[s] = pl.stash_slot(dz_stash[s], l);
+    TRY(layer_wgrad(pl, l, n_app, batched, dy, layer_dims(p, l, ldx).out_pad, x, ldx, save, gr, accumulate,
+                    static_cast<float*>(workspace), workspace_bytes / sizeof(float), pl.layout == 2 ? "fused dW" : "dW",
+                    static_cast<hipStream_t>(stream_)));
   }
   return EMPOSE_OK;
 }
 
 int empose_linear_f32(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K,
-                      const float* scale, const float* shift, int prelu, float slope, empose_stream_t stream_) {
-  if (!A || !W || !C) return fail(EMPOSE_EINVAL, "null argument");
-  if (K % 4 != 0 || lda % 4 != 0 || ldw % 4 != 0) return fail(EMPOSE_EINVAL, "K, lda, ldw must be multiples of 4");
-  if (((uintptr_t)A & 15) || ((uintptr_t)W & 15)) return fail(EMPOSE_EINVAL, "A and W must be 16-byte aligned");
-  GemmBatch b;
-  b.count = 1;
-  GemmProb& p = b.p[0];
-  p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.C = C; p.ldc = ldc; p.M = M; p.N = N; p.K = K;
-  p.scale = scale; p.shift = shift; p.resid = nullptr; p.ldr = 0; p.act = prelu ? 1 : 0; p.slope = slope;
-  HIP_CHECK(launch_gemm(b, static_cast<hipStream_t>(stream_)), "gemm launch");
-  return EMPOSE_OK;
+                      const float* scale, const float* shift, int prelu, float slope, empose_stream_t stream) {
+  return empose_linear_f32_ex(A, lda, W, ldw, C, ldc, M, N, K, scale, shift, nullptr, 0, prelu ? 1 : 0, slope, stream);
 }
 
 }  // extern "C"

@@ -27,6 +27,7 @@ import ctypes as C
 import torch
 
 from em_pose_amd import _lib
+from em_pose_amd.nn import layers as _layers
 
 
 def _ptr(t):
@@ -161,12 +162,17 @@ class _MlpView(object):
         return g
 
 
-class _nothing(object):
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
+def _lstm_params(rnn, input_size, grads=None):
+    """LstmParams of an LSTM stack and, with `grads` (one tensor per weight), LstmGrads; also returns the weights."""
+    weights = [w for unit in rnn._unit_params() for w in unit]
+    p = _lib.LstmParams()
+    p.num_layers, p.input_size, p.hidden_size = rnn.num_layers, input_size, rnn.hidden_size
+    g = None if grads is None else _lib.LstmGrads()
+    for l in range(rnn.num_layers):
+        p.w_ih[l], p.w_hh[l], p.b_ih[l], p.b_hh[l] = [weights[4 * l + k].data_ptr() for k in range(4)]
+        if g is not None:
+            g.w_ih[l], g.w_hh[l], g.b_ih[l], g.b_hh[l] = [grads[4 * l + k].data_ptr() for k in range(4)]
+    return p, g, weights
 
 
 class LgdTrainEngine(object):
@@ -261,11 +267,10 @@ class LgdTrainEngine(object):
         p = view.params()
         save = self.new(self.lib.empose_mlp_train_save_floats(C.byref(p), M))
         nbytes = self.lib.empose_mlp_train_workspace_bytes(C.byref(p), M)
-        with (self._on_side(side) if side is not None else _nothing()):
+        with (self._on_side(side) if side is not None else contextlib.nullcontext()):
             ws = self.ws(nbytes) if side is not None else self._hold(self.ws(nbytes))
             _lib.check(self.lib.empose_mlp_train_fwd(C.byref(p), M, x, ldx, out, ld_out, save.data_ptr(), ws.data_ptr(),
                                                      nbytes, self.stream))
-        from em_pose_amd.nn import layers as _layers
         _layers.BN_STATS_GENERATION[0] += 1
         return save
 
@@ -279,7 +284,6 @@ class LgdTrainEngine(object):
         _lib.check(self.lib.empose_mlp_train_fwd_pair(C.byref(ps[0]), C.byref(ps[1]), M, x, ldx, outs[0], ld_outs[0],
                                                       outs[1], ld_outs[1], saves[0].data_ptr(), saves[1].data_ptr(),
                                                       ws.data_ptr(), nbytes, self.stream))
-        from em_pose_amd.nn import layers as _layers
         _layers.BN_STATS_GENERATION[0] += 2
         return saves
 
@@ -316,7 +320,7 @@ class LgdTrainEngine(object):
         if stash is None:
             stash = self.new(self.lib.empose_mlp_train_stash_floats(C.byref(p), M))
         nbytes = self.lib.empose_mlp_train_workspace_bytes(C.byref(p), M)
-        with (self._on_side(side) if side is not None else _nothing()):
+        with (self._on_side(side) if side is not None else contextlib.nullcontext()):
             ws = self.ws(nbytes) if side is not None else self._hold(self.ws(nbytes))
             _lib.check(self.lib.empose_mlp_train_bwd_deferred(C.byref(p), M, x, ldx, d_out, ld_dout, save.data_ptr(),
                                                               C.byref(g), int(accumulate), stash.data_ptr(),
@@ -426,11 +430,7 @@ class LgdTrainEngine(object):
                 rnn = net.rnn
                 rnn.init_state = rnn.final_state
                 L, H = rnn.num_layers, rnn.hidden_size
-                weights = [w for unit in rnn._unit_params() for w in unit]
-                p = _lib.LstmParams()
-                p.num_layers, p.input_size, p.hidden_size = L, d_in, H
-                for l in range(L):
-                    p.w_ih[l], p.w_hh[l], p.b_ih[l], p.b_hh[l] = [weights[4 * l + k].data_ptr() for k in range(4)]
+                p, _, _ = _lstm_params(rnn, d_in)
                 h0 = c0 = None
                 if rnn.init_state is not None:
                     h0, c0 = [t.detach().to(dev, torch.float32).contiguous() for t in rnn.init_state]
@@ -616,7 +616,7 @@ class LgdTrainEngine(object):
             for k in (0, 1):
                 # (three streams: each network's products follow its own backward on its own stream, no fork needed)
                 where = (1 - k) if three else 0
-                with (self._on_side(where) if side_w else _nothing()):
+                with (self._on_side(where) if side_w else contextlib.nullcontext()):
                     if pend[k]:
                         self._mlp_wgrad(views[k], [q[0] for q in pend[k]], d_x, [q[1] for q in pend[k]],
                                         [q[2] for q in pend[k]], grads[k], T)
@@ -648,15 +648,11 @@ class LgdTrainEngine(object):
                                                         None, None, None if first else dy.data_ptr(), H, 0, 0.0,
                                                         self.stream))
                     first = False
-                weights = [w for unit in rnn._unit_params() for w in unit]
-                p, g = _lib.LstmParams(), _lib.LstmGrads()
-                p.num_layers, p.input_size, p.hidden_size = L, d_in, H
                 self._deposit(named)
                 named = []
+                weights = [w for unit in rnn._unit_params() for w in unit]
                 lg = [self._grad_like(w) for w in weights]
-                for l in range(L):
-                    p.w_ih[l], p.w_hh[l], p.b_ih[l], p.b_hh[l] = [weights[4 * l + k].data_ptr() for k in range(4)]
-                    g.w_ih[l], g.w_hh[l], g.b_ih[l], g.b_hh[l] = [lg[4 * l + k].data_ptr() for k in range(4)]
+                p, g, _ = _lstm_params(rnn, d_in, lg)
                 nbytes = lib.empose_lstm_train_workspace_bytes(C.byref(p), B, F)
                 ws = self.ws(nbytes)
                 _lib.check(lib.empose_lstm_train_bwd(C.byref(p), B, F, ctx['x0'].data_ptr(), d_in, ctx['lens32'].data_ptr(),

@@ -321,10 +321,11 @@ def _mlp_pair(in_dim, hidden, seed):
     return [n.to(DEV).train() for n in nets]
 
 
-def _run_mlp_train(nets, x, d_outs, M, pair, deferred=True, saves_from=None):
+def _run_mlp_train(nets, x, d_outs, M, pair, deferred=True, saves_from=None, after_forward=None):
     """forward + reverse sweep of both networks through the C ABI; returns everything they write.  `saves_from`: the
     reverse sweep reads these saved activations instead of its own forward's (same PReLU branch decisions for two
-    reverse paths under comparison: an activation within rounding of zero flips one element's branch otherwise)."""
+    reverse paths under comparison: an activation within rounding of zero flips one element's branch otherwise).
+    `after_forward`: called between the forward and the reverse sweep (tests/test_train_mlp_layout.py flips options there)."""
     import ctypes as C
     from em_pose_amd.nn.train_engine import _MlpView
     lib = _lib.lib()
@@ -350,6 +351,8 @@ def _run_mlp_train(nets, x, d_outs, M, pair, deferred=True, saves_from=None):
         _lib.check(lib.empose_mlp_train_fwd_pair(C.byref(ps[0]), C.byref(ps[1]), M, _lib.dptr(x), ldx, _lib.dptr(outs[0]), 66,
                                                  _lib.dptr(outs[1]), 10, _lib.dptr(saves[0]), _lib.dptr(saves[1]),
                                                  _lib.dptr(ws), nbytes, stream))
+        if after_forward is not None:
+            after_forward()
         if saves_from is not None:
             fwd_saves = [t.clone() for t in saves]
             for t, src in zip(saves, saves_from):
@@ -362,6 +365,8 @@ def _run_mlp_train(nets, x, d_outs, M, pair, deferred=True, saves_from=None):
         for i in (0, 1):
             _lib.check(lib.empose_mlp_train_fwd(C.byref(ps[i]), M, _lib.dptr(x), ldx, _lib.dptr(outs[i]), outs[i].shape[1],
                                                 _lib.dptr(saves[i]), _lib.dptr(ws), nbytes, stream))
+        if after_forward is not None:
+            after_forward()
         if saves_from is not None:
             fwd_saves = [t.clone() for t in saves]
             for t, src in zip(saves, saves_from):
@@ -376,7 +381,7 @@ def _run_mlp_train(nets, x, d_outs, M, pair, deferred=True, saves_from=None):
                                                     _lib.dptr(saves[i]), C.byref(gs[i]), 0, _lib.dptr(ws), nbytes, stream))
     torch.cuda.synchronize()
     _lib.check(lib.empose_async_status())
-    res = {'out': outs, 'save': saves if saves_from is None else fwd_saves, 'stash': stashes, 'grads': grads}
+    res = {'out': outs, 'save': saves if saves_from is None else fwd_saves, 'stash': stashes, 'grads': grads, 'views': views}
     res['bn'] = [[t.clone() for k, t in n.state_dict().items() if 'running_' in k or 'num_batches' in k] for n in nets]
     return res
 
