@@ -142,42 +142,43 @@ struct Mlp {
   Dense layers[EMPOSE_MAX_DENSE];
 };
 
+// The three-piece bf16 weights of a stack, per unit, in the fragment order of one family of step kernels (api_lstm.hip
+// LSTM_LAYOUTS): chain -- lstm_x3.hip, lstm_rows_x3.hip; mid -- lstm_mid_x3.hip, lstm_midseq_x3.hip; mid16 -- lstm_mid16_x3.hip
+enum LstmLayout { LSTM_CHAIN = 0, LSTM_MID, LSTM_MID16, LSTM_N_LAYOUTS };
+struct LstmW3 { unsigned short* ih[8] = {}; unsigned short* hh[8] = {}; };
 struct Lstm {   // unit u = layer * dirs + direction
   int num_layers = 0, input_size = 0, H = 0, dirs = 1;
-  float* w_ih[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  float* w_hh[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  float* bias[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};  // b_ih + b_hh
-  // the same matrices as three bf16 pieces per weight in the fragment order of lstm_x3.hip (uni-directional stacks only)
-  unsigned short* w3_ih[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  unsigned short* w3_hh[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  // ... and in the fragment order of lstm_mid_x3.hip (8-unit blocks, the four gates of a unit in one 32-column tile)
-  unsigned short* w3m_ih[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  unsigned short* w3m_hh[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  // ... and in the order of lstm_mid16_x3.hip (4-unit blocks, k-steps of 32)
-  unsigned short* w3q_ih[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-  unsigned short* w3q_hh[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  float* w_ih[8] = {};
+  float* w_hh[8] = {};
+  float* bias[8] = {};   // b_ih + b_hh
+  LstmW3 w3[LSTM_N_LAYOUTS];   // uni-directional stacks with H % 32 == 0 only, else null
 };
 
 // Uploads an LSTM stack (api_lstm.hip): fp32 weights, summed biases and, for uni-directional stacks with H % 32 == 0, the
-// three-piece bf16 weights in the orders of the x3 step kernels.
+// three-piece bf16 weights in every layout of the table above.
 int pack_lstm(std::vector<void*>& allocs, const empose_lstm_desc& r, int dirs, const float* const* w_ih,
               const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, Lstm* out);
 
 // ---- the LSTM dispatcher (api_lstm.hip) ------------------------------------------------------------------------
-// The static choice (plan_lstm) for a stack and a batch under the options of the moment: which whole-sequence
-// cooperative kernels get buffers, and which kernel runs the steps.  The cooperative launches may still fall back to
-// the steps at run time.
-enum class LstmStep { wave, chain_x3, rows_x3, mid_x3, mid16_x3 };
+// What one call does, decided in ONE place (plan_lstm) from the stack, the shape and the options of the moment: which
+// whole-sequence kernels get buffers (persist and seq by shape alone, midseq by shape and options); the cooperative
+// launches to try, in order -- each may report done = false at run time (its workgroups cannot all be resident) -- and
+// the step kernel that runs when none finished, with its weight layout and how it treats the state of new sequences.
+enum class LstmStep { wave, chain_x3, rows_x3, mid_x3, mid16_x3 };   // wave: lstm_wave (fp32); else three bf16 pieces
+enum class LstmCoop { persist, seq, midseq };   // lstm_persist_kernel (small), lstm_seq_kernel (large), lstm_midseq_x3.hip
 struct LstmPlan {
-  bool persist = false;   // lstm_persist_kernel, small batches (its exchange words; the launch checks option lstm_persist)
-  bool seq = false;       // lstm_seq_kernel, large batches (third hidden buffers + counters; the launch checks lstm_seq)
-  bool midseq = false;    // lstm_midseq_x3.hip, medium batches
+  bool persist = false;   // exchange words of lstm_persist_kernel
+  bool seq = false;       // third hidden buffers + counters of lstm_seq_kernel
+  bool midseq = false;    // hidden-state plane sets + progress counters of lstm_midseq_x3.hip
   bool x3 = false;        // the bf16 piece planes of the inputs and hidden states (a three-piece step kernel or midseq)
-  LstmStep step = LstmStep::wave;   // wave: lstm_wave (fp32); else the three-piece step kernel
+  int n_coop = 0; LstmCoop coop[3];
+  LstmStep step = LstmStep::wave; LstmLayout layout = LSTM_CHAIN;   // (the layout of the three-piece step kernel)
+  // three-piece steps on new sequences (option lstm_state_direct): the zero hidden-state planes by one fill, and on the
+  // chain kernel h_n / c_n stored by the last step of each layer
+  bool zero_planes = false, state_direct = false;
 };
 
 struct LstmWs {
-  LstmPlan plan;
   float* h[8][2];
   float* c[8];
   float* yb[2];   // [B][F][2H] ping-pong between the layers of a bidirectional stack
