@@ -55,6 +55,13 @@ struct Carver {
     off += align_up(count * sizeof(float));
     return r;
   }
+  // The bytes a layout takes: `carve` run on a null base (the workspace-size queries).
+  template <typename Carve>
+  static size_t measure(Carve carve) {
+    Carver c(nullptr);
+    carve(c);
+    return c.off;
+  }
 };
 
 template <typename T>
@@ -141,6 +148,32 @@ struct Mlp {
   int n_layers = 0, skip = 0;
   Dense layers[EMPOSE_MAX_DENSE];
 };
+
+// ---- operand set-ups the host drivers share ---------------------------------------------------------------------
+// One product with no epilogue: C[M][N] = A . W^T.
+inline GemmProb plain_prob(const float* A, int lda, const float* W, int ldw, float* C, int ldc, int M, int N, int K) {
+  GemmProb p;
+  p.A = A; p.lda = lda; p.W = W; p.ldw = ldw; p.C = C; p.ldc = ldc;
+  p.M = M; p.N = N; p.K = K;
+  p.scale = nullptr; p.shift = nullptr; p.resid = nullptr; p.ldr = 0; p.act = 0; p.slope = 0.f;
+  return p;
+}
+// A packed layer on M rows: the product with the layer's epilogue.
+inline GemmProb linear_prob(const float* A, int lda, const Dense& d, float* C, int ldc, int M) {
+  GemmProb p = plain_prob(A, lda, d.w, d.in_dim, C, ldc, M, d.out_dim, d.in_dim);
+  p.scale = d.scale; p.shift = d.shift; p.act = d.act; p.slope = d.slope;
+  return p;
+}
+// Plain evaluation: the caller's rows are read in place (no update: the kernel does not write them back), no copies.
+// Where rot / feat / theta_t go, T, F and the Rodrigues convention are the evaluation's to fill in.
+inline FeatArgs plain_feat_args(const float* theta, int ld_theta, const float* beta, int ld_beta) {
+  FeatArgs fa;
+  fa.theta = const_cast<float*>(theta); fa.ld_theta = ld_theta; fa.beta = const_cast<float*>(beta); fa.ld_beta = ld_beta;
+  fa.d_theta = nullptr; fa.d_beta = nullptr; fa.theta_step = 0.f; fa.beta_keep = 1.f; fa.beta_step = 0.f;
+  fa.shape_avg = 0;
+  fa.out_theta = fa.out_beta = fa.out_theta2 = fa.out_beta2 = nullptr;
+  return fa;
+}
 
 // The three-piece bf16 weights of a stack, per unit, in the fragment order of one family of step kernels (api_lstm.hip
 // LSTM_LAYOUTS): chain -- lstm_x3.hip, lstm_rows_x3.hip; mid -- lstm_mid_x3.hip, lstm_midseq_x3.hip; mid16 -- lstm_mid16_x3.hip

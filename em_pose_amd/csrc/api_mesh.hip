@@ -190,37 +190,46 @@ MeshWs carve_mesh(Carver& c, const empose_mesh* mesh, size_t S) {
   return w;
 }
 
-// Slab by slab: Rodrigues + feature row, rest joints (the joint rows of wc), kinematic chain (all n_joints posed
-// joints + the 22 skinning transforms) and, when `vertices` is given, the full-mesh kernel.
-int run_mesh(const empose_mesh_t* mesh, int T, const float* poses, const float* betas, const float* trans,
-                    float* vertices, float* joints, void* workspace, hipStream_t stream, bool bf16x3 = false) {
+// The forward prologue of the slab of n frames from t0: Rodrigues + feature row, rest joints (the joint rows of wc) and,
+// when `joints` says where the posed joints go, the kinematic chain (all n_joints posed joints + the 22 skinning
+// transforms in w.xf); `trans`: the slab's translations, or null when none applies.
+int mesh_slab_prologue(const empose_mesh* mesh, const MeshWs& w, const float* poses, const float* betas, int t0, int n,
+                       const float* trans, float* joints, hipStream_t stream) {
+  const int jw = mesh->ncp - mesh->j_off;
+  FeatArgs fa = plain_feat_args(poses + (size_t)t0 * 66, 66, betas + (size_t)t0 * 10, 10);
+  fa.rot = w.rot; fa.feat = w.feat; fa.T = n; fa.F = 1; fa.rod_conv = mesh->rod_conv;
+  HIP_CHECK(launch_update_feat(fa, stream), "update_feat kernel");
+  GemmBatch b;
+  b.count = 1;
+  b.p[0] = plain_prob(w.feat, 200, mesh->wc + (size_t)mesh->j_off * 200, 200, w.jrest, jw, n, jw, 200);
+  HIP_CHECK(launch_gemm(b, stream), "rest-joint gemm");
+  if (!joints) return EMPOSE_OK;
+  MeshChainArgs ca;
+  ca.rot = w.rot; ca.out = w.jrest; ca.ncp = jw; ca.j_off = 0; ca.parents = mesh->parents;
+  ca.trans = trans; ca.xf = w.xf; ca.joints = joints; ca.T = n; ca.n_joints = mesh->n_joints;
+  HIP_CHECK(launch_mesh_chain(ca, stream), "mesh chain");
+  return EMPOSE_OK;
+}
+
+// The three forward entry points, checked: slab by slab the prologue and, with `want_vertices`, the full-mesh kernel --
+// the default arithmetic, or with `bf16x3` the two-piece bf16 variant.
+int mesh_fwd(const empose_mesh_t* mesh, int T, const float* poses, const float* betas, const float* trans,
+             bool want_vertices, float* vertices, float* joints, void* workspace, size_t workspace_bytes,
+             empose_stream_t stream_, bool bf16x3) {
+  if (!mesh || !poses || !betas || (want_vertices && !vertices) || !joints || !workspace)
+    return fail(EMPOSE_EINVAL, "null argument");
+  if (bf16x3 && !mesh->wc_bf16) return fail(EMPOSE_EINVAL, "the mesh handle was created without with_bf16x3");
+  if (T <= 0) return fail(EMPOSE_EINVAL, "T must be positive");
+  if (workspace_bytes < empose_mesh_workspace_bytes(mesh, T)) return fail(EMPOSE_ENOMEM, "workspace too small");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
   const int S = T < MESH_SLAB ? T : MESH_SLAB;
-  const int jw = mesh->ncp - mesh->j_off, nj = mesh->n_joints;
   Carver c(workspace);
   const MeshWs w = carve_mesh(c, mesh, (size_t)S);
   for (int t0 = 0; t0 < T; t0 += S) {
     const int n = (T - t0) < S ? (T - t0) : S;
-    FeatArgs fa;   // plain evaluation: the caller's rows are read in place
-    fa.theta = const_cast<float*>(poses) + (size_t)t0 * 66; fa.ld_theta = 66;
-    fa.beta = const_cast<float*>(betas) + (size_t)t0 * 10; fa.ld_beta = 10;
-    fa.d_theta = nullptr; fa.d_beta = nullptr; fa.theta_step = 0.f; fa.beta_keep = 1.f; fa.beta_step = 0.f;
-    fa.shape_avg = 0; fa.rot = w.rot; fa.feat = w.feat;
-    fa.out_theta = fa.out_beta = fa.out_theta2 = fa.out_beta2 = nullptr;
-    fa.T = n; fa.F = 1; fa.rod_conv = mesh->rod_conv;
-    HIP_CHECK(launch_update_feat(fa, stream), "update_feat kernel");
-    GemmBatch b;
-    b.count = 1;
-    GemmProb& p = b.p[0];
-    p.A = w.feat; p.lda = 200; p.W = mesh->wc + (size_t)mesh->j_off * 200; p.ldw = 200; p.C = w.jrest; p.ldc = jw;
-    p.M = n; p.N = jw; p.K = 200;
-    p.scale = nullptr; p.shift = nullptr; p.resid = nullptr; p.ldr = 0; p.act = 0; p.slope = 0.f;
-    HIP_CHECK(launch_gemm(b, stream), "rest-joint gemm");
     const float* tr = trans ? trans + (size_t)t0 * 3 : nullptr;
-    MeshChainArgs ca;
-    ca.rot = w.rot; ca.out = w.jrest; ca.ncp = jw; ca.j_off = 0; ca.parents = mesh->parents;
-    ca.trans = tr; ca.xf = w.xf; ca.joints = joints + (size_t)t0 * nj * 3; ca.T = n; ca.n_joints = nj;
-    HIP_CHECK(launch_mesh_chain(ca, stream), "mesh chain");
-    if (!vertices) continue;
+    TRY(mesh_slab_prologue(mesh, w, poses, betas, t0, n, tr, joints + (size_t)t0 * mesh->n_joints * 3, stream));
+    if (!want_vertices) continue;
     MeshSkinArgs sa;
     sa.feat = w.feat; sa.wc = mesh->wc; sa.xf = w.xf; sa.skin_idx = mesh->skin_idx; sa.skin_w = mesh->skin_w;
     sa.kb = mesh->kb; sa.trans = tr; sa.vertices = vertices + (size_t)t0 * mesh->V * 3; sa.T = n; sa.V = mesh->V;
@@ -293,9 +302,7 @@ int empose_virtual_sensors_fwd(int T, int V, const float* vertices, int M, int m
 // ---- virtual sensors: vector-Jacobian product --------------------------------------------------------------------
 size_t empose_virtual_sensors_vjp_workspace_bytes(int T, int M) {
   if (T <= 0 || M <= 0) return 0;
-  Carver c(nullptr);
-  c.f((size_t)sensors_vjp_slab(T, M) * M * SENSOR_VJP_ROW);
-  return c.off;
+  return Carver::measure([&](Carver& c) { c.f((size_t)sensors_vjp_slab(T, M) * M * SENSOR_VJP_ROW); });
 }
 
 int empose_virtual_sensors_vjp(int T, int V, const float* vertices, int M, int max_deg, const int* center,
@@ -390,45 +397,31 @@ int empose_mesh_n_joints(const empose_mesh_t* mesh) { return mesh ? mesh->n_join
 
 size_t empose_mesh_workspace_bytes(const empose_mesh_t* mesh, int T) {
   if (!mesh || T <= 0) return 0;
-  Carver c(nullptr);
-  carve_mesh(c, mesh, T < MESH_SLAB ? T : MESH_SLAB);
-  return c.off;
+  return Carver::measure([&](Carver& c) { carve_mesh(c, mesh, T < MESH_SLAB ? T : MESH_SLAB); });
 }
 
 int empose_mesh_vertices_fwd(const empose_mesh_t* mesh, int T, const float* poses, const float* betas,
                              const float* trans, float* vertices, float* joints, void* workspace,
                              size_t workspace_bytes, empose_stream_t stream_) {
-  if (!mesh || !poses || !betas || !vertices || !joints || !workspace) return fail(EMPOSE_EINVAL, "null argument");
-  if (T <= 0) return fail(EMPOSE_EINVAL, "T must be positive");
-  if (workspace_bytes < empose_mesh_workspace_bytes(mesh, T)) return fail(EMPOSE_ENOMEM, "workspace too small");
-  return run_mesh(mesh, T, poses, betas, trans, vertices, joints, workspace, static_cast<hipStream_t>(stream_));
+  return mesh_fwd(mesh, T, poses, betas, trans, true, vertices, joints, workspace, workspace_bytes, stream_, false);
 }
 
 int empose_mesh_vertices_fwd_bf16x3(const empose_mesh_t* mesh, int T, const float* poses, const float* betas,
                                     const float* trans, float* vertices, float* joints, void* workspace,
                                     size_t workspace_bytes, empose_stream_t stream_) {
-  if (!mesh || !poses || !betas || !vertices || !joints || !workspace) return fail(EMPOSE_EINVAL, "null argument");
-  if (!mesh->wc_bf16) return fail(EMPOSE_EINVAL, "the mesh handle was created without with_bf16x3");
-  if (T <= 0) return fail(EMPOSE_EINVAL, "T must be positive");
-  if (workspace_bytes < empose_mesh_workspace_bytes(mesh, T)) return fail(EMPOSE_ENOMEM, "workspace too small");
-  return run_mesh(mesh, T, poses, betas, trans, vertices, joints, workspace, static_cast<hipStream_t>(stream_), true);
+  return mesh_fwd(mesh, T, poses, betas, trans, true, vertices, joints, workspace, workspace_bytes, stream_, true);
 }
 
 int empose_mesh_joints_fwd(const empose_mesh_t* mesh, int T, const float* poses, const float* betas,
                            const float* trans, float* joints, void* workspace, size_t workspace_bytes,
                            empose_stream_t stream_) {
-  if (!mesh || !poses || !betas || !joints || !workspace) return fail(EMPOSE_EINVAL, "null argument");
-  if (T <= 0) return fail(EMPOSE_EINVAL, "T must be positive");
-  if (workspace_bytes < empose_mesh_workspace_bytes(mesh, T)) return fail(EMPOSE_ENOMEM, "workspace too small");
-  return run_mesh(mesh, T, poses, betas, trans, nullptr, joints, workspace, static_cast<hipStream_t>(stream_));
+  return mesh_fwd(mesh, T, poses, betas, trans, false, nullptr, joints, workspace, workspace_bytes, stream_, false);
 }
 
 // ---- full-mesh vector-Jacobian product -------------------------------------------------------------------------
 size_t empose_mesh_vjp_workspace_bytes(const empose_mesh_t* mesh, int T) {
   if (!mesh || T <= 0) return 0;
-  Carver c(nullptr);
-  carve_mesh_vjp(c, mesh, T);
-  return c.off;
+  return Carver::measure([&](Carver& c) { carve_mesh_vjp(c, mesh, T); });
 }
 
 int empose_mesh_vjp(const empose_mesh_t* mesh, int T, const float* poses, const float* betas, const float* d_vertices,
@@ -446,30 +439,12 @@ int empose_mesh_vjp(const empose_mesh_t* mesh, int T, const float* poses, const 
   const MeshVjpWs w = carve_mesh_vjp(c, mesh, T);
   for (int t0 = 0; t0 < T; t0 += S) {
     const int n = (T - t0) < S ? (T - t0) : S;
-    // the forward's rotations, features, rest joints and transforms (as run_mesh)
-    FeatArgs fa;
-    fa.theta = const_cast<float*>(poses) + (size_t)t0 * 66; fa.ld_theta = 66;
-    fa.beta = const_cast<float*>(betas) + (size_t)t0 * 10; fa.ld_beta = 10;
-    fa.d_theta = nullptr; fa.d_beta = nullptr; fa.theta_step = 0.f; fa.beta_keep = 1.f; fa.beta_step = 0.f;
-    fa.shape_avg = 0; fa.rot = w.f.rot; fa.feat = w.f.feat;
-    fa.out_theta = fa.out_beta = fa.out_theta2 = fa.out_beta2 = nullptr;
-    fa.T = n; fa.F = 1; fa.rod_conv = mesh->rod_conv;
-    HIP_CHECK(launch_update_feat(fa, stream), "update_feat kernel");
-    GemmBatch b;
-    b.count = 1;
-    GemmProb& p = b.p[0];
-    p.A = w.f.feat; p.lda = 200; p.W = mesh->wc + (size_t)mesh->j_off * 200; p.ldw = 200; p.C = w.f.jrest; p.ldc = jw;
-    p.M = n; p.N = jw; p.K = 200;
-    p.scale = nullptr; p.shift = nullptr; p.resid = nullptr; p.ldr = 0; p.act = 0; p.slope = 0.f;
-    HIP_CHECK(launch_gemm(b, stream), "rest-joint gemm");
+    // the forward's rotations, features and rest joints, and for the vertex sweeps the transforms: their posed joints are
+    // not needed and land in the reverse's scratch, which is written later
     const float* dv = d_vertices ? d_vertices + (size_t)t0 * mesh->V * 3 : nullptr;
+    static_assert(MESH_MAX_JOINTS * 3 <= 200, "posed joints fit a feature row");
+    TRY(mesh_slab_prologue(mesh, w.f, poses, betas, t0, n, nullptr, dv ? w.dfeat : nullptr, stream));
     if (dv) {
-      // the transforms; the posed joints are not needed and land in the reverse's scratch, which is written later
-      MeshChainArgs ca;
-      ca.rot = w.f.rot; ca.out = w.f.jrest; ca.ncp = jw; ca.j_off = 0; ca.parents = mesh->parents;
-      ca.trans = nullptr; ca.xf = w.f.xf; ca.joints = w.dfeat; ca.T = n; ca.n_joints = nj;
-      static_assert(MESH_MAX_JOINTS * 3 <= 200, "posed joints fit a feature row");
-      HIP_CHECK(launch_mesh_chain(ca, stream), "mesh chain");
       MeshVjpArgs va;
       va.feat = w.f.feat; va.xf = w.f.xf; va.dv = dv;
       va.wc_frag = mesh->wc_frag; va.wc_vjp = mesh->wc_vjp; va.skin_dense = mesh->skin_dense;
@@ -492,10 +467,8 @@ int empose_mesh_vjp(const empose_mesh_t* mesh, int T, const float* poses, const 
     // d_feat = (vertex sweep) + d_jrest . wc[j_off:]
     GemmBatch g;
     g.count = 1;
-    GemmProb& q = g.p[0];
-    q.A = w.djrest; q.lda = mesh->jw4; q.W = mesh->wj_t; q.ldw = mesh->jw4; q.C = w.dfeat; q.ldc = 200;
-    q.M = n; q.N = 200; q.K = mesh->jw4;
-    q.scale = nullptr; q.shift = nullptr; q.resid = dv ? w.dfeat_v : nullptr; q.ldr = 200; q.act = 0; q.slope = 0.f;
+    g.p[0] = plain_prob(w.djrest, mesh->jw4, mesh->wj_t, mesh->jw4, w.dfeat, 200, n, 200, mesh->jw4);
+    g.p[0].resid = dv ? w.dfeat_v : nullptr; g.p[0].ldr = 200;
     HIP_CHECK(launch_gemm(g, stream), "rest-joint reverse gemm");
     RodBwdArgs ra;
     ra.theta = poses + (size_t)t0 * 66; ra.ld_theta = 66; ra.d_rot = w.drot; ra.d_feat = w.dfeat;
@@ -531,9 +504,7 @@ int empose_root_frame_fwd(int T, int seg_len, int rodrigues, const float* root, 
 
 size_t empose_root_frame_vjp_workspace_bytes(int T, int seg_len) {
   if (T <= 0 || seg_len <= 0 || T % seg_len != 0) return 0;
-  Carver c(nullptr);
-  c.f((size_t)root_frame_vjp_waves(T, seg_len) * ROOT_FRAME_SUMS);
-  return c.off;
+  return Carver::measure([&](Carver& c) { c.f((size_t)root_frame_vjp_waves(T, seg_len) * ROOT_FRAME_SUMS); });
 }
 
 int empose_root_frame_vjp(int T, int seg_len, int rodrigues, const float* root, int ld_root, const float* trans,

@@ -212,222 +212,258 @@ SmplWs carve_smpl(Carver& c, const empose_model* m, int T) {
   w.tgt_t = c.f(Tp * 144);
   return w;
 }
-// The frame-per-lane path pays once its 64-frame workgroups fill the 256 CUs (one per CU, 152 KB of LDS each): from
-// 16384 frames on.  Measured at 8192 frames (the training step at 256 windows): 2 % slower than the general kernel.
-// Option "smpl_tile": 0 never, 1 by size, 2 always (tests).
-bool use_tile_path(const empose_model* m, int T, const float* cot_joints = nullptr) {
-  const int opt = options().smpl_tile;
-  return m->tile_ok && opt != 0 && !cot_joints && (opt == 2 || T >= 16384);
-}
 
-struct UpdWs {
-  float* buf[3];  // [2 nets][T][hidden_max] each; buf[2] only when a net uses skip connections
-};
+struct UpdWs { float* buf[3]; };  // [2 nets][T][hidden_max] each; buf[2] only when a net uses skip connections
 UpdWs carve_upd(Carver& c, const empose_model* m, int T) {
-  UpdWs w;
-  w.buf[0] = c.f((size_t)2 * T * m->hidden_max);
-  w.buf[1] = c.f((size_t)2 * T * m->hidden_max);
-  w.buf[2] = m->any_skip ? c.f((size_t)2 * T * m->hidden_max) : nullptr;
-  return w;
+  const size_t n = (size_t)2 * T * m->hidden_max;
+  return {{c.f(n), c.f(n), m->any_skip ? c.f(n) : nullptr}};
 }
 
-GemmProb linear_prob(const float* A, int lda, const Dense& d, float* C, int ldc, int M) {
-  GemmProb p;
-  p.A = A; p.lda = lda; p.W = d.w; p.ldw = d.in_dim; p.C = C; p.ldc = ldc;
-  p.M = M; p.N = d.out_dim; p.K = d.in_dim;
-  p.scale = d.scale; p.shift = d.shift; p.resid = nullptr; p.ldr = 0; p.act = d.act; p.slope = d.slope;
+// One or two MLPs that share the input x (the update nets / the init nets), both nets per launch.
+struct MlpRun {
+  const Mlp* nets[2]; int n_nets;
+  float* outs[2]; int out_ld[2];
+  const float* x; int ldx; int T;
+  bool init_net;   // (profiler tag only)
+};
+
+// Large batches: every layer of both nets in ONE launch (mlp_fused.hip); a workgroup keeps 128 rows through all the
+// layers. Needs enough row panels to fill the chip and layers no wider than the four 128-column waves.
+// x3: fp32 products from three bf16 pieces per operand on the bf16 matrix path (mlp_fused_x3.hip; fp32-equivalent, 2.7
+// times the fp32 instruction's rate): needs every hidden width to be whole quads of k-steps of the next layer.
+struct MlpPlan { bool one_launch, x3; };
+MlpPlan plan_mlps(const MlpRun& r) {
+  const int L = r.nets[0]->n_layers;
+  MlpPlan p;
+  p.one_launch = options().mlp_fused != 0 && L <= FUSED_MAX_LAYERS && (long)((r.T + 63) / 64) * r.n_nets >= 256;
+  p.x3 = options().mlp_x3 != 0;
+  for (int i = 0; i < r.n_nets; ++i) {
+    const Mlp& net = *r.nets[i];
+    if (net.skip || net.layers[0].in_dim > FUSED_MAX_WIDTH) p.one_launch = false;   // no room for a block input
+    for (int l = 0; l < L; ++l) {
+      const Dense& d = net.layers[l];
+      if (d.out_dim > FUSED_MAX_WIDTH || d.act > 1) p.one_launch = false;
+      if (l + 1 < L && (d.out_dim % 64 != 0 || !d.wp3)) p.x3 = false;
+    }
+  }
+  p.x3 = p.x3 && p.one_launch;
   return p;
 }
 
-// Runs one or two MLPs that share the input x (the update nets / the init nets) layer by layer, both nets per launch.
-// Hidden blocks are layer pairs (1,2), (3,4), ...; with skip connections the block input is added to the block
-// output (reference layers.py:35-43), which needs the block input kept alive in a third buffer.
-int run_mlps(const Mlp* nets[2], int n_nets, float* outs[2], const int out_ld[2], const float* x, int ldx, int T,
-             const UpdWs& ws, int hidden_max, hipStream_t stream, bool init_net = false) {
-  const int L = nets[0]->n_layers;
-  for (int i = 1; i < n_nets; ++i)
-    if (nets[i]->n_layers != L) return fail(EMPOSE_EINVAL, "paired MLPs must have the same depth");
-
-  // Large batches: every layer of both nets in ONE launch (mlp_fused.hip); a workgroup keeps 128 rows through all the
-  // layers. Needs enough row panels to fill the chip and layers no wider than the four 128-column waves.
-  {
-    bool ok = options().mlp_fused != 0 && L <= FUSED_MAX_LAYERS && (long)((T + 63) / 64) * n_nets >= 256;
-    for (int i = 0; i < n_nets && ok; ++i) {
-      if (nets[i]->skip || nets[i]->layers[0].in_dim > FUSED_MAX_WIDTH) ok = false;   // no room for a block input
-      for (int l = 0; l < L; ++l) {
-        const Dense& d = nets[i]->layers[l];
-        if (d.out_dim > FUSED_MAX_WIDTH || d.act > 1) ok = false;
-      }
-    }
-    if (ok) {
-      // fp32 products from three bf16 pieces per operand on the bf16 matrix path (mlp_fused_x3.hip; fp32-equivalent, 2.7
-      // times the fp32 instruction's rate): needs every hidden width to be whole quads of k-steps of the next layer
-      bool x3 = options().mlp_x3 != 0;
-      for (int i = 0; i < n_nets && x3; ++i)
-        for (int l = 0; l + 1 < L; ++l)
-          if (nets[i]->layers[l].out_dim % 64 != 0 || !nets[i]->layers[l].wp3) x3 = false;
-      FusedMlpArgs fa;
-      fa.count = n_nets; fa.M = T;
-      for (int i = 0; i < n_nets; ++i) {
-        FusedNet& fn = fa.net[i];
-        fn.x = x; fn.ldx = ldx; fn.out = outs[i]; fn.ld_out = out_ld[i];
-        fn.n_layers = L;   // the activations stay in LDS: no scratch
-        for (int l = 0; l < L; ++l) {
-          const Dense& d = nets[i]->layers[l];
-          FusedLayer& fl = fn.layer[l];
-          fl.W = x3 ? d.wp3 : d.wp; fl.K = d.in_dim; fl.N = d.out_dim; fl.scale = d.scale; fl.shift = d.shift;
-          fl.slope = d.slope; fl.act = d.act;
-        }
-      }
-      prof_mark(init_net ? P_INIT_MLP : P_MLP_FUSED, stream);
-      HIP_CHECK(x3 ? launch_mlp_fused_x3(fa, stream) : launch_mlp_fused(fa, stream), "fused mlp launch");
-      prof_mark(P_END, stream);   // close the dominant kernel's interval at its completion, not at the next launch
-      return EMPOSE_OK;
+int run_mlps_one_launch(const MlpRun& r, bool x3, hipStream_t stream) {
+  FusedMlpArgs fa;
+  fa.count = r.n_nets; fa.M = r.T;
+  for (int i = 0; i < r.n_nets; ++i) {
+    FusedNet& fn = fa.net[i];
+    fn.x = r.x; fn.ldx = r.ldx; fn.out = r.outs[i]; fn.ld_out = r.out_ld[i];
+    fn.n_layers = r.nets[i]->n_layers;   // the activations stay in LDS: no scratch
+    for (int l = 0; l < fn.n_layers; ++l) {
+      const Dense& d = r.nets[i]->layers[l];
+      FusedLayer& fl = fn.layer[l];
+      fl.W = x3 ? d.wp3 : d.wp; fl.K = d.in_dim; fl.N = d.out_dim; fl.scale = d.scale; fl.shift = d.shift;
+      fl.slope = d.slope; fl.act = d.act;
     }
   }
+  prof_mark(r.init_net ? P_INIT_MLP : P_MLP_FUSED, stream);
+  HIP_CHECK(x3 ? launch_mlp_fused_x3(fa, stream) : launch_mlp_fused(fa, stream), "fused mlp launch");
+  prof_mark(P_END, stream);   // close the dominant kernel's interval at its completion, not at the next launch
+  return EMPOSE_OK;
+}
 
+// Layer by layer.  Hidden blocks are layer pairs (1,2), (3,4), ...; with skip connections the block input is added to
+// the block output (reference layers.py:35-43), which needs the block input kept alive in a third buffer.
+int run_mlps_layers(const MlpRun& r, const UpdWs& ws, int hidden_max, hipStream_t stream) {
+  const int L = r.nets[0]->n_layers, T = r.T;
   int cur[2] = {-1, -1}, block_in[2] = {-1, -1};
   for (int l = 0; l < L; ++l) {
     GemmBatch b;
-    b.count = n_nets;
+    b.count = r.n_nets;
     int nxt[2] = {-1, -1};
-    for (int i = 0; i < n_nets; ++i) {
-      const Dense& d = nets[i]->layers[l];
+    for (int i = 0; i < r.n_nets; ++i) {
+      const Mlp& net = *r.nets[i];
+      const Dense& d = net.layers[l];
       auto buf = [&](int k) { return ws.buf[k] + (size_t)i * T * hidden_max; };
-      const float* in = (l == 0) ? x : buf(cur[i]);
-      const int ld_in = (l == 0) ? ldx : nets[i]->layers[l - 1].out_dim;
+      const float* in = (l == 0) ? r.x : buf(cur[i]);
+      const int ld_in = (l == 0) ? r.ldx : net.layers[l - 1].out_dim;
       const bool block_first = (l >= 1) && (l % 2 == 1) && (l < L - 1);
       const bool block_last = (l >= 2) && (l % 2 == 0) && (l < L - 1);
       if (block_first) block_in[i] = cur[i];
-      float* out;
-      int ld_out;
-      if (l == L - 1) {
-        out = outs[i];
-        ld_out = out_ld[i];
-      } else {
+      float* out = r.outs[i];
+      int ld_out = r.out_ld[i];
+      if (l < L - 1) {
         int k = 0;
-        while (k == cur[i] || (nets[i]->skip && k == block_in[i])) ++k;
+        while (k == cur[i] || (net.skip && k == block_in[i])) ++k;
         if (k > 2 || !ws.buf[k]) return fail(EMPOSE_EINVAL, "internal: MLP scratch buffers exhausted");
         nxt[i] = k;
         out = buf(k);
         ld_out = d.out_dim;
       }
       b.p[i] = linear_prob(in, ld_in, d, out, ld_out, T);
-      if (block_last && nets[i]->skip) {
+      if (block_last && net.skip) {
         b.p[i].resid = buf(block_in[i]);
         b.p[i].ldr = d.out_dim;
       }
     }
-    b.role = (!init_net && l > 0 && l < L - 1) ? 1 : 0;
-    prof_mark(init_net ? P_INIT_MLP : (l == 0 ? P_MLP_IN : (l == L - 1 ? P_MLP_OUT : P_MLP_HIDDEN)), stream);
+    b.role = (!r.init_net && l > 0 && l < L - 1) ? 1 : 0;
+    prof_mark(r.init_net ? P_INIT_MLP : (l == 0 ? P_MLP_IN : (l == L - 1 ? P_MLP_OUT : P_MLP_HIDDEN)), stream);
     HIP_CHECK(launch_gemm(b, stream), "gemm launch");
-    for (int i = 0; i < n_nets; ++i) cur[i] = nxt[i];
+    for (int i = 0; i < r.n_nets; ++i) cur[i] = nxt[i];
   }
   return EMPOSE_OK;
 }
 
-// Where the residual gradient of one SMPL evaluation goes (null: no gradient wanted).
+int run_mlps(const MlpRun& r, const UpdWs& ws, int hidden_max, hipStream_t stream) {
+  for (int i = 1; i < r.n_nets; ++i)
+    if (r.nets[i]->n_layers != r.nets[0]->n_layers) return fail(EMPOSE_EINVAL, "paired MLPs must have the same depth");
+  const MlpPlan p = plan_mlps(r);
+  return p.one_launch ? run_mlps_one_launch(r, p.x3, stream) : run_mlps_layers(r, ws, hidden_max, stream);
+}
+
+// Where the residual gradient of one SMPL evaluation goes.
 struct GradOut {
   float* g_theta; int ld_g; float* g_beta; int ld_gb;
   float* trace_g_theta; float* trace_g_beta;
 };
-// One SMPL evaluation: pose / shape update + feature row (fa: what to update and where the copies go; rot / feat /
-// theta_t are filled in here), blend GEMM, chain + skinning + sensors (+ reverse), transposed GEMM, Rodrigues reverse.
-// On the frame-per-lane path the first and the last step ride on the GEMMs (option "smpl_fuse", default on).
-int run_smpl_eval(const empose_model* m, int T, int F, const SmplWs& ws, FeatArgs fa, const float* offset_r,
-                  const float* offset_t, const float* tgt, int ld_tgt, const float* frame_scale, float* pos, float* ori,
-                  float* joints, float* pos2, float* ori2, float* joints2, hipStream_t stream,
-                  const float* cot_pos = nullptr, const float* cot_ori = nullptr, const float* cot_joints = nullptr,
-                  const float* tgt_t = nullptr, const GradOut* go = nullptr) {
-  const bool bwd = tgt || cot_pos;
-  const bool tile = use_tile_path(m, T, cot_joints);
-  const bool fuse = tile && options().smpl_fuse != 0;
-  fa.rot = tile ? nullptr : ws.rot; fa.feat = ws.feat; fa.theta_t = tile ? ws.theta_t : nullptr;
+// One SMPL evaluation, as its caller asks for it.  What is not filled in is not wanted.
+struct SmplEval {
+  FeatArgs update;   // the pose / shape update and where its copies go (rot / feat / theta_t, T, F: filled in by run_smpl_eval)
+  const float* offset_r = nullptr; const float* offset_t = nullptr;
+  float* pos = nullptr; float* ori = nullptr; float* joints = nullptr;      // sensor outputs
+  float* pos2 = nullptr; float* ori2 = nullptr; float* joints2 = nullptr;   // ... second copies
+  // the reverse: none, or the residual against a target (tgt_t: its tile-layout copy, on the frame-per-lane path), or
+  // external cotangents -- either needs `grad`
+  const float* tgt = nullptr; int ld_tgt = 0; const float* frame_scale = nullptr; const float* tgt_t = nullptr;
+  const float* cot_pos = nullptr; const float* cot_ori = nullptr; const float* cot_joints = nullptr;
+  const GradOut* grad = nullptr;
+};
+
+// How an entry point evaluates SMPL: the one place that reads the options "smpl_tile", "smpl_fuse", "rows_x3" and
+// "last_pass_joints" for this path.  The callers take from it whether scratch outputs and tile-layout targets are
+// needed, the evaluation which launches to make.
+//   tile  the frame-per-lane path.  It pays once its 64-frame workgroups fill the 256 CUs (one per CU, 152 KB of LDS
+//         each): from 16384 frames on.  Measured at 8192 frames (the training step at 256 windows): 2 % slower than the
+//         general kernel.  Option "smpl_tile": 0 never, 1 by size, 2 always (tests).  Joint cotangents: general path.
+//   fuse, rx3  on that path the update + feature row and the Rodrigues reverse ride on the GEMMs ("smpl_fuse"), which
+//         multiply three bf16 pieces per operand ("rows_x3")
+//   bwd, joints_only  of the request: it wants a gradient; or ("last_pass_joints"; the last pass of an LGD forward
+//         without histories) no gradient and no sensor output, so of the blend product only the 66 rest-joint columns are
+//         read -- the GEMM multiplies just their column tiles (same fragments, same order: same bits) and the tile kernel
+//         stops after the chain
+struct SmplPlan {
+  bool tile = false, fuse = false, rx3 = false, bwd = false, joints_only = false;
+  bool joints_opt = false;   // "last_pass_joints" as read with the others
+  // The same path for another request of the same call (the passes of the LGD loop); reads no option.
+  SmplPlan with(const SmplEval& rq) const {
+    SmplPlan p = *this;
+    p.bwd = rq.tgt || rq.cot_pos;
+    p.joints_only = fuse && joints_opt && !p.bwd && !rq.pos && !rq.ori && !rq.pos2 && !rq.ori2 && (rq.joints || rq.joints2);
+    return p;
+  }
+};
+SmplPlan plan_smpl(const empose_model* m, int T, const SmplEval& rq) {
+  const Options& o = options();
+  SmplPlan p;
+  p.tile = m->tile_ok && o.smpl_tile != 0 && !rq.cot_joints && (o.smpl_tile == 2 || T >= 16384);
+  p.fuse = p.tile && o.smpl_fuse != 0;
+  p.rx3 = p.tile && o.rows_x3 != 0 && m->wc2_frag3 && m->wc2t_frag3;
+  p.joints_opt = o.last_pass_joints != 0;
+  return p.with(rq);
+}
+
+// What ChainArgs and TileArgs share: the sensor side of a request.
+template <typename Args>
+void set_sensor_io(Args& a, const empose_model* m, int T, int F, const SmplEval& rq) {
+  a.offset_r = rq.offset_r; a.offset_t = rq.offset_t; a.tgt = rq.tgt; a.ld_tgt = rq.ld_tgt; a.frame_scale = rq.frame_scale;
+  a.n_markers = m->n_markers;
+  for (int i = 0; i < 12; ++i) a.used_slot[i] = m->used_slot[i];
+  a.pos = rq.pos; a.ori = rq.ori; a.joints = rq.joints; a.pos2 = rq.pos2; a.ori2 = rq.ori2; a.joints2 = rq.joints2;
+  a.T = T; a.F = F;
+  a.cot_pos = rq.cot_pos; a.cot_ori = rq.cot_ori;
+}
+// What RodBwdArgs and RodBwdTArgs share.
+template <typename Args>
+void set_rod_bwd(Args& ra, const empose_model* m, int T, const SmplEval& rq) {
+  ra.theta = rq.update.theta; ra.ld_theta = rq.update.ld_theta;
+  ra.g_theta = rq.grad->g_theta; ra.ld_g = rq.grad->ld_g; ra.g_beta = rq.grad->g_beta; ra.ld_gb = rq.grad->ld_gb;
+  ra.trace_g_theta = rq.grad->trace_g_theta; ra.trace_g_beta = rq.grad->trace_g_beta;
+  ra.T = T; ra.rod_conv = m->rod_conv;
+}
+
+// Frame-per-lane path: blend GEMM -> tile layout -> smpl_tile_kernel -> tile layout -> transposed GEMM.
+int smpl_eval_tile(const empose_model* m, int T, int F, const SmplWs& ws, const SmplPlan& plan, const SmplEval& rq,
+                   hipStream_t stream) {
+  const FeatArgs& fa = rq.update;
+  const int lo = plan.joints_only ? m->tile_j_off2 : 0, hi = plan.joints_only ? m->tile_j_off2 + 66 : 0;
+  prof_mark(P_BLEND_GEMM, stream);
+  HIP_CHECK(plan.fuse ? launch_blend_feat_gemm(fa, plan.rx3 ? m->wc2_frag3 : m->wc2_frag, ws.out, m->ncp2, m->ncp2, plan.rx3, stream, lo, hi)
+                      : launch_gemm_rows_t(ws.feat, 200, false, m->wc2_frag, ws.out, m->ncp2, T, m->ncp2, 200, stream),
+            "blend gemm (tile)");
+  TileArgs a;
+  set_sensor_io(a, m, T, F, rq);
+  a.tab = m->tile_tab; a.theta = fa.theta; a.ld_theta = fa.ld_theta; a.out_t = ws.out;
+  a.theta_t = ws.theta_t; a.tgt_t = rq.tgt ? rq.tgt_t : nullptr;
+  a.d_out_t = ws.d_out; a.d_rot_t = ws.d_rot; a.rod_conv = m->rod_conv;
+  prof_mark(P_CHAIN, stream);
+  HIP_CHECK(launch_smpl_tile(a, plan.bwd, m->tile_nloc, m->tile_nbl, stream, plan.joints_only), "smpl tile kernel");
+  if (!plan.bwd) return EMPOSE_OK;
+  RodBwdTArgs ra;
+  set_rod_bwd(ra, m, T, rq);
+  ra.theta_t = ws.theta_t; ra.d_rot_t = ws.d_rot; ra.d_feat_t = ws.d_feat; ra.ld_feat_t = D_FEAT_T_COLS;
+  prof_mark(P_BLEND_T_GEMM, stream);
+  if (plan.fuse) {
+    HIP_CHECK(launch_blend_t_gemm_rod(ws.d_out, m->ncp2, plan.rx3 ? m->wc2t_frag3 : m->wc2t_frag, m->ncp2, ra, plan.rx3, stream), "blend^T gemm + rodrigues_bwd (tile)");
+    return EMPOSE_OK;
+  }
+  HIP_CHECK(launch_gemm_rows_t(ws.d_out, m->ncp2, true, m->wc2t_frag, ws.d_feat, D_FEAT_T_COLS, T, 200, m->ncp2, stream), "blend^T gemm (tile)");
+  prof_mark(P_ROD_BWD, stream);
+  HIP_CHECK(launch_rodrigues_bwd_t(ra, stream), "rodrigues_bwd (tile) kernel");
+  return EMPOSE_OK;
+}
+
+// General path: blend GEMM, chain + skinning + sensors (+ reverse), transposed GEMM, Rodrigues reverse.
+int smpl_eval_rows(const empose_model* m, int T, int F, const SmplWs& ws, const SmplPlan& plan, const SmplEval& rq,
+                   hipStream_t stream) {
+  const int ncp = m->tab.ncp;
+  GemmBatch b;
+  b.count = 1;
+  b.p[0] = plain_prob(ws.feat, 200, m->tab.wc, 200, ws.out, ncp, T, ncp, 200);
+  prof_mark(P_BLEND_GEMM, stream);
+  HIP_CHECK((m->wc_frag && gemm_rows_applicable(T, ncp, 200))
+                ? launch_gemm_rows(ws.feat, 200, m->wc_frag, ws.out, ncp, T, ncp, 200, stream)
+                : launch_gemm(b, stream), "blend gemm");
+  ChainArgs c;
+  set_sensor_io(c, m, T, F, rq);
+  c.tab = m->tab;
+  c.rot = ws.rot; c.out = ws.out; c.d_out = ws.d_out; c.d_rot = ws.d_rot; c.cot_joints = rq.cot_joints;
+  prof_mark(P_CHAIN, stream);
+  HIP_CHECK(launch_chain_sensors(c, stream), "chain kernel");
+  if (!plan.bwd) return EMPOSE_OK;
+  b.p[0] = plain_prob(ws.d_out, ncp, m->tab.wct, ncp, ws.d_feat, 200, T, 200, ncp);
+  prof_mark(P_BLEND_T_GEMM, stream);
+  HIP_CHECK((m->wct_frag && gemm_rows_applicable(T, 200, ncp))
+                ? launch_gemm_rows(ws.d_out, ncp, m->wct_frag, ws.d_feat, 200, T, 200, ncp, stream)
+                : launch_gemm(b, stream), "blend^T gemm");
+  RodBwdArgs ra;
+  set_rod_bwd(ra, m, T, rq);
+  ra.d_rot = ws.d_rot; ra.d_feat = ws.d_feat;
+  prof_mark(P_ROD_BWD, stream);
+  HIP_CHECK(launch_rodrigues_bwd(ra, stream), "rodrigues_bwd kernel");
+  return EMPOSE_OK;
+}
+
+// One SMPL evaluation by `plan` (made for this request): pose / shape update + feature row -- on the fused
+// frame-per-lane path it rides on the blend GEMM -- then the path's own launches.
+int run_smpl_eval(const empose_model* m, int T, int F, const SmplWs& ws, const SmplPlan& plan, SmplEval rq,
+                  hipStream_t stream) {
+  if (plan.bwd && !rq.grad) return fail(EMPOSE_EINVAL, "gradient outputs missing");
+  FeatArgs& fa = rq.update;
+  fa.rot = plan.tile ? nullptr : ws.rot; fa.feat = ws.feat; fa.theta_t = plan.tile ? ws.theta_t : nullptr;
   fa.T = T; fa.F = F; fa.rod_conv = m->rod_conv;
-  if (bwd && !go) return fail(EMPOSE_EINVAL, "gradient outputs missing");
-  if (!fuse) {
+  if (!plan.fuse) {
     prof_mark(P_UPDATE_FEAT, stream);
     HIP_CHECK(launch_update_feat(fa, stream), "update_feat kernel");
   }
-  if (tile) {
-    // frame-per-lane path: blend GEMM -> tile layout -> smpl_tile_kernel -> tile layout -> transposed GEMM
-    prof_mark(P_BLEND_GEMM, stream);
-    const bool rx3 = options().rows_x3 != 0 && m->wc2_frag3 && m->wc2t_frag3;
-    // Joints only (option last_pass_joints; the last pass of an LGD forward without histories): no gradient, no sensor
-    // output, so of the blend product only the 66 rest-joint columns are read -- the GEMM multiplies just their column
-    // tiles (same fragments, same order: same bits) and the tile kernel stops after the chain.
-    const bool joints_only = fuse && options().last_pass_joints != 0 && !bwd && !pos && !ori && !pos2 && !ori2 &&
-                             (joints || joints2);
-    const int j_off2 = m->tile_j_off2;
-    HIP_CHECK(fuse ? launch_blend_feat_gemm(fa, rx3 ? m->wc2_frag3 : m->wc2_frag, ws.out, m->ncp2, m->ncp2, rx3, stream,
-                                            joints_only ? j_off2 : 0, joints_only ? j_off2 + 66 : 0)
-                   : launch_gemm_rows_t(ws.feat, 200, false, m->wc2_frag, ws.out, m->ncp2, T, m->ncp2, 200, stream),
-              "blend gemm (tile)");
-    TileArgs a;
-    a.tab = m->tile_tab; a.theta = fa.theta; a.ld_theta = fa.ld_theta; a.out_t = ws.out;
-    a.theta_t = ws.theta_t; a.tgt_t = tgt ? tgt_t : nullptr;
-    a.offset_r = offset_r; a.offset_t = offset_t; a.tgt = tgt; a.ld_tgt = ld_tgt; a.frame_scale = frame_scale;
-    a.n_markers = m->n_markers;
-    for (int i = 0; i < 12; ++i) a.used_slot[i] = m->used_slot[i];
-    a.pos = pos; a.ori = ori; a.joints = joints; a.pos2 = pos2; a.ori2 = ori2; a.joints2 = joints2;
-    a.d_out_t = ws.d_out; a.d_rot_t = ws.d_rot; a.T = T; a.F = F; a.rod_conv = m->rod_conv;
-    a.cot_pos = cot_pos; a.cot_ori = cot_ori;
-    prof_mark(P_CHAIN, stream);
-    HIP_CHECK(launch_smpl_tile(a, bwd, m->tile_nloc, m->tile_nbl, stream, joints_only), "smpl tile kernel");
-    if (bwd) {
-      RodBwdTArgs ra;
-      ra.theta = fa.theta; ra.ld_theta = fa.ld_theta; ra.theta_t = ws.theta_t; ra.d_rot_t = ws.d_rot;
-      ra.d_feat_t = ws.d_feat; ra.ld_feat_t = D_FEAT_T_COLS;
-      ra.g_theta = go->g_theta; ra.ld_g = go->ld_g; ra.g_beta = go->g_beta; ra.ld_gb = go->ld_gb;
-      ra.trace_g_theta = go->trace_g_theta; ra.trace_g_beta = go->trace_g_beta;
-      ra.T = T; ra.rod_conv = m->rod_conv;
-      prof_mark(P_BLEND_T_GEMM, stream);
-      if (fuse) {
-        HIP_CHECK(launch_blend_t_gemm_rod(ws.d_out, m->ncp2, rx3 ? m->wc2t_frag3 : m->wc2t_frag, m->ncp2, ra, rx3, stream), "blend^T gemm + rodrigues_bwd (tile)");
-        return EMPOSE_OK;
-      }
-      HIP_CHECK(launch_gemm_rows_t(ws.d_out, m->ncp2, true, m->wc2t_frag, ws.d_feat, D_FEAT_T_COLS, T, 200, m->ncp2, stream), "blend^T gemm (tile)");
-      prof_mark(P_ROD_BWD, stream);
-      HIP_CHECK(launch_rodrigues_bwd_t(ra, stream), "rodrigues_bwd (tile) kernel");
-    }
-    return EMPOSE_OK;
-  }
-  GemmBatch b;
-  b.count = 1;
-  GemmProb& p = b.p[0];
-  p.A = ws.feat; p.lda = 200; p.W = m->tab.wc; p.ldw = 200; p.C = ws.out; p.ldc = m->tab.ncp;
-  p.M = T; p.N = m->tab.ncp; p.K = 200;
-  p.scale = nullptr; p.shift = nullptr; p.resid = nullptr; p.ldr = 0; p.act = 0; p.slope = 0.f;
-  prof_mark(P_BLEND_GEMM, stream);
-  HIP_CHECK((m->wc_frag && gemm_rows_applicable(T, m->tab.ncp, 200))
-                ? launch_gemm_rows(ws.feat, 200, m->wc_frag, ws.out, m->tab.ncp, T, m->tab.ncp, 200, stream)
-                : launch_gemm(b, stream), "blend gemm");
-  ChainArgs c;
-  c.tab = m->tab;
-  c.rot = ws.rot; c.out = ws.out; c.offset_r = offset_r; c.offset_t = offset_t;
-  c.tgt = tgt; c.ld_tgt = ld_tgt; c.frame_scale = frame_scale;
-  c.n_markers = m->n_markers;
-  for (int i = 0; i < 12; ++i) c.used_slot[i] = m->used_slot[i];
-  c.pos = pos; c.ori = ori; c.joints = joints; c.pos2 = pos2; c.ori2 = ori2; c.joints2 = joints2;
-  c.d_out = ws.d_out; c.d_rot = ws.d_rot; c.T = T; c.F = F;
-  c.cot_pos = cot_pos; c.cot_ori = cot_ori; c.cot_joints = cot_joints;
-  prof_mark(P_CHAIN, stream);
-  HIP_CHECK(launch_chain_sensors(c, stream), "chain kernel");
-  if (tgt || cot_pos) {
-    p.A = ws.d_out; p.lda = m->tab.ncp; p.W = m->tab.wct; p.ldw = m->tab.ncp; p.C = ws.d_feat; p.ldc = 200;
-    p.M = T; p.N = 200; p.K = m->tab.ncp;
-    prof_mark(P_BLEND_T_GEMM, stream);
-    HIP_CHECK((m->wct_frag && gemm_rows_applicable(T, 200, m->tab.ncp))
-                  ? launch_gemm_rows(ws.d_out, m->tab.ncp, m->wct_frag, ws.d_feat, 200, T, 200, m->tab.ncp, stream)
-                  : launch_gemm(b, stream), "blend^T gemm");
-    RodBwdArgs ra;
-    ra.theta = fa.theta; ra.ld_theta = fa.ld_theta; ra.d_rot = ws.d_rot; ra.d_feat = ws.d_feat;
-    ra.g_theta = go->g_theta; ra.ld_g = go->ld_g; ra.g_beta = go->g_beta; ra.ld_gb = go->ld_gb;
-    ra.trace_g_theta = go->trace_g_theta; ra.trace_g_beta = go->trace_g_beta; ra.T = T; ra.rod_conv = m->rod_conv;
-    prof_mark(P_ROD_BWD, stream);
-    HIP_CHECK(launch_rodrigues_bwd(ra, stream), "rodrigues_bwd kernel");
-  }
-  return EMPOSE_OK;
+  return plan.tile ? smpl_eval_tile(m, T, F, ws, plan, rq, stream) : smpl_eval_rows(m, T, F, ws, plan, rq, stream);
 }
 
 struct LgdWs {
@@ -458,6 +494,91 @@ LgdWs carve_lgd(Carver& c, const empose_model* m, int B, int F) {
     w.y = nullptr;
   }
   return w;
+}
+
+
+// One LGD forward: the model, the caller's tensors, the carved workspace and how this call evaluates SMPL.
+struct LgdRun {
+  const empose_model* m; const empose_lgd_io* io; int B, F, T;
+  LgdWs w; SmplPlan path; hipStream_t stream;
+  float* x_col(int c) const { return w.x + m->d_in + c; }   // the columns of the network input x after the sensors:
+  float* x_theta() const { return x_col(0); }               // theta | beta | g_theta | g_beta
+  float* x_beta() const { return x_col(66); }
+};
+
+// EMPOSE_LGD_PHASE_INIT: the network input and the initial estimate (reference models.py:511-526).
+int lgd_init(const LgdRun& r) {
+  const empose_model* m = r.m; const empose_lgd_io* io = r.io; const LgdWs& w = r.w;
+  const int dx = m->d_x, T = r.T;
+  PackArgs pa;
+  pa.marker_pos = io->marker_pos; pa.marker_oris = io->marker_oris; pa.marker_masks = io->marker_masks;
+  pa.seq_lengths = io->seq_lengths; pa.x = w.x; pa.ldx = dx; pa.frame_scale = w.scale;
+  pa.B = r.B; pa.F = r.F; pa.n_markers = m->n_markers;
+  pa.rows_as_unpadded = (m->shape_avg == 2) ? 1 : 0;
+  pa.suppress_missing = io->suppress_missing; pa.mask_value = io->mask_value;
+  for (int i = 0; i < 12; ++i) pa.marker_idx[i] = m->marker_idx[i];
+  prof_mark(P_PACK, r.stream);
+  HIP_CHECK(launch_pack_inputs(pa, r.stream), "pack kernel");
+  if (m->use_gradient && m->N > 0 && r.path.tile)   // the targets of the frame-per-lane kernel, once per forward
+    HIP_CHECK(launch_rows_to_tile(w.x, dx, m->d_in, w.x_t, T, r.stream), "tile transpose");
+  if (!m->rnn_init) {
+    const MlpRun init{{&m->pose_init, &m->shape_init}, 2, {r.x_theta(), w.d_shape}, {dx, 10}, w.x, dx, T, true};
+    return run_mlps(init, w.upd, m->hidden_max, r.stream);
+  }
+  const int H = m->rnn.H;
+  TRY(run_lstm(m->rnn, r.B, r.F, w.x, dx, io->seq_lengths, io->h0, io->c0, w.y, io->h_n, io->c_n, w.lstm, r.stream));
+  GemmBatch b;
+  b.count = 2;
+  b.p[0] = linear_prob(w.y, H, m->pose_head, r.x_theta(), dx, T);
+  b.p[1] = linear_prob(w.y, H, m->shape_head, w.d_shape, 10, T);
+  prof_mark(P_HEADS, r.stream);
+  const bool rows = m->heads_frag && options().heads_rows != 0 && heads_rows_applicable(T, H);
+  const bool rx3 = options().rows_x3 != 0 && m->heads_frag3;
+  HIP_CHECK(rows ? launch_heads_rows(w.y, H, rx3 ? m->heads_frag3 : m->heads_frag, m->heads_bias, r.x_theta(), dx,
+                                     w.d_shape, 10, T, H, 66, 10, rx3, r.stream)
+                 : launch_gemm(b, r.stream), "head gemm");
+  return EMPOSE_OK;
+}
+
+// EMPOSE_LGD_PHASE_ITER: N + 1 SMPL evaluations with the update nets between them.
+int lgd_iterate(const LgdRun& r) {
+  const empose_model* m = r.m; const empose_lgd_io* io = r.io; const LgdWs& w = r.w;
+  const int dx = m->d_x, T = r.T, N = m->N;
+  const bool tile = r.path.tile;
+  auto hist = [&](float* base, int i, size_t width) -> float* { return base ? base + (size_t)i * T * width : nullptr; };
+  for (int i = 0; i <= N; ++i) {
+    SmplEval rq;
+    FeatArgs& fa = rq.update;
+    fa.theta = r.x_theta(); fa.ld_theta = dx; fa.beta = r.x_beta(); fa.ld_beta = dx;
+    fa.shape_avg = m->shape_avg; fa.seq_lengths = io->seq_lengths;
+    fa.d_theta = i ? w.d_pose : nullptr; fa.theta_step = i ? m->step : 0.f;   // pass 0 takes the initial estimate as it is
+    fa.d_beta = w.d_shape; fa.beta_keep = i ? 1.f : 0.f; fa.beta_step = i ? m->step : 1.f;
+    fa.out_theta = hist(io->hist_pose, i, 66); fa.out_beta = hist(io->hist_shape, i, 10);
+    fa.out_theta2 = (i == N) ? io->pose_hat : nullptr; fa.out_beta2 = (i == N) ? io->shape_hat : nullptr;
+    float* hm = hist(io->hist_markers, i, 36);
+    float* ho = hist(io->hist_markers_ori, i, 108);
+    float* hj = hist(io->hist_joints, i, 66);
+    if ((hm == nullptr) != (ho == nullptr)) return fail(EMPOSE_EINVAL, "hist_markers and hist_markers_ori go together");
+    // (the frame-per-lane kernel skips outputs nobody asked for; the general kernel always writes its scratch copies)
+    rq.offset_r = io->offset_r; rq.offset_t = io->offset_t;
+    rq.pos = hm ? hm : (tile ? nullptr : w.pos); rq.ori = ho ? ho : (tile ? nullptr : w.ori);
+    rq.joints = (i == N) ? io->joints_hat : (hj ? hj : (tile ? nullptr : w.joints));
+    rq.joints2 = (i == N) ? hj : nullptr;
+    rq.ld_tgt = dx; rq.frame_scale = w.scale; rq.tgt_t = w.x_t;
+    const GradOut go{r.x_col(76), dx, r.x_col(142), dx, hist(io->trace_g_pose, i, 66), hist(io->trace_g_shape, i, 10)};
+    if (i < N && m->use_gradient) { rq.tgt = w.x; rq.grad = &go; }
+    TRY(run_smpl_eval(m, T, r.F, w.smpl, r.path.with(rq), rq, r.stream));
+    if (i == N) break;
+    const MlpRun upd{{&m->pose_iter, &m->shape_iter}, 2, {w.d_pose, w.d_shape}, {66, 10}, w.x, dx, T, false};
+    TRY(run_mlps(upd, w.upd, m->hidden_max, r.stream));
+  }
+  prof_end_forward(r.stream);
+  return EMPOSE_OK;
+}
+
+// empose_smpl_sensors_vjp: the SMPL workspace, then the scratch sensor outputs of the general kernel.
+size_t smpl_vjp_bytes(const empose_model* m, int T) {
+  return empose_smpl_workspace_bytes(m, T) + (size_t)T * (36 + 108 + 66) * sizeof(float) + 1024;
 }
 
 }  // namespace
@@ -595,22 +716,15 @@ int empose_model_create(const empose_model_desc* d, empose_model_t** out) {
 int empose_smpl_tile_supported(const empose_model_t* m) { return m && m->tile_ok ? 1 : 0; }
 
 size_t empose_smpl_workspace_bytes(const empose_model_t* m, int T) {
-  Carver c(nullptr);
-  carve_smpl(c, m, T);
-  return c.off;
+  return m && T > 0 ? Carver::measure([&](Carver& c) { carve_smpl(c, m, T); }) : 0;
 }
 
 size_t empose_update_workspace_bytes(const empose_model_t* m, int T) {
-  Carver c(nullptr);
-  carve_upd(c, m, T);
-  return c.off;
+  return m && T > 0 ? Carver::measure([&](Carver& c) { carve_upd(c, m, T); }) : 0;
 }
 
 size_t empose_lgd_workspace_bytes(const empose_model_t* m, int B, int F) {
-  if (!m || B <= 0 || F <= 0) return 0;
-  Carver c(nullptr);
-  carve_lgd(c, m, B, F);
-  return c.off;
+  return m && B > 0 && F > 0 ? Carver::measure([&](Carver& c) { carve_lgd(c, m, B, F); }) : 0;
 }
 
 int empose_lgd_forward(const empose_model_t* m, const empose_lgd_io* io, void* workspace, size_t workspace_bytes,
@@ -629,90 +743,10 @@ int empose_lgd_forward_phase(const empose_model_t* m, const empose_lgd_io* io, v
       !io->joints_hat)
     return fail(EMPOSE_EINVAL, "null input/output tensor");
   if (workspace_bytes < empose_lgd_workspace_bytes(m, B, F)) return fail(EMPOSE_ENOMEM, "workspace too small");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const int T = B * F;
   Carver c(workspace);
-  LgdWs w = carve_lgd(c, m, B, F);
-  const int dx = m->d_x, din = m->d_in;
-  float* x_theta = w.x + din;
-  float* x_beta = w.x + din + 66;
-  float* x_gtheta = w.x + din + 76;
-  float* x_gbeta = w.x + din + 142;
-
-  if (phases & EMPOSE_LGD_PHASE_INIT) {
-  PackArgs pa;
-  pa.marker_pos = io->marker_pos; pa.marker_oris = io->marker_oris; pa.marker_masks = io->marker_masks;
-  pa.seq_lengths = io->seq_lengths; pa.x = w.x; pa.ldx = dx; pa.frame_scale = w.scale;
-  pa.B = B; pa.F = F; pa.n_markers = m->n_markers;
-  pa.rows_as_unpadded = (m->shape_avg == 2) ? 1 : 0;
-  pa.suppress_missing = io->suppress_missing; pa.mask_value = io->mask_value;
-  for (int i = 0; i < 12; ++i) pa.marker_idx[i] = m->marker_idx[i];
-  prof_mark(P_PACK, stream);
-  HIP_CHECK(launch_pack_inputs(pa, stream), "pack kernel");
-  if (m->use_gradient && m->N > 0 && use_tile_path(m, T)) {   // the targets of the frame-per-lane kernel, once per forward
-    HIP_CHECK(launch_rows_to_tile(w.x, dx, m->d_in, w.x_t, T, stream), "tile transpose");
-  }
-
-  // ---- initial estimate (reference models.py:511-526)
-  if (m->rnn_init) {
-    TRY(run_lstm(m->rnn, B, F, w.x, dx, io->seq_lengths, io->h0, io->c0, w.y, io->h_n, io->c_n, w.lstm, stream));
-    GemmBatch b;
-    b.count = 2;
-    b.p[0] = linear_prob(w.y, m->rnn.H, m->pose_head, x_theta, dx, T);
-    b.p[1] = linear_prob(w.y, m->rnn.H, m->shape_head, w.d_shape, 10, T);
-    prof_mark(P_HEADS, stream);
-    const bool rows = m->heads_frag && options().heads_rows != 0 && heads_rows_applicable(T, m->rnn.H);
-    const bool rx3 = options().rows_x3 != 0 && m->heads_frag3;
-    HIP_CHECK(rows ? launch_heads_rows(w.y, m->rnn.H, rx3 ? m->heads_frag3 : m->heads_frag, m->heads_bias, x_theta, dx,
-                                       w.d_shape, 10, T, m->rnn.H, 66, 10, rx3, stream)
-                   : launch_gemm(b, stream), "head gemm");
-  } else {
-    const Mlp* nets[2] = {&m->pose_init, &m->shape_init};
-    float* outs[2] = {x_theta, w.d_shape};
-    const int lds[2] = {dx, 10};
-    TRY(run_mlps(nets, 2, outs, lds, w.x, dx, T, w.upd, m->hidden_max, stream, true));
-  }
-  }   // EMPOSE_LGD_PHASE_INIT
-  if (!(phases & EMPOSE_LGD_PHASE_ITER)) return EMPOSE_OK;
-
-  const int N = m->N;
-  auto hist = [&](float* base, int i, size_t width) -> float* { return base ? base + (size_t)i * T * width : nullptr; };
-  for (int i = 0; i <= N; ++i) {
-    FeatArgs fa;
-    fa.theta = x_theta; fa.ld_theta = dx; fa.beta = x_beta; fa.ld_beta = dx;
-    fa.shape_avg = m->shape_avg;
-    fa.seq_lengths = io->seq_lengths;
-    if (i == 0) {
-      fa.d_theta = nullptr; fa.theta_step = 0.f;
-      fa.d_beta = w.d_shape; fa.beta_keep = 0.f; fa.beta_step = 1.f;
-    } else {
-      fa.d_theta = w.d_pose; fa.theta_step = m->step;
-      fa.d_beta = w.d_shape; fa.beta_keep = 1.f; fa.beta_step = m->step;
-    }
-    const bool tile = use_tile_path(m, T);
-    fa.out_theta = hist(io->hist_pose, i, 66); fa.out_beta = hist(io->hist_shape, i, 10);
-    fa.out_theta2 = (i == N) ? io->pose_hat : nullptr;
-    fa.out_beta2 = (i == N) ? io->shape_hat : nullptr;
-
-    const bool need_grad = (i < N) && m->use_gradient;
-    float* hm = hist(io->hist_markers, i, 36);
-    float* ho = hist(io->hist_markers_ori, i, 108);
-    float* hj = hist(io->hist_joints, i, 66);
-    if ((hm == nullptr) != (ho == nullptr)) return fail(EMPOSE_EINVAL, "hist_markers and hist_markers_ori go together");
-    GradOut go{x_gtheta, dx, x_gbeta, dx, hist(io->trace_g_pose, i, 66), hist(io->trace_g_shape, i, 10)};
-    // (the frame-per-lane kernel skips outputs nobody asked for; the general kernel always writes its scratch copies)
-    TRY(run_smpl_eval(m, T, F, w.smpl, fa, io->offset_r, io->offset_t, need_grad ? w.x : nullptr, dx, w.scale,
-                      hm ? hm : (tile ? nullptr : w.pos), ho ? ho : (tile ? nullptr : w.ori),
-                      (i == N) ? io->joints_hat : (hj ? hj : (tile ? nullptr : w.joints)),
-                      nullptr, nullptr, (i == N) ? hj : nullptr, stream, nullptr, nullptr, nullptr, w.x_t,
-                      need_grad ? &go : nullptr));
-    if (i == N) break;
-    const Mlp* nets[2] = {&m->pose_iter, &m->shape_iter};
-    float* outs[2] = {w.d_pose, w.d_shape};
-    const int lds[2] = {66, 10};
-    TRY(run_mlps(nets, 2, outs, lds, w.x, dx, T, w.upd, m->hidden_max, stream));
-  }
-  prof_end_forward(stream);
+  const LgdRun r{m, io, B, F, B * F, carve_lgd(c, m, B, F), plan_smpl(m, B * F, SmplEval()), static_cast<hipStream_t>(stream_)};
+  if (phases & EMPOSE_LGD_PHASE_INIT) TRY(lgd_init(r));
+  if (phases & EMPOSE_LGD_PHASE_ITER) TRY(lgd_iterate(r));
   return EMPOSE_OK;
 }
 
@@ -728,20 +762,20 @@ int empose_smpl_sensors_fwd_bwd(const empose_model_t* m, int T, int F, const flo
   if (workspace_bytes < empose_smpl_workspace_bytes(m, T)) return fail(EMPOSE_ENOMEM, "workspace too small");
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   Carver c(workspace);
-  SmplWs ws = carve_smpl(c, m, T);
-  FeatArgs fa;   // the caller's rows are read in place (no update: the kernel does not write them back)
-  fa.theta = const_cast<float*>(theta); fa.ld_theta = ld_theta; fa.beta = const_cast<float*>(beta); fa.ld_beta = ld_beta;
-  fa.d_theta = nullptr; fa.d_beta = nullptr; fa.theta_step = 0.f; fa.beta_keep = 1.f; fa.beta_step = 0.f;
-  const bool tile = use_tile_path(m, T);
-  fa.shape_avg = 0;
-  fa.out_theta = fa.out_beta = fa.out_theta2 = fa.out_beta2 = nullptr;
-  if (tgt && tile) {
+  const SmplWs ws = carve_smpl(c, m, T);
+  const GradOut go{g_theta, ld_g, g_beta, ld_gb, nullptr, nullptr};
+  SmplEval rq;
+  rq.update = plain_feat_args(theta, ld_theta, beta, ld_beta);
+  rq.offset_r = offset_r; rq.offset_t = offset_t;
+  rq.pos = pos; rq.ori = ori; rq.joints = joints;
+  rq.tgt = tgt; rq.ld_tgt = ld_tgt; rq.frame_scale = frame_scale;
+  if (tgt) rq.grad = &go;
+  const SmplPlan plan = plan_smpl(m, T, rq);
+  if (tgt && plan.tile) {
     HIP_CHECK(launch_rows_to_tile(tgt, ld_tgt, 12 * m->n_markers, ws.tgt_t, T, stream), "tile transpose");
+    rq.tgt_t = ws.tgt_t;
   }
-  GradOut go{g_theta, ld_g, g_beta, ld_gb, nullptr, nullptr};
-  TRY(run_smpl_eval(m, T, F, ws, fa, offset_r, offset_t, tgt, ld_tgt, frame_scale, pos, ori, joints, nullptr, nullptr,
-                    nullptr, stream, nullptr, nullptr, nullptr, tile ? ws.tgt_t : nullptr, tgt ? &go : nullptr));
-  return EMPOSE_OK;
+  return run_smpl_eval(m, T, F, ws, plan, rq, stream);
 }
 
 int empose_smpl_sensors_vjp(const empose_model_t* m, int T, int F, const float* theta, int ld_theta, const float* beta,
@@ -751,42 +785,37 @@ int empose_smpl_sensors_vjp(const empose_model_t* m, int T, int F, const float* 
   if (!m || !theta || !beta || !offset_r || !offset_t || !d_pos || !d_ori || !g_theta || !g_beta || !workspace)
     return fail(EMPOSE_EINVAL, "null argument");
   if (T <= 0 || F <= 0 || T % F != 0) return fail(EMPOSE_EINVAL, "T must be a positive multiple of F");
-  if (workspace_bytes < empose_smpl_workspace_bytes(m, T) + (size_t)T * (36 + 108 + 66) * sizeof(float) + 1024)
+  if (workspace_bytes < smpl_vjp_bytes(m, T))
     return fail(EMPOSE_ENOMEM, "workspace too small (need empose_smpl_vjp_workspace_bytes)");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
   Carver c(workspace);
-  SmplWs ws = carve_smpl(c, m, T);
+  const SmplWs ws = carve_smpl(c, m, T);
   float* pos = c.f((size_t)T * 36);
   float* ori = c.f((size_t)T * 108);
   float* joints = c.f((size_t)T * 66);
-  FeatArgs fa;   // the caller's rows are read in place (no update: the kernel does not write them back)
-  fa.theta = const_cast<float*>(theta); fa.ld_theta = ld_theta; fa.beta = const_cast<float*>(beta); fa.ld_beta = ld_beta;
-  fa.d_theta = nullptr; fa.d_beta = nullptr; fa.theta_step = 0.f; fa.beta_keep = 1.f; fa.beta_step = 0.f;
-  const bool tile = use_tile_path(m, T, d_joints);
-  fa.shape_avg = 0;
-  fa.out_theta = fa.out_beta = fa.out_theta2 = fa.out_beta2 = nullptr;
-  GradOut go{g_theta, 66, g_beta, 10, nullptr, nullptr};
-  TRY(run_smpl_eval(m, T, F, ws, fa, offset_r, offset_t, nullptr, 0, nullptr, tile ? nullptr : pos, tile ? nullptr : ori,
-                    tile ? nullptr : joints, nullptr, nullptr, nullptr, stream, d_pos, d_ori, d_joints, nullptr, &go));
-  return EMPOSE_OK;
+  const GradOut go{g_theta, 66, g_beta, 10, nullptr, nullptr};
+  SmplEval rq;
+  rq.update = plain_feat_args(theta, ld_theta, beta, ld_beta);
+  rq.offset_r = offset_r; rq.offset_t = offset_t;
+  rq.cot_pos = d_pos; rq.cot_ori = d_ori; rq.cot_joints = d_joints;
+  rq.grad = &go;
+  const SmplPlan plan = plan_smpl(m, T, rq);
+  if (!plan.tile) { rq.pos = pos; rq.ori = ori; rq.joints = joints; }   // the general kernel always writes them: to scratch
+  return run_smpl_eval(m, T, F, ws, plan, rq, static_cast<hipStream_t>(stream_));
 }
 
-size_t empose_smpl_vjp_workspace_bytes(const empose_model_t* m, int T) {
-  return empose_smpl_workspace_bytes(m, T) + (size_t)T * (36 + 108 + 66) * sizeof(float) + 1024;
-}
+size_t empose_smpl_vjp_workspace_bytes(const empose_model_t* m, int T) { return smpl_vjp_bytes(m, T); }
 
 int empose_update_nets_fwd(const empose_model_t* m, int T, const float* x, int ldx, float* d_pose, float* d_shape,
                            void* workspace, size_t workspace_bytes, empose_stream_t stream_) {
   if (!m || !x || !d_pose || !d_shape || !workspace) return fail(EMPOSE_EINVAL, "null argument");
+  if (T <= 0) return fail(EMPOSE_EINVAL, "T must be positive");
   if (m->pose_iter.n_layers == 0) return fail(EMPOSE_EINVAL, "model has no update nets");
   if (ldx < m->d_x || ldx % 4 != 0) return fail(EMPOSE_EINVAL, "ldx must be >= %d and a multiple of 4", m->d_x);
   if (workspace_bytes < empose_update_workspace_bytes(m, T)) return fail(EMPOSE_ENOMEM, "workspace too small");
   Carver c(workspace);
-  UpdWs ws = carve_upd(c, m, T);
-  const Mlp* nets[2] = {&m->pose_iter, &m->shape_iter};
-  float* outs[2] = {d_pose, d_shape};
-  const int lds[2] = {66, 10};
-  return run_mlps(nets, 2, outs, lds, x, ldx, T, ws, m->hidden_max, static_cast<hipStream_t>(stream_));
+  const UpdWs ws = carve_upd(c, m, T);
+  const MlpRun upd{{&m->pose_iter, &m->shape_iter}, 2, {d_pose, d_shape}, {66, 10}, x, ldx, T, false};
+  return run_mlps(upd, ws, m->hidden_max, static_cast<hipStream_t>(stream_));
 }
 
 }  // extern "C"

@@ -64,6 +64,13 @@ def test_bad_descriptors_are_rejected_without_a_gpu():
     assert lib.empose_lgd_workspace_bytes(None, 4, 4) == 0
 
 
+def test_model_workspace_queries_return_zero_for_a_null_handle():
+    lib = _lib.lib()
+    for T in (96, 0, -1):
+        assert lib.empose_smpl_workspace_bytes(None, T) == 0
+        assert lib.empose_update_workspace_bytes(None, T) == 0
+
+
 def test_training_bookkeeping_calls_refuse_bad_arguments_without_a_gpu():
     """Every check of the loss and bookkeeping entry points (csrc/api_train.hip) precedes its launch: the calls below
     return an error before any GPU work, so the pointers only have to be non-NULL."""

@@ -1,7 +1,7 @@
 """
 Work the LGD forward skips because its result is never read (run with `-m gpu` on an MI355X).
 
-  * option `last_pass_joints` (csrc/api_model.hip run_smpl_eval): an SMPL evaluation of the frame-per-lane path that is
+  * option `last_pass_joints` (csrc/api_model.hip plan_smpl): an SMPL evaluation of the frame-per-lane path that is
     asked for joints only -- the last pass of a forward without histories -- multiplies only the rest-joint column tiles
     of the blend matrix and runs the chain alone;
   * option `lstm_state_direct` (csrc/api_lstm.hip run_lstm): new sequences get their zero hidden-state planes by one fill,
