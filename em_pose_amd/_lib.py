@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get('EMPOSE_LIB_PATH') or os.path.join(_HERE, 'csrc', 'lib
 MAX_DENSE = 8
 RODRIGUES = {'smplx': 0, 'so3': 1}   # EMPOSE_RODRIGUES_* (include/empose_hip.h)
 ROOT_FRAME_ROTATE, ROOT_FRAME_SUBTRACT = 1, 2   # EMPOSE_ROOT_FRAME_*
+SAMPLE_LOCAL_NONE, SAMPLE_LOCAL_WINDOW, SAMPLE_LOCAL_FRAME = 0, 1, 2   # EMPOSE_SAMPLE_LOCAL_*
 c_float_p = C.POINTER(C.c_float)
 c_int_p = C.POINTER(C.c_int)
 
@@ -228,6 +229,16 @@ SIGNATURES = {
     'empose_virtual_sensors_vjp': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 +
                                             [C.c_int] + [C.c_void_p] * 7 + [C.c_int] + [C.c_void_p] * 6 +
                                             [C.c_size_t, C.c_void_p]),
+    # (N, F, V, vertices, M, max_deg; center, helper, deg, faces; mode, local, r; the six outputs; stream)
+    'empose_sample_sensors_fwd': (C.c_int, [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 +
+                                           [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p]),
+    'empose_sample_sensors_vjp_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int]),
+    # (... faces; n_sub_faces and the seven reverse tables; n_touched, touched; mode, local, r; the six cotangents;
+    # d_vertices; workspace, its bytes; stream)
+    'empose_sample_sensors_vjp': (C.c_int, [C.c_int] * 3 + [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 +
+                                           [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p] +
+                                           [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p] +
+                                           [C.c_void_p, C.c_size_t, C.c_void_p]),
     'empose_profile_enable': (C.c_int, [C.c_int]),
     'empose_profile_enable_only': (C.c_int, [C.c_char_p]),
     'empose_profile_ntags': (C.c_int, []),

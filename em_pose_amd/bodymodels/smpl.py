@@ -10,6 +10,7 @@ the saved poses and betas; single backward only).  Otherwise the call is the pla
 `fk_joints` stays forward-only.  `normalize_root=True` re-expresses the sequence in the frame of its first root
 orientation and position (reference smpl.py:112-119) with the root-frame kernel (csrc/root_frame.hip) in front of the mesh
 kernels; under autograd it is a node of its own in front of the mesh node, with empose_root_frame_vjp as its backward.
+`sub_mesh(vertex_ids)` gives the same layer on the vertices the virtual sensors at `vertex_ids` read (`SubMeshLayer`).
 Differences to the reference, on purpose:
   * `normalize_root=True`: the exponential map follows `rodrigues_convention`, the logarithm is accurate up to pi, and
     the backward is the derivative of the exact maps, finite at the first frame, where the reference's acos-based
@@ -142,7 +143,7 @@ class SMPLLayer(nn.Module):
         if self._mesh is not None and self._mesh[1] == key:
             return self._mesh[0]
         self._release()
-        tab = TB.build_full_mesh_tables(self.model, self.num_betas)
+        tab = self._mesh_tables()
         desc = _lib.MeshDesc()
         desc.n_vertices, desc.j_off, desc.ncp, desc.kb = tab['n_vertices'], tab['j_off'], tab['ncp'], tab['kb']
         desc.wc, desc.skin_idx = _lib.fptr(tab['wc']), _lib.iptr(tab['skin_idx'])
@@ -154,6 +155,18 @@ class SMPLLayer(nn.Module):
             _lib.check(_lib.lib().empose_mesh_create(_lib.C.byref(desc), _lib.C.byref(handle)))
         self._mesh = (handle, key)
         return handle
+
+    def _mesh_tables(self):
+        return TB.build_full_mesh_tables(self.model, self.num_betas)
+
+    def sub_mesh(self, vertex_ids):
+        """The layer restricted to what the virtual sensors at `vertex_ids` read of the mesh (`SubMeshLayer`), cached
+        per id tuple."""
+        key = tuple(int(v) for v in vertex_ids)
+        cache = self.__dict__.setdefault('_sub_meshes', {})
+        if key not in cache:
+            cache[key] = SubMeshLayer(self, key)
+        return cache[key]
 
     def _release(self):
         if self._mesh is not None:
@@ -260,6 +273,88 @@ class SMPLLayer(nn.Module):
 
     def forward(self, *args, **kwargs):
         return self.fk(*args, **kwargs)
+
+
+class SubMeshLayer(object):
+    """`SMPLLayer.sub_mesh(vertex_ids)`: the parent layer on the sensor sub-mesh -- the sensor vertices, their helper
+    vertices and the corners of their incident faces (`needed`, ascending original ids; 84 of 6890 for the 12 sensors).
+    `fk` / `forward` / `fk_joints` as the parent's, with `vertices` (N, len(needed), 3) and the same `joints` (N, 52, 3):
+    the same kernels on a mesh handle of its own whose tables are the gathered rows of the parent's
+    (bodymodels/tables.py build_sub_mesh_tables), so the full mesh is never written and, under autograd, its backward
+    (empose_mesh_vjp on this handle) never sees a full-mesh cotangent.  The Rodrigues convention and `arithmetic` are the
+    parent's; the tables are rebuilt when the parent's `tables_version` changes.  `model['f']`, `faces` and `n_vertices`
+    describe the restricted mesh in local numbering, which is what `VirtualMarkerHelper` reads: use it with
+    `local_ids(vertex_ids)`."""
+
+    def __init__(self, parent, vertex_ids):
+        self.parent, self.vertex_ids = parent, tuple(vertex_ids)
+        self.num_betas = parent.num_betas
+        self._mesh = None
+        self._version = None
+        self._sync()
+
+    def _sync(self):
+        if self._version != self.parent.tables_version:
+            self._release()
+            self._tables = TB.build_sub_mesh_tables(self.parent.model, self.vertex_ids, self.num_betas)
+            self._model = {'f': self._tables['faces']}
+            self._faces = None
+            self._version = self.parent.tables_version
+
+    rodrigues_convention = property(lambda self: self.parent.rodrigues_convention)
+    arithmetic = property(lambda self: self.parent.arithmetic)
+
+    @property
+    def needed(self):
+        """Original ids of the sub-mesh vertices, ascending (numpy int64)."""
+        self._sync()
+        return self._tables['needed']
+
+    @property
+    def model(self):
+        self._sync()
+        return self._model
+
+    @property
+    def n_vertices(self):
+        return len(self.needed)
+
+    @property
+    def n_joints(self):
+        self._sync()
+        return self._tables['n_joints']
+
+    @property
+    def faces(self):
+        self._sync()
+        if self._faces is None:
+            self._faces = torch.from_numpy(self._tables['faces']).to(dtype=torch.int32, device=self.parent.bm.f.device)
+        return self._faces
+
+    def local_ids(self, vertex_ids):
+        """Positions in `needed` of original vertex ids; ValueError for one the sub-mesh does not hold."""
+        ids = np.asarray([int(v) for v in vertex_ids], dtype=np.int64)
+        loc = np.minimum(np.searchsorted(self.needed, ids), len(self.needed) - 1)
+        if not np.array_equal(self.needed[loc], ids):
+            raise ValueError('vertices {} are not part of the sub-mesh'.format(ids[self.needed[loc] != ids].tolist()))
+        return [int(i) for i in loc]
+
+    def _mesh_tables(self):
+        return self._tables
+
+    def _mesh_handle(self, device):
+        self._sync()
+        return SMPLLayer._mesh_handle(self, device)
+
+    # the evaluation itself is the parent class's, on this object's handle and sizes
+    _release, __del__ = SMPLLayer._release, SMPLLayer.__del__
+    _fk, _pack, _fk_packed, _vjp_packed = SMPLLayer._fk, SMPLLayer._pack, SMPLLayer._fk_packed, SMPLLayer._vjp_packed
+    fk_joints, fk = SMPLLayer.fk_joints, SMPLLayer.fk
+
+    def forward(self, *args, **kwargs):
+        return self.fk(*args, **kwargs)
+
+    __call__ = forward
 
 
 def root_frame_fwd(rows, trans, seg_len, rodrigues, flags=None):

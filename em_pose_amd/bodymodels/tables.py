@@ -253,3 +253,34 @@ def build_full_mesh_tables(model, num_betas=10, dtype=np.float32, n_joints=None)
             'skin_idx': np.ascontiguousarray(skin_idx, dtype=np.int32),
             'skin_w': np.ascontiguousarray(skin_w, dtype=dtype),
             'parents': np.ascontiguousarray(parents52[:n_joints], dtype=np.int32)}
+
+
+def sub_mesh_vertices(faces, vertex_ids):
+    """What the virtual sensors at `vertex_ids` read of a mesh: (needed, sub_faces_local).  `needed`: the sensor
+    vertices, their helper vertices and every corner of their incident faces, ascending original id.  `sub_faces_local`:
+    the incident faces in ascending face id, renumbered by position in `needed`.  The numbering keeps every face's id
+    order and corner order, so `sensor_topology` on the restricted faces with the local ids gives the helpers and the
+    fan order of the full mesh (tests/test_sample_sensors_cpu.py pins it)."""
+    vertex_ids = [int(v) for v in vertex_ids]
+    sub_faces, _, helpers = sensor_topology(faces, vertex_ids)   # sub_faces: ascending face id (np.unique)
+    needed = np.unique(np.concatenate([np.asarray(vertex_ids, dtype=np.int64), helpers, sub_faces.reshape(-1)]))
+    return needed, np.searchsorted(needed, sub_faces)
+
+
+def build_sub_mesh_tables(model, vertex_ids, num_betas=10, dtype=np.float32, n_joints=None):
+    """`build_full_mesh_tables` restricted to the vertices the sensors at `vertex_ids` read (`sub_mesh_vertices`): the
+    same dictionary with the `wc`, `skin_idx` and `skin_w` rows of the needed vertices only -- the rows of the full
+    tables, gathered, with the full mesh's `kb` -- and all joint rows, plus `needed` (original ids, int64) and `faces`
+    (the restricted faces in local numbering, int64).  A valid mesh for empose_mesh_create: its tables are per-vertex
+    rows and the joint rows regress from blend shapes that are folded into them, not from the vertices."""
+    full = build_full_mesh_tables(model, num_betas, dtype, n_joints)
+    needed, faces = sub_mesh_vertices(model['f'], vertex_ids)
+    V, nv = full['n_vertices'], len(needed)
+    n_joint_rows = full['n_joints'] * 3
+    rows = np.concatenate([(needed[:, None] * 3 + np.arange(3)[None, :]).reshape(-1), V * 3 + np.arange(n_joint_rows)])
+    wc = np.zeros((_round_up(len(rows), 4), K_FEAT), dtype=full['wc'].dtype)
+    wc[:len(rows)] = full['wc'][rows]
+    return {'n_vertices': nv, 'j_off': nv * 3, 'ncp': wc.shape[0], 'kb': full['kb'], 'n_joints': full['n_joints'],
+            'wc': np.ascontiguousarray(wc), 'skin_idx': np.ascontiguousarray(full['skin_idx'][needed]),
+            'skin_w': np.ascontiguousarray(full['skin_w'][needed]), 'parents': full['parents'],
+            'needed': needed, 'faces': np.ascontiguousarray(faces, dtype=np.int64)}

@@ -230,6 +230,9 @@ LstmWs carve_lstm_of(Carver& c, const Lstm& r, int B, int F);
 int run_lstm(const Lstm& r, int B, int F, const float* x, int ldx, const int* seq_lengths, const float* h0,
              const float* c0, float* y, float* h_n, float* c_n, const LstmWs& ws, hipStream_t stream);
 
+// Frames per pass of the virtual-sensor reverse (api_mesh.hip), shared by empose_sample_sensors_vjp (api_sample.hip).
+int sensors_vjp_slab(int T, int M);
+
 }  // namespace api
 }  // namespace empose
 

@@ -275,15 +275,15 @@ MeshVjpWs carve_mesh_vjp(Carver& c, const empose_mesh* mesh, int T) {
   return w;
 }
 
-// Frames per pass of empose_virtual_sensors_vjp: the scratch (nine floats per frame and sensor) stays below 128 MB
-// whatever T and M, and a slab never exceeds MESH_SLAB frames.
-int sensors_vjp_slab(int T, int M) {
+}  // namespace
+
+// Frames per pass of empose_virtual_sensors_vjp (and of empose_sample_sensors_vjp, api_sample.hip): the scratch (nine
+// floats per frame and sensor) stays below 128 MB whatever T and M, and a slab never exceeds MESH_SLAB frames.
+int empose::api::sensors_vjp_slab(int T, int M) {
   const size_t cap = ((size_t)128 << 20) / (sizeof(float) * SENSOR_VJP_ROW * (size_t)M);
   const size_t s = std::min<size_t>({(size_t)T, (size_t)MESH_SLAB, std::max<size_t>(cap, 1)});
   return (int)s;
 }
-
-}  // namespace
 
 extern "C" {
 

@@ -843,6 +843,34 @@ struct SensorVjpArgs {
 };
 hipError_t launch_sensors_vjp(const SensorVjpArgs& a, hipStream_t stream);
 
+// Synthetic sensor sampling (sensor_sample.hip): the frames of virtual_sensors_kernel plus the per-subject offsets,
+// pos_synth = pos + ori . local, ori_synth = ori . r, in one launch; and the fold of the reverse, which turns the
+// cotangents of the six outputs into those of (pos, ori) for launch_sensors_vjp.
+constexpr int SAMPLE_LOCAL_NONE = 0;     // EMPOSE_SAMPLE_LOCAL_* (include/empose_hip.h)
+constexpr int SAMPLE_LOCAL_WINDOW = 1;   // local [N][M][3]
+constexpr int SAMPLE_LOCAL_FRAME = 2;    // local [N * F][M][3]
+struct SampleSensorsArgs {
+  const float* vertices;   // [T][V][3], T = N * F
+  const int* center; const int* helper; const int* deg; const int* faces;   // as VirtualSensorArgs
+  const float* local;      // by mode, or nullptr (SAMPLE_LOCAL_NONE)
+  const float* r;          // [N][M][3][3] or nullptr (identity)
+  float* pos; float* ori; float* normals;                   // [T][M][3], [T][M][9], [T][M][3], each or nullptr
+  float* pos_synth; float* ori_synth; float* normal_synth;  // likewise
+  int T, F, V, M, max_deg, mode;
+};
+hipError_t launch_sample_sensors(const SampleSensorsArgs& a, hipStream_t stream);
+// One slab of T frames whose first frame is frame t0 of the batch (t0 selects the window of local and r); the pointers
+// of the cotangents and of the outputs start at the slab.  d_pos_out is written when d_pos or d_pos_synth is given,
+// d_ori_out when any of d_ori, d_ori_synth, d_normal_synth or (mode != NONE and d_pos_synth) is.
+struct SampleFoldArgs {
+  const float* d_pos; const float* d_ori;                                        // un-offset outputs, each or nullptr
+  const float* d_pos_synth; const float* d_ori_synth; const float* d_normal_synth;   // each or nullptr
+  const float* local; const float* r;   // whole batch, as SampleSensorsArgs
+  float* d_pos_out; float* d_ori_out;   // [T][M][3], [T][M][9], each or nullptr
+  int T, t0, F, M, mode;
+};
+hipError_t launch_sample_fold(const SampleFoldArgs& a, hipStream_t stream);
+
 // Root normalisation and its vector-Jacobian product (root_frame.hip).  T frames in segments of seg_len rows; the root
 // axis-angles are the first three columns of rows of ld_root floats.  `flags`: what happens to the translation.
 constexpr int ROOT_FRAME_ROTATE = 1;     // trans_out = R_0^T trans

@@ -24,6 +24,7 @@ class ABatch(object):
         self.offset_r = offset_r
         self.joints_hat = None
         self.vertices = None
+        self.vertices_subset = None  # original ids of `vertices` when they are a sub-mesh (SMPLFK(vertex_ids=...))
         self.marker_pos_real = self.marker_ori_real = self.marker_normal_real = None
         self.marker_pos_synth = self.marker_ori_synth = self.marker_normal_synth = None
         self.marker_pos_vertex = self.marker_ori_vertex = None

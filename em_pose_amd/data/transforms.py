@@ -7,7 +7,9 @@ The few transforms `evaluate_real` needs before the model sees a recording (refe
   ResampleSequence       reference scripts/preprocess_amass_3dpw.py:146-148 a sequence to 60 Hz, on the GPU
 
   SMPLFK, SampleMarkersWithOffsets, get_end_to_end_preprocess_fn   reference transforms.py:259-282,132-226,23-48 on the
-                         HIP full-mesh kernel (pinned by tests/golden/preprocess.npz)
+                         HIP full-mesh kernel (pinned by tests/golden/preprocess.npz); opt-in without
+                         the mesh: SMPLFK(vertex_ids=...) on the sensor sub-mesh, SampleMarkersWithOffsets(on_device=True)
+                         as one launch of empose_sample_sensors_fwd (csrc/sensor_sample.hip) with a HIP reverse
 
 The sensor-noise augmentation of the reference (noise_functions.py: spherical noise, sensor suppression) is
 data/noise_functions.py on the sensor-noise kernel; `get_end_to_end_preprocess_fn` adds it with `device_noise=True` and
@@ -140,10 +142,14 @@ class NormalizeRoot(object):
 
 
 class SMPLFK(object):
-    """Ground-truth joints and vertices for a batch (reference transforms.py:259-282) through the HIP full-mesh layer."""
+    """Ground-truth joints and vertices for a batch (reference transforms.py:259-282) through the HIP full-mesh layer.
+    With `vertex_ids` (the sensor vertices) only the sensor sub-mesh is evaluated (`smpl_model.sub_mesh(vertex_ids)`):
+    `batch.vertices` is (n, f, len(needed) * 3) and `batch.vertices_subset` holds `needed`, the original ids of its
+    vertices; the joints are the same.  `SampleMarkersWithOffsets` reads either."""
 
-    def __init__(self, smpl_model):
+    def __init__(self, smpl_model, vertex_ids=None):
         self.smpl_model = smpl_model
+        self.vertex_ids = None if vertex_ids is None else tuple(int(v) for v in vertex_ids)
         self.max_window_size = 1000
 
     def __call__(self, batch):
@@ -152,10 +158,11 @@ class SMPLFK(object):
         s = batch.shapes.unsqueeze(1).repeat(1, f, 1).reshape(n * f, -1)
         r = batch.poses_root.reshape(n * f, -1)
         t = batch.trans.reshape(n * f, -1)
-        vertices, joints = self.smpl_model(poses_body=p, betas=s, poses_root=r, trans=t,
-                                           window_size=self.max_window_size)
+        layer = self.smpl_model if self.vertex_ids is None else self.smpl_model.sub_mesh(self.vertex_ids)
+        vertices, joints = layer(poses_body=p, betas=s, poses_root=r, trans=t, window_size=self.max_window_size)
         batch.joints_gt = joints[:, :22].reshape(n, f, -1)
         batch.vertices = vertices.reshape(n, f, -1)
+        batch.vertices_subset = None if self.vertex_ids is None else layer.needed
         batch.joints_hat = batch.joints_gt.clone().detach()
         return batch
 
@@ -179,9 +186,18 @@ class SampleMarkersWithOffsets(object):
     window from N(means, covs), 1 one draw per frame, 2 no positional offset, 3 no positional and no rotational offset.
     The draws come from torch's global generator (`MultivariateNormal.sample`), like the reference's.
     `offset_t_augmented` always carries the means: that is what is known at test time.
+
+    `on_device=True`: frames and offsets are one launch (empose_sample_sensors_fwd, csrc/sensor_sample.hip) instead of
+    the sensor kernel followed by a dozen small torch launches.  The host draws are the same calls in the same order
+    (`plan`); the gathered means, the gathered r and the selected draws go up in one pinned block with one copy that
+    does not block, and nothing in `__call__` waits for the device.  When `batch.vertices` requires grad the call is an
+    autograd node whose backward is empose_sample_sensors_vjp (single backward only; no gradient for the offsets).
+
+    Either path accepts a sub-mesh batch (`batch.vertices_subset`, SMPLFK(vertex_ids=...)): the sensors are then read
+    with the topology restricted to the subset, in its numbering.  A subset without a sensor's fan raises ValueError.
     """
 
-    def __init__(self, smpl_model, offset_sets, noise_level=-1):
+    def __init__(self, smpl_model, offset_sets, noise_level=-1, on_device=False):
         from em_pose_amd.data.virtual_sensors import VirtualMarkerHelper
         if isinstance(offset_sets, (dict, str)):
             offset_sets = [offset_sets]
@@ -195,7 +211,9 @@ class SampleMarkersWithOffsets(object):
         self.offset_means = np.stack([np.asarray(o['means'], dtype=np.float32) for o in offset_sets])
         self.r = np.stack([np.asarray(o['r'], dtype=np.float32) for o in offset_sets])
         self.vertex_ids = [int(v) for v in np.asarray(offset_sets[-1]['vertex_ids']).tolist()]
+        self.smpl_model, self.on_device = smpl_model, on_device
         self.virtual_helper = VirtualMarkerHelper(smpl_model)
+        self._subset_helpers = {}
         self.offset_rng = np.random.RandomState(6273)
         self.normal_dists = None
         if noise_level in (0, 1):
@@ -205,10 +223,85 @@ class SampleMarkersWithOffsets(object):
             self.normal_dists = torch.distributions.MultivariateNormal(
                 loc=torch.from_numpy(self.offset_means), covariance_matrix=torch.from_numpy(covs))
 
+    def _helper_and_ids(self, batch):
+        """The helper and the sensor ids in the numbering of `batch.vertices`: the body model's, or for a sub-mesh
+        batch those of the sensor topology restricted to `batch.vertices_subset` (ascending original ids)."""
+        subset = getattr(batch, 'vertices_subset', None)
+        if subset is None:
+            return self.virtual_helper, self.vertex_ids
+        from em_pose_amd.bodymodels import tables as TB
+        from em_pose_amd.data.virtual_sensors import VirtualMarkerHelper
+        subset = np.asarray(subset.detach().cpu() if torch.is_tensor(subset) else subset, dtype=np.int64).reshape(-1)
+        key = (subset.tobytes(), getattr(self.smpl_model, 'tables_version', 0))
+        if key not in self._subset_helpers:
+            if np.any(np.diff(subset) <= 0):
+                raise ValueError('vertices_subset must hold ascending vertex ids')
+            needed, faces = TB.sub_mesh_vertices(self.smpl_model.model['f'], self.vertex_ids)
+            if not np.isin(needed, subset).all():
+                raise ValueError('vertices_subset lacks vertices {} of the sensors\' fans'.format(
+                    needed[~np.isin(needed, subset)].tolist()))
+            stub = type('SubMeshFaces', (object,), {})()
+            stub.model = {'f': np.searchsorted(subset, needed[faces])}   # the restricted faces, renumbered by position
+            ids = [int(i) for i in np.searchsorted(subset, np.asarray(self.vertex_ids, dtype=np.int64))]
+            self._subset_helpers = {key: (VirtualMarkerHelper(stub), ids)}   # one subset at a time
+        return self._subset_helpers[key]
+
+    def plan(self, n, f):
+        """The host side of one call, the reference's draws in its order -- the offset sets from RandomState(6273), then
+        `MultivariateNormal.sample` from torch's global generator with the shapes of the torch path -- as
+        (means (n, M, 3), r (n, M, 3, 3) with the identity at level 3, local, mode): `local` is (n, M, 3) for
+        SAMPLE_LOCAL_WINDOW, (n, f, M, 3) for SAMPLE_LOCAL_FRAME, None for SAMPLE_LOCAL_NONE.  Host float32 tensors."""
+        from em_pose_amd import _lib
+        s_np = self.offset_rng.randint(0, self.n_offsets, n)
+        s_idxs = torch.from_numpy(s_np).long()
+        means = torch.from_numpy(self.offset_means[s_np])
+        r = torch.from_numpy(self.r[s_np])
+        local, mode = means, _lib.SAMPLE_LOCAL_WINDOW
+        if self.noise_level == 0:
+            local = self.normal_dists.sample((n,))[torch.arange(n), s_idxs]
+        elif self.noise_level == 1:
+            local, mode = self.normal_dists.sample((n, f))[torch.arange(n), :, s_idxs], _lib.SAMPLE_LOCAL_FRAME
+        elif self.noise_level in (2, 3):
+            local, mode = None, _lib.SAMPLE_LOCAL_NONE
+        if self.noise_level == 3:
+            r = torch.eye(3).expand(n, r.shape[1], 3, 3).contiguous()
+        return means, r, local, mode
+
+    def _call_on_device(self, batch):
+        from em_pose_amd.data.noise_functions import _Plan
+        n, f = batch.batch_size, batch.seq_length
+        helper, ids = self._helper_and_ids(batch)
+        vs = batch.vertices.reshape(n * f, -1, 3)
+        if not vs.is_cuda:
+            from em_pose_amd import _lib
+            raise _lib.EmposeError('SampleMarkersWithOffsets(on_device=True) needs GPU tensors; there is no CPU fallback')
+        means, r, local, mode = self.plan(n, f)
+        arrays = {'means': means, 'r': r}
+        if local is not None and self.noise_level >= 0:
+            arrays['local'] = local.float()
+        with torch.cuda.device(vs.device):
+            dev = _Plan(arrays).upload(vs.device)
+        local_dev = dev.get('local', dev['means']) if local is not None else None
+        r_dev = None if self.noise_level == 3 else dev['r']    # the kernel's identity: no product
+        if torch.is_grad_enabled() and vs.requires_grad:
+            outs = _SampleSensorsFn.apply(helper, vs, tuple(ids), f, mode, local_dev, r_dev)
+        else:
+            outs = sample_sensors_fwd(helper, vs.contiguous().float(), ids, f, mode, local_dev, r_dev)
+        m = len(ids)
+        for name, x in zip(('marker_pos_vertex', 'marker_ori_vertex', 'marker_normal_vertex', 'marker_pos_synth',
+                            'marker_ori_synth', 'marker_normal_synth'), outs):
+            setattr(batch, name, x.reshape(n, f, -1))
+        batch.offset_t_augmented = dev['means']
+        batch.offset_r_augmented = dev['r']
+        return batch
+
     def __call__(self, batch):
+        if self.on_device:
+            return self._call_on_device(batch)
         n, f = batch.batch_size, batch.seq_length
         vs = batch.vertices.reshape(n * f, -1, 3)
-        markers, oris, normals = self.virtual_helper.get_virtual_pos_and_rot(vs, self.vertex_ids)
+        helper, ids = self._helper_and_ids(batch)
+        markers, oris, normals = helper.get_virtual_pos_and_rot(vs, ids)
         dev = markers.device
         batch.marker_pos_vertex = markers.reshape(n, f, -1)
         batch.marker_ori_vertex = oris.reshape(n, f, -1)
@@ -239,8 +332,66 @@ class SampleMarkersWithOffsets(object):
         return batch
 
 
+def sample_sensors_fwd(helper, v, vertex_ids, f, mode, local, r):
+    """empose_sample_sensors_fwd on fp32 contiguous vertices (n * f, V, 3) with `helper`'s tables (VirtualMarkerHelper):
+    (pos, ori, normals, pos_synth, ori_synth, normal_synth).  `local`, `r`: device tensors by `mode`, or None."""
+    from em_pose_amd import _lib
+    t, nv, m = v.shape[0], v.shape[1], len(vertex_ids)
+    center, hlp, deg, faces, max_deg = helper._tables(vertex_ids, v.device)
+    new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=v.device)
+    with torch.cuda.device(v.device):
+        outs = (new(t, m, 3), new(t, m, 3, 3), new(t, m, 3), new(t, m, 3), new(t, m, 3, 3), new(t, m, 3))
+        _lib.check(_lib.lib().empose_sample_sensors_fwd(
+            t // f, f, nv, _lib.dptr(v), m, max_deg, _lib.dptr(center), _lib.dptr(hlp), _lib.dptr(deg), _lib.dptr(faces),
+            mode, _lib.dptr(local), _lib.dptr(r), *[_lib.dptr(o) for o in outs], _lib.current_stream()))
+    return outs
+
+
+def sample_sensors_vjp(helper, v, vertex_ids, f, mode, local, r, cotangents):
+    """empose_sample_sensors_vjp: d_vertices (n * f, V, 3) fp32 for the six cotangents (any but not all may be None)."""
+    from em_pose_amd import _lib
+    t, nv, m = v.shape[0], v.shape[1], len(vertex_ids)
+    center, hlp, deg, faces, max_deg = helper._tables(vertex_ids, v.device)
+    rev = helper._reverse_tables(vertex_ids, nv, v.device)
+    lib = _lib.lib()
+    with torch.cuda.device(v.device):
+        d_v = torch.empty(t, nv, 3, dtype=torch.float32, device=v.device)
+        ws_bytes = lib.empose_sample_sensors_vjp_workspace_bytes(t, m)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=v.device)
+        _lib.check(lib.empose_sample_sensors_vjp(
+            t // f, f, nv, _lib.dptr(v), m, max_deg, _lib.dptr(center), _lib.dptr(hlp), _lib.dptr(deg), _lib.dptr(faces),
+            rev[0].shape[0], *[_lib.dptr(a) for a in rev[:7]], rev[7].shape[0], _lib.dptr(rev[7]),
+            mode, _lib.dptr(local), _lib.dptr(r), *[_lib.dptr(c) for c in cotangents],
+            _lib.dptr(d_v), _lib.dptr(ws), ws_bytes, _lib.current_stream()))
+    return d_v
+
+
+class _SampleSensorsFn(torch.autograd.Function):
+    """`SampleMarkersWithOffsets(on_device=True)` under autograd: the forward is the launch of the no-grad call; the
+    backward is empose_sample_sensors_vjp on the saved vertices (single backward only).  `local` and `r` are
+    constants."""
+
+    @staticmethod
+    def forward(ctx, helper, vertices, vertex_ids, f, mode, local, r):
+        ctx.helper, ctx.vertex_ids, ctx.f, ctx.mode = helper, vertex_ids, f, mode
+        ctx.save_for_backward(vertices, local, r)
+        ctx.set_materialize_grads(False)
+        return sample_sensors_fwd(helper, vertices.contiguous().float(), vertex_ids, f, mode, local, r)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *cotangents):
+        if all(c is None for c in cotangents):
+            return (None,) * 7
+        vertices, local, r = ctx.saved_tensors
+        f32 = lambda t: t.contiguous().float() if t is not None else None
+        d_v = sample_sensors_vjp(ctx.helper, f32(vertices), ctx.vertex_ids, ctx.f, ctx.mode, local, r,
+                                 [f32(c) for c in cotangents])
+        return (None, d_v.to(vertices.dtype).reshape(vertices.shape)) + (None,) * 5
+
+
 def get_end_to_end_preprocess_fn(config, smpl_model, offset_files, randomize_if_configured=False,
-                                 device_normalize=False, device_noise=False):
+                                 device_normalize=False, device_noise=False, device_offsets=False, sensors_only=False):
     """
     The reference's preprocessing factory (transforms.py:23-48): NormalizeRoot -> SMPLFK -> SampleMarkersWithOffsets ->
     sensor noise, with the configured offset noise level when `randomize_if_configured`.  `offset_files`: the
@@ -248,7 +399,9 @@ def get_end_to_end_preprocess_fn(config, smpl_model, offset_files, randomize_if_
     NormalizeRoot(on_device=True).  `device_noise`: the reference's sensor-noise function (`get_noise_fn`) on the
     sensor-noise kernel (data/noise_functions.py; GPU batches only); it runs after the sensors are sampled and receives
     the keyword arguments of the call, as in the reference.  Without the switch a configuration that asks for sensor noise
-    is refused.
+    is refused.  `device_offsets`: SampleMarkersWithOffsets(on_device=True), the sensors and their offsets in one launch.
+    `sensors_only`: SMPLFK evaluates the sensor sub-mesh only (SMPLFK(vertex_ids=the sensors')), so `batch.vertices` holds
+    the vertices the sensors read instead of the mesh.  All four switches compose; all are off by default.
     """
     if not getattr(config, 'use_real_offsets', True):
         raise ValueError('We expect to use the real offsets.')
@@ -263,9 +416,11 @@ def get_end_to_end_preprocess_fn(config, smpl_model, offset_files, randomize_if_
         # marker suppression).  It runs on the GPU only and is opt-in: refuse instead of silently training without it.
         raise NotImplementedError('sensor-noise augmentation (spherical_noise_length / suppression_noise_length > 0) '
                                   'is not implemented in this build without device_noise=True (the sensor-noise kernel)')
-    normalize_root, fk = NormalizeRoot(on_device=device_normalize), SMPLFK(smpl_model)
     noise_level = getattr(config, 'offset_noise_level', -1) if randomize_if_configured else -1
-    sample_markers = SampleMarkersWithOffsets(smpl_model, list(offset_files), noise_level=noise_level)
+    sample_markers = SampleMarkersWithOffsets(smpl_model, list(offset_files), noise_level=noise_level,
+                                              on_device=device_offsets)
+    normalize_root = NormalizeRoot(on_device=device_normalize)
+    fk = SMPLFK(smpl_model, vertex_ids=sample_markers.vertex_ids if sensors_only else None)
 
     def _preprocess_fn(sample, mode='all', **noise_kwargs):
         noise = (lambda b: noise_fn(b, **noise_kwargs)) if noise_fn is not None else (lambda b: b)
@@ -277,4 +432,5 @@ def get_end_to_end_preprocess_fn(config, smpl_model, offset_files, randomize_if_
             return noise(sample_markers(fk(sample)))
         raise ValueError("Mode '{}' unknown.".format(mode))
     _preprocess_fn.noise_fn = noise_fn   # None: the plain pipeline
+    _preprocess_fn.fk, _preprocess_fn.sample_markers = fk, sample_markers
     return _preprocess_fn

@@ -598,6 +598,8 @@ int empose_virtual_sensors_fwd(int T, int V, const float* vertices, int M, int m
  *   vs_role                          sensor m with center[m] == u (role 0) or helper[m] == u (role 1), ascending
  *   touched       [n_touched]        the vertices u with entries in either CSR, ascending.  When they are at most a
  *                                    quarter of the mesh, d_vertices is cleared and only their rows are computed
+ *                                    (a few sensors on the full mesh).  On a sensor sub-mesh (SMPLLayer.sub_mesh)
+ *                                    every vertex is touched: there the dense form is the common case
  * Workspace: empose_virtual_sensors_vjp_workspace_bytes(T, M) -- 36 bytes per (frame, sensor) for a slab of frames
  * capped at 16384 and at 128 MB (0 for T or M <= 0).  Returns EMPOSE_EINVAL for a NULL vertex, table or d_vertices
  * pointer, T, V, M, max_deg, n_sub_faces or n_touched <= 0, all three cotangents NULL or a workspace that is too
@@ -609,6 +611,47 @@ int empose_virtual_sensors_vjp(int T, int V, const float* vertices, int M, int m
                                const int* vf_corner, const int* vs_ptr, const int* vs_role, int n_touched,
                                const int* touched, const float* d_pos, const float* d_ori, const float* d_normals,
                                float* d_vertices, void* workspace, size_t workspace_bytes, empose_stream_t stream);
+
+/* ---- synthetic sensor sampling (reference data/transforms.py:132-226, SampleMarkersWithOffsets) ------------------- */
+/* Forward, one launch (csrc/sensor_sample.hip), one lane per (frame, sensor): the virtual sensors of
+ * empose_virtual_sensors_fwd -- same tables, same arithmetic in the same order (csrc/sensor_frame.h) -- of N windows of
+ * F frames, vertices [N * F][V][3], and on top of them the per-subject offsets:
+ *   pos_synth    [N * F][M][3]     = pos + ori . local
+ *   ori_synth    [N * F][M][3][3]  = ori . r[i][m] for window i; r [N][M][3][3], or NULL for the identity
+ *   normal_synth [N * F][M][3]     = the third column of ori_synth
+ * `mode` says what `local` is: EMPOSE_SAMPLE_LOCAL_WINDOW one offset per window [N][M][3], EMPOSE_SAMPLE_LOCAL_FRAME
+ * one per frame [N * F][M][3], EMPOSE_SAMPLE_LOCAL_NONE none (`local` is ignored, pos_synth = pos).  pos, ori and normals
+ * are the three outputs of empose_virtual_sensors_fwd.  Any of the six outputs may be NULL, not all.  fp32; repeated
+ * calls give the same bits.  Returns EMPOSE_EINVAL, before any GPU work, for a NULL vertex or table pointer, N, F, V, M or
+ * max_deg <= 0 (or N * F * M above 2^31 - 1), an unknown mode, `local` NULL in a mode that reads it, or six NULL outputs.
+ * Indices are not checked: the tables must be consistent with V and M. */
+#define EMPOSE_SAMPLE_LOCAL_NONE 0
+#define EMPOSE_SAMPLE_LOCAL_WINDOW 1
+#define EMPOSE_SAMPLE_LOCAL_FRAME 2
+int empose_sample_sensors_fwd(int N, int F, int V, const float* vertices, int M, int max_deg, const int* center,
+                              const int* helper, const int* deg, const int* faces, int mode, const float* local,
+                              const float* r, float* pos, float* ori, float* normals, float* pos_synth,
+                              float* ori_synth, float* normal_synth, empose_stream_t stream);
+
+/* Vector-Jacobian product of empose_sample_sensors_fwd with respect to the vertices (`local` and `r` are constants and
+ * get no cotangent): for the cotangents of the six outputs (any may be NULL, not all) it writes d_vertices
+ * [N * F][V][3], every element.  One launch folds the synth cotangents into those of (pos, ori),
+ *   d_pos = d_pos_synth,   d_ori = d_pos_synth (x) local + (d_ori_synth + d_normal_synth in column 2) . r^T,
+ * and adds d_pos and d_ori; the sensor and vertex passes of empose_virtual_sensors_vjp, with its tables and its choice
+ * between the dense and the touched-vertices form, do the rest.  Deterministic, no atomics.
+ * Workspace: empose_sample_sensors_vjp_workspace_bytes(N * F, M) -- 84 bytes per (frame, sensor) for a slab of frames
+ * with the caps of empose_virtual_sensors_vjp_workspace_bytes (0 for T or M <= 0).  Returns EMPOSE_EINVAL, before any GPU
+ * work, for what the forward refuses, a NULL reverse table or d_vertices, n_sub_faces or n_touched <= 0, six NULL
+ * cotangents or a workspace that is too small. */
+size_t empose_sample_sensors_vjp_workspace_bytes(int T, int M);
+int empose_sample_sensors_vjp(int N, int F, int V, const float* vertices, int M, int max_deg, const int* center,
+                              const int* helper, const int* deg, const int* faces, int n_sub_faces,
+                              const int* sub_faces, const int* face_ptr, const int* face_sensors, const int* vf_ptr,
+                              const int* vf_corner, const int* vs_ptr, const int* vs_role, int n_touched,
+                              const int* touched, int mode, const float* local, const float* r, const float* d_pos,
+                              const float* d_ori, const float* d_normals, const float* d_pos_synth,
+                              const float* d_ori_synth, const float* d_normal_synth, float* d_vertices,
+                              void* workspace, size_t workspace_bytes, empose_stream_t stream);
 
 /* ---- optional per-launch timing ------------------------------------------------------------------------------- */
 /* While enabled, every kernel launch issued by the entry points above is bracketed by HIP events on the launch stream

@@ -108,10 +108,10 @@ def train_on_amass(args, dev, rank, world):
     if not offsets:
         raise SystemExit('no *_offsets.npz files: pass --offset_files or set EM_DATA_REAL')
     buckets = make_buckets(net, params, world, args)
-    fn_train = get_end_to_end_preprocess_fn(cfg, smpl, offsets, randomize_if_configured=True,
-                                            device_normalize=args.device_normalize, device_noise=True)
-    fn_valid = get_end_to_end_preprocess_fn(cfg, smpl, offsets, randomize_if_configured=False,
-                                            device_normalize=args.device_normalize, device_noise=True)
+    switches = dict(device_normalize=args.device_normalize, device_noise=True, device_offsets=args.device_offsets,
+                    sensors_only=args.sensors_only)
+    fn_train = get_end_to_end_preprocess_fn(cfg, smpl, offsets, randomize_if_configured=True, **switches)
+    fn_valid = get_end_to_end_preprocess_fn(cfg, smpl, offsets, randomize_if_configured=False, **switches)
 
     # The sequences: AMASS npz files under --amass_dir, or the records of an LMDB database in the reference's key schema
     # (--amass_lmdb, + optionally a separate --valid_lmdb as the reference trains on AMASS and validates on 3DPW).
@@ -292,6 +292,10 @@ def main():
     p.add_argument('--data_workers', type=int, default=0)
     p.add_argument('--device_normalize', action='store_true', help='normalise the root orientations of a batch with the '
                    'root-frame kernel on the GPU instead of the float64 host round trip (NormalizeRoot(on_device=True))')
+    p.add_argument('--device_offsets', action='store_true', help='sample the synthetic sensors and apply their offsets in '
+                   'one launch of the sample-sensors kernel (SampleMarkersWithOffsets(on_device=True))')
+    p.add_argument('--sensors_only', action='store_true', help='ground-truth preprocessing evaluates the sensor sub-mesh '
+                   '(84 of 6890 vertices) instead of the full mesh (SMPLFK(vertex_ids=...))')
     p.add_argument('--resample_fps', type=float, default=None,
                    help='--amass_dir only: resample every sequence to this rate (the reference trains on 60 Hz) with the '
                         'resampling kernels when it is first loaded; default: the recorded rate, as it is')
