@@ -239,6 +239,13 @@ SIGNATURES = {
                                            [C.c_int] + [C.c_void_p] * 7 + [C.c_int, C.c_void_p] +
                                            [C.c_int] + [C.c_void_p] * 8 + [C.c_void_p] +
                                            [C.c_void_p, C.c_size_t, C.c_void_p]),
+    'empose_offset_stats_workspace_bytes': (C.c_size_t, [C.c_int] * 3),
+    # (T, V, vertices, M, max_deg; center, helper, deg, faces; p, R, masks; G and the group table (numpy records of
+    # data/offsets.py GROUP_DTYPE) on the host and on the device; means, covs, r, r_trace, counts; local_f, q_f;
+    # workspace, its bytes; stream)
+    'empose_offset_stats': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 +
+                                     [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 +
+                                     [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t, C.c_void_p]),
     'empose_profile_enable': (C.c_int, [C.c_int]),
     'empose_profile_enable_only': (C.c_int, [C.c_char_p]),
     'empose_profile_ntags': (C.c_int, []),

@@ -921,6 +921,31 @@ struct SensorNoiseArgs {
 };
 hipError_t launch_sensor_noise(const SensorNoiseArgs& a, hipStream_t stream);
 
+// Per-subject sensor offsets from calibration recordings (offset_stats.hip): the inverse of launch_sample_sensors.  Per
+// frame f and sensor m, with (pos, ori) the frame of sensor_frame.h on the ground-truth mesh and (p, R) the real reading,
+//   o = ori^T (p - pos),   Q = ori^T R,
+// and per (group, sensor) over the group's frames with mask == 1: the mean and the sample covariance of o, and the
+// rotation closest to the mean of Q.  A group is a run of consecutive frames; the layout of a row is that of
+// empose_offset_group (include/empose_hip.h).
+constexpr int OFFSET_STATS_CHUNK = 256;   // frames per workgroup of the first pass, counted from the group's first frame
+constexpr int OFFSET_STATS_SUMS = 19;     // count | sum o (3) | sum o o^T xx xy xz yy yz zz | sum Q (9)
+struct OffsetGroup {
+  int first_frame, n_frames;
+};
+struct OffsetStatsArgs {
+  const float* vertices;   // [T][V][3]
+  const int* center; const int* helper; const int* deg; const int* faces;   // as VirtualSensorArgs
+  const float* p; const float* R;   // [T][M][3], [T][M][9]
+  const float* masks;               // [T][M] or nullptr (every frame counts)
+  const OffsetGroup* groups; int G; // device table
+  double* sums;                     // [n_chunks][M][OFFSET_STATS_SUMS], a group's chunks after those of the groups before it
+  float* local_f; float* q_f;       // [T][M][3], [T][M][9] or nullptr; written for the frames of the groups only
+  float* means; float* covs; float* r; float* r_trace; int* counts;   // [G][M][3], [G][M][9], [G][M][9], [G][M], [G][M]
+  int T, V, M, max_deg;
+  int n_chunks;                     // sum over the groups of ceil(n_frames / OFFSET_STATS_CHUNK)
+};
+hipError_t launch_offset_stats(const OffsetStatsArgs& a, hipStream_t stream);
+
 struct MetricsArgs {
   const float* joints_gt; const float* joints_hat;   // [T][22][3]
   const float* pose_gt; const float* pose_hat;       // [T][63] body axis-angles (no root) or nullptr

@@ -653,6 +653,44 @@ int empose_sample_sensors_vjp(int N, int F, int V, const float* vertices, int M,
                               const float* d_ori_synth, const float* d_normal_synth, float* d_vertices,
                               void* workspace, size_t workspace_bytes, empose_stream_t stream);
 
+/* ---- per-subject sensor offsets from calibration recordings (the inverse of empose_sample_sensors_fwd) -------------- */
+/* The offset sets empose_sample_sensors_fwd consumes, estimated from recordings with ground-truth meshes and real
+ * readings (csrc/offset_stats.hip).  The definition is this library's own: the reference ships the resulting files, not
+ * their estimator.  Per frame f and sensor m, with (pos, ori) the virtual sensor of empose_virtual_sensors_fwd on
+ * vertices [T][V][3] -- same tables, same arithmetic (csrc/sensor_frame.h) -- and (p [T][M][3], R [T][M][3][3]) the real
+ * reading in the same frame:
+ *   o = ori^T (p - pos)        Q = ori^T R
+ * A frame counts for a sensor iff masks [T][M] reads 1 there (masks NULL: every frame counts).  A group is a run of
+ * consecutive frames, one subject's pooled recordings; per (group, sensor), over its n counting frames:
+ *   means   [G][M][3]     sum o / n
+ *   covs    [G][M][3][3]  sum (o - means)(o - means)^T / (n - 1); zeros when n < 2
+ *   r       [G][M][3][3]  the rotation closest to A = sum Q / n: with A = U S V^T, singular values descending,
+ *                         U diag(1, 1, det(U V^T)) V^T
+ *   r_trace [G][M]        s1 + s2 + det(U V^T) s3 = the mean of trace(r^T Q), in [-1, 3]; 3: every Q equals r
+ *   counts  [G][M]        n (int32)
+ * and for n = 0: means = 0, covs = 0, r = I, r_trace = 3.  local_f [T][M][3] and q_f [T][M][3][3], each optional (NULL),
+ * receive o and Q of the frames of the groups, zeros where the frame does not count; frames outside every group are
+ * not written.  o and Q are fp32; the sums are float64, added in a fixed order without atomics, a group in chunks of 256
+ * frames counted from its own first frame: repeated calls give the same bits, and a group gives the same bits alone as
+ * among others.  The outputs are fp32.
+ * The group table is given twice, like the sequence table of empose_resample_rotations: groups_host is checked here,
+ * groups_dev (the same G rows in device memory) is what the kernels read.
+ * Workspace: empose_offset_stats_workspace_bytes(T, G, M) -- 19 doubles per sensor and chunk for ceil(T / 256) + G
+ * chunks, a bound on what non-overlapping groups can own (0 for T, G or M <= 0).
+ * Returns EMPOSE_EINVAL, before any GPU work, for a NULL vertex, table, reading, group-table or statistics pointer, T, V,
+ * M, max_deg or G <= 0 (or T * M or G * M above 2^31 - 1), a group with n_frames < 0, with frames outside [0, T) or
+ * starting before the end of the group before it (groups ascend and do not overlap; n_frames = 0 is allowed), or a
+ * workspace that is too small.  Indices are not checked: the tables must be consistent with V and M. */
+typedef struct {
+  int first_frame, n_frames;
+} empose_offset_group;
+size_t empose_offset_stats_workspace_bytes(int T, int G, int M);
+int empose_offset_stats(int T, int V, const float* vertices, int M, int max_deg, const int* center, const int* helper,
+                        const int* deg, const int* faces, const float* p, const float* R, const float* masks, int G,
+                        const empose_offset_group* groups_host, const empose_offset_group* groups_dev, float* means,
+                        float* covs, float* r, float* r_trace, int* counts, float* local_f, float* q_f,
+                        void* workspace, size_t workspace_bytes, empose_stream_t stream);
+
 /* ---- optional per-launch timing ------------------------------------------------------------------------------- */
 /* While enabled, every kernel launch issued by the entry points above is bracketed by HIP events on the launch stream
  * and attributed to one of empose_profile_ntags() categories (GEMMs by role, LSTM step, chain kernel, ...).
