@@ -156,6 +156,17 @@ class _HipLinearLargeFn(torch.autograd.Function):
         return dx, dw, db
 
 
+def lstm_structs(weights, n_layers, input_size, hidden_size, grads=None):
+    """LstmParams of a flat weight list (w_ih, w_hh, b_ih, b_hh per layer) and, with `grads` (one tensor per weight), LstmGrads."""
+    p, g = _lib.LstmParams(), None if grads is None else _lib.LstmGrads()
+    p.num_layers, p.input_size, p.hidden_size = n_layers, input_size, hidden_size
+    for l in range(n_layers):
+        p.w_ih[l], p.w_hh[l], p.b_ih[l], p.b_hh[l] = [w.data_ptr() for w in weights[4 * l:4 * l + 4]]
+        if g is not None:
+            g.w_ih[l], g.w_hh[l], g.b_ih[l], g.b_hh[l] = [t.data_ptr() for t in grads[4 * l:4 * l + 4]]
+    return p, g
+
+
 class _LstmTrainFn(torch.autograd.Function):
     """Stacked uni-directional LSTM over ragged rows with hand-written forward and back-propagation through time
     (`empose_lstm_train_fwd/bwd`): the forward is the inference wavefront kernel saving gates / cell states / incoming
@@ -168,11 +179,8 @@ class _LstmTrainFn(torch.autograd.Function):
         B, F, K = x.shape
         H = weights[1].shape[1]
         dev, lib = x.device, _lib.lib()
-        p = _lib.LstmParams()
-        p.num_layers, p.input_size, p.hidden_size = n_layers, K, H
         ws_ = [w.contiguous() for w in weights]
-        for l in range(n_layers):
-            p.w_ih[l], p.w_hh[l], p.b_ih[l], p.b_hh[l] = [ws_[4 * l + k].data_ptr() for k in range(4)]
+        p, _ = lstm_structs(ws_, n_layers, K, H)
         y = torch.empty(B, F, H, dtype=torch.float32, device=dev)
         h_n = torch.empty(n_layers, B, H, dtype=torch.float32, device=dev)
         c_n = torch.empty(n_layers, B, H, dtype=torch.float32, device=dev)
@@ -196,12 +204,8 @@ class _LstmTrainFn(torch.autograd.Function):
         B, F, K = x.shape
         H = weights[1].shape[1]
         dev, lib = x.device, _lib.lib()
-        p, g = _lib.LstmParams(), _lib.LstmGrads()
-        p.num_layers, p.input_size, p.hidden_size = L, K, H
         grads = [torch.empty_like(w) for w in weights]
-        for l in range(L):
-            p.w_ih[l], p.w_hh[l], p.b_ih[l], p.b_hh[l] = [weights[4 * l + k].data_ptr() for k in range(4)]
-            g.w_ih[l], g.w_hh[l], g.b_ih[l], g.b_hh[l] = [grads[4 * l + k].data_ptr() for k in range(4)]
+        p, g = lstm_structs(weights, L, K, H, grads)
         dx = torch.empty_like(x) if ctx.needs_input_grad[0] else None
         # the cotangents of a given initial state (a learned one, reference layers.py:121-131), where autograd wants them
         d_h0 = d_c0 = None

@@ -847,21 +847,18 @@ class IterativeErrorFeedback(BaseModel):
             hists.append(res['hist'])
             traces.append(res['trace'])
 
-        bsz = batch.batch_size
-        if self.keep_history:
-            # Same shapes as reference models.py:611-629: history entry h is (B, -1, last_dim of the flat tensor).
-            def merged(key, inner):
-                res = []
-                for h in range(self.N + 1):
-                    parts = [hw[key][h].reshape(bsz, -1, inner) for hw in hists]
-                    res.append(_cat_windows(parts))
-                return res
-            self.pose_hat_history = merged('pose', 66)
-            self.shape_hat_history = merged('shape', 10)
-            self.joints_hat_history = merged('joints', 3)
-            self.markers_hat_history = merged('markers', 3)
-            self.markers_ori_hat_history = merged('markers_ori', 3)
         self.gradient_trace = traces if self.keep_gradient_trace else None
+        return self._merge_windows(batch.batch_size, outs, hists if self.keep_history else None)
+
+    def _merge_windows(self, bsz, outs, hists):
+        """The model output over all windows and, with `hists`, the merged histories (same shapes as reference
+        models.py:611-629: history entry h is (B, -1, last_dim of the flat tensor))."""
+        if hists is not None:
+            def merged(key, inner):
+                return [_cat_windows([hw[key][h].reshape(bsz, -1, inner) for hw in hists]) for h in range(self.N + 1)]
+            self.pose_hat_history, self.shape_hat_history = merged('pose', 66), merged('shape', 10)
+            self.joints_hat_history, self.markers_hat_history = merged('joints', 3), merged('markers', 3)
+            self.markers_ori_hat_history = merged('markers_ori', 3)
         pose = _cat_windows([o['pose'] for o in outs])
         return {'pose_hat': pose[:, :, 3:], 'root_ori_hat': pose[:, :, :3],
                 'shape_hat': _cat_windows([o['shape'] for o in outs]),
@@ -884,19 +881,7 @@ class IterativeErrorFeedback(BaseModel):
                 out, hist = self._forward_train(batch_inputs)
             outs.append(out)
             hists.append(hist)
-        bsz = batch.batch_size
-
-        def merged(key, inner):
-            return [_cat_windows([hw[key][h].reshape(bsz, -1, inner) for hw in hists]) for h in range(self.N + 1)]
-        self.pose_hat_history = merged('pose', 66)
-        self.shape_hat_history = merged('shape', 10)
-        self.joints_hat_history = merged('joints', 3)
-        self.markers_hat_history = merged('markers', 3)
-        self.markers_ori_hat_history = merged('markers_ori', 3)
-        pose = _cat_windows([o['pose'] for o in outs])
-        return {'pose_hat': pose[:, :, 3:], 'root_ori_hat': pose[:, :, :3],
-                'shape_hat': _cat_windows([o['shape'] for o in outs]),
-                'joints_hat': _cat_windows([o['joints'] for o in outs])}
+        return self._merge_windows(batch.batch_size, outs, hists)
 
     def _select_markers(self, t):
         """(bs, f, 12, d) -> the model's sensors; the index lives on the device (no host copy per call)."""

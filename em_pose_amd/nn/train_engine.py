@@ -21,6 +21,7 @@ computation as an explicit forward sweep and an explicit reverse sweep over the 
 Covers the released configurations (no skip connections, BatchNorm on, dropout 0, one window per forward); anything
 else stays on the autograd path of nn/models.py.
 """
+import collections
 import contextlib
 import ctypes as C
 
@@ -28,6 +29,12 @@ import torch
 
 from em_pose_amd import _lib
 from em_pose_amd.nn import layers as _layers
+
+# row widths (floats) of the estimates and of what the body model makes of them
+POSE, SHAPE, MARKERS, ORIS = 66, 10, 36, 108
+POSE_PAD, SHAPE_PAD = 68, 12     # cotangent rows of the networks' outputs: padded to a multiple of 4 with zero columns
+# a network input row is [x0 (d_in) | pose_i | shape_i | g_pose | g_shape]: where the gradient features start, past d_in
+G_POSE_COL, G_SHAPE_COL = POSE + SHAPE, POSE + SHAPE + POSE
 
 
 def _ptr(t):
@@ -43,8 +50,7 @@ class _MlpView(object):
         self.mlp = mlp
         self.specs = mlp.dense_specs()
         self.n_layers = len(self.specs)
-        self.in_dim = self.specs[0][0].in_features
-        self.hidden = self.specs[0][0].out_features
+        self.in_dim, self.hidden = self.specs[0][0].in_features, self.specs[0][0].out_features
         self.out_dim = self.specs[-1][0].out_features
         self.weight_t = None
         self.weight_x3 = None     # pack_forward_x3(): three-piece bf16 copies of the hidden layers' weights (large batches)
@@ -55,8 +61,7 @@ class _MlpView(object):
         """Pin the save-buffer layout of this step to what the library's options select NOW: the backward and weight-gradient
         calls then read the buffer the way the forward wrote it, whatever happens to the options in between."""
         self.save_layout = 0
-        p = self.params()
-        layout = lib.empose_mlp_train_save_layout(C.byref(p), int(M))
+        layout = lib.empose_mlp_train_save_layout(C.byref(self.params()), int(M))
         if layout <= 0:
             _lib.check(layout)
         self.save_layout = layout
@@ -87,16 +92,18 @@ class _MlpView(object):
                 p.prelu[l] = act.weight.data_ptr()
                 p.bn_eps, p.bn_momentum = float(bn.eps), float(bn.momentum)
         p.save_layout = self.save_layout
-        for l, t in enumerate(self.weight_t or ()):   # transposed once per step (prepare_backward)
-            if t is not None:
-                p.weight_t[l] = t.data_ptr()
-        for name in ('weight_x3', 'weight_t_x3'):     # packed once per step (pack_forward_x3 / prepare_backward)
+        for name in ('weight_t', 'weight_x3', 'weight_t_x3'):     # once per step (prepare_backward / pack_forward_x3)
             for l, t in enumerate(getattr(self, name) or ()):
                 if t is not None:
                     getattr(p, name)[l] = t.data_ptr()
         return p
 
     X3_MIN_ROWS = 1024       # below, the library runs these layers on other kernels (one-launch layers, fp32 tiles)
+
+    def wants_x3(self, lib, M):
+        """Whether the hidden layers' products of M rows run on three bf16 pieces (and so need the packed weights)."""
+        return M is not None and M >= _MlpView.X3_MIN_ROWS and self.hidden % 64 == 0 and \
+            lib.empose_get_option(b'train_x3') != 0
 
     def _pack_x3(self, lib, stream, W, ld, n_rows, n_cols):
         nbytes = lib.empose_pack_weight_x3_bytes(int(n_rows), int(n_cols))
@@ -108,7 +115,7 @@ class _MlpView(object):
         """Three-piece bf16 copies (fragment order) of the hidden layers' weights for the forward products of this step:
         once per step, like the transposed copies -- the weights do not change inside a step.  Large batches only."""
         self.weight_x3 = None
-        if M < _MlpView.X3_MIN_ROWS or self.hidden % 64 != 0 or lib.empose_get_option(b'train_x3') == 0:
+        if not self.wants_x3(lib, M):
             return
         self.weight_x3 = []
         for lin, bn, _ in self.specs:
@@ -121,8 +128,7 @@ class _MlpView(object):
         reads W itself (the one-launch layers of small batches)."""
         self.weight_t = None
         if M is not None and not _MlpView.always_transpose:
-            p = self.params()
-            uses = lib.empose_mlp_train_uses_weight_t(C.byref(p), int(M))
+            uses = lib.empose_mlp_train_uses_weight_t(C.byref(self.params()), int(M))
             if uses < 0:
                 _lib.check(uses)
             if uses == 0:
@@ -138,41 +144,69 @@ class _MlpView(object):
         # ... and their three-piece bf16 copies for dA = dY . W on the bf16 matrix cores (the product against W^T
         # [in][ld]: "N" = in features, "K" = ld = out features padded to a multiple of 4 with zero columns)
         self.weight_t_x3 = None
-        if M is not None and M >= _MlpView.X3_MIN_ROWS and self.hidden % 64 == 0 and lib.empose_get_option(b'train_x3') != 0:
+        if self.wants_x3(lib, M):
             self.weight_t_x3 = [None] + [self._pack_x3(lib, stream, t, t.shape[1], t.shape[0], t.shape[1])
                                          for t in self.weight_t[1:]]
 
     def parameter_list(self):
-        out = []
-        for lin, bn, act in self.specs:
-            out += [lin.weight, lin.bias]
-            if bn is not None:
-                out += [bn.weight, bn.bias, act.weight]
-        return out
+        return [t for lin, bn, act in self.specs
+                for t in (lin.weight, lin.bias) + ((bn.weight, bn.bias, act.weight) if bn is not None else ())]
 
     def grads(self, tensors):
-        g = _lib.MlpGrads()
-        k = 0
+        g, ptrs = _lib.MlpGrads(), iter([t.data_ptr() for t in tensors])     # (in the order of parameter_list())
         for l, (lin, bn, act) in enumerate(self.specs):
-            g.weight[l], g.bias[l] = tensors[k].data_ptr(), tensors[k + 1].data_ptr()
-            k += 2
+            g.weight[l], g.bias[l] = next(ptrs), next(ptrs)
             if bn is not None:
-                g.bn_weight[l], g.bn_bias[l], g.prelu[l] = [t.data_ptr() for t in tensors[k:k + 3]]
-                k += 3
+                g.bn_weight[l], g.bn_bias[l], g.prelu[l] = next(ptrs), next(ptrs), next(ptrs)
         return g
 
 
 def _lstm_params(rnn, input_size, grads=None):
     """LstmParams of an LSTM stack and, with `grads` (one tensor per weight), LstmGrads; also returns the weights."""
     weights = [w for unit in rnn._unit_params() for w in unit]
-    p = _lib.LstmParams()
-    p.num_layers, p.input_size, p.hidden_size = rnn.num_layers, input_size, rnn.hidden_size
-    g = None if grads is None else _lib.LstmGrads()
-    for l in range(rnn.num_layers):
-        p.w_ih[l], p.w_hh[l], p.b_ih[l], p.b_hh[l] = [weights[4 * l + k].data_ptr() for k in range(4)]
-        if g is not None:
-            g.w_ih[l], g.w_hh[l], g.b_ih[l], g.b_hh[l] = [grads[4 * l + k].data_ptr() for k in range(4)]
-    return p, g, weights
+    return _layers.lstm_structs(weights, rnn.num_layers, input_size, rnn.hidden_size, grads) + (weights,)
+
+
+MAIN = None      # a stream of the plan is MAIN or the index of a side stream (0, 1)
+StreamPlan = collections.namedtuple('StreamPlan', 'fwd_split bwd_split pose_bwd shape_bwd pose_wgrad shape_wgrad '
+                                                  'join_before_wgrad fork_before_wgrad')
+
+
+def stream_plan(use_side, side_parts, deferred):
+    """Which stream runs which update network in a training step, decided once (the table is in DESIGN.md, section 8).
+    Without `use_side` (the step is too small for `two_streams`) everything is on MAIN; without `deferred` (the weight
+    gradients are formed per application) the reverse sweep is.  fwd_split / bwd_split: the shape network on side 0, forked
+    every iteration (and joined in the forward only), instead of one paired call on MAIN.  'bwd3' needs 'bwd'."""
+    on = lambda part: bool(use_side) and part in side_parts
+    bwd_split, side_w = bool(deferred) and on('bwd'), bool(deferred) and on('wgrad')
+    third = bwd_split and 'bwd3' in side_parts
+    return StreamPlan(on('fwd'), bwd_split, 1 if third else MAIN, 0 if bwd_split else MAIN,
+                      (1 if third else 0) if side_w else MAIN, 0 if side_w else MAIN,
+                      bool(use_side and deferred and not side_w), side_w and not third)
+
+
+# what produced the initial estimate and what its backward reads: the LSTM + two linear heads, or the two init MLPs
+_LstmStart = collections.namedtuple('_LstmStart', 'y c0 lstm_save')
+_MlpStart = collections.namedtuple('_MlpStart', 'views params saves')
+
+
+class _Step(object):
+    """What a training step keeps between forward() and backward() and between their phases; all on the main stream's pool."""
+    __slots__ = ('B', 'F', 'T', 'deferred', 'plan',              # windows, frames, rows = B * F; see _prepare
+                 'x0', 'scale',                                  # packed input rows (T, d_in); per-frame residual weight
+                 'lens32', 'masks', 'offset_r', 'offset_t',
+                 'pose_hist', 'shape_hist', 'markers_hist', 'ori_hist', 'joints_hist',    # (N + 1, T, width) each
+                 'X', 'views', 'params', 'saves',                # update networks: input rows (N, T, d_x), _MlpViews,
+                 'smpl_h', 'start',                              # MlpParams, saves per iteration; _LstmStart / _MlpStart
+                 'tmp10', 'dp', 'ws_smpl', 'nb_smpl',            # scratch of the forward sweep; below, the reverse sweep:
+                 # cotangents, the update networks' gradients (tensors, MlpGrads), (x, save, stash) per deferred application
+                 'd_pose', 'd_shape', 'd_mark', 'd_ori', 'd_joints', 'loss_vals', 'Dp', 'Ds', 'vp', 'vs', 'dpad', 'dspad',
+                 'ws_vjp', 'nb_vjp', 'grads', 'gstructs', 'pend')
+
+    def __init__(self, **fields):
+        for name in self.__slots__:
+            setattr(self, name, fields.pop(name, None))
+        assert not fields, fields.keys()
 
 
 class LgdTrainEngine(object):
@@ -186,19 +220,19 @@ class LgdTrainEngine(object):
     # launches and the cross-stream hand-offs cost more than the overlap gives (12 windows: 4.2 -> 4.9 ms).
     two_streams = True
     two_streams_min_frames = 2048
-    # which uses of the side streams are on (A/B: scripts/train.py --streams): 'fwd' the shape network's forward beside the
-    # pose network's; 'bwd' its backward; 'bwd3' the pose network's backward on a second side stream, so that the main
-    # stream is only the cotangent chain, the heads and back-propagation through time; 'wgrad' the weight-gradient products
-    # behind them.  Measured at 256 windows (frames/s): none 684 k, fwd 713 k, bwd 714 k, wgrad 695 k, all 795-810 k.
+    # which uses of the side streams are on (A/B: scripts/train.py --streams; placements: stream_plan()): 'fwd' the shape
+    # network's forward beside the pose network's; 'bwd' its backward; 'bwd3' the pose network's backward on a second side
+    # stream, so that the main stream is only the cotangent chain, the heads and back-propagation through time; 'wgrad' the
+    # weight-gradient products behind them.  Measured at 256 windows (frames/s): none 684 k, fwd 713 k, bwd 714 k,
+    # wgrad 695 k, all 795-810 k.
     side_parts = ('fwd', 'bwd', 'bwd3', 'wgrad')
 
     def __init__(self, net):
         self.net = net
-        self.ctx = None
+        self.step = None          # _Step of the forward() that backward() has not consumed yet
         self._side_streams = {}
         self._use_side = False
-        self._held = []
-        self._forked = set()      # side streams forked and not yet joined
+        self._held, self._forked = [], set()      # main-stream workspaces held; side streams forked and not yet joined
 
     # ---- the side stream ------------------------------------------------------------------------------------------
     def _side(self, k=0):
@@ -223,6 +257,12 @@ class LgdTrainEngine(object):
         if not self._forked:
             self._held = []       # nothing is running beside the main stream: its workspaces may go back to the allocator
 
+    def _join_all(self):
+        """Join every side stream that is still forked, in index order (and no other: see _join)."""
+        for k in sorted(self._forked):
+            self._join(k)
+        self._held = []
+
     def _hold(self, t):
         """A main-stream workspace must not go back to the allocator between a fork and the next join: the block would be
         handed to the next main-pool allocation, and that tensor may be written by the side stream (which forked before
@@ -236,7 +276,7 @@ class LgdTrainEngine(object):
         """Launches (and transient allocations: workspaces, freed right after the launch, must belong to the stream that
         uses them) inside go to the side stream.  Long-lived tensors are allocated outside, on the main stream's pool,
         and freed only after a join."""
-        if not self._use_side:
+        if not self._use_side or k is MAIN:
             yield
             return
         main_raw = self.stream
@@ -249,8 +289,7 @@ class LgdTrainEngine(object):
 
     @staticmethod
     def supported(net):
-        if net.skip_connections or getattr(net.config, 'm_dropout_hidden', 0.0) > 0 or \
-                getattr(net.config, 'm_dropout', 0.0) > 0:
+        if net.skip_connections or getattr(net.config, 'm_dropout_hidden', 0.0) > 0 or getattr(net.config, 'm_dropout', 0.0) > 0:
             return False
         mlps = [net.pose_net_iter, net.shape_net_iter] + ([] if net.rnn_init else [net.pose_net_init, net.shape_net_init])
         if not all(_MlpView.supported(m) for m in mlps):
@@ -263,81 +302,58 @@ class LgdTrainEngine(object):
     def _axpby(self, rows, cols, alpha, x, ldx, beta, y, ldy, out, ldo):
         _lib.check(self.lib.empose_axpby2d(rows, cols, alpha, x, ldx, beta, y, ldy, out, ldo, self.stream))
 
-    def _mlp_fwd(self, view, x, ldx, out, ld_out, M, side=None):
-        p = view.params()
-        save = self.new(self.lib.empose_mlp_train_save_floats(C.byref(p), M))
-        nbytes = self.lib.empose_mlp_train_workspace_bytes(C.byref(p), M)
-        with (self._on_side(side) if side is not None else contextlib.nullcontext()):
-            ws = self.ws(nbytes) if side is not None else self._hold(self.ws(nbytes))
-            _lib.check(self.lib.empose_mlp_train_fwd(C.byref(p), M, x, ldx, out, ld_out, save.data_ptr(), ws.data_ptr(),
-                                                     nbytes, self.stream))
+    def _call(self, where, fn, nbytes, *args):
+        """check(fn(*args, workspace, nbytes, stream)) with the workspace allocated on the stream that uses it -- MAIN: the
+        main stream's pool, held while a side stream is forked (_hold); k: side stream k's, inside _on_side."""
+        with self._on_side(where):
+            ws = self._hold(self.ws(nbytes)) if where is MAIN else self.ws(nbytes)
+            _lib.check(fn(*args, ws.data_ptr(), nbytes, self.stream))
+
+    def _mlp_fwd(self, p, x, ldx, out, ld_out, M, where=MAIN):
+        lib, rp = self.lib, C.byref(p)
+        save = self.new(lib.empose_mlp_train_save_floats(rp, M))
+        self._call(where, lib.empose_mlp_train_fwd, lib.empose_mlp_train_workspace_bytes(rp, M),
+                   rp, M, x, ldx, out, ld_out, save.data_ptr())
         _layers.BN_STATS_GENERATION[0] += 1
         return save
 
-    def _mlp_fwd_pair(self, views, x, ldx, outs, ld_outs, M):
+    def _mlp_fwd_pair(self, ps, x, ldx, outs, ld_outs, M):
         """Both update networks of an iteration in one call (empose_mlp_train_fwd_pair: at the reference's training batch
         every layer of both is one launch); returns their save buffers."""
-        ps = [v.params() for v in views]
-        saves = [self.new(self.lib.empose_mlp_train_save_floats(C.byref(p), M)) for p in ps]
-        nbytes = self.lib.empose_mlp_train_pair_workspace_bytes(C.byref(ps[0]), C.byref(ps[1]), M)
-        ws = self._hold(self.ws(nbytes))
-        _lib.check(self.lib.empose_mlp_train_fwd_pair(C.byref(ps[0]), C.byref(ps[1]), M, x, ldx, outs[0], ld_outs[0],
-                                                      outs[1], ld_outs[1], saves[0].data_ptr(), saves[1].data_ptr(),
-                                                      ws.data_ptr(), nbytes, self.stream))
+        lib, r0, r1 = self.lib, C.byref(ps[0]), C.byref(ps[1])
+        s0, s1 = [self.new(lib.empose_mlp_train_save_floats(r, M)) for r in (r0, r1)]
+        self._call(MAIN, lib.empose_mlp_train_fwd_pair, lib.empose_mlp_train_pair_workspace_bytes(r0, r1, M),
+                   r0, r1, M, x, ldx, outs[0], ld_outs[0], outs[1], ld_outs[1], s0.data_ptr(), s1.data_ptr())
         _layers.BN_STATS_GENERATION[0] += 2
-        return saves
+        return s0, s1
 
-    def _mlp_bwd_deferred_pair(self, views, x, ldx, d_outs, ld_douts, saves, grads, accumulate, M, stashes):
-        ps = [v.params() for v in views]
-        gs = [v.grads(g) for v, g in zip(views, grads)]
-        nbytes = self.lib.empose_mlp_train_pair_workspace_bytes(C.byref(ps[0]), C.byref(ps[1]), M)
-        ws = self._hold(self.ws(nbytes))
-        _lib.check(self.lib.empose_mlp_train_bwd_deferred_pair(
-            C.byref(ps[0]), C.byref(ps[1]), M, x, ldx, d_outs[0], ld_douts[0], d_outs[1], ld_douts[1],
-            saves[0].data_ptr(), saves[1].data_ptr(), C.byref(gs[0]), C.byref(gs[1]), int(accumulate),
-            stashes[0].data_ptr(), stashes[1].data_ptr(), ws.data_ptr(), nbytes, self.stream))
-        return stashes
+    def _mlp_bwd_deferred_pair(self, ps, gs, x, ldx, d_outs, ld_douts, saves, accumulate, M, stashes):
+        lib, r0, r1 = self.lib, C.byref(ps[0]), C.byref(ps[1])
+        self._call(MAIN, lib.empose_mlp_train_bwd_deferred_pair, lib.empose_mlp_train_pair_workspace_bytes(r0, r1, M),
+                   r0, r1, M, x, ldx, d_outs[0], ld_douts[0], d_outs[1], ld_douts[1], saves[0].data_ptr(),
+                   saves[1].data_ptr(), C.byref(gs[0]), C.byref(gs[1]), int(accumulate), stashes[0].data_ptr(),
+                   stashes[1].data_ptr())
 
-    def _mlp_bwd(self, view, x, ldx, d_out, ld_dout, save, grads, accumulate, M):
-        p = view.params()
-        g = view.grads(grads)
-        nbytes = self.lib.empose_mlp_train_workspace_bytes(C.byref(p), M)
-        ws = self.ws(nbytes)
-        _lib.check(self.lib.empose_mlp_train_bwd(C.byref(p), M, x, ldx, d_out, ld_dout, save.data_ptr(), C.byref(g),
-                                                 int(accumulate), ws.data_ptr(), nbytes, self.stream))
-
-    def _new_stash(self, view, M):
+    def _new_stash(self, p, M):
         """Stash of one deferred application + the address of its d_out slot (row stride (out_dim + 3) & ~3): the
         cotangent kernel writes the output cotangent there directly, so the deferred backward copies nothing."""
-        p = view.params()
         stash = self.new(self.lib.empose_mlp_train_stash_floats(C.byref(p), M))
-        return stash, stash.data_ptr() + 4 * M * (view.n_layers - 1) * view.hidden
+        return stash, stash.data_ptr() + 4 * M * (p.n_layers - 1) * p.hidden
 
-    def _mlp_bwd_deferred(self, view, x, ldx, d_out, ld_dout, save, grads, accumulate, M, stash=None, side=None):
-        """Backward of one application that keeps the layer cotangents instead of forming dW / db; returns the stash."""
-        p = view.params()
-        g = view.grads(grads)
-        if stash is None:
-            stash = self.new(self.lib.empose_mlp_train_stash_floats(C.byref(p), M))
-        nbytes = self.lib.empose_mlp_train_workspace_bytes(C.byref(p), M)
-        with (self._on_side(side) if side is not None else contextlib.nullcontext()):
-            ws = self.ws(nbytes) if side is not None else self._hold(self.ws(nbytes))
-            _lib.check(self.lib.empose_mlp_train_bwd_deferred(C.byref(p), M, x, ldx, d_out, ld_dout, save.data_ptr(),
-                                                              C.byref(g), int(accumulate), stash.data_ptr(),
-                                                              ws.data_ptr(), nbytes, self.stream))
-        return stash
+    def _mlp_bwd(self, p, g, x, ldx, d_out, ld_dout, save, accumulate, M, stash=None, where=MAIN):
+        """Backward of one application: dW / db into `g`, or (deferred) the layer cotangents kept in `stash` instead."""
+        lib, rp = self.lib, C.byref(p)
+        fn, tail = (lib.empose_mlp_train_bwd, ()) if stash is None else (lib.empose_mlp_train_bwd_deferred, (stash.data_ptr(),))
+        self._call(where, fn, lib.empose_mlp_train_workspace_bytes(rp, M),
+                   rp, M, x, ldx, d_out, ld_dout, save.data_ptr(), C.byref(g), int(accumulate), *tail)
 
-    def _mlp_wgrad(self, view, xs, ldx, saves, stashes, grads, M):
-        """dW, db of one network over all its applications: one A^T B product per layer (empose_mlp_train_wgrad)."""
-        p = view.params()
-        g = view.grads(grads)
-        n = len(xs)
-        arr = lambda ptrs: (C.c_void_p * n)(*ptrs)
-        nbytes = self.lib.empose_mlp_train_wgrad_workspace_bytes(C.byref(p), n, M)
-        ws = self.ws(nbytes)
-        _lib.check(self.lib.empose_mlp_train_wgrad(C.byref(p), n, M, arr(xs), ldx, arr([t.data_ptr() for t in saves]),
-                                                   arr([t.data_ptr() for t in stashes]), C.byref(g), 0, ws.data_ptr(),
-                                                   nbytes, self.stream))
+    def _mlp_wgrad(self, p, g, pend, ldx, M, where=MAIN):
+        """dW, db of one network over all its applications `pend` = [(x, save, stash)]: one A^T B product per layer
+        (empose_mlp_train_wgrad)."""
+        lib, rp, n = self.lib, C.byref(p), len(pend)
+        xs, saves, stashes = [(C.c_void_p * n)(*col) for col in zip(*[(x, sv.data_ptr(), sh.data_ptr()) for x, sv, sh in pend])]
+        self._call(where, lib.empose_mlp_train_wgrad, lib.empose_mlp_train_wgrad_workspace_bytes(rp, n, M),
+                   rp, n, M, xs, ldx, saves, stashes, C.byref(g), 0)
 
     def ws(self, nbytes):
         return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=self.dev)
@@ -348,16 +364,11 @@ class LgdTrainEngine(object):
         """The parameters in the order in which the reverse sweep finishes their gradients: update networks, then what
         produced the initial estimate (heads, LSTM last).  `helpers.distributed.GradientBuckets` lays its flat buckets
         out in this order so that the first buckets can be all-reduced while the rest is still being computed."""
-        order = []
-        for mlp in (net.pose_net_iter, net.shape_net_iter):
-            order += _MlpView(mlp).parameter_list()
+        mlps = [net.pose_net_iter, net.shape_net_iter] + ([] if net.rnn_init else [net.pose_net_init, net.shape_net_init])
+        order = [p for mlp in mlps for p in _MlpView(mlp).parameter_list()]
         if net.rnn_init:
-            order += [net.pose_net_init.weight, net.pose_net_init.bias, net.shape_net_init.weight,
-                      net.shape_net_init.bias]
+            order += [net.pose_net_init.weight, net.pose_net_init.bias, net.shape_net_init.weight, net.shape_net_init.bias]
             order += [w for unit in net.rnn._unit_params() for w in unit]
-        else:
-            for mlp in (net.pose_net_init, net.shape_net_init):
-                order += _MlpView(mlp).parameter_list()
         seen, out = set(), []
         for p in order:
             if id(p) not in seen and p.requires_grad:
@@ -375,305 +386,294 @@ class LgdTrainEngine(object):
                 return view
         return torch.empty_like(p)
 
-    def _deposit(self, named):
-        """autograd's AccumulateGrad for a finished group of parameters, then tell the sink that they are final."""
+    def _deposit(self, named, where=MAIN):
+        """autograd's AccumulateGrad for a finished group of parameters, then tell the sink that they are final: in the
+        context of the stream that formed the gradients."""
         sink = getattr(self.net, '_grad_sink', None)
-        for p_, g_ in named:
-            if not p_.requires_grad:
-                continue
-            if p_.grad is None:
-                p_.grad = g_
-            elif p_.grad.data_ptr() != g_.data_ptr():
-                self._axpby(1, g_.numel(), 1.0, g_.data_ptr(), g_.numel(), 1.0, p_.grad.data_ptr(), g_.numel(),
-                            p_.grad.data_ptr(), g_.numel())
-            if sink is not None:
-                sink.stage(p_)
+        with self._on_side(where):
+            for p_, g_ in named:
+                if not p_.requires_grad:
+                    continue
+                if p_.grad is None:
+                    p_.grad = g_
+                elif p_.grad.data_ptr() != g_.data_ptr():
+                    self._axpby(1, g_.numel(), 1.0, g_.data_ptr(), g_.numel(), 1.0, p_.grad.data_ptr(), g_.numel(),
+                                p_.grad.data_ptr(), g_.numel())
+                if sink is not None:
+                    sink.stage(p_)
 
     def new(self, *shape):
         return torch.empty(*shape, dtype=torch.float32, device=self.dev)
 
     # ---- forward ------------------------------------------------------------------------------------------------
     def forward(self, batch_inputs):
+        net, N = self.net, self.net.N
+        st = self.step = self._prepare(batch_inputs)
+        T, tmp10, shape0 = st.T, st.tmp10.data_ptr(), st.shape_hist[0].data_ptr()
+        with torch.cuda.device(self.dev):
+            st.smpl_h = net._ensure_smpl_handle(self.dev)
+            st.start = self._lstm_start() if net.rnn_init else self._mlp_start()     # pose_0, and shape rows in tmp10
+            if net.shape_avg:                                                        # shape_0: their window mean
+                _lib.check(self.lib.empose_window_mean(T, st.F, SHAPE, tmp10, SHAPE, shape0, SHAPE, self.stream))
+            else:
+                self._axpby(T, SHAPE, 1.0, tmp10, SHAPE, 0.0, None, 0, shape0, SHAPE)
+            (st.views, st.params), st.saves = self._views((net.pose_net_iter, net.shape_net_iter), T), []
+            st.X, st.dp = self.new(max(N, 1), T, net.input_iter_size), self.new(T, POSE)
+            st.nb_smpl = self.lib.empose_smpl_workspace_bytes(st.smpl_h, T)
+            st.ws_smpl = self.ws(st.nb_smpl)
+            for i in range(N + 1):
+                self._iteration_fwd(i)
+        st.tmp10 = st.dp = st.ws_smpl = None
+        hist = {'pose': list(st.pose_hist), 'shape': list(st.shape_hist), 'joints': list(st.joints_hist),
+                'markers': list(st.markers_hist), 'markers_ori': list(st.ori_hist)}
+        out = {'pose': st.pose_hist[N].reshape(st.B, st.F, POSE), 'shape': st.shape_hist[N].reshape(st.B, st.F, SHAPE),
+               'joints': st.joints_hist[N].reshape(st.B, st.F, POSE)}
+        return out, hist
+
+    def _prepare(self, batch_inputs):
+        """Device and stream of the step, its packed inputs, its stream plan and its history buffers.  What lives until
+        backward() is allocated here and in the phases on the MAIN stream's pool, never inside _on_side."""
         net = self.net
         if not batch_inputs['marker_pos'].is_cuda:
             raise _lib.EmposeError('IterativeErrorFeedback needs GPU tensors; there is no CPU fallback')
         dev = self.dev = batch_inputs['marker_pos'].device
-        lib = self.lib = _lib.lib()
+        self.lib = _lib.lib()
         self.stream = _lib.current_stream()
-        seq_lengths = batch_inputs['seq_lengths'].to(dev)
-        lens32 = seq_lengths.to(torch.int32).contiguous()
-        masks = batch_inputs['marker_masks']
-        masks = None if masks is None else masks.to(dev, torch.float32).contiguous()
+        lens32 = batch_inputs['seq_lengths'].to(dev).to(torch.int32).contiguous()
+        masks = batch_inputs['marker_masks'] if batch_inputs['marker_masks'] is None else \
+            batch_inputs['marker_masks'].to(dev, torch.float32).contiguous()
         # network input rows + the per-frame weight of the in-loop residual (reference loss.py:36-39 times the B * F
         # rescale of models.py:578-579) in one launch
         from em_pose_amd.nn.models import pack_sensor_inputs
         inputs_, scale = pack_sensor_inputs(batch_inputs['marker_pos'], batch_inputs['marker_oris'], net.marker_idxs,
                                             masks, lens32, want_frame_weight=True)
-        B, F = inputs_.shape[0], inputs_.shape[1]
-        T, N, s = B * F, net.N, float(net.step_size)
+        (B, F), n_hist = inputs_.shape[:2], net.N + 1
+        T = B * F
         self._use_side = bool(self.two_streams and T >= self.two_streams_min_frames)
-        d_in, d_x = net.input_size, net.input_iter_size
-        x0 = inputs_.reshape(T, d_in)
-        masks = None if masks is None else masks.reshape(T, 12)
-        offset_r = batch_inputs['offset_r'].to(dev, torch.float32).contiguous()
-        offset_t = batch_inputs['offset_t'].to(dev, torch.float32).contiguous()
+        deferred = self.batched_wgrad and 1 <= net.N <= 8   # (row counts off the 32-row grid: per application inside)
+        return _Step(B=B, F=F, T=T, deferred=deferred, plan=stream_plan(self._use_side, self.side_parts, deferred),
+                     x0=inputs_.reshape(T, net.input_size), scale=scale, lens32=lens32,
+                     masks=None if masks is None else masks.reshape(T, 12),
+                     offset_r=batch_inputs['offset_r'].to(dev, torch.float32).contiguous(),
+                     offset_t=batch_inputs['offset_t'].to(dev, torch.float32).contiguous(),
+                     pose_hist=self.new(n_hist, T, POSE), shape_hist=self.new(n_hist, T, SHAPE),
+                     markers_hist=self.new(n_hist, T, MARKERS), ori_hist=self.new(n_hist, T, ORIS),
+                     joints_hist=self.new(n_hist, T, POSE), tmp10=self.new(T, SHAPE))
 
-        ctx = self.ctx = {'B': B, 'F': F, 'x0': x0, 'lens32': lens32, 'masks': masks, 'offset_r': offset_r,
-                          'offset_t': offset_t}
-        pose_hist, shape_hist = self.new(N + 1, T, 66), self.new(N + 1, T, 10)
-        markers_hist, ori_hist = self.new(N + 1, T, 36), self.new(N + 1, T, 108)
-        joints_hist = self.new(N + 1, T, 66)
-        tmp10 = self.new(T, 10)
-        with torch.cuda.device(dev):
-            smpl_h = net._ensure_smpl_handle(dev)
-            if net.rnn_init:
-                rnn = net.rnn
-                rnn.init_state = rnn.final_state
-                L, H = rnn.num_layers, rnn.hidden_size
-                p, _, _ = _lstm_params(rnn, d_in)
-                h0 = c0 = None
-                if rnn.init_state is not None:
-                    h0, c0 = [t.detach().to(dev, torch.float32).contiguous() for t in rnn.init_state]
-                y = self.new(T, H)
-                h_n, c_n = self.new(L, B, H), self.new(L, B, H)
-                save = self.new(lib.empose_lstm_train_save_floats(L, B, F, H))
-                nbytes = lib.empose_lstm_train_workspace_bytes(C.byref(p), B, F)
-                ws = self.ws(nbytes)
-                _lib.check(lib.empose_lstm_train_fwd(C.byref(p), B, F, x0.data_ptr(), d_in, lens32.data_ptr(), _ptr(h0),
-                                                     _ptr(c0), y.data_ptr(), h_n.data_ptr(), c_n.data_ptr(),
-                                                     save.data_ptr(), ws.data_ptr(), nbytes, self.stream))
-                rnn.final_state = (h_n, c_n)
-                ctx.update({'lstm_save': save, 'y': y, 'c0': c0})
-                for lin, out, ld in ((net.pose_net_init, pose_hist[0], 66), (net.shape_net_init, tmp10, 10)):
-                    _lib.check(lib.empose_linear_f32(y.data_ptr(), H, lin.weight.data_ptr(), H, out.data_ptr(), ld, T,
-                                                     lin.out_features, H, None, lin.bias.data_ptr(), 0, 0.0, self.stream))
-            else:
-                ctx['init_views'] = (_MlpView(net.pose_net_init), _MlpView(net.shape_net_init))
-                for v in ctx['init_views']:
-                    v.fix_layout(self.lib, T)
-                    v.pack_forward_x3(self.lib, self.stream, T)
-                ctx['init_saves'] = (self._mlp_fwd(ctx['init_views'][0], x0.data_ptr(), d_in, pose_hist[0].data_ptr(), 66, T),
-                                     self._mlp_fwd(ctx['init_views'][1], x0.data_ptr(), d_in, tmp10.data_ptr(), 10, T))
-            if net.shape_avg:
-                _lib.check(lib.empose_window_mean(T, F, 10, tmp10.data_ptr(), 10, shape_hist[0].data_ptr(), 10, self.stream))
-            else:
-                self._axpby(T, 10, 1.0, tmp10.data_ptr(), 10, 0.0, None, 0, shape_hist[0].data_ptr(), 10)
+    def _views(self, mlps, M):
+        """_MlpViews of `mlps` with the save layout pinned and the x3 weights packed for M rows, and their MlpParams."""
+        views = tuple(_MlpView(mlp) for mlp in mlps)
+        for v in views:
+            v.fix_layout(self.lib, M)
+            v.pack_forward_x3(self.lib, self.stream, M)
+        return views, [v.params() for v in views]
 
-            views = (_MlpView(net.pose_net_iter), _MlpView(net.shape_net_iter))
-            for v in views:
-                v.fix_layout(self.lib, T)
-                v.pack_forward_x3(self.lib, self.stream, T)
-            X = self.new(max(N, 1), T, d_x)
-            dp, ds = self.new(T, 66), self.new(T, 10)
-            saves = []
-            nb_smpl = lib.empose_smpl_workspace_bytes(smpl_h, T)
-            ws_smpl = self.ws(nb_smpl)
-            for i in range(N + 1):
-                want_g = i < N and net.use_gradient
-                Xi = X[i] if i < N else None
-                _lib.check(lib.empose_smpl_sensors_fwd_bwd(
-                    smpl_h, T, F, pose_hist[i].data_ptr(), 66, shape_hist[i].data_ptr(), 10, offset_r.data_ptr(),
-                    offset_t.data_ptr(), x0.data_ptr() if want_g else None, d_in, scale.data_ptr() if want_g else None,
-                    markers_hist[i].data_ptr(), ori_hist[i].data_ptr(), joints_hist[i].data_ptr(),
-                    Xi[:, d_in + 76:].data_ptr() if want_g else None, d_x,
-                    Xi[:, d_in + 142:].data_ptr() if want_g else None, d_x, ws_smpl.data_ptr(), nb_smpl, self.stream))
-                if i == N:
-                    break
-                # network input rows [x0 | pose_i | shape_i | g_pose | g_shape] (the gradients are already there)
-                _lib.check(lib.empose_lgd_assemble_inputs(T, d_in, x0.data_ptr(), d_in, pose_hist[i].data_ptr(),
-                                                          shape_hist[i].data_ptr(), Xi.data_ptr(), d_x, self.stream))
-                side_fwd = self._use_side and 'fwd' in self.side_parts
-                if side_fwd:
-                    self._fork()                               # the two networks side by side
-                    sp = self._mlp_fwd(views[0], Xi.data_ptr(), d_x, dp.data_ptr(), 66, T)
-                    ss = self._mlp_fwd(views[1], Xi.data_ptr(), d_x, tmp10.data_ptr(), 10, T, side=0)
-                    self._join()
-                else:                                          # one stream: both networks per call (paired launches)
-                    sp, ss = self._mlp_fwd_pair(views, Xi.data_ptr(), d_x, (dp.data_ptr(), tmp10.data_ptr()), (66, 10), T)
-                saves.append((sp, ss))
-                # pose_{i+1} = pose_i + s dp, shape_{i+1} = shape_i + s (window mean of) ds
-                _lib.check(lib.empose_lgd_additive_update(B, F, s, int(bool(net.shape_avg)), pose_hist[i].data_ptr(),
-                                                          dp.data_ptr(), shape_hist[i].data_ptr(), tmp10.data_ptr(),
-                                                          pose_hist[i + 1].data_ptr(), shape_hist[i + 1].data_ptr(),
-                                                          self.stream))
-        ctx.update({'pose_hist': pose_hist, 'shape_hist': shape_hist, 'markers_hist': markers_hist, 'ori_hist': ori_hist,
-                    'joints_hist': joints_hist, 'X': X, 'views': views, 'saves': saves, 'smpl_h': smpl_h})
-        hist = {'pose': list(pose_hist), 'shape': list(shape_hist), 'joints': list(joints_hist),
-                'markers': list(markers_hist), 'markers_ori': list(ori_hist)}
-        out = {'pose': pose_hist[N].reshape(B, F, 66), 'shape': shape_hist[N].reshape(B, F, 10),
-               'joints': joints_hist[N].reshape(B, F, 66)}
-        return out, hist
+    def _lstm_start(self):
+        """pose_0 and the shape rows (tmp10) from the LSTM over the input rows and the two linear heads."""
+        net, lib, st, rnn = self.net, self.lib, self.step, self.net.rnn
+        B, F, T, d_in, L, H = st.B, st.F, st.T, net.input_size, rnn.num_layers, rnn.hidden_size
+        rnn.init_state = rnn.final_state
+        p, _, _ = _lstm_params(rnn, d_in)
+        h0, c0 = [t if t is None else t.detach().to(self.dev, torch.float32).contiguous() for t in rnn.init_state or (None, None)]
+        y, h_n, c_n = self.new(T, H), self.new(L, B, H), self.new(L, B, H)
+        save = self.new(lib.empose_lstm_train_save_floats(L, B, F, H))
+        self._call(MAIN, lib.empose_lstm_train_fwd, lib.empose_lstm_train_workspace_bytes(C.byref(p), B, F),
+                   C.byref(p), B, F, st.x0.data_ptr(), d_in, st.lens32.data_ptr(), _ptr(h0), _ptr(c0), y.data_ptr(),
+                   h_n.data_ptr(), c_n.data_ptr(), save.data_ptr())
+        rnn.final_state = (h_n, c_n)
+        for lin, out, ld in ((net.pose_net_init, st.pose_hist[0], POSE), (net.shape_net_init, st.tmp10, SHAPE)):
+            _lib.check(lib.empose_linear_f32(y.data_ptr(), H, lin.weight.data_ptr(), H, out.data_ptr(), ld, T,
+                                             lin.out_features, H, None, lin.bias.data_ptr(), 0, 0.0, self.stream))
+        return _LstmStart(y, c0, save)
+
+    def _mlp_start(self):
+        """pose_0 and the shape rows (tmp10) from the two init MLPs over the input rows."""
+        st, d_in = self.step, self.net.input_size
+        views, params = self._views((self.net.pose_net_init, self.net.shape_net_init), st.T)
+        return _MlpStart(views, params, (
+            self._mlp_fwd(params[0], st.x0.data_ptr(), d_in, st.pose_hist[0].data_ptr(), POSE, st.T),
+            self._mlp_fwd(params[1], st.x0.data_ptr(), d_in, st.tmp10.data_ptr(), SHAPE, st.T)))
+
+    def _iteration_fwd(self, i):
+        """Body model (+ residual gradient) of estimate i and, for i < N, the two update networks and estimate i + 1."""
+        net, lib, st = self.net, self.lib, self.step
+        T, N, d_in, d_x = st.T, net.N, net.input_size, net.input_iter_size
+        want_g = i < N and net.use_gradient
+        Xi = st.X[i] if i < N else None
+        _lib.check(lib.empose_smpl_sensors_fwd_bwd(
+            st.smpl_h, T, st.F, st.pose_hist[i].data_ptr(), POSE, st.shape_hist[i].data_ptr(), SHAPE,
+            st.offset_r.data_ptr(), st.offset_t.data_ptr(), st.x0.data_ptr() if want_g else None, d_in,
+            st.scale.data_ptr() if want_g else None, st.markers_hist[i].data_ptr(), st.ori_hist[i].data_ptr(),
+            st.joints_hist[i].data_ptr(), Xi[:, d_in + G_POSE_COL:].data_ptr() if want_g else None, d_x,
+            Xi[:, d_in + G_SHAPE_COL:].data_ptr() if want_g else None, d_x, st.ws_smpl.data_ptr(), st.nb_smpl, self.stream))
+        if i == N:
+            return
+        # network input rows [x0 | pose_i | shape_i | g_pose | g_shape] (the gradients are already there)
+        _lib.check(lib.empose_lgd_assemble_inputs(T, d_in, st.x0.data_ptr(), d_in, st.pose_hist[i].data_ptr(),
+                                                  st.shape_hist[i].data_ptr(), Xi.data_ptr(), d_x, self.stream))
+        dp, ds = st.dp.data_ptr(), st.tmp10.data_ptr()
+        if st.plan.fwd_split:                          # the two networks side by side
+            self._fork(0)
+            sp = self._mlp_fwd(st.params[0], Xi.data_ptr(), d_x, dp, POSE, T)
+            ss = self._mlp_fwd(st.params[1], Xi.data_ptr(), d_x, ds, SHAPE, T, where=0)
+            self._join(0)
+        else:                                          # one stream: both networks per call (paired launches)
+            sp, ss = self._mlp_fwd_pair(st.params, Xi.data_ptr(), d_x, (dp, ds), (POSE, SHAPE), T)
+        st.saves.append((sp, ss))
+        # pose_{i+1} = pose_i + s dp, shape_{i+1} = shape_i + s (window mean of) ds
+        _lib.check(lib.empose_lgd_additive_update(
+            st.B, st.F, float(net.step_size), int(bool(net.shape_avg)), st.pose_hist[i].data_ptr(), dp,
+            st.shape_hist[i].data_ptr(), ds, st.pose_hist[i + 1].data_ptr(), st.shape_hist[i + 1].data_ptr(), self.stream))
 
     # ---- backward -----------------------------------------------------------------------------------------------
     def backward(self, batch, as_tensors=False):
         """Loss values + parameter gradients (added to `.grad`).  :return: (total loss tensor, loss_vals dict)"""
-        net, ctx = self.net, self.ctx
-        if ctx is None:
+        if self.step is None:
             raise RuntimeError('backward() needs the preceding training-mode forward()')
-        lib, dev = self.lib, self.dev
-        B, F = ctx['B'], ctx['F']
-        T, N, s = B * F, net.N, float(net.step_size)
-        d_in, d_x = net.input_size, net.input_iter_size
-        f32 = lambda t: t.to(dev, torch.float32).contiguous()
-        io = _lib.LossIO()
-        io.B, io.F, io.n_hist, io.n_markers = B, F, N + 1, net.n_markers
-        for k, v in enumerate(net.marker_idxs):
-            io.marker_idx[k] = v
-        pose_gt, shape_gt = f32(batch.poses).reshape(T, 66), f32(batch.shapes)
-        joints_gt = f32(batch.joints_gt).reshape(T, 66) if net.do_fk else None
-        d_pose, d_shape = self.new(N + 1, T, 66), self.new(N + 1, T, 10)
-        d_mark, d_ori, d_joints = self.new(N + 1, T, 36), self.new(N + 1, T, 108), self.new(T, 66)
-        loss_vals = self.new(5)
-        io.pose_hist, io.shape_hist = ctx['pose_hist'].data_ptr(), ctx['shape_hist'].data_ptr()
-        io.markers_hist, io.markers_ori_hist = ctx['markers_hist'].data_ptr(), ctx['ori_hist'].data_ptr()
-        io.joints_final = ctx['joints_hist'][N].data_ptr()
-        io.pose_gt, io.shape_gt, io.joints_gt = pose_gt.data_ptr(), shape_gt.data_ptr(), _ptr(joints_gt)
-        io.inputs, io.ld_inputs = ctx['x0'].data_ptr(), d_in
-        io.seq_lengths, io.marker_masks = ctx['lens32'].data_ptr(), _ptr(ctx['masks'])
-        io.w_pose, io.w_shape = float(net.pose_weight), float(net.shape_weight)
-        io.w_fk, io.w_rec = float(net.fk_loss_weight) if net.do_fk else 0.0, float(net.r_weight)
-        io.d_pose, io.d_shape, io.d_markers, io.d_markers_ori = [t.data_ptr() for t in (d_pose, d_shape, d_mark, d_ori)]
-        io.d_joints, io.loss_vals = d_joints.data_ptr(), loss_vals.data_ptr()
-        with torch.cuda.device(dev):
+        st, T = self.step, self.step.T
+        with torch.cuda.device(self.dev):
             self.stream = _lib.current_stream()
-            nbytes = lib.empose_lgd_losses_workspace_bytes(B, F, N + 1)
-            ws = self.ws(nbytes)
-            _lib.check(lib.empose_lgd_losses(C.byref(io), ws.data_ptr(), nbytes, self.stream))
-
-            smpl_h = ctx['smpl_h']
-            nb_vjp = lib.empose_smpl_vjp_workspace_bytes(smpl_h, T)
-            ws_vjp = self.ws(nb_vjp)
-            Dp, Ds = self.new(T, 66), self.new(T, 10)
-            vp, vs = self.new(T, 66), self.new(T, 10)
-            dpad = torch.zeros(T, 68, dtype=torch.float32, device=dev)     # zero padding columns for the GEMMs
-            dspad = torch.zeros(T, 12, dtype=torch.float32, device=dev)
-            tmp10 = self.new(T, 10)
-            views = ctx['views']
-            grads = [[self._grad_like(p) for p in v.parameter_list()] for v in views]
-            X = ctx['X']
-            deferred = self.batched_wgrad and 1 <= N <= 8   # (row counts off the 32-row grid: per application inside)
-            for v in views:
-                v.prepare_backward(lib, self.stream, T)
-            pend = ([], [])
-            for i in range(N, -1, -1):
-                _lib.check(lib.empose_smpl_sensors_vjp(
-                    smpl_h, T, F, ctx['pose_hist'][i].data_ptr(), 66, ctx['shape_hist'][i].data_ptr(), 10,
-                    ctx['offset_r'].data_ptr(), ctx['offset_t'].data_ptr(), d_mark[i].data_ptr(), d_ori[i].data_ptr(),
-                    d_joints.data_ptr() if i == N else None, vp.data_ptr(), vs.data_ptr(), ws_vjp.data_ptr(), nb_vjp,
-                    self.stream))
-                # running cotangents of the estimates (loss terms + body-model VJP + the reference's in-forward
-                # `E_i.backward()` deposit, models.py:576: dE_i/d(pose_i) = g_i / (B F) flows into everything that produced
-                # pose_i) and, for i > 0, the zero-padded cotangents of the update networks' outputs of iteration i - 1
-                deposit = i < N and net.use_gradient
-                dp_ptr, ds_ptr = dpad.data_ptr(), dspad.data_ptr()
-                if deferred and i > 0:   # straight into the d_out slots of this application's stashes
-                    (st_p, dp_ptr), (st_s, ds_ptr) = self._new_stash(views[0], T), self._new_stash(views[1], T)
-                _lib.check(lib.empose_lgd_cotangent_step(
-                    B, F, int(i == N), d_pose[i].data_ptr(), d_shape[i].data_ptr(), vp.data_ptr(), vs.data_ptr(),
-                    X[i][:, d_in + 76:].data_ptr() if deposit else None, d_x,
-                    X[i][:, d_in + 142:].data_ptr() if deposit else None, d_x, Dp.data_ptr(), Ds.data_ptr(), s,
-                    int(bool(net.shape_avg)), dp_ptr if i > 0 else None, ds_ptr if i > 0 else None,
-                    self.stream))
-                if i == 0:
-                    break
-                sp, ss = ctx['saves'][i - 1]
-                acc = i < N
-                if deferred:
-                    # weight gradients once over all N applications (one A^T B per layer instead of N).  Nothing below
-                    # reads what these two calls write until the weight-gradient products: the shape network's backward
-                    # of every iteration trails on the side stream, in order, without a join
-                    side_bwd = self._use_side and 'bwd' in self.side_parts
-                    side_pose = 1 if (side_bwd and 'bwd3' in self.side_parts) else None   # third stream: the pose net too
-                    if side_bwd:
-                        self._fork(0)
-                    if side_pose is not None:
-                        self._fork(1)
-                    if not side_bwd:                           # one stream: both networks per call (paired launches)
-                        self._mlp_bwd_deferred_pair(views, X[i - 1].data_ptr(), d_x, (dp_ptr, ds_ptr), (68, 12), (sp, ss),
-                                                    grads, acc, T, (st_p, st_s))
-                        pend[0].append((X[i - 1].data_ptr(), sp, st_p))
-                        pend[1].append((X[i - 1].data_ptr(), ss, st_s))
-                        continue
-                    pend[0].append((X[i - 1].data_ptr(), sp,
-                                    self._mlp_bwd_deferred(views[0], X[i - 1].data_ptr(), d_x, dp_ptr, 68, sp,
-                                                           grads[0], acc, T, stash=st_p, side=side_pose)))
-                    pend[1].append((X[i - 1].data_ptr(), ss,
-                                    self._mlp_bwd_deferred(views[1], X[i - 1].data_ptr(), d_x, ds_ptr, 12, ss,
-                                                           grads[1], acc, T, stash=st_s, side=0 if side_bwd else None)))
-                else:
-                    self._mlp_bwd(views[0], X[i - 1].data_ptr(), d_x, dpad.data_ptr(), 68, sp, grads[0], acc, T)
-                    self._mlp_bwd(views[1], X[i - 1].data_ptr(), d_x, dspad.data_ptr(), 12, ss, grads[1], acc, T)
-            # Both networks' weight gradients on the side stream (after the pose network's backward, which ran on the main
-            # stream), beside the initial estimate's backward below on the main stream.
-            # (per-application gradients -- `deferred` off -- were formed on the main stream: nothing to move aside)
-            side_w = deferred and 'wgrad' in self.side_parts
-            three = side_w and 'bwd3' in self.side_parts and 'bwd' in self.side_parts
-            if deferred and not side_w:     # (A/B: backward on side streams but the products on the main one)
-                self._join(0)
-                self._join(1)
-            if side_w and not three:
-                self._fork(0)
-            for k in (0, 1):
-                # (three streams: each network's products follow its own backward on its own stream, no fork needed)
-                where = (1 - k) if three else 0
-                with (self._on_side(where) if side_w else contextlib.nullcontext()):
-                    if pend[k]:
-                        self._mlp_wgrad(views[k], [q[0] for q in pend[k]], d_x, [q[1] for q in pend[k]],
-                                        [q[2] for q in pend[k]], grads[k], T)
-                    if N > 0:   # final: a gradient sink may start averaging them while the rest of the sweep runs
-                        self._deposit(list(zip(views[k].parameter_list(), grads[k])))
-            # ---- initial estimate
-            self._axpby(T, 66, 1.0, Dp.data_ptr(), 66, 0.0, None, 0, dpad.data_ptr(), 68)
-            if net.shape_avg:
-                _lib.check(lib.empose_window_mean(T, F, 10, Ds.data_ptr(), 10, tmp10.data_ptr(), 10, self.stream))
-                self._axpby(T, 10, 1.0, tmp10.data_ptr(), 10, 0.0, None, 0, dspad.data_ptr(), 12)
-            else:
-                self._axpby(T, 10, 1.0, Ds.data_ptr(), 10, 0.0, None, 0, dspad.data_ptr(), 12)
-            named = []
-            if net.rnn_init:
-                rnn, y = net.rnn, ctx['y']
-                H, L = rnn.hidden_size, rnn.num_layers
-                dy = self.new(T, H)
-                first = True
-                for lin, dpd, ld, n_out in ((net.pose_net_init, dpad, 68, 66), (net.shape_net_init, dspad, 12, 10)):
-                    gw, gb = self._grad_like(lin.weight), self._grad_like(lin.bias)
-                    nb = lib.empose_gemm_atb_workspace_bytes(T, n_out, H)
-                    wsa = self.ws(nb)
-                    _lib.check(lib.empose_gemm_atb_f32(T, n_out, H, dpd.data_ptr(), ld, y.data_ptr(), H, gw.data_ptr(), H,
-                                                       gb.data_ptr(), wsa.data_ptr(), wsa.numel(), self.stream))
-                    named += [(lin.weight, gw), (lin.bias, gb)]
-                    wt = torch.zeros(H, ld, dtype=torch.float32, device=dev)
-                    _lib.check(lib.empose_transpose_f32(n_out, H, lin.weight.data_ptr(), H, wt.data_ptr(), ld, self.stream))
-                    _lib.check(lib.empose_linear_f32_ex(dpd.data_ptr(), ld, wt.data_ptr(), ld, dy.data_ptr(), H, T, H, ld,
-                                                        None, None, None if first else dy.data_ptr(), H, 0, 0.0,
-                                                        self.stream))
-                    first = False
-                self._deposit(named)
-                named = []
-                weights = [w for unit in rnn._unit_params() for w in unit]
-                lg = [self._grad_like(w) for w in weights]
-                p, g, _ = _lstm_params(rnn, d_in, lg)
-                nbytes = lib.empose_lstm_train_workspace_bytes(C.byref(p), B, F)
-                ws = self.ws(nbytes)
-                _lib.check(lib.empose_lstm_train_bwd(C.byref(p), B, F, ctx['x0'].data_ptr(), d_in, ctx['lens32'].data_ptr(),
-                                                     _ptr(ctx['c0']), ctx['lstm_save'].data_ptr(), dy.data_ptr(), None,
-                                                     C.byref(g), ws.data_ptr(), nbytes, self.stream))
-                named += list(zip(weights, lg))
-            else:
-                for v, sv, dpd, ld in zip(ctx['init_views'], ctx['init_saves'], (dpad, dspad), (68, 12)):
-                    gi = [self._grad_like(p_) for p_ in v.parameter_list()]
-                    self._mlp_bwd(v, ctx['x0'].data_ptr(), d_in, dpd.data_ptr(), ld, sv, gi, False, T)
-                    named += list(zip(v.parameter_list(), gi))
-            self._deposit(named)
-            self._join(0)
-            if 'bwd3' in self.side_parts:
-                self._join(1)
-        self.ctx = None
-        total = loss_vals[4]
+            self._losses(batch)
+            st.nb_vjp = self.lib.empose_smpl_vjp_workspace_bytes(st.smpl_h, T)
+            st.ws_vjp = self.ws(st.nb_vjp)
+            st.Dp, st.Ds, st.vp, st.vs = self.new(T, POSE), self.new(T, SHAPE), self.new(T, POSE), self.new(T, SHAPE)
+            st.dpad, st.dspad = [torch.zeros(T, w, dtype=torch.float32, device=self.dev)   # zero padding columns for the GEMMs
+                                 for w in (POSE_PAD, SHAPE_PAD)]
+            st.grads = [[self._grad_like(p) for p in v.parameter_list()] for v in st.views]
+            for v in st.views:
+                v.prepare_backward(self.lib, self.stream, T)
+            st.params = [v.params() for v in st.views]        # (with this step's weight_t / weight_t_x3)
+            st.gstructs = [v.grads(g) for v, g in zip(st.views, st.grads)]
+            st.pend = ([], [])
+            for i in range(self.net.N, -1, -1):
+                self._iteration_bwd(i)
+            self._update_wgrads()
+            self._start_bwd()
+            self._join_all()
+        self.step = None
         keys = ('pose', 'shape', 'reconstruction', 'fk', 'total_loss')
-        if as_tensors:
-            vals = {k: loss_vals[j] for j, k in enumerate(keys)}
-        else:
-            host = loss_vals.tolist()
-            vals = {k: host[j] for j, k in enumerate(keys)}
-        return total, vals
+        host = st.loss_vals if as_tensors else st.loss_vals.tolist()
+        return st.loss_vals[4], {k: host[j] for j, k in enumerate(keys)}
+
+    def _losses(self, batch):
+        """All loss terms and the cotangents of every history entry in one kernel (empose_lgd_losses)."""
+        net, lib, st = self.net, self.lib, self.step
+        B, F, T, n_hist = st.B, st.F, st.T, net.N + 1
+        f32 = lambda t: t.to(self.dev, torch.float32).contiguous()
+        io = _lib.LossIO()
+        io.B, io.F, io.n_hist, io.n_markers = B, F, n_hist, net.n_markers
+        io.marker_idx[:len(net.marker_idxs)] = [int(v) for v in net.marker_idxs]
+        pose_gt, shape_gt = f32(batch.poses).reshape(T, POSE), f32(batch.shapes)
+        joints_gt = f32(batch.joints_gt).reshape(T, POSE) if net.do_fk else None
+        st.d_pose, st.d_shape, st.d_joints = self.new(n_hist, T, POSE), self.new(n_hist, T, SHAPE), self.new(T, POSE)
+        st.d_mark, st.d_ori, st.loss_vals = self.new(n_hist, T, MARKERS), self.new(n_hist, T, ORIS), self.new(5)
+        io.pose_hist, io.shape_hist, io.joints_final = [_ptr(t) for t in (st.pose_hist, st.shape_hist, st.joints_hist[net.N])]
+        io.markers_hist, io.markers_ori_hist = st.markers_hist.data_ptr(), st.ori_hist.data_ptr()
+        io.pose_gt, io.shape_gt, io.joints_gt = pose_gt.data_ptr(), shape_gt.data_ptr(), _ptr(joints_gt)
+        io.inputs, io.ld_inputs, io.seq_lengths, io.marker_masks = st.x0.data_ptr(), net.input_size, _ptr(st.lens32), _ptr(st.masks)
+        io.w_pose, io.w_shape, io.w_rec = float(net.pose_weight), float(net.shape_weight), float(net.r_weight)
+        io.w_fk = float(net.fk_loss_weight) if net.do_fk else 0.0
+        io.d_pose, io.d_shape, io.d_markers, io.d_markers_ori = [_ptr(t) for t in (st.d_pose, st.d_shape, st.d_mark, st.d_ori)]
+        io.d_joints, io.loss_vals = st.d_joints.data_ptr(), st.loss_vals.data_ptr()
+        self._call(MAIN, lib.empose_lgd_losses, lib.empose_lgd_losses_workspace_bytes(B, F, n_hist), C.byref(io))
+
+    def _iteration_bwd(self, i):
+        """Cotangent of estimate i and, for i > 0, the backward of the update networks' application that produced it."""
+        net, lib, st = self.net, self.lib, self.step
+        T, N, d_in, d_x, plan = st.T, net.N, net.input_size, net.input_iter_size, st.plan
+        _lib.check(lib.empose_smpl_sensors_vjp(
+            st.smpl_h, T, st.F, st.pose_hist[i].data_ptr(), POSE, st.shape_hist[i].data_ptr(), SHAPE,
+            st.offset_r.data_ptr(), st.offset_t.data_ptr(), st.d_mark[i].data_ptr(), st.d_ori[i].data_ptr(),
+            st.d_joints.data_ptr() if i == N else None, st.vp.data_ptr(), st.vs.data_ptr(), st.ws_vjp.data_ptr(), st.nb_vjp,
+            self.stream))
+        # running cotangents of the estimates (loss terms + body-model VJP + the reference's in-forward
+        # `E_i.backward()` deposit, models.py:576: dE_i/d(pose_i) = g_i / (B F) flows into everything that produced
+        # pose_i) and, for i > 0, the zero-padded cotangents of the update networks' outputs of iteration i - 1
+        deposit = i < N and net.use_gradient
+        dp_ptr, ds_ptr = st.dpad.data_ptr(), st.dspad.data_ptr()
+        if st.deferred and i > 0:   # straight into the d_out slots of this application's stashes
+            (stash_p, dp_ptr), (stash_s, ds_ptr) = self._new_stash(st.params[0], T), self._new_stash(st.params[1], T)
+        _lib.check(lib.empose_lgd_cotangent_step(
+            st.B, st.F, int(i == N), st.d_pose[i].data_ptr(), st.d_shape[i].data_ptr(), st.vp.data_ptr(),
+            st.vs.data_ptr(), st.X[i][:, d_in + G_POSE_COL:].data_ptr() if deposit else None, d_x,
+            st.X[i][:, d_in + G_SHAPE_COL:].data_ptr() if deposit else None, d_x, st.Dp.data_ptr(), st.Ds.data_ptr(),
+            float(net.step_size), int(bool(net.shape_avg)), dp_ptr if i > 0 else None, ds_ptr if i > 0 else None, self.stream))
+        if i == 0:
+            return
+        x, (sp, ss), acc, (p_p, p_s), (g_p, g_s) = st.X[i - 1].data_ptr(), st.saves[i - 1], i < N, st.params, st.gstructs
+        if not st.deferred:
+            self._mlp_bwd(p_p, g_p, x, d_x, dp_ptr, POSE_PAD, sp, acc, T)
+            self._mlp_bwd(p_s, g_s, x, d_x, ds_ptr, SHAPE_PAD, ss, acc, T)
+            return
+        # weight gradients once over all N applications (one A^T B per layer instead of N).  Nothing below reads what
+        # these calls write until the weight-gradient products: the backward of every iteration trails on its side
+        # stream (shape network: side 0; pose network: main, or side 1 as the third stream), in order, without a join
+        if plan.bwd_split:
+            self._fork(plan.shape_bwd)
+            if plan.pose_bwd is not MAIN:
+                self._fork(plan.pose_bwd)
+            self._mlp_bwd(p_p, g_p, x, d_x, dp_ptr, POSE_PAD, sp, acc, T, stash_p, where=plan.pose_bwd)
+            self._mlp_bwd(p_s, g_s, x, d_x, ds_ptr, SHAPE_PAD, ss, acc, T, stash_s, where=plan.shape_bwd)
+        else:                                          # one stream: both networks per call (paired launches)
+            self._mlp_bwd_deferred_pair(st.params, st.gstructs, x, d_x, (dp_ptr, ds_ptr), (POSE_PAD, SHAPE_PAD),
+                                        (sp, ss), acc, T, (stash_p, stash_s))
+        st.pend[0].append((x, sp, stash_p))
+        st.pend[1].append((x, ss, stash_s))
+
+    def _update_wgrads(self):
+        """Weight gradients of both update networks over all deferred applications where the plan puts them: on side streams
+        they run beside the initial estimate's backward on the main stream (three streams: each network's products follow
+        its own backward on its own stream, no fork needed).  Per-application gradients (`deferred` off) are only deposited."""
+        st, plan = self.step, self.step.plan
+        if plan.join_before_wgrad:       # (A/B: backward on side streams but the products on the main one)
+            self._join_all()
+        if plan.fork_before_wgrad:
+            self._fork(0)
+        for k, where in enumerate((plan.pose_wgrad, plan.shape_wgrad)):
+            if st.pend[k]:
+                self._mlp_wgrad(st.params[k], st.gstructs[k], st.pend[k], self.net.input_iter_size, st.T, where)
+            if self.net.N > 0:   # final: a gradient sink may start averaging them while the rest of the sweep runs
+                self._deposit(list(zip(st.views[k].parameter_list(), st.grads[k])), where)
+
+    def _start_bwd(self):
+        """Backward of what produced the initial estimate, from the zero-padded cotangents of pose_0 and shape_0."""
+        net, st, T = self.net, self.step, self.step.T
+        self._axpby(T, POSE, 1.0, st.Dp.data_ptr(), POSE, 0.0, None, 0, st.dpad.data_ptr(), POSE_PAD)
+        Ds = st.Ds
+        if net.shape_avg:
+            Ds = self.new(T, SHAPE)
+            _lib.check(self.lib.empose_window_mean(T, st.F, SHAPE, st.Ds.data_ptr(), SHAPE, Ds.data_ptr(), SHAPE, self.stream))
+        self._axpby(T, SHAPE, 1.0, Ds.data_ptr(), SHAPE, 0.0, None, 0, st.dspad.data_ptr(), SHAPE_PAD)
+        (self._lstm_start_bwd if isinstance(st.start, _LstmStart) else self._mlp_start_bwd)(st.start)
+
+    def _lstm_start_bwd(self, start):
+        """The two heads (weight gradients, cotangent of the LSTM output), then back-propagation through time."""
+        net, lib, st, rnn = self.net, self.lib, self.step, self.net.rnn
+        T, H, d_in = st.T, rnn.hidden_size, net.input_size
+        dy, named = self.new(T, H), []
+        for lin, dpd, ld, n_out in ((net.pose_net_init, st.dpad, POSE_PAD, POSE), (net.shape_net_init, st.dspad, SHAPE_PAD, SHAPE)):
+            gw, gb = self._grad_like(lin.weight), self._grad_like(lin.bias)
+            wsa = self.ws(lib.empose_gemm_atb_workspace_bytes(T, n_out, H))
+            _lib.check(lib.empose_gemm_atb_f32(T, n_out, H, dpd.data_ptr(), ld, start.y.data_ptr(), H, gw.data_ptr(), H,
+                                               gb.data_ptr(), wsa.data_ptr(), wsa.numel(), self.stream))
+            wt = torch.zeros(H, ld, dtype=torch.float32, device=self.dev)
+            _lib.check(lib.empose_transpose_f32(n_out, H, lin.weight.data_ptr(), H, wt.data_ptr(), ld, self.stream))
+            _lib.check(lib.empose_linear_f32_ex(dpd.data_ptr(), ld, wt.data_ptr(), ld, dy.data_ptr(), H, T, H, ld,
+                                                None, None, dy.data_ptr() if named else None, H, 0, 0.0, self.stream))
+            named += [(lin.weight, gw), (lin.bias, gb)]
+        self._deposit(named)
+        lg = [self._grad_like(w) for unit in rnn._unit_params() for w in unit]
+        p, g, weights = _lstm_params(rnn, d_in, lg)
+        self._call(MAIN, lib.empose_lstm_train_bwd, lib.empose_lstm_train_workspace_bytes(C.byref(p), st.B, st.F),
+                   C.byref(p), st.B, st.F, st.x0.data_ptr(), d_in, st.lens32.data_ptr(), _ptr(start.c0),
+                   start.lstm_save.data_ptr(), dy.data_ptr(), None, C.byref(g))
+        self._deposit(list(zip(weights, lg)))
+
+    def _mlp_start_bwd(self, start):
+        """The two init MLPs, weight gradients per network (one application each)."""
+        st, named = self.step, []
+        for v, p, sv, dpd, ld in zip(start.views, start.params, start.saves, (st.dpad, st.dspad), (POSE_PAD, SHAPE_PAD)):
+            gi = [self._grad_like(p_) for p_ in v.parameter_list()]
+            self._mlp_bwd(p, v.grads(gi), st.x0.data_ptr(), self.net.input_size, dpd.data_ptr(), ld, sv, False, st.T)
+            named += list(zip(v.parameter_list(), gi))
+        self._deposit(named)
