@@ -176,7 +176,8 @@ inline FeatArgs plain_feat_args(const float* theta, int ld_theta, const float* b
 }
 
 // The three-piece bf16 weights of a stack, per unit, in the fragment order of one family of step kernels (api_lstm.hip
-// LSTM_LAYOUTS): chain -- lstm_x3.hip, lstm_rows_x3.hip; mid -- lstm_mid_x3.hip, lstm_midseq_x3.hip; mid16 -- lstm_mid16_x3.hip
+// LSTM_LAYOUTS): chain -- lstm_x3.hip, lstm_rows_x3.hip; mid -- lstm_mid_x3.hip, lstm_midseq_x3.hip; mid16 -- lstm_mid16_x3.hip,
+// lstm_chain16_x3.hip
 enum LstmLayout { LSTM_CHAIN = 0, LSTM_MID, LSTM_MID16, LSTM_N_LAYOUTS };
 struct LstmW3 { unsigned short* ih[8] = {}; unsigned short* hh[8] = {}; };
 struct Lstm {   // unit u = layer * dirs + direction
@@ -197,7 +198,7 @@ int pack_lstm(std::vector<void*>& allocs, const empose_lstm_desc& r, int dirs, c
 // whole-sequence kernels get buffers (persist and seq by shape alone, midseq by shape and options); the cooperative
 // launches to try, in order -- each may report done = false at run time (its workgroups cannot all be resident) -- and
 // the step kernel that runs when none finished, with its weight layout and how it treats the state of new sequences.
-enum class LstmStep { wave, chain_x3, rows_x3, mid_x3, mid16_x3 };   // wave: lstm_wave (fp32); else three bf16 pieces
+enum class LstmStep { wave, chain_x3, rows_x3, mid_x3, mid16_x3, chain16_x3 };   // wave: lstm_wave (fp32); else three bf16 pieces
 enum class LstmCoop { persist, seq, midseq };   // lstm_persist_kernel (small), lstm_seq_kernel (large), lstm_midseq_x3.hip
 struct LstmPlan {
   bool persist = false;   // exchange words of lstm_persist_kernel
@@ -207,8 +208,9 @@ struct LstmPlan {
   int n_coop = 0; LstmCoop coop[3];
   LstmStep step = LstmStep::wave; LstmLayout layout = LSTM_CHAIN;   // (the layout of the three-piece step kernel)
   // three-piece steps on new sequences (option lstm_state_direct): the zero hidden-state planes by one fill, and on the
-  // chain kernel h_n / c_n stored by the last step of each layer
+  // chain kernels h_n / c_n stored by the last step of each layer
   bool zero_planes = false, state_direct = false;
+  bool skip_dead = false;   // chain kernels, option lstm_skip_dead: zero-state k-steps and unread fp32 state traffic left out
 };
 
 struct LstmWs {

@@ -20,7 +20,8 @@ bool has_layout(const Lstm& r, LstmLayout y) {
 // The step kernels by LstmStep (wave: fp32, none of this).  A new one is an entry here, one in the enum, a line in plan_lstm.
 struct X3Step { hipError_t (*launch)(const LstmX3Args&, hipStream_t); LstmLayout layout; };
 const X3Step X3_STEPS[] = {{nullptr, LSTM_CHAIN}, {launch_lstm_chain_x3, LSTM_CHAIN}, {launch_lstm_rows_x3, LSTM_CHAIN},
-                           {launch_lstm_mid_x3, LSTM_MID}, {launch_lstm_mid16_x3, LSTM_MID16}};
+                           {launch_lstm_mid_x3, LSTM_MID}, {launch_lstm_mid16_x3, LSTM_MID16},
+                           {launch_lstm_chain16_x3, LSTM_MID16}};
 // medium batches step on lstm_mid_x3.hip from 17 rows (below: lstm_persist_kernel / lstm_fewrows_kernel), and from 9 with the
 // 4-unit tiles of lstm_mid16_x3.hip (7.0 us per step against 7.8 - 10.7 of lstm_fewrows_kernel at 9 - 16 rows)
 constexpr int LSTM_MID16_MIN_B = 9;
@@ -44,8 +45,12 @@ LstmPlan plan_lstm(const Lstm& r, int B, int F, bool fresh_state) {
     for (int l = 0; l < r.num_layers; ++l) ks_in[l] = l == 0 ? (r.input_size + 15) / 16 : r.H / 16;
     p.midseq = lstm_midseq_shape_ok(B, r.H, r.num_layers, ks_in);
   }
-  // the steps: large batches on lstm_x3.hip (or lstm_rows_x3.hip), medium ones on lstm_mid16_x3.hip / lstm_mid_x3.hip
-  if (x3 && B >= LSTM_SEQ_MIN_B && has_layout(r, LSTM_CHAIN)) p.step = o.lstm_x3 == 2 ? LstmStep::rows_x3 : LstmStep::chain_x3;
+  // the steps: large batches on lstm_x3.hip (or lstm_rows_x3.hip / lstm_chain16_x3.hip), medium ones on lstm_mid16_x3.hip /
+  // lstm_mid_x3.hip
+  if (x3 && B >= LSTM_SEQ_MIN_B && has_layout(r, LSTM_CHAIN)) {
+    p.step = o.lstm_x3 == 2 ? LstmStep::rows_x3 : LstmStep::chain_x3;
+    if (o.lstm_x3 == 3 && has_layout(r, LSTM_MID16)) p.step = LstmStep::chain16_x3;
+  }
   else if (mid && B >= (tiles16 ? LSTM_MID16_MIN_B : LSTM_PERSIST_B + 1) && B < LSTM_SEQ_MIN_B)
     p.step = tiles16 ? LstmStep::mid16_x3 : LstmStep::mid_x3;
   p.layout = X3_STEPS[(int)p.step].layout;
@@ -57,7 +62,9 @@ LstmPlan plan_lstm(const Lstm& r, int B, int F, bool fresh_state) {
     if (p.midseq) p.coop[p.n_coop++] = LstmCoop::midseq;
   }
   p.zero_planes = p.step != LstmStep::wave && fresh_state && o.lstm_state_direct != 0;
-  p.state_direct = p.zero_planes && p.step == LstmStep::chain_x3;
+  const bool chain = p.step == LstmStep::chain_x3 || p.step == LstmStep::chain16_x3;
+  p.state_direct = p.zero_planes && chain;
+  p.skip_dead = chain && o.lstm_skip_dead != 0;
   return p;
 }
 
@@ -196,6 +203,9 @@ struct LstmRun {
     for (int s = 0; s < F + L - 1; ++s) {
       LstmX3Args xa;
       xa.n_units = 0; xa.seq_lengths = seq_lengths; xa.B = B; xa.F = F; xa.H = H;
+      // (without lengths every row is live at every step: h_prev is never used, and on the direct path h_next is only the
+      // next step's h_prev)
+      xa.skip_h_state = p.skip_dead && p.state_direct && !seq_lengths;
       for (int l = 0; l < L; ++l) {
         const int t = s - l;
         if (t < 0 || t >= F) continue;
@@ -203,6 +213,8 @@ struct LstmRun {
         xu.w3_ih = w3.ih[l]; xu.w3_hh = w3.hh[l]; xu.bias = r.bias[l];
         xu.a3_in = l == 0 ? ws.x3 + (size_t)t * ws.x3_t_stride : ws.a3[l - 1][(t + 1) & 1];
         xu.ks_in = ks_in(l);
+        // (a new sequence's first step: h_{-1} is the zero plane -- its k-steps only add +-0)
+        xu.ks_rec = p.skip_dead && p.zero_planes && t == 0 ? 0 : ks_in(1);
         xu.a3_rec = ws.a3[l][t & 1]; xu.a3_out = ws.a3[l][(t + 1) & 1];
         xu.h_prev = ws.h[l][t & 1]; xu.h_next = ws.h[l][(t + 1) & 1]; xu.c = ws.c[l];
         xu.y = l == L - 1 ? y : nullptr; xu.y_ld = H; xu.y_col = 0; xu.t = t;

@@ -39,7 +39,11 @@ namespace empose {
   X(lstm_x3, 1)        /* large-batch LSTM steps (inference, uni-directional): fp32 products as six bf16-MFMA products of three \
                              bf16 pieces per operand; 1: lstm_x3.hip (K-split waves); 2: lstm_rows_x3.hip (row-split waves, weights \
                              through LDS, cell update in registers -- round 6, measured 10 % SLOWER: 47.5 against 42.9 us per \
-                             launch, profiles/r06_lstm_rows_lab.txt, so opt-in); 0: the fp32 MFMA instruction (lstm_chain_kernel) */ \
+                             launch, profiles/r06_lstm_rows_lab.txt, so opt-in); 3: lstm_chain16_x3.hip, kernel 1 on \
+                             v_mfma_f32_16x16x32_bf16 -- measured FASTER: 37.8 against 39.5 us per launch in the headline profile, \
+                             38.8 against 40.7 stand-alone, 5.20 against 5.30 ms per step (profiles/r07_*; docs/history.md \
+                             "LSTM"), equal to rounding only, opt-in until the default pinned in the tests moves with it; \
+                             0: the fp32 MFMA instruction (lstm_chain_kernel) */ \
   X(train_cols, 1)     /* training at <= 512 rows: a layer's product + BatchNorm + PReLU as one launch, both update networks \
                              side by side (train_cols.hip); 0: a product and a BatchNorm launch per layer and network */ \
   X(cols_coop, 1)      /* those one-launch layers, eager: launched with hipLaunchCooperativeKernel (all workgroups resident by \
@@ -70,7 +74,10 @@ namespace empose {
                              chain alone (smpl_tile_kernel, CHAIN_ONLY); 0: the whole sub-mesh, as for every other pass */ \
   X(lstm_state_direct, 1) /* large-batch LSTM steps (lstm_x3.hip), new sequences: the piece planes of the zero initial state by \
                              one fill, h_n / c_n stored by the last step of each layer; 0: a split launch and a fill per layer, \
-                             2 L trailing copies */
+                             2 L trailing copies */ \
+  X(lstm_skip_dead, 1) /* chain step kernels (lstm_x3 = 1 / 3): work whose result nobody reads is left out, same bits -- the \
+                             recurrent k-steps of a unit whose h_{t-1} is the zero state of a new sequence, and without \
+                             seq_lengths (lstm_state_direct path) the fp32 h_prev loads / h_next stores; 0: all of it runs */
 
 struct Options {
 #define EMPOSE_OPTION_FIELD(name, default_value) int name = default_value;
@@ -374,13 +381,16 @@ struct LstmX3Unit {
   const float* bias;                 // [4H] = b_ih + b_hh
   const unsigned short* a3_in;       // the unit's input at this step: planes of x_t, or of the unit below's new hidden state
   int ks_in;                         // k-steps of 16 of that input
+  // k-steps of 16 of the recurrent operand the chain kernels multiply: H / 16, or 0 where h_{t-1} is the zero state of a new
+  // sequence (its products are all +-0: leaving them out changes no bit).  The other step kernels walk H / 16 regardless.
+  int ks_rec;
   const unsigned short* a3_rec;      // planes of h_{t-1}
   unsigned short* a3_out;            // planes of h_t
   const float* h_prev; float* h_next; float* c;   // [B][H] fp32: state hand-over and rows past their length
   float* y; int y_ld, y_col;         // output sequence [B][F][y_ld] or nullptr
   int t;                             // the unit's time step in this launch
   // the layer's slices of h_n / c_n ([B][H]) on the launch of its last step, else nullptr: a second copy of what goes to
-  // h_next / c (lstm_chain_x3_kernel only; the other step kernels ignore them and the caller copies the state out)
+  // h_next / c (the chain kernels only; the other step kernels ignore them and the caller copies the state out)
   float* h_final = nullptr; float* c_final = nullptr;
 };
 struct LstmX3Args {
@@ -388,8 +398,13 @@ struct LstmX3Args {
   int n_units, units_per_block;      // blockIdx.z walks units [z * units_per_block, ...)
   const int* seq_lengths;
   int B, F, H;
+  // chain kernels: nobody reads the fp32 hidden-state buffers (no seq_lengths: every row live at every step; the last step
+  // stores h_final) -- h_prev is not loaded, h_next not stored
+  int skip_h_state = 0;
 };
 hipError_t launch_lstm_chain_x3(const LstmX3Args& a, hipStream_t stream);
+// the same step on v_mfma_f32_16x16x32_bf16, weights in the LSTM_MID16 order (lstm_chain16_x3.hip; option lstm_x3 = 3)
+hipError_t launch_lstm_chain16_x3(const LstmX3Args& a, hipStream_t stream);
 // the same step with the waves splitting ROWS, the weight block of a k-step shared through LDS and the cell update in
 // registers (lstm_rows_x3.hip; option lstm_x3 = 2): one unit per workgroup, `units_per_block` unused
 hipError_t launch_lstm_rows_x3(const LstmX3Args& a, hipStream_t stream);

@@ -74,7 +74,8 @@ __global__ __launch_bounds__(lx::NT) void lstm_chain_x3_kernel(LstmX3Args a) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int l31 = lane & 31, lh = lane >> 5;
-  const int KS_h = H / 16;
+  const int KS_h = H / 16;                        // k-steps of 16 of a hidden-state plane
+  const bool skip_h = a.skip_h_state != 0;
   // the finishing thread's element group: row f_row, units j0 + 8 f_ug .. + 7 (all four gates).  (Four lanes per row --
   // whole 128-byte lines of c / h / y per row -- measured the same: the finish is its 128 LDS reads and 40 transcendental
   // functions per thread, 5.1 k of the 39 k clocks a unit takes, scripts/dev/lstm_x3_lab.hip with -DLX_LAB_TIMES)
@@ -86,18 +87,20 @@ __global__ __launch_bounds__(lx::NT) void lstm_chain_x3_kernel(LstmX3Args a) {
   const int u_end = u_beg + a.units_per_block < a.n_units ? u_beg + a.units_per_block : a.n_units;
   for (int u = u_beg; u < u_end; ++u) {
     const LstmX3Unit& U = a.unit[u];
-    const int KS_in = U.ks_in, KS = KS_in + KS_h;
+    const int KS_in = U.ks_in, KS = KS_in + U.ks_rec;   // (ks_rec = 0: the recurrent operand is the zero state)
     const int t = U.t;
     // ---- what the finish reads besides the sums, fetched now (latency under the K loop)
-    f32x4 e_c[2], e_hp[2];
+    f32x4 e_c[2], e_hp[2] = {f32x4{0.f, 0.f, 0.f, 0.f}, f32x4{0.f, 0.f, 0.f, 0.f}};
     float e_bias[4][8];
     const int e_len = a.seq_lengths ? a.seq_lengths[g_rowc] : F;
     {
       const size_t hc = (size_t)g_rowc * H + g_unit;
       e_c[0] = *reinterpret_cast<const f32x4*>(U.c + hc);
       e_c[1] = *reinterpret_cast<const f32x4*>(U.c + hc + 4);
-      e_hp[0] = *reinterpret_cast<const f32x4*>(U.h_prev + hc);
-      e_hp[1] = *reinterpret_cast<const f32x4*>(U.h_prev + hc + 4);
+      if (!skip_h) {
+        e_hp[0] = *reinterpret_cast<const f32x4*>(U.h_prev + hc);
+        e_hp[1] = *reinterpret_cast<const f32x4*>(U.h_prev + hc + 4);
+      }
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         const f32x4 b0 = *reinterpret_cast<const f32x4*>(U.bias + q * H + g_unit);
@@ -218,8 +221,11 @@ __global__ __launch_bounds__(lx::NT) void lstm_chain_x3_kernel(LstmX3Args a) {
       const size_t hc = (size_t)g_row * H + g_unit;
       *reinterpret_cast<f32x4*>(U.c + hc) = f32x4{cv[0], cv[1], cv[2], cv[3]};
       *reinterpret_cast<f32x4*>(U.c + hc + 4) = f32x4{cv[4], cv[5], cv[6], cv[7]};
-      *reinterpret_cast<f32x4*>(U.h_next + hc) = f32x4{hv[0], hv[1], hv[2], hv[3]};
-      *reinterpret_cast<f32x4*>(U.h_next + hc + 4) = f32x4{hv[4], hv[5], hv[6], hv[7]};
+      // (skip_h: every row is live at every step and the last step stores h_final -- nobody reads h_next)
+      if (!skip_h) {
+        *reinterpret_cast<f32x4*>(U.h_next + hc) = f32x4{hv[0], hv[1], hv[2], hv[3]};
+        *reinterpret_cast<f32x4*>(U.h_next + hc + 4) = f32x4{hv[4], hv[5], hv[6], hv[7]};
+      }
       // the layer's last step: the same values once more, where the caller wants h_n / c_n (rows past their length carry
       // their frozen state through every step, so every row of the final state is written here)
       if (U.h_final) {

@@ -69,7 +69,9 @@ const char* empose_arch(void);
  * products with fp32 accumulation, fp32-equivalent and 2.7 times the fp32 instruction's rate -- when every hidden width
  * is a multiple of 64: 1 [default]; 0 = the fp32 MFMA instruction; 2 = a variant whose waves share the operand split
  * through LDS, measured slower), "lstm_x3" (the same arithmetic for the LSTM steps of batches above 256 rows, inference,
- * uni-directional stacks with a hidden size of whole 32s: 1 [default]; 0 = the fp32 MFMA instruction), "rows_x3" (the
+ * uni-directional stacks with a hidden size of whole 32s: 1 [default]; 0 = the fp32 MFMA instruction; 2 = a row-split
+ * variant, measured slower; 3 = the default kernel with its products on the 16x16x32 form of the bf16 instruction --
+ * equal to rounding, not to the bit; measured 4 % faster per launch, opt-in), "rows_x3" (the
  * same arithmetic for the row-block products with fused prologue / epilogue: the blend products of the frame-per-lane
  * SMPL path and the stacked init heads; 0 = the fp32 MFMA instruction), "train_cols" (training at up to 512 rows: a
  * layer's product + BatchNorm + PReLU as one launch, forward and backward, both update networks side by side -- see
@@ -82,7 +84,10 @@ const char* empose_arch(void);
  * kept -- multiplies just the rest-joint column tiles of the blend matrix and runs the kinematic chain without the
  * sensors, bit-identical; 0 = the whole sub-mesh as in every other pass), "lstm_state_direct" (LSTM steps of batches above
  * 256 rows, new sequences [h0 = c0 = NULL]: the zero initial hidden-state planes by one fill and h_n / c_n stored by the
- * last step of each layer, bit-identical; 0 = a split launch and a fill per layer and 2 x layers trailing copies).
+ * last step of each layer, bit-identical; 0 = a split launch and a fill per layer and 2 x layers trailing copies),
+ * "lstm_skip_dead" (those LSTM steps with lstm_x3 = 1 or 3: work whose result nobody reads is left out, bit-identical --
+ * the recurrent half of the first step of a new sequence, whose hidden state is zero, and without seq_lengths the fp32
+ * copy of the hidden state that only rows past their length need; 0 = all of it runs).
  * empose_get_option returns -1 for an unknown name.  New in this library (no counterpart in the reference). */
 int empose_set_option(const char* name, int value);
 int empose_get_option(const char* name);

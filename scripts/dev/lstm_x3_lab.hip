@@ -37,7 +37,7 @@ int main(int argc, char** argv) {
     u.w3_hh = dev_rand<unsigned short>((size_t)KS_h * (H / 32) * 4 * 3 * 512, rng, 0.02f);
     u.bias = dev_rand<float>(4 * H, rng, 0.1f);
     u.a3_in = dev_rand<unsigned short>((size_t)RT * ks_in * 3 * 512, rng, 0.5f);
-    u.ks_in = ks_in;
+    u.ks_in = ks_in; u.ks_rec = KS_h;
     u.a3_rec = dev_rand<unsigned short>((size_t)RT * KS_h * 3 * 512, rng, 0.5f);
     u.a3_out = dev_rand<unsigned short>((size_t)RT * KS_h * 3 * 512, rng, 0.5f);
     u.h_prev = dev_rand<float>((size_t)B * H, rng, 0.5f);
