@@ -49,7 +49,9 @@ LstmPlan plan_lstm(const Lstm& r, int B, int F, bool fresh_state) {
   // lstm_mid_x3.hip
   if (x3 && B >= LSTM_SEQ_MIN_B && has_layout(r, LSTM_CHAIN)) {
     p.step = o.lstm_x3 == 2 ? LstmStep::rows_x3 : LstmStep::chain_x3;
-    if (o.lstm_x3 == 3 && has_layout(r, LSTM_MID16)) p.step = LstmStep::chain16_x3;
+    // the same step on the 16x16x32 instruction: what the default takes (lstm_chain16), and what lstm_x3 = 3 forces
+    const bool want16 = o.lstm_x3 == 3 || (o.lstm_x3 == 1 && o.lstm_chain16 != 0);
+    if (want16 && has_layout(r, LSTM_MID16)) p.step = LstmStep::chain16_x3;
   }
   else if (mid && B >= (tiles16 ? LSTM_MID16_MIN_B : LSTM_PERSIST_B + 1) && B < LSTM_SEQ_MIN_B)
     p.step = tiles16 ? LstmStep::mid16_x3 : LstmStep::mid_x3;

@@ -168,8 +168,26 @@ int pack_fragments_x3_raw(std::vector<void*>& allocs, const float* weight, int N
   }), out);
 }
 
+// The same pieces in the order v_mfma_f32_16x16x32_bf16 consumes them (mlp_fused_x3_kernel<16>): for every k-step of 32,
+// every 16-column tile and every piece one 1 KB wave fragment -- lane (n = lane & 15, q = lane >> 4) owns
+// piece[tile * 16 + n][ks * 32 + q * 8 .. + 7]; k-steps padded with zeros to an even count (the kernel walks pairs).
+int pack_fragments_x3_16_raw(std::vector<void*>& allocs, const float* weight, int N, int K, float** out) {
+  const int KS = (K + 31) / 32, NT = (N + 15) / 16;
+  const int KS2 = (KS + 1) & ~1;
+  return upload_bf16(allocs, pack_fragments_x3((size_t)KS2 * NT, K, [&](size_t f, int lane, const float** row, int* k0) {
+    const int ks = (int)(f / NT), n = (int)(f % NT) * 16 + (lane & 15);
+    if (n >= N) return false;
+    *row = weight + (size_t)n * K;
+    *k0 = ks * 32 + (lane >> 4) * 8;      // (k past K, the padding k-step included: nothing written)
+    return true;
+  }), out);
+}
+
+// Both instruction shapes' orders are packed here, at creation: the options choose between them at run time, and the
+// library does not allocate after creation (12 bytes per weight together).
 int pack_fragments(std::vector<void*>& allocs, const empose_dense_desc& d, Dense* out) {
   TRY(pack_fragments_x3_raw(allocs, d.weight, d.out_dim, d.in_dim, &out->wp3));
+  TRY(pack_fragments_x3_16_raw(allocs, d.weight, d.out_dim, d.in_dim, &out->wp3_16));
   return pack_fragments_raw(allocs, d.weight, d.out_dim, d.in_dim, &out->wp);
 }
 
@@ -231,12 +249,14 @@ struct MlpRun {
 // layers. Needs enough row panels to fill the chip and layers no wider than the four 128-column waves.
 // x3: fp32 products from three bf16 pieces per operand on the bf16 matrix path (mlp_fused_x3.hip; fp32-equivalent, 2.7
 // times the fp32 instruction's rate): needs every hidden width to be whole quads of k-steps of the next layer.
-struct MlpPlan { bool one_launch, x3; };
+// shape16: that kernel on the 16x16x32 form of the instruction (option mlp_fused16; the kernel of mlp_x3 = 1 only).
+struct MlpPlan { bool one_launch, x3, shape16; };
 MlpPlan plan_mlps(const MlpRun& r) {
   const int L = r.nets[0]->n_layers;
   MlpPlan p;
   p.one_launch = options().mlp_fused != 0 && L <= FUSED_MAX_LAYERS && (long)((r.T + 63) / 64) * r.n_nets >= 256;
   p.x3 = options().mlp_x3 != 0;
+  p.shape16 = options().mlp_x3 == 1 && options().mlp_fused16 != 0;
   for (int i = 0; i < r.n_nets; ++i) {
     const Mlp& net = *r.nets[i];
     if (net.skip || net.layers[0].in_dim > FUSED_MAX_WIDTH) p.one_launch = false;   // no room for a block input
@@ -244,13 +264,16 @@ MlpPlan plan_mlps(const MlpRun& r) {
       const Dense& d = net.layers[l];
       if (d.out_dim > FUSED_MAX_WIDTH || d.act > 1) p.one_launch = false;
       if (l + 1 < L && (d.out_dim % 64 != 0 || !d.wp3)) p.x3 = false;
+      if (!d.wp3_16) p.shape16 = false;
     }
   }
   p.x3 = p.x3 && p.one_launch;
+  p.shape16 = p.shape16 && p.x3;
   return p;
 }
 
-int run_mlps_one_launch(const MlpRun& r, bool x3, hipStream_t stream) {
+int run_mlps_one_launch(const MlpRun& r, const MlpPlan& plan, hipStream_t stream) {
+  const bool x3 = plan.x3;
   FusedMlpArgs fa;
   fa.count = r.n_nets; fa.M = r.T;
   for (int i = 0; i < r.n_nets; ++i) {
@@ -260,12 +283,12 @@ int run_mlps_one_launch(const MlpRun& r, bool x3, hipStream_t stream) {
     for (int l = 0; l < fn.n_layers; ++l) {
       const Dense& d = r.nets[i]->layers[l];
       FusedLayer& fl = fn.layer[l];
-      fl.W = x3 ? d.wp3 : d.wp; fl.K = d.in_dim; fl.N = d.out_dim; fl.scale = d.scale; fl.shift = d.shift;
+      fl.W = plan.shape16 ? d.wp3_16 : x3 ? d.wp3 : d.wp; fl.K = d.in_dim; fl.N = d.out_dim; fl.scale = d.scale; fl.shift = d.shift;
       fl.slope = d.slope; fl.act = d.act;
     }
   }
   prof_mark(r.init_net ? P_INIT_MLP : P_MLP_FUSED, stream);
-  HIP_CHECK(x3 ? launch_mlp_fused_x3(fa, stream) : launch_mlp_fused(fa, stream), "fused mlp launch");
+  HIP_CHECK(x3 ? launch_mlp_fused_x3(fa, plan.shape16, stream) : launch_mlp_fused(fa, stream), "fused mlp launch");
   prof_mark(P_END, stream);   // close the dominant kernel's interval at its completion, not at the next launch
   return EMPOSE_OK;
 }
@@ -316,7 +339,7 @@ int run_mlps(const MlpRun& r, const UpdWs& ws, int hidden_max, hipStream_t strea
   for (int i = 1; i < r.n_nets; ++i)
     if (r.nets[i]->n_layers != r.nets[0]->n_layers) return fail(EMPOSE_EINVAL, "paired MLPs must have the same depth");
   const MlpPlan p = plan_mlps(r);
-  return p.one_launch ? run_mlps_one_launch(r, p.x3, stream) : run_mlps_layers(r, ws, hidden_max, stream);
+  return p.one_launch ? run_mlps_one_launch(r, p, stream) : run_mlps_layers(r, ws, hidden_max, stream);
 }
 
 // Where the residual gradient of one SMPL evaluation goes.

@@ -42,7 +42,7 @@ namespace empose {
                              launch, profiles/r06_lstm_rows_lab.txt, so opt-in); 3: lstm_chain16_x3.hip, kernel 1 on \
                              v_mfma_f32_16x16x32_bf16 -- measured FASTER: 37.8 against 39.5 us per launch in the headline profile, \
                              38.8 against 40.7 stand-alone, 5.20 against 5.30 ms per step (profiles/r07_*; docs/history.md \
-                             "LSTM"), equal to rounding only, opt-in until the default pinned in the tests moves with it; \
+                             "LSTM"), equal to rounding only: what the default 1 takes while lstm_chain16 is on, 3 forces it; \
                              0: the fp32 MFMA instruction (lstm_chain_kernel) */ \
   X(train_cols, 1)     /* training at <= 512 rows: a layer's product + BatchNorm + PReLU as one launch, both update networks \
                              side by side (train_cols.hip); 0: a product and a BatchNorm launch per layer and network */ \
@@ -68,7 +68,8 @@ namespace empose {
   X(mlp_x3, 1)         /* fused update MLPs: fp32 products as six bf16-MFMA products of three bf16 pieces per operand \
                              (mlp_fused_x3.hip: fp32-equivalent accuracy, measured equal to the fp32 instruction's against \
                              float64); 0: the fp32 MFMA instruction (mlp_fused.hip); 2: the variant whose waves share the \
-                             A-side split through LDS (a barrier per k-step; measured 9 % slower) */ \
+                             A-side split through LDS (a barrier per k-step; measured 9 % slower).  Which instruction kernel 1 \
+                             issues is mlp_fused16's choice */ \
   X(last_pass_joints, 1) /* LGD forward, frame-per-lane path: an SMPL evaluation nobody asks sensor outputs of (the last pass \
                              without histories) multiplies only the rest-joint column tiles of the blend matrix and runs the \
                              chain alone (smpl_tile_kernel, CHAIN_ONLY); 0: the whole sub-mesh, as for every other pass */ \
@@ -77,7 +78,12 @@ namespace empose {
                              2 L trailing copies */ \
   X(lstm_skip_dead, 1) /* chain step kernels (lstm_x3 = 1 / 3): work whose result nobody reads is left out, same bits -- the \
                              recurrent k-steps of a unit whose h_{t-1} is the zero state of a new sequence, and without \
-                             seq_lengths (lstm_state_direct path) the fp32 h_prev loads / h_next stores; 0: all of it runs */
+                             seq_lengths (lstm_state_direct path) the fp32 h_prev loads / h_next stores; 0: all of it runs */ \
+  X(mlp_fused16, 1)    /* fused update MLPs with mlp_x3 = 1: the products on v_mfma_f32_16x16x32_bf16 (mlp_fused_x3_kernel<16>, \
+                             weights in the [k-step of 32][16-column tile][piece] order); 0: v_mfma_f32_32x32x16_bf16 \
+                             (mlp_fused_x3_kernel<32>).  Equal to rounding, not to the bit */ \
+  X(lstm_chain16, 1)   /* large-batch LSTM steps with lstm_x3 = 1: lstm_chain16_x3.hip (v_mfma_f32_16x16x32_bf16) where the model \
+                             has the LSTM_MID16 weight order; 0: lstm_chain_x3_kernel (32x32x16) */
 
 struct Options {
 #define EMPOSE_OPTION_FIELD(name, default_value) int name = default_value;
@@ -310,8 +316,9 @@ struct FusedNet {
 struct FusedMlpArgs { FusedNet net[2]; int count; int M; };
 hipError_t launch_mlp_fused(const FusedMlpArgs& args, hipStream_t stream);
 // The same launch with FusedLayer::W = three bf16 pieces per weight in bf16-MFMA fragment order (api_model.hip
-// pack_fragments_x3_raw): mlp_fused_x3.hip.  Hidden widths must be multiples of 64.
-hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, hipStream_t stream);
+// pack_fragments_x3_raw): mlp_fused_x3.hip.  Hidden widths must be multiples of 64.  shape16: the kernel on
+// v_mfma_f32_16x16x32_bf16, W then in the order of pack_fragments_x3_16_raw.
+hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, bool shape16, hipStream_t stream);
 // One linear layer C = A . W^T with A's row block resident in LDS and W (fragment order) streamed from L2.
 bool gemm_rows_applicable(int M, int N, int K);
 hipError_t launch_gemm_rows(const float* A, int lda, const float* Wp, float* C, int ldc, int M, int N, int K,

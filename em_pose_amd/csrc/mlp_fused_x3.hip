@@ -422,6 +422,213 @@ __device__ __forceinline__ void x3c_layer(const FusedNet& net, const FusedLayer&
   __syncthreads();
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same layer on v_mfma_f32_16x16x32_bf16 (option mlp_fused16): same workgroup, same single fp32 activation buffer, same
+// pieces of the same values, weights from L2 into registers, no barrier in the K loop.  Where the chip holds its clock down
+// under matrix load it holds a higher one on this shape at equal cycles per FLOP; what the shape takes away is issue room --
+// an MFMA gap is 16 cycles, 8 of them the MFMA's own -- so every filler has its place:
+//   * a wave's 64 x 128 tile is 4 x 8 accumulator tiles of 16 x 16 (C layout: col = lane & 15, row = 4 (lane >> 4) + reg); a
+//     k-step is 32 wide and lane (r = lane & 15, q = lane >> 4) owns k = 8 q .. 8 q + 7 of it, on both operands;
+//   * weights in the order of api_model.hip pack_fragments_x3_16_raw: [k-step of 32][16-column tile][piece] -> 1 KB;
+//   * a step is 8 chunks, one per column tile: the tile's 24 MFMAs (six products x four row tiles; the products of one
+//     accumulator in the order of bf16x3.h) with, between them, the split of two of the next step's 16 k pairs (22 VALU),
+//     one ds_read_b128 and the three weight fragments of the tile just finished, for the next step.  So ONE set of weight
+//     registers (96) and ONE of raw fp32 A values (32) are each refilled 7/8 of a step (~2,700 cycles) before their use;
+//     only the A pieces (2 x 48) are double.  With the 128 accumulators ~350 registers;
+//   * the A read -- 16 rows at stride LDA = 516 floats, four k-quarters 8 floats apart -- is 2-way conflicted in each of the
+//     ds_read_b128's groups of 16 lanes (rows 12, 13 of quarter q meet rows 4, 5 of quarter q + 1), and no pad repairs it:
+//     a group holds two quarters of 8 rows each, and the quarters' offset of two 16-byte slots is even.  8 LDS cycles per
+//     read instead of 4, 32 reads per step and workgroup: 256 of a step's 3,072 cycles of an otherwise idle LDS.  Left;
+//   * layer 0's ragged K (296 = 9 steps and a quarter): the lanes whose k does not exist read ZEROS that the staging loop
+//     wrote (it fills up to whole pairs of steps, kpad), and the packed weights are zero there too: 0 x 0, never 0 x garbage;
+//   * layers of up to 128 columns (the output layers: 66 -> 5 tiles, 10 -> 1; hidden widths 64, 128) are split over the waves
+//     by K instead of by columns (KSPLIT): every wave multiplies all 64 rows x NCT column tiles for the steps w, w + 4, ...,
+//     the partial sums meet in the (then free) activation buffer and are added in wave order.  Split by rows, each wave
+//     would stream all of the layer's weights: four times the L2 traffic for the same MFMAs;
+//   * every layer leaves its results in the activation buffer; the last one's then go out to global memory by all threads,
+//     coalesced, after the barrier: no global store while any MFMA of the workgroup is in flight (bf16x3.h).
+template <int NCT, bool KSPLIT>
+__device__ __forceinline__ void x16_layer(const FusedNet& net, const FusedLayer& L, int M, int m0, float* act, int lda,
+                                          int wave, bool last) {
+  constexpr int RT = 4, NCHUNK = 8;
+  static_assert(NCT >= 1 && NCT <= 8, "a wave owns up to 128 columns");
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int l15 = lane & 15, lq = lane >> 4;
+  const int K = L.K, N = L.N;
+  const int NT16 = (N + 15) / 16;
+  const int KS2 = ((K + 31) / 32 + 1) & ~1;                 // k-steps of the packed weights (zero-padded to whole pairs)
+  const int col_tile0 = KSPLIT ? 0 : wave * NCT;
+  // the wave's steps: g0, g0 + gs, ... (n_w of them; a wave that owns no column of the layer has none)
+  const int g0 = KSPLIT ? wave : 0, gs = KSPLIT ? 4 : 1;
+  const int n_w = KSPLIT ? (KS2 - wave + 3) / 4 : (col_tile0 < NT16 ? KS2 : 0);
+  auto gk = [&](int i) { const int g = g0 + i * gs; return g < KS2 ? g : KS2 - 1; };   // (look-ahead past the end: clamped)
+  // a fragment's address: wave-uniform (step, column tile: scalar registers) + the lane's 16 bytes (one register for all)
+  const unsigned b_lane = (unsigned)lane * 16u;
+  auto tile_off = [&](int j) { return (size_t)(col_tile0 + j < NT16 ? col_tile0 + j : NT16 - 1) * 3072; };
+  fx_gbyte_t wb = (fx_gbyte_t)L.W;
+  const size_t step_bytes = (size_t)NT16 * 3072;
+  const float* a_rd = act + l15 * lda + lq * 8;
+
+  f32x4 acc[RT][NCT];
+  f32x4 raw[RT][2];                // raw fp32 A, slot c = (row tile c / 2, half c % 2): split in chunk c, read again in chunk c + 1
+  Pieces ap[2][RT];                // the pieces of the step being multiplied and of the next one, being made
+  u32x4_t fb[NCT][3];              // weight pieces of column tile j: multiplied in chunk j, loaded again in chunk j + 1
+
+  auto bload = [&](u32x4_t (&b)[3], fx_gbyte_t p, int j) {
+#pragma unroll
+    for (int q = 0; q < 3; ++q) b[q] = *(x3_gvec_t)(p + tile_off(j) + q * 1024 + b_lane);
+  };
+  auto aread = [&](f32x4& r, const float* p, int c) {
+    r = *reinterpret_cast<const f32x4*>(p + (c / 2) * 16 * lda + (c % 2) * 4);
+  };
+  auto split_slot = [&](const f32x4& v, Pieces& q, int h) {   // the two k pairs of half h of a lane's 8 k
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+      unsigned ph, pm, pl;
+      split_pair(v[2 * e], v[2 * e + 1], ph, pm, pl);
+      q.p[0][2 * h + e] = ph; q.p[1][2 * h + e] = pm; q.p[2][2 * h + e] = pl;
+    }
+  };
+  // the wave's step number i: multiplies ap_cur by fb, makes ap_nxt
+  auto step = [&](int i, const Pieces (&ap_cur)[RT], Pieces (&ap_nxt)[RT]) {
+    const int g1 = gk(i + 1);
+    fx_gbyte_t pb_cur = wb + (size_t)gk(i) * step_bytes, pb_nxt = wb + (size_t)g1 * step_bytes;
+    const float* pa1 = a_rd + g1 * 32;
+    const float* pa2 = a_rd + gk(i + 2) * 32;
+#pragma unroll
+    for (int c = 0; c < NCHUNK; ++c) {
+      // ---- refills: what the previous chunk has finished with (chunk 0: the last slots, still for this / the next step)
+      if (c == 0) {
+        if constexpr (NCT == 8) bload(fb[NCT - 1], pb_cur, NCT - 1);
+        aread(raw[RT - 1][1], pa1, NCHUNK - 1);
+      } else {
+        if (c - 1 < NCT) bload(fb[c - 1 < NCT ? c - 1 : 0], pb_nxt, c - 1 < NCT ? c - 1 : 0);
+        aread(raw[(c - 1) / 2][(c - 1) % 2], pa2, c - 1);
+      }
+      // ---- the split of slot c of the next step
+      split_slot(raw[c / 2][c % 2], ap_nxt[c / 2], c % 2);
+      // ---- the 24 MFMAs of column tile c
+      if (c < NCT) {
+        const int j = c < NCT ? c : 0;
+#pragma unroll
+        for (int mm = 0; mm < 6 * RT; ++mm) {
+          const int t = mm / RT, r = mm % RT;
+          acc[r][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8_t, ap_cur[r].p[X3_PA[t]]),
+                                                              __builtin_bit_cast(bf16x8_t, fb[j][X3_PB[t]]), acc[r][j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int mm = 0; mm < 6 * RT; ++mm) { SGB(SG_MFMA, 1); SGB(SG_VALU, 1); if (mm < 4) SGB(SG_VMEM_RD | SG_DS_RD, 1); }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+#pragma unroll
+  for (int r = 0; r < RT; ++r)
+#pragma unroll
+    for (int j = 0; j < NCT; ++j) acc[r][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // ---- prologue: weights of the first step (all but the tile its chunk 0 loads), its pieces, the raw values of the second
+  {
+    fx_gbyte_t pb0 = wb + (size_t)gk(0) * step_bytes;
+#pragma unroll
+    for (int j = 0; j < (NCT == 8 ? NCT - 1 : NCT); ++j) bload(fb[j], pb0, j);
+#pragma unroll
+    for (int c = 0; c < NCHUNK; ++c) aread(raw[c / 2][c % 2], a_rd + gk(0) * 32, c);
+#pragma unroll
+    for (int c = 0; c < NCHUNK; ++c) split_slot(raw[c / 2][c % 2], ap[0][c / 2], c % 2);
+#pragma unroll
+    for (int c = 0; c < NCHUNK - 1; ++c) aread(raw[c / 2][c % 2], a_rd + gk(1) * 32, c);
+  }
+  // the first pair is peeled so that the loop header merges two states with the same outstanding loads (mlp_fused.hip):
+  // entered from the prologue, the loop began with a wait for ALL of them
+  int i = 0;
+  if (n_w >= 2) {
+    step(0, ap[0], ap[1]);
+    step(1, ap[1], ap[0]);
+    i = 2;
+  }
+  for (; i + 2 <= n_w; i += 2) {
+    step(i, ap[0], ap[1]);
+    step(i + 1, ap[1], ap[0]);
+  }
+  if (i < n_w) step(i, ap[0], ap[1]);
+
+  const float e_slope = L.act == 1 ? L.slope : 1.f;         // slope 1: no activation (exact identity)
+  const float* const scale = L.scale;
+  const float* const shift = L.shift;
+  if constexpr (!KSPLIT) {
+    float e_sc[NCT], e_sh[NCT];
+#pragma unroll
+    for (int j = 0; j < NCT; ++j) {
+      const int n = (col_tile0 + j) * 16 + l15;
+      const bool real = n < N;
+      const int nc = real ? n : N - 1;
+      e_sc[j] = real ? (scale ? scale[nc] : 1.f) : 0.f;
+      e_sh[j] = real ? (shift ? shift[nc] : 0.f) : 0.f;
+    }
+    __syncthreads();   // every wave has read its last A values: the buffer may be overwritten
+#pragma unroll
+    for (int j = 0; j < NCT; ++j) {
+      if (col_tile0 + j >= NT16) continue;
+      const int n = (col_tile0 + j) * 16 + l15;
+#pragma unroll
+      for (int r = 0; r < RT; ++r)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float y = acc[r][j][e] * e_sc[j] + e_sh[j];
+          act[(r * 16 + 4 * lq + e) * lda + n] = y >= 0.f ? y : y * e_slope;
+        }
+    }
+  } else {
+    constexpr int NC = NCT * 16;   // partial sums [wave][64][NC]
+    __syncthreads();   // every wave has read its last A values: the buffer is free for the partial sums
+    {
+      float* pw = act + ((size_t)wave * fx::BM + 4 * lq) * NC + l15;
+#pragma unroll
+      for (int j = 0; j < NCT; ++j)
+#pragma unroll
+        for (int r = 0; r < RT; ++r)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) pw[(r * 16 + e) * NC + j * 16] = acc[r][j][e];
+    }
+    __syncthreads();
+    // thread (c16 = tid & 15, r16 = tid >> 4) takes column c16 of every column tile and rows r16, r16 + 16, ..: shifts and
+    // masks only (a division by NC here is loop-invariant, gets hoisted out of the layer loop and lives through every K loop)
+    const int c16 = tid & 15, r16 = tid >> 4;
+    float y[NCT][4];
+#pragma unroll
+    for (int j = 0; j < NCT; ++j) {
+      const int n = j * 16 + c16;
+      const bool real = n < N;
+      const int nc = real ? n : N - 1;
+      const float sc = real ? (scale ? scale[nc] : 1.f) : 0.f, sh = real ? (shift ? shift[nc] : 0.f) : 0.f;
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const float* ps = act + (r16 + 16 * rr) * NC + n;
+        const float sum = ((ps[0] + ps[fx::BM * NC]) + ps[2 * fx::BM * NC]) + ps[3 * fx::BM * NC];
+        const float v = sum * sc + sh;
+        y[j][rr] = v >= 0.f ? v : v * e_slope;
+      }
+    }
+    __syncthreads();   // the partial sums are read: the activations take their place
+#pragma unroll
+    for (int j = 0; j < NCT; ++j)
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) act[(r16 + 16 * rr) * lda + j * 16 + c16] = y[j][rr];
+  }
+  __syncthreads();
+  if (last) {          // (no MFMA of the workgroup is in flight: every accumulator was read before the barrier)
+    float* const out = net.out;
+    const int ld_out = net.ld_out;
+    const int rows = M - m0 < fx::BM ? M - m0 : fx::BM;
+    for (int idx = tid; idx < rows * N; idx += fx::NT) {
+      const int r = idx / N, n = idx - r * N;
+      out[(size_t)(m0 + r) * ld_out + n] = act[r * lda + n];
+    }
+  }
+}
+
 __global__ __launch_bounds__(fx::NT) void mlp_fused_x3c_kernel(FusedMlpArgs args) {
   X3_EXCLUSIVE_SIMD();
   using namespace fx;
@@ -452,16 +659,20 @@ __global__ __launch_bounds__(fx::NT) void mlp_fused_x3c_kernel(FusedMlpArgs args
   }
 }
 
+// SHAPE: the bf16 MFMA the products run on -- 32: v_mfma_f32_32x32x16_bf16 (x3_layer), 16: v_mfma_f32_16x16x32_bf16
+// (x16_layer); each with its own order of the packed weights.  One name for both, as the profile readers know it.
+template <int SHAPE>
 __global__ __launch_bounds__(fx::NT) void mlp_fused_x3_kernel(FusedMlpArgs args) {
   X3_EXCLUSIVE_SIMD();
   using namespace fx;
+  static_assert(SHAPE == 32 || SHAPE == 16, "the two shapes of the bf16 MFMA");
   extern __shared__ __attribute__((aligned(16))) float act[];
   const FusedNet& net = args.net[blockIdx.y];
   const int M = args.M, m0 = blockIdx.x * BM;
   const int tid = threadIdx.x;
   {
     const int K0 = net.layer[0].K;
-    const int kpad = (K0 + 63) / 64 * 64;   // whole quads of k-steps
+    const int kpad = (K0 + 63) / 64 * 64;   // whole quads of k-steps of 16 = whole pairs of k-steps of 32
     const int c4n = kpad / 4;
     for (int i = tid; i < BM * c4n; i += NT) {
       const int r = i / c4n, c = (i % c4n) * 4;
@@ -476,18 +687,27 @@ __global__ __launch_bounds__(fx::NT) void mlp_fused_x3_kernel(FusedMlpArgs args)
     const FusedLayer& L = net.layer[l];
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool last = l == net.n_layers - 1;
-    if (L.N <= 32) x3_layer<1, 1>(net, L, M, m0, act, LDA, wave & 1, wave >> 1, last);
-    else if (L.N <= 128) x3_layer<1, 2>(net, L, M, m0, act, LDA, wave & 1, (wave >> 1) * 2, last);
-    else x3_layer<2, 4>(net, L, M, m0, act, LDA, 0, wave * 4, last);
+    if constexpr (SHAPE == 32) {
+      if (L.N <= 32) x3_layer<1, 1>(net, L, M, m0, act, LDA, wave & 1, wave >> 1, last);
+      else if (L.N <= 128) x3_layer<1, 2>(net, L, M, m0, act, LDA, wave & 1, (wave >> 1) * 2, last);
+      else x3_layer<2, 4>(net, L, M, m0, act, LDA, 0, wave * 4, last);
+    } else {
+      if (L.N <= 16) x16_layer<1, true>(net, L, M, m0, act, LDA, wave, last);
+      else if (L.N <= 64) x16_layer<4, true>(net, L, M, m0, act, LDA, wave, last);
+      else if (L.N <= 80) x16_layer<5, true>(net, L, M, m0, act, LDA, wave, last);
+      else if (L.N <= 128) x16_layer<8, true>(net, L, M, m0, act, LDA, wave, last);
+      else x16_layer<8, false>(net, L, M, m0, act, LDA, wave, last);
+    }
   }
 }
 
-hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, hipStream_t stream) {
+hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, bool shape16, hipStream_t stream) {
   dim3 grid((args.M + fx::BM - 1) / fx::BM, args.count);
   if (options().mlp_x3 >= 2) {   // opt-in: the cooperative split (measured slower, see x3c_layer)
     return launch_lds(mlp_fused_x3c_kernel, grid, dim3(fx::NT), fx::LDS_BYTES_C, stream, args);
   }
-  return launch_lds(mlp_fused_x3_kernel, grid, dim3(fx::NT), fx::LDS_BYTES, stream, args);
+  if (shape16) return launch_lds(mlp_fused_x3_kernel<16>, grid, dim3(fx::NT), fx::LDS_BYTES, stream, args);
+  return launch_lds(mlp_fused_x3_kernel<32>, grid, dim3(fx::NT), fx::LDS_BYTES, stream, args);
 }
 
 }  // namespace empose

@@ -70,8 +70,10 @@ const char* empose_arch(void);
  * is a multiple of 64: 1 [default]; 0 = the fp32 MFMA instruction; 2 = a variant whose waves share the operand split
  * through LDS, measured slower), "lstm_x3" (the same arithmetic for the LSTM steps of batches above 256 rows, inference,
  * uni-directional stacks with a hidden size of whole 32s: 1 [default]; 0 = the fp32 MFMA instruction; 2 = a row-split
- * variant, measured slower; 3 = the default kernel with its products on the 16x16x32 form of the bf16 instruction --
- * equal to rounding, not to the bit; measured 4 % faster per launch, opt-in), "rows_x3" (the
+ * variant, measured slower; 3 = force the kernel on the 16x16x32 form of the bf16 instruction), "lstm_chain16" (those
+ * steps with lstm_x3 = 1 on the 16x16x32 form of the bf16 instruction -- equal to the 32x32x16 form to rounding, not to the
+ * bit; measured 3 to 6 % faster per launch: 1 [default]; 0 = the 32x32x16 form), "mlp_fused16" (the same choice for the
+ * fused update MLPs with mlp_x3 = 1; measured 4 to 8 % faster per launch: 1 [default]; 0 = the 32x32x16 form), "rows_x3" (the
  * same arithmetic for the row-block products with fused prologue / epilogue: the blend products of the frame-per-lane
  * SMPL path and the stacked init heads; 0 = the fp32 MFMA instruction), "train_cols" (training at up to 512 rows: a
  * layer's product + BatchNorm + PReLU as one launch, forward and backward, both update networks side by side -- see

@@ -12,6 +12,31 @@ torch.manual_seed(0)
 net = create_model(lgd_config(12, True, 4), SMPLLayer(synthetic.make_model())).to(dev).eval()
 h = net._ensure_handle(dev)
 lib = _lib.lib()
+if '--ab' in sys.argv:
+    # Interleaved A/B over option mlp_fused16 (the 16x16x32 against the 32x32x16 form of the bf16 MFMA) on RANDOM inputs --
+    # zeros hide the clock the chip holds under matrix load: rounds of 50 back-to-back launches per arm, arms alternating.
+    x = torch.randn(T, 296, device=dev)
+    dp, ds = torch.empty(T, 66, device=dev), torch.empty(T, 10, device=dev)
+    nb = lib.empose_update_workspace_bytes(h, T); ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+    def run():
+        _lib.check(lib.empose_update_nets_fwd(h, T, _lib.dptr(x), 296, _lib.dptr(dp), _lib.dptr(ds), _lib.dptr(ws), nb, None))
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    us = {0: [], 1: []}
+    for rnd in range(9):
+        for arm in ((0, 1) if rnd % 2 == 0 else (1, 0)):
+            _lib.check(lib.empose_set_option(b'mlp_fused16', arm))
+            for _ in range(5): run()
+            e0.record()
+            for _ in range(50): run()
+            e1.record(); torch.cuda.synchronize()
+            if rnd > 0:   # (the first round warms the chip)
+                us[arm].append(e0.elapsed_time(e1) / 50 * 1e3)
+    lib.empose_reset_options()
+    for arm in (0, 1):
+        v = sorted(us[arm])
+        print('mlp_fused16=%d T=%d: median %.1f us/launch (min %.1f, max %.1f, %d rounds of 50)'
+              % (arm, T, v[len(v) // 2], v[0], v[-1], len(v)))
+    sys.exit(0)
 flush = torch.empty(160 * 1024 * 1024, device=dev)  # 640 MB: evicts L2 and the 256 MB Infinity Cache
 for kind in ('randn', 'zeros', 'randn+flush'):
     x = torch.zeros(T, 296, device=dev) if kind == 'zeros' else torch.randn(T, 296, device=dev)
