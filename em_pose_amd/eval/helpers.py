@@ -7,18 +7,25 @@ Evaluation driver (mirror of reference empose/eval/helpers.py:30-200 and scripts
                           recording are serially dependent through the LSTM state and must stay on one GPU)
   evaluate_sequences      the per-recording loop of evaluate_real.py (state carry, first chunk's shape for the whole
                           recording, metrics on all frames / per recording)
+  evaluate_sequences_batched, plan_rows   NEW: chunk c of all recordings as one ragged batch, and its plan of rows
 """
+import collections
+import contextlib
 import glob
 import os
+import time
 from collections import defaultdict
 
 import numpy as np
 import torch
+from torch.nn.utils.rnn import pad_sequence
 
+from em_pose_amd import _lib
 from em_pose_amd.data.data import RealBatch
 from em_pose_amd.eval.metrics import MetricsEngine
 from em_pose_amd.helpers.configuration import CONSTANTS as C
 from em_pose_amd.helpers.configuration import Configuration
+from em_pose_amd.nn.models import IterativeErrorFeedback, create_model
 
 
 def window_generator(batch, window_size):
@@ -78,7 +85,6 @@ def load_model(model_id, device=None):
     """reference eval/helpers.py:148-164: config.json -> body model -> network -> model.pth (whose `smpl.bm.*` buffers
     replace what `model.npz` held, as `load_state_dict` does in the reference)."""
     from em_pose_amd.bodymodels.smpl import create_default_smpl_model
-    from em_pose_amd.nn.models import create_model
     device = C.DEVICE if device is None else device
     model_dir = get_model_dir(C.EXPERIMENT_DIR, model_id)
     config = Configuration.from_json(os.path.join(model_dir, 'config.json'))
@@ -170,16 +176,98 @@ def _check_async(dev):
     """After a synchronisation: a cooperative LSTM kernel that gave up on a poll poisoned its outputs with NaN and counted
     itself (include/empose_hip.h, empose_async_status) -- raise instead of averaging NaNs into the metrics table."""
     if torch.device(dev).type == 'cuda':
-        from em_pose_amd import _lib
         _lib.check(_lib.lib().empose_async_status())
 
 
-class _nothing(object):
+def _laps(host_times):
+    """lap(key): (dev) the host seconds since the last lap, added to host_times[key] (None: nothing is measured)."""
+    t = [time.perf_counter()]
+
+    def lap(key):
+        if host_times is not None:
+            now = time.perf_counter()
+            host_times[key], t[0] = host_times.get(key, 0.0) + now - t[0], now
+    return lap
+
+
+class _ChunkPipeline(object):
+    """Chunks of a recording depend on each other only through the LSTM state, so chunk c + 1's packing + LSTM (current
+    stream) runs beside chunk c's refinement iterations and metrics (a side stream, IterativeErrorFeedback.iter_stream);
+    nothing in a driver's loop waits for the device.  Same results as one chunk after the other.  On the CPU, and for a
+    model without the two-part forward, there is no side stream: everything runs where the caller is."""
+
+    def __init__(self, net, device):
+        self.net, self.dev, self.side = net, torch.device(device), None
+        if isinstance(net, IterativeErrorFeedback) and self.dev.type == 'cuda' and not net.training:
+            # one side stream per network, kept: a fresh stream per call may land on the hardware queue of the current
+            # stream (measured: the first pass pipelined, later passes with their new streams did not)
+            self.side = getattr(net, '_side_stream', None)
+            if self.side is None or self.side.device != self.dev:
+                self.side = net._side_stream = torch.cuda.Stream(device=self.dev)
+
     def __enter__(self):
+        if self.side is not None:
+            self.net.iter_stream = self.side
         return self
 
     def __exit__(self, *exc):
-        return False
+        if self.side is not None:
+            self.net.iter_stream = None
+
+    def forward(self, chunk, is_new_sequence):
+        out = self.net(chunk, is_new_sequence=is_new_sequence)
+        if self.side is not None and self.net.outputs_ready is None:
+            # the forward did not go through the two-stream path (autograd forward of a `differentiable` net with grad
+            # enabled): its outputs are on the current stream, the metrics are on the side stream
+            self.side.wait_stream(torch.cuda.current_stream(self.dev))
+        return out
+
+    def metrics(self, chunk, *more):
+        """Context of a chunk's metrics; the chunk (and `more`) live in memory of the current stream's pool."""
+        if self.side is None:
+            return contextlib.nullcontext()
+        for t in (chunk.poses, chunk.shapes, chunk.seq_lengths) + more:
+            t.record_stream(self.side)
+        return torch.cuda.stream(self.side)
+
+    def drain(self):
+        if self.side is not None:
+            torch.cuda.current_stream(self.dev).wait_stream(self.side)   # every chunk's outputs / rows are complete
+
+
+def _recording_metrics(smpl_model, state, base, i):
+    me = MetricsEngine(smpl_model)
+    me.merge({key: v[base[i]:base[i + 1]] for key, v in state.items()})
+    return me.get_metrics()
+
+
+def _tables(smpl_model, ids, state, base, ready=None):
+    """`state` of an engine with the rows in recording order, recording i owning rows base[i] .. base[i + 1] -> (overall
+    engine, [(recording id, metrics dict)]); `ready[i]`: a recording's metrics where they are worked out already."""
+    ready = [None] * len(ids) if ready is None else ready
+    per_sequence = [(sid, ready[i] or _recording_metrics(smpl_model, state, base, i)) for i, sid in enumerate(ids)]
+    me_all = MetricsEngine(smpl_model)
+    me_all.merge(state)
+    return me_all, per_sequence
+
+
+def _flush_deferred(engine, deferred):
+    # On the device path the metrics of the sequential driver are computed ONCE, over the frames of all chunks: a chunk
+    # only leaves its tensors in `deferred` (the per-chunk forward-kinematics + metrics launches and the tensor plumbing
+    # around them were 0.27 ms of host time per chunk, a quarter of a pass that is bound by the host).  Here:
+    # one forward-kinematics launch and one metrics launch over the frames of the deferred chunks, in chunk order; shapes
+    # per frame (ground truth: the recording's; estimate: the recording's first chunk's, evaluate_real.py:63-68).  Called
+    # at the end of the pass and whenever DEFER_FRAME_BUDGET frames have piled up (each deferred chunk pins its staging
+    # buffer and outputs, ~1.8 KB per frame; the rows of a flush stay on the device until the pass ends, 65 doubles per frame)
+    if not deferred:
+        return
+    frames_of = lambda t: t.reshape(-1, t.shape[-1])
+    cat = lambda k: torch.cat([frames_of(d[k]) for d in deferred]).unsqueeze(0)
+    per_frame = lambda k, alt: torch.cat([(d[k] if d[k] is not None else d[alt]).reshape(1, -1)
+                                          .expand(d[0].shape[1], -1) for d in deferred]).unsqueeze(0)
+    engine.compute(cat(0), per_frame(1, 1), cat(2), per_frame(3, 1), None, cat(4), cat(5),
+                   valid=torch.cat([d[6].reshape(-1) for d in deferred]).unsqueeze(0))
+    del deferred[:]
 
 
 def evaluate_sequences(net, batches, smpl_model, device, window_size=256, log=None, host_times=None):
@@ -187,62 +275,20 @@ def evaluate_sequences(net, batches, smpl_model, device, window_size=256, log=No
     :param batches: iterable of single-recording `RealBatch`es (root already normalised), on the CPU.
     :return: (overall MetricsEngine, [(recording id, metrics dict)], frames processed)
     """
-    from em_pose_amd.nn.models import IterativeErrorFeedback
-    import time as _time
-    _t = [_time.perf_counter()]
-
-    def lap(key):   # (dev) host seconds per section of the loop
-        if host_times is not None:
-            now = _time.perf_counter()
-            host_times[key] = host_times.get(key, 0.0) + now - _t[0]
-            _t[0] = now
+    lap = _laps(host_times)
+    ws = window_size if isinstance(net, IterativeErrorFeedback) else None
     # ONE engine collects the rows of every chunk of every recording (on the device, in call order); they are read back
     # once, after the last recording, and split by the per-recording counts of valid frames.  Reading them back per
     # recording (as the reference's two engines would) drains the two-stream pipeline 36 times: 3.3 ms each, 0.12 of the
     # 0.25 s of a pass.
     me_rows = MetricsEngine(smpl_model)
     ids, counts, frames = [], [], 0
-    # ... and on the device path the metrics themselves are computed ONCE, over the frames of all chunks: a chunk only
-    # leaves its tensors in `deferred` (the per-chunk forward-kinematics + metrics launches and the tensor plumbing around
-    # them were 0.27 ms of host time per chunk, a quarter of a pass that is bound by the host).
-    deferred, deferred_frames = [], 0
-    defer = getattr(me_rows, 'angle_glob', False) and hasattr(smpl_model, 'fk_joints')
-
-    def flush_deferred():
-        # one forward-kinematics launch and one metrics launch over the frames of the deferred chunks, in chunk order; shapes
-        # per frame (ground truth: the recording's; estimate: the recording's first chunk's, evaluate_real.py:63-68).  Called
-        # at the end of the pass and whenever DEFER_FRAME_BUDGET frames have piled up (each deferred chunk pins its staging
-        # buffer and outputs, ~1.8 KB per frame; the rows of a flush stay on the device until the pass ends, 65 doubles per frame)
-        nonlocal deferred, deferred_frames
-        if not deferred:
-            return
-        frames_of = lambda t: t.reshape(-1, t.shape[-1])
-        cat = lambda k: torch.cat([frames_of(d[k]) for d in deferred]).unsqueeze(0)
-        per_frame = lambda k, alt: torch.cat([(d[k] if d[k] is not None else d[alt]).reshape(1, -1)
-                                              .expand(d[0].shape[1], -1) for d in deferred]).unsqueeze(0)
-        me_rows.compute(cat(0), per_frame(1, 1), cat(2), per_frame(3, 1), None, cat(4), cat(5),
-                        valid=torch.cat([d[6].reshape(-1) for d in deferred]).unsqueeze(0))
-        deferred, deferred_frames = [], 0
-    is_lgd = isinstance(net, IterativeErrorFeedback)
-    ws = window_size if is_lgd else None
-    # Chunks of a recording depend on each other only through the LSTM state, so chunk c + 1's packing + LSTM (current
-    # stream) runs beside chunk c's refinement iterations and metrics (a side stream, IterativeErrorFeedback.iter_stream).
-    # Same results as one chunk after the other.
-    dev = torch.device(device)
-    pipelined = is_lgd and dev.type == 'cuda' and not net.training
-    side = None
-    if pipelined:
-        # one side stream per network, kept: a fresh stream per call may land on the hardware queue of the current
-        # stream (measured: the first pass pipelined, later passes with their new streams did not)
-        side = getattr(net, '_side_stream', None)
-        if side is None or side.device != dev:
-            side = net._side_stream = torch.cuda.Stream(device=dev)
-        net.iter_stream = side
-    try:
+    deferred, deferred_frames = [], 0    # (`_flush_deferred`)
+    with _ChunkPipeline(net, device) as pipe:
+        defer = pipe.side is not None and getattr(me_rows, 'angle_glob', False) and hasattr(smpl_model, 'fk_joints')
         for batch in batches:
             if log:
                 log('Evaluate {} ({} frames)'.format(batch.ids[0], int(batch.seq_lengths[0])))
-            first_shape_hat = None
             ids.append(batch.ids[0])
             counts.append(0)
             # (Staging the whole recording on the device once and slicing views was measured slower: recordings have 36
@@ -256,51 +302,171 @@ def evaluate_sequences(net, batches, smpl_model, device, window_size=256, log=No
                 lap('cut_chunk')
                 chunk = chunk.to_gpu(device)
                 lap('to_gpu')
-                out = net(chunk, is_new_sequence=(c == 0))
+                out = pipe.forward(chunk, is_new_sequence=(c == 0))
                 lap('forward_enqueue')
-                if side is not None and net.outputs_ready is None:
-                    # the forward did not go through the two-stream path (autograd forward of a `differentiable` net with
-                    # grad enabled): its outputs are on the current stream, the metrics below are on the side stream
-                    side.wait_stream(torch.cuda.current_stream(dev))
-                if defer and side is not None and out['pose_hat'].is_cuda:
-                    if c == 0:  # the first chunk's shape is used for the whole recording (evaluate_real.py:63-68)
-                        first_shape_hat = out['shape_hat'][:, 0] if out['shape_hat'] is not None else None
+                if c == 0:  # the first chunk's shape is used for the whole recording (evaluate_real.py:63-68)
+                    first_shape_hat = out['shape_hat'][:, 0] if out['shape_hat'] is not None else None
+                if defer and out['pose_hat'].is_cuda:
                     deferred.append((chunk.poses_body, chunk.shapes, out['pose_hat'], first_shape_hat, chunk.poses_root,
                                      out['root_ori_hat'], valid))
                     deferred_frames += chunk.seq_length
                     if deferred_frames >= DEFER_FRAME_BUDGET:   # bound what is kept alive: row order is unchanged
-                        torch.cuda.current_stream(dev).wait_stream(side)
-                        flush_deferred()
-                    lap('metrics_enqueue')
-                    continue
-                with torch.cuda.stream(side) if side is not None else _nothing():
-                    if side is not None:   # the chunk lives in memory of the current stream's pool
-                        for t in (chunk.poses, chunk.shapes, chunk.seq_lengths):
-                            t.record_stream(side)
-                    if c == 0:  # the first chunk's shape is used for the whole recording (evaluate_real.py:63-68)
-                        first_shape_hat = out['shape_hat'][:, 0] if out['shape_hat'] is not None else None
-                    # the reference feeds the same chunk to two engines (evaluate_real.py:70-81); compute once per chunk
-                    me_rows.compute(chunk.poses_body, chunk.shapes, out['pose_hat'], first_shape_hat, chunk.seq_lengths,
-                                   chunk.poses_root, out['root_ori_hat'], frame_mask=chunk.marker_masks, valid=valid)
+                        pipe.drain()
+                        _flush_deferred(me_rows, deferred)
+                        deferred_frames = 0
+                else:
+                    with pipe.metrics(chunk):
+                        # the reference feeds the same chunk to two engines (evaluate_real.py:70-81); compute once per chunk
+                        me_rows.compute(chunk.poses_body, chunk.shapes, out['pose_hat'], first_shape_hat,
+                                        chunk.seq_lengths, chunk.poses_root, out['root_ori_hat'],
+                                        frame_mask=chunk.marker_masks, valid=valid)
                 lap('metrics_enqueue')
-        if side is not None:
-            torch.cuda.current_stream(dev).wait_stream(side)   # every chunk's outputs / rows are complete
-        flush_deferred()
+        pipe.drain()
+        _flush_deferred(me_rows, deferred)
         st = me_rows.state()        # (reads the rows back: the device is in sync afterwards)
-        _check_async(dev)
+        _check_async(device)
         lap('wait_for_device_and_rows')
-        me_all, per_sequence, at = MetricsEngine(smpl_model), [], 0
-        for sid, m in zip(ids, counts):
-            me_ind = MetricsEngine(smpl_model)
-            me_ind.merge({key: v[at:at + m] for key, v in st.items()})
-            at += m
-            me_all.merge(me_ind.state())
-            per_sequence.append((sid, me_ind.get_metrics()))
+        me_all, per_sequence = _tables(smpl_model, ids, st, np.concatenate([[0], np.cumsum(counts, dtype=np.int64)]))
         lap('per_recording_metrics')
-    finally:
-        if pipelined:
-            net.iter_stream = None
     return me_all, per_sequence, frames
+
+
+RowPlan = collections.namedtuple('RowPlan', 'order lengths valid base total chunks lens dest')
+RowPlanChunk = collections.namedtuple('RowPlanChunk', 'sf f k lens ended')
+
+
+def plan_rows(lengths, valid_per_recording, window_size):
+    """How the batched driver cuts its chunks and where every frame's metric row goes, from the recordings' lengths and
+    their frames that count (per recording, bool (frames,)).  Batch row j is recording order[j]: `lengths`, `valid`, `dest`
+    (rows, longest) and `lens` (chunks, rows) are per batch row, `base` is per recording, `ended` lists recordings."""
+    n = len(lengths)
+    # Longest recording first: the rows that still have frames in chunk c are then a PREFIX of the batch, so a chunk is
+    # a slice [:k, sf:sf + f] of one padded block per field (no per-row cutting, padding and concatenating: that was
+    # 47 of the 82 ms of a pass, all of it host time -- the device waits for the host in this driver).
+    order = sorted(range(n), key=lambda i: (-lengths[i], i))
+    sl = np.asarray([lengths[i] for i in order], dtype=np.int64)
+    n_chunks = (int(sl[0]) + window_size - 1) // window_size
+    valid = np.zeros((n, int(sl[0])), dtype=bool)
+    for j, i in enumerate(order):
+        valid[j, :sl[j]] = valid_per_recording[i]
+    # Where every frame's row goes: recording i owns rows base[i] .. base[i + 1] of one block, its valid frames in
+    # frame order (what the sequential driver accumulates, recording after recording); frames that do not count go to
+    # a spare row past the end.
+    base = np.zeros(n + 1, dtype=np.int64)
+    base[1:][order] = valid.sum(axis=1)
+    base = np.cumsum(base)
+    total = int(base[-1])
+    dest = np.where(valid, np.cumsum(valid, axis=1) - 1 + base[:-1][order][:, None], total)
+    lens = np.clip(sl[None, :] - window_size * np.arange(n_chunks)[:, None], 0, window_size).astype(np.int32)
+    rows = (lens > 0).sum(axis=1).tolist() + [0]     # per chunk, and none after the last
+    chunks = [RowPlanChunk(c * window_size, int(lens[c, 0]), k, lens[c, :k], [order[j] for j in range(rows[c + 1], k)])
+              for c, k in enumerate(rows[:-1])]
+    return RowPlan(order, sl, valid, base, total, chunks, lens, dest)
+
+
+class _PlacedRows(object):
+    """The metric rows of a chunk are scattered on the device to where they belong in ONE block in recording order; a
+    recording's rows go to the host (pinned memory, side stream) with the chunk it ends in, and its table row is worked
+    out while the device runs the chunks after it -- the host part of the metrics (a third of a pass when it ran after the
+    last chunk) is hidden behind the device, which is the bound of the batched driver (the LSTM's dependent steps)."""
+
+    def __init__(self, plan, smpl_model, device):
+        self.plan, self.smpl_model = plan, smpl_model
+        self.dest = torch.from_numpy(np.ascontiguousarray(plan.dest)).pin_memory().to(device, non_blocking=True)
+        self.rows = torch.empty(plan.total + 1, 65, dtype=torch.float64, device=device)
+        self.rows_host = torch.empty(max(plan.total, 1), 65, dtype=torch.float64, pin_memory=True)
+        r = self.rows_host.numpy()[:plan.total]   # (the view keeps the pinned block alive; torch caches it afterwards)
+        self.state = {'eucl': r[:, :22], 'eucl_pa': r[:, 22:44], 'angle': r[:, 44:]}
+        self.arrived = []                         # (event, recordings whose rows it brings), in chunk order
+        self.ready = [None] * len(plan.order)     # per recording: its metrics
+
+    def place(self, rows, ch):
+        base = self.plan.base
+        self.rows.index_copy_(0, self.dest[:ch.k, ch.sf:ch.sf + ch.f].reshape(-1), rows)
+        for i in ch.ended:
+            if base[i + 1] > base[i]:
+                self.rows_host[base[i]:base[i + 1]].copy_(self.rows[base[i]:base[i + 1]], non_blocking=True)
+        self.arrived.append((torch.cuda.current_stream().record_event(), ch.ended))
+
+    def take_arrived(self, wait):
+        while self.arrived and (wait or self.arrived[0][0].query()):
+            ev, recs = self.arrived.pop(0)
+            ev.synchronize()
+            for i in recs:
+                self.ready[i] = _recording_metrics(self.smpl_model, self.state, self.plan.base, i)
+
+
+def _rows_in_recording_order(state, plan):
+    """Host rows as the chunks left them (chunk after chunk, batch row after batch row) -> recording order."""
+    of = lambda a, ch: a[:ch.k, ch.sf:ch.sf + ch.f]
+    back = np.argsort(np.concatenate([of(plan.dest, ch)[of(plan.valid, ch)] for ch in plan.chunks]))
+    return {key: v[back] if v.shape[0] else v for key, v in state.items()}     # (a family without rows stays without)
+
+
+def _prepare_batched(batches, smpl_model, dev, window_size, lap):
+    """-> the row plan, one padded block per field on the device (rows as in the plan), the engine, the placed rows."""
+    lengths = [int(b.seq_lengths[0]) for b in batches]
+    order = sorted(range(len(batches)), key=lambda i: (-lengths[i], i))   # (`plan_rows`, which comes after the upload)
+    # (a recording a loader has pinned -- RealBatch.pin_memory -- goes up as ONE block, without staging and without
+    # blocking the host: 36 copies per pass instead of 288)
+    on_dev = [batches[i].device_fields(dev) for i in order]
+    fields = ('poses', 'trans', 'marker_pos_real', 'marker_ori_real', 'marker_masks')
+    packed = {k: pad_sequence([d[k][0] for d in on_dev], batch_first=True) for k in fields}
+    packed.update({k: torch.cat([d[k] for d in on_dev]) for k in ('shapes', 'offset_t', 'offset_r')})
+    del on_dev
+    lap('upload_and_pack')
+    # the frames that count -- inside the recording and every sensor present -- from the host copies of the masks
+    # (numpy: a torch CPU op on a 36 x 256 x 12 block wakes the whole intra-op thread pool)
+    valid = [(b.marker_masks[0].numpy() != 0).all(axis=-1) for b in batches]
+    lap('valid_frames')
+    plan = plan_rows(lengths, valid, window_size)
+    packed['ids'] = [batches[i].ids[0] for i in plan.order]
+    me_chunks = MetricsEngine(smpl_model)
+    # placed: `compute` queues device rows (its device path); otherwise it accumulates on the host and the rows are
+    # put into recording order after the loop
+    placed = _PlacedRows(plan, smpl_model, dev) if me_chunks.queues_device_rows(dev) else None
+    # the lengths of every chunk's rows in ONE pinned block and one copy that does not block (a pageable copy would make
+    # the host wait for the stream; a pinned block per chunk asks the host allocator 14 times a pass, and a request it
+    # cannot serve from its cache waits for the device)
+    packed['lens'] = torch.from_numpy(plan.lens)
+    if dev.type == 'cuda':
+        packed['lens'] = packed['lens'].pin_memory().to(dev, non_blocking=True)
+    lap('row_plan')
+    return plan, packed, me_chunks, placed
+
+
+def _run_batched_chunks(net, pipe, plan, packed, me_chunks, placed, lap):
+    state, first_shape = None, None
+    on_side = (placed.dest, placed.rows) if placed is not None else ()   # what the metrics stream uses beside the chunk
+    for c, ch in enumerate(plan.chunks):
+        cut = lambda name: packed[name][:ch.k, ch.sf:ch.sf + ch.f]
+        chunk = RealBatch(packed['ids'][:ch.k], packed['lens'][c, :ch.k], cut('poses'), packed['shapes'][:ch.k],
+                          cut('trans'), cut('marker_pos_real'), cut('marker_ori_real'), cut('marker_masks'),
+                          packed['offset_t'][:ch.k], packed['offset_r'][:ch.k]).to_gpu(pipe.dev)
+        if net.rnn_init and c > 0:   # the rows that go on are the first k of the previous chunk's
+            net.rnn.final_state = (state[0][:, :ch.k].contiguous(), state[1][:, :ch.k].contiguous())
+        lap('chunk_prep')
+        out = pipe.forward(chunk, is_new_sequence=(c == 0))
+        lap('forward_enqueue')
+        if net.rnn_init:
+            state = net.rnn.final_state
+        with pipe.metrics(chunk, *on_side):
+            if c == 0:   # the first chunk's shape estimate stands for the whole recording (evaluate_real.py:63-68)
+                first_shape = out['shape_hat'][:, 0].contiguous()
+            valid = torch.from_numpy(np.ascontiguousarray(plan.valid[:ch.k, ch.sf:ch.sf + ch.f]))
+            queued = me_chunks.compute(chunk.poses_body, chunk.shapes, out['pose_hat'], first_shape[:ch.k],
+                                       chunk.seq_lengths, chunk.poses_root, out['root_ori_hat'],
+                                       frame_mask=chunk.marker_masks, valid=valid)
+            if queued != (placed is not None):
+                raise RuntimeError('MetricsEngine.compute %s device rows, the driver expected the opposite'
+                                   % ('queued' if queued else 'did not queue'))
+            if placed is not None:
+                (rows, _, _), = me_chunks.take_device_rows()
+                placed.place(rows, ch)
+        lap('metrics_enqueue')
+        if placed is not None:
+            placed.take_arrived(wait=False)
+        lap('per_recording_metrics')
 
 
 def evaluate_sequences_batched(net, batches, smpl_model, device, window_size=256, host_times=None):
@@ -310,194 +476,36 @@ def evaluate_sequences_batched(net, batches, smpl_model, device, window_size=256
     independent of each other in the model, so this only changes how much work one launch carries:
     36 recordings need 14 launches of the loop instead of 211.
 
-    The metric rows of a chunk are scattered on the device to where they belong in ONE block in recording order; a
-    recording's rows go to the host (pinned memory, side stream) with the chunk it ends in, and its table row is worked
-    out while the device runs the chunks after it -- the host part of the metrics (a third of a pass when it ran after the
-    last chunk) is hidden behind the device, which is the bound of this driver (the LSTM's dependent steps).
-
     `host_times` (a dict, optional): seconds of host time per section of the pass (dev: where a slow pass spends it).
     """
-    import time as _time
-    _t = [_time.perf_counter()]
-
-    def lap(key):
-        if host_times is not None:
-            now = _time.perf_counter()
-            host_times[key] = host_times.get(key, 0.0) + now - _t[0]
-            _t[0] = now
-    from em_pose_amd.nn.models import IterativeErrorFeedback
+    lap = _laps(host_times)
     assert isinstance(net, IterativeErrorFeedback)
     if len(batches) == 0:      # (a rank of a multi-GPU run that got no recording)
         return MetricsEngine(smpl_model), [], 0
+    dev = torch.device(device)
+    plan, packed, me_chunks, placed = _prepare_batched(batches, smpl_model, dev, window_size, lap)
     # rows shorter than the chunk are padded: average the shape over their valid frames only, which is what the
     # unpadded one-recording chunk of the sequential driver averages over
-    was_valid_only = net.shape_avg_valid_only
-    net.shape_avg_valid_only = True
+    was_valid_only, net.shape_avg_valid_only = net.shape_avg_valid_only, True
     try:
-        import numpy as np
-        from torch.nn.utils.rnn import pad_sequence
-        n = len(batches)
-        lengths = [int(b.seq_lengths[0]) for b in batches]
-        # Longest recording first: the rows that still have frames in chunk c are then a PREFIX of the batch, so a chunk is
-        # a slice [:k, sf:sf + f] of one padded block per field (no per-row cutting, padding and concatenating: that was
-        # 47 of the 82 ms of a pass, all of it host time -- the device waits for the host in this driver).
-        order = sorted(range(n), key=lambda i: (-lengths[i], i))
-        sl = [lengths[i] for i in order]
-        n_chunks = (sl[0] + window_size - 1) // window_size
-        dev = torch.device(device)
-        on_gpu = dev.type == 'cuda'
-        # (a recording a loader has pinned -- RealBatch.pin_memory -- goes up as ONE block, without staging and without
-        # blocking the host: 36 copies per pass instead of 288)
-        on_dev = [batches[i].device_fields(device) for i in order]
-        fields = ('poses', 'trans', 'marker_pos_real', 'marker_ori_real', 'marker_masks')
-        packed = {k: pad_sequence([d[k][0] for d in on_dev], batch_first=True) for k in fields}
-        whole = {k: torch.cat([d[k] for d in on_dev]) for k in ('shapes', 'offset_t', 'offset_r')}
-        del on_dev
-        lap('upload_and_pack')
-        # the frames that count -- inside the recording and every sensor present -- from the host copies of the masks
-        # (numpy: a torch CPU op on a 36 x 256 x 12 block wakes the whole intra-op thread pool)
-        valid_all = np.zeros((n, sl[0]), dtype=bool)
-        for j, i in enumerate(order):
-            valid_all[j, :sl[j]] = (batches[i].marker_masks[0].numpy() != 0).all(axis=-1)
-        # As in `evaluate_sequences`: chunk c + 1's packing and LSTM (current stream) beside chunk c's refinement
-        # iterations and metrics (side stream); nothing in the loop waits for the device.
-        side = None
-        if on_gpu and not net.training:
-            side = getattr(net, '_side_stream', None)
-            if side is None or side.device != dev:
-                side = net._side_stream = torch.cuda.Stream(device=dev)
-            net.iter_stream = side
-        lap('valid_frames')
-        me_chunks = MetricsEngine(smpl_model)
-        # placed: `compute` queues device rows (its device path); otherwise it accumulates on the host and the rows are
-        # split per recording after the loop
-        placed = me_chunks.queues_device_rows(dev)
-        # Where every frame's row goes: recording i owns rows base[i] .. base[i + 1] of one block, its valid frames in
-        # frame order (what the sequential driver accumulates, recording after recording); frames that do not count go to
-        # a spare row past the end.
-        per_row = valid_all.sum(axis=1)
-        base = np.zeros(n + 1, dtype=np.int64)
-        base[1:][order] = per_row
-        base = np.concatenate([[0], np.cumsum(base[1:])])
-        total = int(base[-1])
-        if placed:
-            dest_all = np.where(valid_all, np.cumsum(valid_all, axis=1) - 1 + base[:-1][order][:, None], total)
-            dest_host = torch.from_numpy(np.ascontiguousarray(dest_all, dtype=np.int64)).pin_memory()
-            dest_dev = dest_host.to(device, non_blocking=True)
-            rows_dev = torch.empty(total + 1, 65, dtype=torch.float64, device=dev)
-            rows_host = torch.empty(max(total, 1), 65, dtype=torch.float64, pin_memory=True)
-            rows_np = rows_host.numpy()[:total]   # (the view keeps the pinned block alive; torch caches it afterwards)
-        counts = []                             # not placed: per chunk, the valid frames of each of its rows
-        arrived = []                            # placed: (event, recordings whose rows it brings), in chunk order
-        results = [None] * n                    # per recording: its table row
-
-        def table_row(i):
-            me = MetricsEngine(smpl_model)
-            r = rows_np[base[i]:base[i + 1]]
-            me.merge({'eucl': r[:, :22], 'eucl_pa': r[:, 22:44], 'angle': r[:, 44:]})
-            results[i] = (batches[i].ids[0], me.get_metrics())
-
-        def take_arrived(wait):
-            while arrived and (wait or arrived[0][0].query()):
-                ev, recs = arrived.pop(0)
-                ev.synchronize()
-                for i in recs:
-                    table_row(i)
-        # the lengths of every chunk's rows in ONE pinned block and one copy that does not block (a pageable copy would make
-        # the host wait for the stream; a pinned block per chunk asks the host allocator 14 times a pass, and a request it
-        # cannot serve from its cache waits for the device)
-        lens_all = np.clip(np.asarray(sl, dtype=np.int64)[None, :] - window_size * np.arange(n_chunks)[:, None], 0,
-                           window_size).astype(np.int32)
-        lens_all_dev = torch.from_numpy(lens_all)
-        if on_gpu:
-            lens_all_dev = lens_all_dev.pin_memory().to(device, non_blocking=True)
-        state, first_shape, frames = None, None, 0
-        lap('row_plan')
-        for c in range(n_chunks):
-            sf = c * window_size
-            k = sum(1 for L in sl if L > sf)
-            k_next = sum(1 for L in sl if L > sf + window_size)
-            lens = [min(window_size, L - sf) for L in sl[:k]]
-            f = lens[0]
-            cut = lambda name: packed[name][:k, sf:sf + f]
-            lens_dev = lens_all_dev[c, :k]
-            chunk = RealBatch([batches[i].ids[0] for i in order[:k]], lens_dev, cut('poses'),
-                              whole['shapes'][:k], cut('trans'), cut('marker_pos_real'), cut('marker_ori_real'),
-                              cut('marker_masks'), whole['offset_t'][:k], whole['offset_r'][:k]).to_gpu(device)
-            valid_np = valid_all[:k, sf:sf + f]
-            if net.rnn_init and c > 0:   # the rows that go on are the first k of the previous chunk's
-                net.rnn.final_state = (state[0][:, :k].contiguous(), state[1][:, :k].contiguous())
-            lap('chunk_prep')
-            out = net(chunk, is_new_sequence=(c == 0))
-            lap('forward_enqueue')
-            if net.rnn_init:
-                state = net.rnn.final_state
-            if side is not None and net.outputs_ready is None:   # (see evaluate_sequences)
-                side.wait_stream(torch.cuda.current_stream(dev))
-            with torch.cuda.stream(side) if side is not None else _nothing():
-                if side is not None:   # the chunk lives in memory of the current stream's pool
-                    for t in (chunk.poses, chunk.shapes, chunk.seq_lengths):
-                        t.record_stream(side)
-                if c == 0:   # the first chunk's shape estimate stands for the whole recording (evaluate_real.py:63-68)
-                    first_shape = out['shape_hat'][:, 0].contiguous()
-                queued = me_chunks.compute(chunk.poses_body, chunk.shapes, out['pose_hat'], first_shape[:k],
-                                           chunk.seq_lengths, chunk.poses_root, out['root_ori_hat'],
-                                           frame_mask=chunk.marker_masks,
-                                           valid=torch.from_numpy(np.ascontiguousarray(valid_np)))
-                if queued != placed:
-                    raise RuntimeError('MetricsEngine.compute %s device rows, the driver expected the opposite'
-                                       % ('queued' if queued else 'did not queue'))
-                if placed:
-                    (rows, _, _), = me_chunks.take_device_rows()
-                    if side is not None:
-                        dest_dev.record_stream(side)
-                        rows_dev.record_stream(side)
-                    rows_dev.index_copy_(0, dest_dev[:k, sf:sf + f].reshape(-1), rows)
-                    ended = [order[j] for j in range(k_next, k)]   # the recordings whose last chunk this was
-                    for i in ended:
-                        if base[i + 1] > base[i]:
-                            rows_host[base[i]:base[i + 1]].copy_(rows_dev[base[i]:base[i + 1]], non_blocking=True)
-                    ev = torch.cuda.Event()
-                    ev.record()
-                    arrived.append((ev, ended))
-            if not placed:
-                counts.append(valid_np.sum(axis=1).tolist())
-            frames += sum(lens)
-            lap('metrics_enqueue')
-            take_arrived(wait=False)
-            lap('per_recording_metrics')
-        if placed:
-            take_arrived(wait=True)     # (the last event is the end of the side stream's work)
+        with _ChunkPipeline(net, dev) as pipe:
+            _run_batched_chunks(net, pipe, plan, packed, me_chunks, placed, lap)
+            if placed is not None:
+                placed.take_arrived(wait=True)     # (the last event is the end of the side stream's work)
+                lap('wait_for_device')
+            pipe.drain()
+            if dev.type == 'cuda':
+                torch.cuda.synchronize(dev)
+                _check_async(dev)
             lap('wait_for_device')
-        if side is not None:
-            torch.cuda.current_stream(dev).wait_stream(side)
-        if on_gpu:
-            torch.cuda.synchronize(dev)
-            _check_async(dev)
-        lap('wait_for_device')
-        if placed:
-            for i in range(n):          # (a recording without a single frame never ended in a chunk: an empty table row)
-                if results[i] is None:
-                    table_row(i)
-            me_all = MetricsEngine(smpl_model)
-            me_all.merge({'eucl': rows_np[:, :22], 'eucl_pa': rows_np[:, 22:44], 'angle': rows_np[:, 44:]})
-            return me_all, results, frames
-        st = me_chunks.state()    # one device-side gather of the valid rows, one copy to (cached) pinned host memory
-        engines = [MetricsEngine(smpl_model) for _ in range(n)]
-        at = 0
-        for cnt in counts:
-            for j, m in enumerate(cnt):
-                if m:
-                    engines[order[j]].merge({key: v[at:at + m] for key, v in st.items()})
-                at += m
+            if placed is not None:
+                rows, ready = placed.state, placed.ready
+            else:   # one device-side gather of the valid rows, one copy to (cached) pinned host memory
+                rows, ready = _rows_in_recording_order(me_chunks.state(), plan), None
+                lap('merge_rows')
     finally:
         net.shape_avg_valid_only = was_valid_only
-        net.iter_stream = None
-    lap('merge_rows')
-    me_all = MetricsEngine(smpl_model)
-    per_sequence = []
-    for i in range(n):  # recording order, exactly as the sequential driver accumulates
-        me_all.merge(engines[i].state())
-        per_sequence.append((batches[i].ids[0], engines[i].get_metrics()))
+    # (a recording without a single frame never ended in a chunk: its empty table row is made here)
+    me_all, per_sequence = _tables(smpl_model, [b.ids[0] for b in batches], rows, plan.base, ready)
     lap('per_recording_metrics')
-    return me_all, per_sequence, frames
+    return me_all, per_sequence, int(plan.lengths.sum())

@@ -12,6 +12,7 @@ forward() packs the parameters once into an opaque HIP model (include/empose_hip
 residual gradient by a hand-derived reverse pass instead of autograd (so `torch.set_grad_enabled` is left alone,
 unlike reference models.py:487).  There is no CPU path: CPU tensors raise.
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -383,6 +384,27 @@ class SimpleRNN(BaseModel):
         return self._baseline_backward(batch, model_out, writer, global_step)
 
 
+_PHASE_INIT, _PHASE_ITER = 1, 2   # EMPOSE_LGD_PHASE_INIT / _ITER (include/empose_hip.h)
+_LgdInputs = collections.namedtuple('_LgdInputs', 'marker_pos marker_oris offset_t offset_r marker_masks seq_lengths h0 c0')
+
+
+class _TwoWorkspaces(object):
+    """A two-stream forward takes the workspace the previous one did not (whose iterations may still run); `free[k]` is
+    the event after which workspace k may be used again."""
+
+    def __init__(self, dev):
+        self.dev, self.turn, self.ws, self.free = dev, 0, [None, None], [None, None]
+
+    def take_turn(self, need, cur, side):
+        k = self.turn = 1 - self.turn
+        if self.ws[k] is None or self.ws[k].numel() < need:
+            self.ws[k] = torch.empty(need, dtype=torch.uint8, device=self.dev)
+            self.ws[k].record_stream(side)
+        if self.free[k] is not None:
+            cur.wait_event(self.free[k])     # the iterations of two chunks ago are done with it
+        return self.ws[k]
+
+
 class IterativeErrorFeedback(BaseModel):
     """The LGD / LGD-RNN model."""
 
@@ -644,91 +666,86 @@ class IterativeErrorFeedback(BaseModel):
             raise RuntimeError('forward_tensors is the inference entry point; in training mode call forward(batch)')
         if not marker_pos.is_cuda:
             raise _lib.EmposeError('IterativeErrorFeedback needs GPU tensors; there is no CPU fallback')
-        dev = marker_pos.device
-        B, F = marker_pos.shape[0], marker_pos.shape[1]
-        T = B * F
+        dev, B, F = marker_pos.device, marker_pos.shape[0], marker_pos.shape[1]
+        inputs = self._lgd_inputs(dev, B, F, marker_pos, marker_oris, offset_t, offset_r, marker_masks, seq_lengths,
+                                  state)
+        with torch.cuda.device(dev):
+            handle = self._ensure_handle(dev)
+            io, out, touched = self._lgd_io(dev, B, F, inputs, keep_history, keep_gradient_trace, suppress_mask_value)
+            need = _lib.lib().empose_lgd_workspace_bytes(handle, B, F)
+            if self.iter_stream is None:
+                self._launch_on_one_stream(handle, io, need, dev)
+            else:
+                self._launch_on_two_streams(handle, io, need, dev, touched)
+        return out
+
+    def _lgd_inputs(self, dev, B, F, marker_pos, marker_oris, offset_t, offset_r, marker_masks, seq_lengths, state):
+        """The arguments of `forward_tensors` as the C ABI takes them: on `dev`, contiguous, fp32 (lengths: int32)."""
         f32 = lambda t: None if t is None else t.to(device=dev, dtype=torch.float32).contiguous()
-        marker_pos, marker_oris = f32(marker_pos).reshape(B, F, 36), f32(marker_oris).reshape(B, F, 108)
         offset_t, offset_r = f32(offset_t), f32(offset_r)
         if offset_t.shape[0] == 1 and B > 1:
             offset_t, offset_r = offset_t.expand(B, 12, 3).contiguous(), offset_r.expand(B, 12, 3, 3).contiguous()
         assert offset_t.shape == (B, 12, 3) and offset_r.shape == (B, 12, 3, 3)
-        marker_masks = f32(marker_masks)
         if seq_lengths is not None:
             seq_lengths = seq_lengths.to(device=dev, dtype=torch.int32).contiguous()
             assert seq_lengths.numel() == B
-        lib = _lib.lib()
-        with torch.cuda.device(dev):
-            handle = self._ensure_handle(dev)
-            new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
-            io = _lib.LgdIO()
-            io.B, io.F = B, F
-            io.marker_pos, io.marker_oris = _lib.dptr(marker_pos), _lib.dptr(marker_oris)
-            io.offset_t, io.offset_r = _lib.dptr(offset_t), _lib.dptr(offset_r)
-            io.marker_masks, io.seq_lengths = _lib.dptr(marker_masks), _lib.dptr(seq_lengths)
-            if suppress_mask_value is not None and marker_masks is not None:
-                io.suppress_missing, io.mask_value = 1, float(suppress_mask_value)
-            out = {'pose': new(B, F, 66), 'shape': new(B, F, 10), 'joints': new(B, F, 66), 'state': None,
-                   'hist': None, 'trace': None}
-            io.pose_hat, io.shape_hat, io.joints_hat = [_lib.dptr(out[k]) for k in ('pose', 'shape', 'joints')]
-            h0 = c0 = None
-            if self.rnn_init:
-                L, H = self.rnn.num_layers, self.rnn.hidden_size
-                if state is not None:
-                    h0, c0 = f32(state[0]), f32(state[1])
-                    assert h0.shape == (L, B, H) and c0.shape == (L, B, H)
-                h_n, c_n = new(L, B, H), new(L, B, H)
-                io.h0, io.c0, io.h_n, io.c_n = _lib.dptr(h0), _lib.dptr(c0), _lib.dptr(h_n), _lib.dptr(c_n)
-                out['state'] = (h_n, c_n)
-            if keep_history:
-                n1 = self.N + 1
-                hist = {'pose': new(n1, T, 66), 'shape': new(n1, T, 10), 'joints': new(n1, T, 66),
-                        'markers': new(n1, T, 36), 'markers_ori': new(n1, T, 108)}
-                io.hist_pose, io.hist_shape, io.hist_joints = [_lib.dptr(hist[k]) for k in ('pose', 'shape', 'joints')]
-                io.hist_markers, io.hist_markers_ori = _lib.dptr(hist['markers']), _lib.dptr(hist['markers_ori'])
-                out['hist'] = hist
-            if keep_gradient_trace and self.use_gradient and self.N > 0:
-                trace = {'g_pose': new(self.N, T, 66), 'g_shape': new(self.N, T, 10)}
-                io.trace_g_pose, io.trace_g_shape = _lib.dptr(trace['g_pose']), _lib.dptr(trace['g_shape'])
-                out['trace'] = trace
-            need = lib.empose_lgd_workspace_bytes(handle, B, F)
-            if self.iter_stream is None:
-                if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
-                    self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-                _lib.check(lib.empose_lgd_forward(handle, C.byref(io), _lib.dptr(self._workspace),
-                                                  self._workspace.numel(), _lib.current_stream()))
-                self.outputs_ready = None
-            else:
-                side, cur = self.iter_stream, torch.cuda.current_stream(dev)
-                if self._pipe is None or self._pipe['dev'] != dev:
-                    self._pipe = {'dev': dev, 'turn': 0, 'ws': [None, None], 'free': [None, None]}
-                k = self._pipe['turn'] = 1 - self._pipe['turn']
-                ws = self._pipe['ws'][k]
-                if ws is None or ws.numel() < need:
-                    ws = self._pipe['ws'][k] = torch.empty(need, dtype=torch.uint8, device=dev)
-                    ws.record_stream(side)
-                if self._pipe['free'][k] is not None:
-                    cur.wait_event(self._pipe['free'][k])     # the iterations of two chunks ago are done with it
-                _lib.check(lib.empose_lgd_forward_phase(handle, C.byref(io), _lib.dptr(ws), ws.numel(),
-                                                        C.c_void_p(cur.cuda_stream), 1))
-                started = torch.cuda.Event()
-                started.record(cur)
-                side.wait_event(started)
-                # what the side stream reads or writes was allocated for the current stream: keep it from being
-                # handed out again before the side stream is done with it
-                touched = [offset_t, offset_r, seq_lengths, out['pose'], out['shape'], out['joints']]
-                touched += list(out['hist'].values()) if out['hist'] else []
-                touched += list(out['trace'].values()) if out['trace'] else []
-                for t in touched:
-                    if t is not None:
-                        t.record_stream(side)
-                _lib.check(lib.empose_lgd_forward_phase(handle, C.byref(io), _lib.dptr(ws), ws.numel(),
-                                                        C.c_void_p(side.cuda_stream), 2))
-                done = torch.cuda.Event()
-                done.record(side)
-                self._pipe['free'][k] = done
-                self.outputs_ready = done
-        return out
+        h0, c0 = (f32(state[0]), f32(state[1])) if self.rnn_init and state is not None else (None, None)
+        assert h0 is None or h0.shape == c0.shape == (self.rnn.num_layers, B, self.rnn.hidden_size)
+        return _LgdInputs(f32(marker_pos).reshape(B, F, 36), f32(marker_oris).reshape(B, F, 108), offset_t, offset_r,
+                          f32(marker_masks), seq_lengths, h0, c0)
+
+    def _lgd_io(self, dev, B, F, inputs, keep_history, keep_gradient_trace, suppress_mask_value):
+        """-> LgdIO of `inputs` and fresh outputs, the outputs, and what of both the iterations read or write."""
+        T = B * F
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        io = _lib.LgdIO()
+        io.B, io.F = B, F
+        for k, t in inputs._asdict().items():
+            setattr(io, k, _lib.dptr(t))
+        if suppress_mask_value is not None and inputs.marker_masks is not None:
+            io.suppress_missing, io.mask_value = 1, float(suppress_mask_value)
+        out = {'pose': new(B, F, 66), 'shape': new(B, F, 10), 'joints': new(B, F, 66), 'state': None,
+               'hist': None, 'trace': None}
+        io.pose_hat, io.shape_hat, io.joints_hat = [_lib.dptr(out[k]) for k in ('pose', 'shape', 'joints')]
+        touched = [t for t in (inputs.offset_t, inputs.offset_r, inputs.seq_lengths) if t is not None] + \
+            [out['pose'], out['shape'], out['joints']]
+        if self.rnn_init:
+            h_n, c_n = [new(self.rnn.num_layers, B, self.rnn.hidden_size) for _ in range(2)]
+            io.h_n, io.c_n, out['state'] = _lib.dptr(h_n), _lib.dptr(c_n), (h_n, c_n)
+        if keep_history:
+            n1 = self.N + 1
+            out['hist'] = hist = {'pose': new(n1, T, 66), 'shape': new(n1, T, 10), 'joints': new(n1, T, 66),
+                                  'markers': new(n1, T, 36), 'markers_ori': new(n1, T, 108)}
+            for k, t in hist.items():
+                setattr(io, 'hist_' + k, _lib.dptr(t))
+            touched += list(hist.values())
+        if keep_gradient_trace and self.use_gradient and self.N > 0:
+            out['trace'] = trace = {'g_pose': new(self.N, T, 66), 'g_shape': new(self.N, T, 10)}
+            io.trace_g_pose, io.trace_g_shape = _lib.dptr(trace['g_pose']), _lib.dptr(trace['g_shape'])
+            touched += list(trace.values())
+        return io, out, touched
+
+    def _launch_on_one_stream(self, handle, io, need, dev):
+        if self._workspace is None or self._workspace.numel() < need or self._workspace.device != dev:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+        _lib.check(_lib.lib().empose_lgd_forward(handle, C.byref(io), _lib.dptr(self._workspace),
+                                                 self._workspace.numel(), _lib.current_stream()))
+        self.outputs_ready = None
+
+    def _launch_on_two_streams(self, handle, io, need, dev, touched):
+        """Input packing + initial estimate on the current stream, then the N iterations on `iter_stream`."""
+        lib, side, cur = _lib.lib(), self.iter_stream, torch.cuda.current_stream(dev)
+        if self._pipe is None or self._pipe.dev != dev:
+            self._pipe = _TwoWorkspaces(dev)
+        ws = self._pipe.take_turn(need, cur, side)
+        _lib.check(lib.empose_lgd_forward_phase(handle, C.byref(io), _lib.dptr(ws), ws.numel(),
+                                                C.c_void_p(cur.cuda_stream), _PHASE_INIT))
+        side.wait_event(cur.record_event())
+        for t in touched:   # allocated for the current stream: not to be handed out again before `side` is done with it
+            t.record_stream(side)
+        _lib.check(lib.empose_lgd_forward_phase(handle, C.byref(io), _lib.dptr(ws), ws.numel(),
+                                                C.c_void_p(side.cuda_stream), _PHASE_ITER))
+        self.outputs_ready = self._pipe.free[self._pipe.turn] = side.record_event()   # (... and with the workspace)
 
     # ---- training path (BASELINE configs[4]) -------------------------------------------------------------------
     def residual_gradient(self, pose, shape, inputs_flat, offset_r, offset_t, frame_scale, F):

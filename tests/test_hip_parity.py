@@ -1090,6 +1090,67 @@ def test_batched_driver_with_a_host_metrics_model_takes_the_unplaced_path():
         np.testing.assert_allclose(sh[key], sd[key], rtol=1e-4, atol=1e-4, err_msg=key)
 
 
+@pytest.fixture(scope='module')
+def sequential_streaming_pass():
+    """(net, smpl, batches) of `_streaming_recordings` and what the sequential driver gives for them as it is used: the
+    metrics of all 1296 frames deferred to one flush after the last recording."""
+    from em_pose_amd.eval.helpers import evaluate_sequences
+    net, smpl, batches = _streaming_recordings()
+    me_all, per_seq, frames = evaluate_sequences(net, batches, smpl, torch.device(DEV))
+    assert frames == 1296
+    return net, smpl, batches, me_all.state(), per_seq
+
+
+def test_sequential_driver_flushing_inside_recordings_gives_the_same_bits(sequential_streaming_pass, monkeypatch):
+    """With a budget of 512 deferred frames the sequential driver flushes inside the second recording (556 frames: the
+    first recording and a chunk of the second), after the third (700 frames of two recordings) and at the end (40), not
+    once after the last recording.  The metrics kernel treats every row on its own and forward kinematics is per
+    frame, so the rows and the table are the same bits (asserted: `np.array_equal`, not the tolerance of
+    test_batched_streaming_equals_sequential)."""
+    from em_pose_amd.eval import helpers as EH
+    net, smpl, batches, want_state, want_seq = sequential_streaming_pass
+    flushes = []
+    flush = EH.MetricsEngine.compute
+    monkeypatch.setattr(EH.MetricsEngine, 'compute', lambda self, pose, *a, **kw: (flushes.append(pose.shape[1]),
+                                                                                   flush(self, pose, *a, **kw))[1])
+    monkeypatch.setattr(EH, 'DEFER_FRAME_BUDGET', 512)
+    me_all, per_seq, frames = EH.evaluate_sequences(net, batches, smpl, torch.device(DEV))
+    assert flushes == [556, 700, 40] and frames == 1296
+    got_state = me_all.state()
+    for key in want_state:
+        print(key, 'max abs difference', np.abs(got_state[key] - want_state[key]).max())
+        assert np.array_equal(got_state[key], want_state[key]), key
+    assert [i for i, _ in per_seq] == [i for i, _ in want_seq]
+    for (sid, got), (_, want) in zip(per_seq, want_seq):
+        print(sid, got, want)
+        assert np.array_equal(list(got.values()), list(want.values())), sid
+
+
+def test_sequential_driver_with_a_host_metrics_model_computes_per_chunk_beside_the_forward(sequential_streaming_pass):
+    """The body model of test_batched_driver_with_a_host_metrics_model_takes_the_unplaced_path in the sequential driver:
+    nothing is deferred, every chunk's metrics are computed (on the host) inside the side-stream context, and the table
+    is that of the device path."""
+    from em_pose_amd.eval.helpers import evaluate_sequences
+    from em_pose_amd.eval.metrics import MetricsEngine
+    net, smpl, batches, want_state, want_seq = sequential_streaming_pass
+
+    class HostFK(object):            # what compute's host path needs: fk() only
+        def __init__(self, inner):
+            self.fk = inner.fk
+
+    host = HostFK(smpl)
+    assert not MetricsEngine(host).queues_device_rows(DEV)
+    h_all, h_seq, h_frames = evaluate_sequences(net, batches, host, torch.device(DEV))
+    assert h_frames == 1296 and [i for i, _ in h_seq] == [i for i, _ in want_seq]
+    for (sid, mh), (_, md) in zip(h_seq, want_seq):
+        for k in md:
+            assert mh[k] == pytest.approx(md[k], rel=1e-5, abs=1e-4), (sid, k)
+    sh = h_all.state()
+    for key in want_state:
+        assert sh[key].shape == want_state[key].shape, key
+        np.testing.assert_allclose(sh[key], want_state[key], rtol=1e-4, atol=1e-4, err_msg=key)
+
+
 # ----------------------------------------------------------------------------------------------------------------------
 # configuration flags and edge shapes (reference configuration.py:171-185; models.py:372-380,424-454)
 # ----------------------------------------------------------------------------------------------------------------------
