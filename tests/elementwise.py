@@ -1,6 +1,7 @@
 """
 Per-element error allowances for the kernels that form fp32 products on the bf16 matrix cores (three bf16 pieces per
-operand, csrc/bf16x3.h), and the check that holds an output to them.
+operand, csrc/bf16x3.h) and for the fp32 GEMM family they are compared against (csrc/gemm_f32.hip, `gemm_reference`),
+and the check that holds an output to them.
 
 A global tolerance lets one wrong element hide below the worst honest rounding error of the whole output.  Here every
 output element gets its own allowance from a float64 MAGNITUDE `m` -- the same operation evaluated on absolute values --
@@ -47,6 +48,61 @@ def linear_allowance(a, w, b, gamma, e_a=None):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# The fp32 GEMM family (csrc/gemm_f32.hip, v_mfma_f32_32x32x2_f32): the contract of empose_linear_f32_ex
+#     C = act(scale (A W^T) + shift) (+ resid)
+# act 0: none; act 1: PReLU(slope), the residual added AFTER it (skip connection of an MLP block); act 2: the residual
+# added first, then ReLU (residual block).  One constant for the whole family, every kernel `launch_gemm` can pick, the
+# strided split-K kernel and A^T B; measured values in the docstring of tests/test_gemm_elementwise.py.
+GAMMA_GEMM = 8
+
+
+def gemm_products(a, w):
+    """(P, R) = (A W^T, sqrt(sum_k s_k^2)) in float64, s_k = sum_{j <= k} a_j w_j the partial sums of the k-ordered chain
+    of each element: what every epilogue form of one shape shares.  K rank-one updates, no (M, N, K) tensor."""
+    a, w = a.detach().double(), w.detach().double()
+    s = torch.zeros(a.shape[0], w.shape[0], dtype=torch.float64, device=a.device)
+    r2 = torch.zeros_like(s)
+    for k in range(a.shape[1]):
+        s.addr_(a[:, k], w[:, k])
+        r2.addcmul_(s, s)
+    return s, torch.sqrt(r2)
+
+
+def gemm_reference(a, w, scale=None, shift=None, resid=None, act=0, slope=0.0, gamma=GAMMA_GEMM, products=None):
+    """float64 result of the contract above and its per-element allowance
+        gamma u L |scale| R  +  3 u (L (|scale| |P| + |shift|) + |resid|),
+    P = A W^T, R = sqrt(sum_k s_k^2) over the partial sums s_k of the element's k-ordered chain (`gemm_products`),
+    L = max(1, |slope|) for the PReLU (an error that moves an element across the kink still moves the result by at most
+    L times itself), L = 1 otherwise (ReLU is 1-Lipschitz).
+
+    Accumulation, root-sum-square: an fp32 chain rounds every partial sum s_k by at most u |s_k|, independently, so the
+    roundings add like u sqrt(sum s_k^2) = u R.  Kernels that split K over waves or lanes (split-K, few-rows, A^T B's
+    row splits) restart their partial sums and stay below the single chain.  Two coarser forms were measured on the
+    MI355X first and do not fit under the family's cap of 8 with the factor 2 it keeps in hand: the worst case
+    u |scale| |A| |W|^T of the three-piece families above (honest kernels reach 6.8 at elements whose terms align, among
+    the 16 million of one case), and R averaged over the orders of k, sqrt(K (P^2 / 3 + Q / 6)) with Q = (A^2) (W^2)^T
+    (5.2: the partial sums of single elements wander far from that average).
+    Epilogue, worst case without gamma: the scale / shift, the slope product and the residual add round at most three
+    times, each by u times a value the second term bounds."""
+    p, r = gemm_products(a, w) if products is None else products
+    f = lambda t: None if t is None else t.detach().double().to(p.device)
+    scale, shift, resid = f(scale), f(shift), f(resid)
+    z, m, acc = p, p.abs(), r
+    if scale is not None:
+        z, m, acc = z * scale, m * scale.abs(), acc * scale.abs()
+    if shift is not None:
+        z, m = z + shift, m + shift.abs()
+    if act == 1:
+        lip = max(1.0, abs(float(slope)))
+        z, m, acc = torch.where(z >= 0, z, slope * z), lip * m, lip * acc
+    if resid is not None:
+        z, m = z + resid, m + resid.abs()
+    if act == 2:
+        z = torch.clamp(z, min=0.0)
+    return z, gamma * U * acc + 3.0 * U * m
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # Update MLPs: Linear - BatchNorm - PReLU blocks, then a Linear (oracle/torch_ref.py::mlp_forward)
 def eval_mlp_layers(sd, prefix, num_layers=2, eps=1e-5):
     """The dense layers of an eval-mode MLP in order: dicts of float64 weight, bias, BatchNorm (scale, mean, beta) or
@@ -72,14 +128,18 @@ def _prelu(y, slope):
     return torch.where(y >= 0, y, slope * y)
 
 
-def eval_mlp_reference(layers, x, gamma):
+def eval_mlp_reference(layers, x, gamma, skip=False):
     """float64 output of the eval-mode MLP and its per-element allowance.  Layer by layer, with h the float64 activation,
     z = W h + b and the BatchNorm magnitude  m = |s| (|W| |h| + |b| + |mean|) + |beta|:
         e_l = max(1, |slope|) (|s| P(e_{l-1}, W) + gamma u m_l) + gamma u |h_l|,
-    and for the output layer  e = P(e, W) + gamma u (|W| |h| + |b|), with P = `propagate`."""
+    and for the output layer  e = P(e, W) + gamma u (|W| |h| + |b|), with P = `propagate`.  `skip`: the input of every
+    hidden block (layer pairs (1, 2), (3, 4), ...) is added to its output, its allowance with it plus gamma u |sum|."""
     h = x.detach().double()
     e = torch.zeros_like(h)
-    for d in layers:
+    block_in = None
+    for l, d in enumerate(layers):
+        if skip and l % 2 == 1 and l < len(layers) - 1:
+            block_in = (h, e)
         w, b = d['w'].to(h.device), d['b'].to(h.device)
         z = h @ w.t() + b
         mag = linear_magnitude(h, w, b)
@@ -97,6 +157,9 @@ def eval_mlp_reference(layers, x, gamma):
         else:
             h_new = z
             e = prop + gamma * U * mag
+        if skip and l >= 2 and l % 2 == 0 and l < len(layers) - 1:
+            h_new = h_new + block_in[0]
+            e = e + block_in[1] + gamma * U * h_new.abs()
         h = h_new
     return h, e
 

@@ -99,7 +99,8 @@ def test_lstm_slice(capsys):
 
 
 def test_linear_and_mesh_slice(capsys):
-    """300 random linear layers (every GEMM tile regime, bias / PReLU / residual) vs float64; 40 full-mesh evaluations
+    """300 random linear layers (every GEMM tile regime incl. one shape of the 256 x 256 tile, scale / bias / PReLU /
+    residual before or after the activation, padded leading dimensions) vs float64; 40 full-mesh evaluations
     x (fp32, split-bf16) x both Rodrigues conventions vs the oracle."""
     from tests.fuzz import fuzz_linear_mesh as F
     r = F.run_linear(seed=4103, n_cases=300)
