@@ -19,6 +19,7 @@
 // Skip connections would need the block input kept besides the activations: such nets take the layer-by-layer path.
 #include "bf16x3.h"
 #include "gemm_epilogue.h"
+#include "stage_block.h"
 #include "feat_rows.h"
 
 namespace empose {
@@ -475,14 +476,7 @@ __global__ __launch_bounds__(fm::NT) void mlp_fused_kernel(FusedMlpArgs args) {
   {
     const int K0 = net.layer[0].K;
     const int kpad = (((K0 + 7) / 8 + 3) & ~3) * 8;   // multiple of 32
-    const int c4n = kpad / 4;                          // 16-byte pieces per row
-    for (int i = tid; i < BM * c4n; i += NT) {
-      const int r = i / c4n, c = (i % c4n) * 4;
-      const int row = m0 + r < M ? m0 + r : M - 1;     // rows past the end repeat the last one (never stored)
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (c < K0) v = *reinterpret_cast<const f32x4*>(net.x + (size_t)row * net.ldx + c);   // K0 % 4 == 0
-      *reinterpret_cast<f32x4*>(act + r * LDA + c) = v;
-    }
+    stage::rows<BM, NT>(net.x, net.ldx, m0, M, K0, kpad, act, LDA);   // rows past the end repeat the last one (never stored)
   }
   __syncthreads();
 
@@ -495,6 +489,12 @@ __global__ __launch_bounds__(fm::NT) void mlp_fused_kernel(FusedMlpArgs args) {
     else fused_layer_t<2, 4>(net, L, M, m0, act, LDA, 0, wave * 4, l, last);                            // 64 x 128 per wave
   }
 }
+
+// Chunks per thread that the single-layer kernels below keep in flight while they stage their A block (stage_block.h):
+// all 32 of the heads' 64 x 512 block and all 20 of the 320 x 64 tile.  Their fp32 instantiations run two workgroups per
+// CU, so registers + accumulators must stay within 256: the 128 staging registers are dead before the K loop starts, and
+// the compiler reports 136-142 registers + 32-80 accumulators for them (blend_t_gemm_rod_kernel<4> had 142 before).
+constexpr int ROWS_BATCH = stage::MAX_BATCH;
 
 // A single linear layer with the same machinery, for contractions whose K fits the LDS with the row block
 // (the SMPL blend-shape GEMMs, K = 200 / 320): the A block [BM][K] is staged once, the weights stream from L2 in
@@ -509,27 +509,7 @@ __global__ __launch_bounds__(fm::NT) void gemm_rows_kernel(FusedMlpArgs args) {
   const int K0 = L.K;
   const RowsLds lay = rows_lds(K0, BM_, false);
   const int kpad = lay.kpad, lda = lay.lda;
-  {
-    const int c4n = kpad / 4;
-    for (int i0 = tid; i0 < BM_ * c4n; i0 += 4 * fm::NT) {   // four 16-byte pieces per thread in flight
-      f32x4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int i = i0 + u * fm::NT;
-        v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (i < BM_ * c4n) {
-          const int r = i / c4n, c = (i % c4n) * 4;
-          const int row = m0 + r < M ? m0 + r : M - 1;
-          if (c < K0) v[u] = *reinterpret_cast<const f32x4*>(net.x + (size_t)row * net.ldx + c);
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int i = i0 + u * fm::NT;
-        if (i < BM_ * c4n) *reinterpret_cast<f32x4*>(act + (i / c4n) * lda + (i % c4n) * 4) = v[u];
-      }
-    }
-  }
+  stage::rows<BM_, fm::NT, ROWS_BATCH>(net.x, net.ldx, m0, M, K0, kpad, act, lda);
   __syncthreads();
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   fused_layer_t<WM, WN>(net, L, M, m0, act, lda, (wave / WCOLS) * WM, (wave % WCOLS) * WN, 0, true);
@@ -571,45 +551,11 @@ namespace rt {
 // A_t[tile][k][64] -> act[k][64] as it lies (fused_layer_t's K-major operand): 16-byte pieces, no transposition; the
 // columns [K0, kpad) are zero
 __device__ __forceinline__ void stage_a_tile(const float* x_t, int ldx, int tile, int K0, int kpad, float* act) {
-  const int tid = threadIdx.x;
-  const f32x4* src = reinterpret_cast<const f32x4*>(x_t + (size_t)tile * ldx * 64);
-  for (int i0 = tid; i0 < kpad * 16; i0 += 4 * fm::NT) {
-    f32x4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + u * fm::NT;
-      v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (i < kpad * 16 && (i >> 4) < K0) v[u] = src[i];
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + u * fm::NT;
-      if (i < kpad * 16) reinterpret_cast<f32x4*>(act)[i] = v[u];
-    }
-  }
+  stage::tile<fm::NT, ROWS_BATCH>(x_t, ldx, tile, K0, kpad, act);
 }
 // row-major A[M][ldx] -> act[64][lda] (rows past the end repeat the last one; never stored)
 __device__ __forceinline__ void stage_a_rows(const float* x, int ldx, int m0, int M, int K0, int kpad, int lda, float* act) {
-  const int tid = threadIdx.x;
-  const int c4n = kpad / 4;
-  for (int i0 = tid; i0 < 64 * c4n; i0 += 4 * fm::NT) {
-    f32x4 v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + u * fm::NT;
-      v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (i < 64 * c4n) {
-        const int r = i / c4n, c = (i % c4n) * 4;
-        const int row = m0 + r < M ? m0 + r : M - 1;
-        if (c < K0) v[u] = *reinterpret_cast<const f32x4*>(x + (size_t)row * ldx + c);
-      }
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + u * fm::NT;
-      if (i < 64 * c4n) *reinterpret_cast<f32x4*>(act + (i / c4n) * lda + (i % c4n) * 4) = v[u];
-    }
-  }
+  stage::rows<64, fm::NT, ROWS_BATCH>(x, ldx, m0, M, K0, kpad, act, lda);
 }
 // C^T in LDS ([column][64], rows rotated by the column; fused_layer_t<.., OUT_T>) out as 16-byte pieces of whole columns
 __device__ __forceinline__ void store_ct(const float* act, int N, float* out_t, int ld_out, int tile) {

@@ -26,6 +26,7 @@
 //     (scripts/dev/bf16_hazard_repro.md).
 #include "bf16x3.h"
 #include "gemm_epilogue.h"
+#include "stage_block.h"
 
 namespace empose {
 
@@ -638,15 +639,7 @@ __global__ __launch_bounds__(fx::NT) void mlp_fused_x3c_kernel(FusedMlpArgs args
   const int tid = threadIdx.x;
   {
     const int K0 = net.layer[0].K;
-    const int kpad = (K0 + 63) / 64 * 64;
-    const int c4n = kpad / 4;
-    for (int i = tid; i < BM * c4n; i += NT) {
-      const int r = i / c4n, c = (i % c4n) * 4;
-      const int row = m0 + r < M ? m0 + r : M - 1;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (c < K0) v = *reinterpret_cast<const f32x4*>(net.x + (size_t)row * net.ldx + c);
-      *reinterpret_cast<f32x4*>(act + r * LDA + c) = v;
-    }
+    stage::rows<BM, NT>(net.x, net.ldx, m0, M, K0, (K0 + 63) / 64 * 64, act, LDA);
   }
   __syncthreads();
   for (int l = 0; l < net.n_layers; ++l) {
@@ -671,16 +664,9 @@ __global__ __launch_bounds__(fx::NT) void mlp_fused_x3_kernel(FusedMlpArgs args)
   const int M = args.M, m0 = blockIdx.x * BM;
   const int tid = threadIdx.x;
   {
-    const int K0 = net.layer[0].K;
+    const int K0 = net.layer[0].K;          // K0 % 4 == 0
     const int kpad = (K0 + 63) / 64 * 64;   // whole quads of k-steps of 16 = whole pairs of k-steps of 32
-    const int c4n = kpad / 4;
-    for (int i = tid; i < BM * c4n; i += NT) {
-      const int r = i / c4n, c = (i % c4n) * 4;
-      const int row = m0 + r < M ? m0 + r : M - 1;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (c < K0) v = *reinterpret_cast<const f32x4*>(net.x + (size_t)row * net.ldx + c);   // K0 % 4 == 0
-      *reinterpret_cast<f32x4*>(act + r * LDA + c) = v;
-    }
+    stage::rows<BM, NT>(net.x, net.ldx, m0, M, K0, kpad, act, LDA);   // all of a thread's loads in flight (stage_block.h)
   }
   __syncthreads();
   for (int l = 0; l < net.n_layers; ++l) {
