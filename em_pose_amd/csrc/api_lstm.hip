@@ -362,7 +362,7 @@ TrainLstmWs carve_train_lstm(Carver& c, const empose_lstm_params* p, int B, int 
   w.lo.wt = c.f((size_t)in_max * 4 * H);
   w.atb_floats = atb_workspace_floats_max(B * F, {{4 * H, p->input_size}, {4 * H, H}});   // dW_ih (layer 0 / above), dW_hh
   w.atb = c.f(w.atb_floats + 64);
-  const size_t ksplit_floats = gemm_ksplit_applicable(B, H, 4 * H) ? gemm_ksplit_workspace_floats(B, H, 4 * H) : 0;
+  const size_t ksplit_floats = rec_ksplit_applicable(B, H, 4 * H) ? rec_ksplit_workspace_floats(B, H, 4 * H, 1) : 0;
   w.ksplit = ksplit_floats ? c.f(ksplit_floats) : nullptr;
   if (L == 2 && options().bptt_wave != 0 && (4 * H) % 256 == 0) {
     if (gemm_fewrows_applicable(B, H, 4 * H) && 4 * H <= 2048) w.wave = 1;
@@ -388,6 +388,15 @@ hipError_t gemm(const GemmProb& g, hipStream_t stream) {
   GemmBatch b;
   b.count = 1; b.p[0] = g;
   return launch_gemm(b, stream);
+}
+// a plain product + residual whose result feeds a cell: one unit of one K segment (C is not written)
+RecBatch rec_batch_of(const GemmProb& g) {
+  RecBatch rb;
+  rb.count = 1;
+  RecProb& q = rb.p[0];
+  q.nseg = 1; q.seg[0] = RecSeg{g.A, g.lda, g.W, g.ldw, g.K};
+  q.M = g.M; q.N = g.N; q.resid = g.resid; q.ldr = g.ldr;
+  return rb;
 }
 
 // Back-propagation through time: the arguments of empose_lstm_train_bwd, the pieces both forms share, the two recurrences.
@@ -494,11 +503,11 @@ struct Bptt {
         if (t == 0) break;
         float* out = w.dh[t & 1];
         const GemmProb g = rec_prob(b, t, out);
-        // a few hundred rows: K split over the workgroups (gemm_ksplit_kernel), whose reduce kernel feeds dh straight into
+        // a few hundred rows: K split over the workgroups (rec_ksplit_kernel), whose reduce kernel feeds dh straight into
         // the cell of step t - 1; the reference's batch: matrix-vector kernel, same fusion; else the GEMM and the cell
         cell_done = w.ksplit || fewrows;
         const LstmCellBwdArgs next = cell_bwd_args(l, t - 1, b, dy_l, nullptr);
-        const hipError_t e = w.ksplit ? launch_gemm_ksplit(g, w.ksplit, stream, &next)
+        const hipError_t e = w.ksplit ? launch_rec_ksplit(rec_batch_of(g), &next, w.ksplit, stream)
                              : fewrows ? launch_gemm_fewrows_cell(g, next, stream) : gemm(g, stream);
         if (e != hipSuccess) return fail(EMPOSE_EHIP, "recurrent backward gemm: %s", hipGetErrorString(e));
         dh_in = out;

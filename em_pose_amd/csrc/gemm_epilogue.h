@@ -1,5 +1,5 @@
-// Shared by the fp32 matrix-core GEMM kernels (gemm_f32.hip, mlp_fused.hip): accumulator vector types and the tile
-// epilogue. Internal, gfx950 only.
+// Shared by the fp32 matrix-core GEMM kernels (gemm_f32.hip, gemm_rec.hip, gemm_train_x3.hip, mlp_fused.hip):
+// accumulator vector types, the tile epilogue and its one-element form. Internal, gfx950 only.
 #pragma once
 #include "kernels.h"
 
@@ -76,6 +76,25 @@ __device__ __forceinline__ void epilogue(const GemmProb& p, const f32x16 (&acc)[
   else if (resid) { if (full) EMPOSE_EPI(1, true); else EMPOSE_EPI(1, false); }
   else { if (full) EMPOSE_EPI(0, true); else EMPOSE_EPI(0, false); }
 #undef EMPOSE_EPI
+}
+
+// The same arithmetic for ONE element (row, n) of a kernel that does not hold 32x32 accumulator tiles per wave (the
+// split-K tile, the matrix-vector kernel): returns act(v * sc + sh) with the residual rules of epilogue_mode; the caller
+// stores it.  sc / sh / slope are column n's constants (slope == 1 without an activation), for a caller that hoists them
+// out of its row loop; the second form fetches them.
+__device__ __forceinline__ float epilogue_elem(const GemmProb& p, int row, int n, float v, float sc, float sh, float slope) {
+  float y = v * sc + sh;
+  if (p.act == 2) {          // relu(W x + b + x), reference layers.py:170-182
+    if (p.resid) y += p.resid[(size_t)row * p.ldr + n];
+    y = y > 0.f ? y : 0.f;
+  } else {
+    y = y >= 0.f ? y : slope * y;
+    if (p.resid) y += p.resid[(size_t)row * p.ldr + n];   // skip connection (after the activation)
+  }
+  return y;
+}
+__device__ __forceinline__ float epilogue_elem(const GemmProb& p, int row, int n, float v) {
+  return epilogue_elem(p, row, n, v, p.scale ? p.scale[n] : 1.f, p.shift ? p.shift[n] : 0.f, p.act == 1 ? p.slope : 1.f);
 }
 
 }  // namespace empose

@@ -10,20 +10,18 @@
 //
 // Tile: 256 threads = 2x2 waves, each wave WM x WN tiles of 32x32 -> block tile (64*WM) x (64*WN), BK = 32.
 // LDS rows are padded to 36 floats: 16 lanes of a ds_read_b128 group then hit 16 distinct 16-byte slots.
+//
+// Besides the tile kernels: the split-K tile for small problems (and its strided form), the matrix-vector kernel for a
+// handful of rows, and the dispatch between them (pick_gemm).  The recurrent products of back-propagation through time
+// are in gemm_rec.hip, the three-piece bf16 training product in gemm_train_x3.hip.
 #include "kernels.h"
 #include <cstdint>
 
-#include "bf16x3.h"
-
-#include "gemm_epilogue.h"
+#include "device_common.h"
 #include "lstm_cell_bwd.h"
-#include "lane_reduce.h"
-
-#include <cstdlib>
-#include <type_traits>
+#include "train_epilogue.h"
 
 namespace empose {
-
 
 // Tile configuration: WR x WC waves per block, each wave WM x WN tiles of 32x32, K tile BK, DB = LDS double buffering
 // (one barrier per K tile instead of two).
@@ -91,147 +89,9 @@ __device__ __forceinline__ void transform_tile(const float4 s, const float4 t, f
   }
 }
 
-// Train-mode epilogues of a wave's WM x WN grid of 32 x 32 tiles (C/D layout: col = lane & 31, row = (r & 3) +
-// 8 (r >> 2) + 4 (lane >> 5)).  Forward: C = acc + shift, and per 32-row block and column the sum and the centred sum of
-// squares -> stat_part [M / 32][2][N].  Backward (e_y set): the product is dA; C = dyh = dA * PReLU'(e_s y + e_t) and
-// stat_part [M / 32][3][N] = sums of dyh, dyh (y - mean) rstd, (yhat <= 0) dA yhat.
-// Addressing as in gemm_epilogue.h: a wave-uniform base plus a 32-bit per-lane byte offset, row bounds resolved outside
-// the loops (FULL) -- the straightforward form of this epilogue cost 15-20 us per 8192 x 512 launch.
-template <int WM, int WN, bool FULL, bool BWD, bool CFULL>   // FULL / CFULL: no row / column of the wave's block is outside the matrix
-__device__ __forceinline__ void train_epilogue_mode(float* __restrict__ C, float* __restrict__ part,
-                                                    const float* __restrict__ shift, const float* __restrict__ ey,
-                                                    const float* __restrict__ e_s, const float* __restrict__ e_t,
-                                                    const float* __restrict__ e_mean, const float* __restrict__ e_rstd,
-                                                    float slope, int M, int N, long ldc, long ldy,
-                                                    const f32x16 (&acc)[WM][WN], int mw0, int nw0, int l31, int lh) {
-  epi_gbyte_t cb = (epi_gbyte_t)(C + (long)mw0 * ldc);
-  epi_cgbyte_t yb = BWD ? (epi_cgbyte_t)(ey + (long)mw0 * ldy) : nullptr;
-  const unsigned ldc4 = (unsigned)ldc * 4u, ldy4 = (unsigned)ldy * 4u;
-  // Every load of the epilogue -- the per-column constants and, reverse, the wave's whole block of y -- is issued before
-  // the first store: loads and stores share one counter here (vmcnt), so a load that follows a tile's stores makes the
-  // wave wait for those stores to drain -- one memory round trip per tile column (measured: the statistics epilogue cost
-  // 10 us per 8192 x 512 x 512 launch that way).
-  float sh[WN], es[WN], et[WN], mu[WN], rs[WN];
-  bool col_ok[WN];
-#pragma unroll
-  for (int j = 0; j < WN; ++j) {
-    const int n = nw0 + j * 32 + l31;
-    col_ok[j] = CFULL || n < N;
-    const int nc = col_ok[j] ? n : N - 1;
-    sh[j] = (!BWD && shift) ? shift[nc] : 0.f;
-    es[j] = BWD ? e_s[nc] : 0.f; et[j] = BWD ? e_t[nc] : 0.f; mu[j] = BWD ? e_mean[nc] : 0.f; rs[j] = BWD ? e_rstd[nc] : 0.f;
-  }
-  float yv[BWD ? WM : 1][BWD ? WN : 1][16];
-  if (BWD) {
-#pragma unroll
-    for (int j = 0; j < WN; ++j) {
-      const int n = nw0 + j * 32 + l31;
-      const unsigned y_lane = (unsigned)(4 * lh) * ldy4 + (unsigned)(col_ok[j] ? n : N - 1) * 4u;
-#pragma unroll
-      for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int dm = i * 32 + (r & 3) + 8 * (r >> 2);
-          yv[BWD ? i : 0][BWD ? j : 0][r] =
-              (FULL || mw0 + 4 * lh + dm < M) ? *(epi_cgfloat_t)(yb + (y_lane + (unsigned)dm * ldy4)) : 0.f;
-        }
-    }
-  }
-  float ps[WM][WN][3];   // the partial sums: stored after the block's last row (a store under a branch in between makes
-                         // the next tile column wait for everything issued so far)
-#pragma unroll
-  for (int j = 0; j < WN; ++j) {
-    const int n = nw0 + j * 32 + l31;
-    if (!CFULL && !col_ok[j]) continue;
-    const unsigned c_lane = (unsigned)(4 * lh) * ldc4 + (unsigned)n * 4u;
-#pragma unroll
-    for (int i = 0; i < WM; ++i) {
-      const int mb = mw0 + i * 32;
-      const int rows_valid = FULL ? 32 : min(32, M - mb);
-      if (!FULL && rows_valid <= 0) continue;
-      if (!BWD) {
-        float s1 = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int dm = i * 32 + (r & 3) + 8 * (r >> 2);
-          if (!FULL && mw0 + 4 * lh + dm >= M) continue;
-          const float y = acc[i][j][r] + sh[j];
-          *(epi_gfloat_t)(cb + (c_lane + (unsigned)dm * ldc4)) = y;
-          s1 += y;
-        }
-        // the block's sum and centred sum of squares (the two halves of the wave hold 16 rows each)
-        s1 += __shfl_xor(s1, 32, 64);
-        const float shift_mean = sh[j] - s1 * (1.f / (float)rows_valid);   // y - mean = acc + (sh - mean)
-        float s2 = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int dm = i * 32 + (r & 3) + 8 * (r >> 2);
-          const float d = acc[i][j][r] + shift_mean;
-          if (FULL || mw0 + 4 * lh + dm < M) s2 += d * d;
-        }
-        s2 += __shfl_xor(s2, 32, 64);
-        ps[i][j][0] = s1; ps[i][j][1] = s2; ps[i][j][2] = 0.f;
-      } else {
-        float sb = 0.f, sg = 0.f, sa = 0.f;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int dm = i * 32 + (r & 3) + 8 * (r >> 2);
-          if (!FULL && mw0 + 4 * lh + dm >= M) continue;
-          const float y = yv[BWD ? i : 0][BWD ? j : 0][r];
-          const float yh = es[j] * y + et[j];
-          const float dA = acc[i][j][r];
-          const float dyh = yh > 0.f ? dA : slope * dA;
-          *(epi_gfloat_t)(cb + (c_lane + (unsigned)dm * ldc4)) = dyh;
-          sb += dyh;
-          sg += dyh * ((y - mu[j]) * rs[j]);
-          sa += yh > 0.f ? 0.f : dA * yh;
-        }
-        sb += __shfl_xor(sb, 32, 64);
-        sg += __shfl_xor(sg, 32, 64);
-        sa += __shfl_xor(sa, 32, 64);
-        ps[i][j][0] = sb; ps[i][j][1] = sg; ps[i][j][2] = sa;
-      }
-    }
-  }
-  if (lh == 0 && part) {
-#pragma unroll
-    for (int j = 0; j < WN; ++j) {
-      const int n = nw0 + j * 32 + l31;
-      if (!CFULL && !col_ok[j]) continue;
-#pragma unroll
-      for (int i = 0; i < WM; ++i) {
-        const int mb = mw0 + i * 32;
-        if (!FULL && mb >= M) continue;
-        float* pp = part + (size_t)(mb >> 5) * (BWD ? 3 : 2) * N;
-        pp[n] = ps[i][j][0];
-        pp[N + n] = ps[i][j][1];
-        if (BWD) pp[2 * N + n] = ps[i][j][2];
-      }
-    }
-  }
-}
-
-template <int WM, int WN, bool BWD>   // BWD: the reverse epilogue (ROLE 3), else the forward one (ROLE 2)
-__device__ __forceinline__ void train_epilogue(const GemmProb& p, const f32x16 (&acc)[WM][WN], int mw0, int nw0, int l31,
-                                               int lh) {
-  float* C = p.C; float* part = p.stat_part;
-  const float* shift = p.shift; const float* ey = p.e_y;
-  const float* e_s = p.e_s; const float* e_t = p.e_t; const float* e_mean = p.e_mean; const float* e_rstd = p.e_rstd;
-  const long ldc = p.ldc, ldy = p.ld_ey;
-  const int M = p.M, N = p.N;
-  const float slope = BWD ? p.e_slope[0] : 0.f;
-  mw0 = __builtin_amdgcn_readfirstlane(mw0);
-  nw0 = __builtin_amdgcn_readfirstlane(nw0);
-  const bool full = mw0 + 32 * WM <= M, cfull = nw0 + 32 * WN <= N;
-#define EMPOSE_TEPI(FULL, BWD, CFULL) \
-  train_epilogue_mode<WM, WN, FULL, BWD, CFULL>(C, part, shift, ey, e_s, e_t, e_mean, e_rstd, slope, M, N, ldc, ldy, acc, mw0, nw0, l31, lh)
-  if (full && cfull) EMPOSE_TEPI(true, BWD, true); else if (full) EMPOSE_TEPI(true, BWD, false); else EMPOSE_TEPI(false, BWD, false);
-#undef EMPOSE_TEPI
-}
-
 // ROLE only separates instantiations by name so that profilers report the update-net hidden layers (ROLE 1) apart
-// from the other users of the same tile configuration; ROLE 2 / 3 add the train-mode fusion above (forward: optional
-// A-operand transform + statistics epilogue; reverse: the dyh epilogue).
+// from the other users of the same tile configuration; ROLE 2 / 3 add the train-mode fusion (forward: optional
+// A-operand transform above + the statistics epilogue of train_epilogue.h; reverse: its dyh epilogue).
 template <typename C, int ROLE>
 __global__ __launch_bounds__(C::NT) void gemm_tn_f32_kernel(GemmBatch batch) {
   constexpr int BM = C::BM, BN = C::BN, BK = C::BK, LDT = C::LDT, WM = C::WM, WN = C::WN;
@@ -552,6 +412,20 @@ static hipError_t launch_large(const GemmBatch& batch, hipStream_t stream) {
   return launch_cfg<CfgX, ROLE>(batch, stream);
 }
 
+// The largest M / N / K and the smallest K of a batch's problems: what the dispatch and the small-problem launchers size by.
+struct BatchExtent { int maxM = 0, maxN = 0, minK = 1 << 30, maxK = 0; };
+static BatchExtent batch_extent(const GemmBatch& batch) {
+  BatchExtent x;
+  for (int i = 0; i < batch.count; ++i) {
+    const GemmProb& p = batch.p[i];
+    x.maxM = p.M > x.maxM ? p.M : x.maxM;
+    x.maxN = p.N > x.maxN ? p.N : x.maxN;
+    x.minK = p.K < x.minK ? p.K : x.minK;
+    x.maxK = p.K > x.maxK ? p.K : x.maxK;
+  }
+  return x;
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // Small problems (a few hundred rows: the streaming driver's 256-frame chunks, single windows): with the tiles above a
 // layer is a few dozen workgroups that each walk the whole K behind LDS staging and barriers -- 19 us for
@@ -609,15 +483,7 @@ __global__ __launch_bounds__(NW * 64) void gemm_splitk_f32_kernel(GemmBatch batc
     float v = red[(0 * 16 + r) * 64 + lane];
 #pragma unroll
     for (int w2 = 1; w2 < NW; ++w2) v += red[(w2 * 16 + r) * 64 + lane];
-    float y = v * sc + sh;
-    if (p.act == 2) {          // relu(W x + b + x), reference layers.py:170-182
-      if (p.resid) y += p.resid[(size_t)row * p.ldr + n];
-      y = y > 0.f ? y : 0.f;
-    } else {
-      y = y >= 0.f ? y : slope * y;
-      if (p.resid) y += p.resid[(size_t)row * p.ldr + n];   // skip connection (after the activation)
-    }
-    p.C[(size_t)row * p.ldc + n] = y;
+    p.C[(size_t)row * p.ldc + n] = epilogue_elem(p, row, n, v, sc, sh, slope);
   }
 }
 
@@ -628,10 +494,8 @@ static hipError_t launch_splitk(const GemmBatch& batch, hipStream_t stream) {
     blocks = t > blocks ? t : blocks;
   }
   if (blocks == 0) return hipSuccess;
-  int minK = 1 << 30;
-  for (int i = 0; i < batch.count; ++i) minK = batch.p[i].K < minK ? batch.p[i].K : minK;
   // a long K on few tiles (the recurrent products of back-propagation through time at a few hundred rows): eight waves
-  if (minK >= 1024 && (long)blocks * batch.count <= 256)
+  if (batch_extent(batch).minK >= 1024 && (long)blocks * batch.count <= 256)
     hipLaunchKernelGGL(gemm_splitk_f32_kernel<8>, dim3(blocks, batch.count), dim3(512), 0, stream, batch);
   else
     hipLaunchKernelGGL(gemm_splitk_f32_kernel<4>, dim3(blocks, batch.count), dim3(256), 0, stream, batch);
@@ -722,123 +586,6 @@ hipError_t launch_strided_gemm(const StridedGemm& p, hipStream_t stream) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// A few hundred rows against a long K with a small output (back-propagation through time at 256 windows: dh = dG . W_hh
-// is 256 x 2048 . 2048 x 512, sixty-two times per step): 32 x 32 tiles that each walk the whole K leave it at 22 us per
-// call (128 workgroups, strided 16-byte operand reads).  Here K is split over the workgroups: a workgroup owns a
-// 64 x 64 output tile for a K slice of 256, stages both operand slices in LDS with coalesced row reads in one round
-// trip, runs 128 MFMAs per wave (four waves, a 32 x 32 quadrant each) without a barrier, and writes its partial tile;
-// a small second kernel adds the partial tiles in slice order (fixed order: reproducible) and applies the epilogue.
-// 32 tiles x 8 slices = 256 workgroups.
-// ---------------------------------------------------------------------------------------------------------------
-constexpr int FEWROWS_MAX_M = 16;   // rows of the matrix-vector kernel further down; more rows can take the K-split kernel
-namespace ks {
-constexpr int BT = 64, KS = 256, LDK = KS + 4;   // tile, K slice per workgroup, LDS row stride (floats)
-constexpr size_t LDS_BYTES = (size_t)2 * BT * LDK * sizeof(float);
-}
-__global__ __launch_bounds__(256) void gemm_ksplit_kernel(GemmProb p, float* partial) {
-  using namespace ks;
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* sA = sm;
-  float* sW = sm + BT * LDK;
-  const int M = p.M, N = p.N, K = p.K;
-  const int nt_n = (N + BT - 1) / BT;
-  const int tile = blockIdx.x, m0 = (tile / nt_n) * BT, n0 = (tile % nt_n) * BT;
-  const int k0 = blockIdx.y * KS;
-  const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  // staging: 64 rows x 256 floats of each operand = 2 x 4096 16-byte pieces over 256 threads, all in flight at once
-  {
-    f32x4 va[16], vw[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int i = tid + u * 256, r = i >> 6, c = (i & 63) * 4;
-      const bool kin = k0 + c < K;   // K % 4 == 0
-      va[u] = kin ? *reinterpret_cast<const f32x4*>(p.A + (size_t)min(m0 + r, M - 1) * p.lda + k0 + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-      vw[u] = kin ? *reinterpret_cast<const f32x4*>(p.W + (size_t)min(n0 + r, N - 1) * p.ldw + k0 + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int i = tid + u * 256, r = i >> 6, c = (i & 63) * 4;
-      *reinterpret_cast<f32x4*>(sA + r * LDK + c) = va[u];
-      *reinterpret_cast<f32x4*>(sW + r * LDK + c) = vw[u];
-    }
-  }
-  __syncthreads();
-  const int mq = (wave >> 1) * 32, nq = (wave & 1) * 32;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  const float* ar = sA + (mq + l31) * LDK + lh * 4;
-  const float* wr = sW + (nq + l31) * LDK + lh * 4;
-#pragma unroll 8
-  for (int g = 0; g < KS / 8; ++g) {   // k-groups of 8: lane half lh holds k = 8 g + 4 lh .. + 3 of both operands
-    const f32x4 fa = *reinterpret_cast<const f32x4*>(ar + g * 8);
-    const f32x4 fb = *reinterpret_cast<const f32x4*>(wr + g * 8);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb[e], acc, 0, 0, 0);
-  }
-  // partial tile of this slice: [slice][tile][wave][reg][lane]; a second kernel adds the slices in order (a last-arriver
-  // reduction inside this kernel was measured: the agent-scope fences it needs write back and invalidate the whole L2
-  // of every workgroup's XCD -- 60 us per call instead of 22)
-  float* pt = partial + (((size_t)blockIdx.y * gridDim.x + tile) * 4 + wave) * 1024;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) pt[r * 64 + lane] = acc[r];
-}
-
-// C = epilogue(sum over the K slices, in slice order): one thread per output element, its S partial values requested
-// together (one round trip) and added in slice order
-constexpr int KSPLIT_MAX_S = 16;
-__global__ __launch_bounds__(256) void gemm_ksplit_reduce_kernel(GemmProb p, const float* partial, int S, int tiles,
-                                                                 LstmCellBwdArgs cell, int with_cell) {
-  using namespace ks;
-  const int M = p.M, N = p.N;
-  const int nt_n = (N + BT - 1) / BT;
-  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;   // position inside one slice's partial buffer
-  if (idx >= (size_t)tiles * 4096) return;
-  float ps[KSPLIT_MAX_S];
-#pragma unroll
-  for (int s2 = 0; s2 < KSPLIT_MAX_S; ++s2) ps[s2] = s2 < S ? partial[(size_t)s2 * tiles * 4096 + idx] : 0.f;
-  float v = 0.f;
-#pragma unroll
-  for (int s2 = 0; s2 < KSPLIT_MAX_S; ++s2) v += ps[s2];   // (slices past S add 0: the same bits as stopping at S)
-  const int tile = (int)(idx >> 12), wave = (int)(idx >> 10) & 3, r = (int)(idx >> 6) & 15, lane = (int)idx & 63;
-  const int m0 = (tile / nt_n) * BT, n0 = (tile % nt_n) * BT;
-  const int mq = (wave >> 1) * 32, nq = (wave & 1) * 32, l31 = lane & 31, lh = lane >> 5;
-  const int row = m0 + mq + (r & 3) + 8 * (r >> 2) + 4 * lh, n = n0 + nq + l31;
-  if (row >= M || n >= N) return;
-  float y = v * (p.scale ? p.scale[n] : 1.f) + (p.shift ? p.shift[n] : 0.f);
-  if (p.act == 2) {
-    if (p.resid) y += p.resid[(size_t)row * p.ldr + n];
-    y = y > 0.f ? y : 0.f;
-  } else {
-    if (p.act == 1) y = y >= 0.f ? y : p.slope * y;
-    if (p.resid) y += p.resid[(size_t)row * p.ldr + n];
-  }
-  // back-propagation through time: y is dh of (row, unit n) for the step below; run that step's cell right here
-  if (with_cell) lstm_cell_bwd_elem(cell, row * cell.H + n, y);
-  else p.C[(size_t)row * p.ldc + n] = y;
-}
-
-bool gemm_ksplit_applicable(int M, int N, int K) {
-  const long tiles = (long)((M + ks::BT - 1) / ks::BT) * ((N + ks::BT - 1) / ks::BT);
-  const int S = (K + ks::KS - 1) / ks::KS;
-  return K % 4 == 0 && M > FEWROWS_MAX_M && S >= 4 && S <= KSPLIT_MAX_S && tiles * S >= 32 && tiles * S <= 1024;
-}
-size_t gemm_ksplit_workspace_floats(int M, int N, int K) {
-  const size_t tiles = (size_t)((M + ks::BT - 1) / ks::BT) * ((N + ks::BT - 1) / ks::BT);
-  const size_t S = (K + ks::KS - 1) / ks::KS;
-  return tiles * S * 4096 + 64;   // partial tiles
-}
-hipError_t launch_gemm_ksplit(const GemmProb& p, float* workspace, hipStream_t stream, const LstmCellBwdArgs* cell) {
-  const int tiles = ((p.M + ks::BT - 1) / ks::BT) * ((p.N + ks::BT - 1) / ks::BT);
-  const int S = (p.K + ks::KS - 1) / ks::KS;
-  if (hipError_t e = launch_lds(gemm_ksplit_kernel, dim3(tiles, S), dim3(256), ks::LDS_BYTES, stream, p, workspace)) return e;
-  hipLaunchKernelGGL(gemm_ksplit_reduce_kernel, dim3(tiles * 16), dim3(256), 0, stream, p, (const float*)workspace, S, tiles,
-                     cell ? *cell : LstmCellBwdArgs{}, cell ? 1 : 0);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------------------
 // A handful of rows against a long K (back-propagation through time at the reference's training batch: dh = dG . W_hh
 // is 12 x 2048 . 2048 x 512, sixty-four times per step): a matrix-vector problem bound by streaming W once.  The 32 x 32
 // split-K tile leaves it on 16 workgroups that each walk 256 KB (19.9 us per call); here a wave owns ONE output column,
@@ -921,14 +668,7 @@ __global__ __launch_bounds__(256) void gemm_fewrows_kernel(GemmBatch b, LstmCell
     if (lane == m) out = v;
   }
   if (lane < M) {
-    float y = out * (p.scale ? p.scale[n] : 1.f) + (p.shift ? p.shift[n] : 0.f);
-    if (p.act == 2) {
-      if (p.resid) y += p.resid[(size_t)lane * p.ldr + n];
-      y = y > 0.f ? y : 0.f;
-    } else {
-      if (p.act == 1) y = y >= 0.f ? y : p.slope * y;
-      if (p.resid) y += p.resid[(size_t)lane * p.ldr + n];
-    }
+    const float y = epilogue_elem(p, lane, n, out);
     // back-propagation through time: y is dh of (row, unit n) for the step below; run that step's cell right here
     if (with_cell) lstm_cell_bwd_elem(cell, lane * cell.H + n, y);
     else p.C[(size_t)lane * p.ldc + n] = y;
@@ -946,23 +686,26 @@ static hipError_t launch_fewrows_cfg(const GemmBatch& batch, int maxN, int maxK,
 }
 
 static hipError_t launch_fewrows(const GemmBatch& batch, hipStream_t stream, const LstmCellBwdArgs* cell = nullptr) {
-  int maxN = 0, maxM = 0, maxK = 0;
-  for (int i = 0; i < batch.count; ++i) {
-    maxN = batch.p[i].N > maxN ? batch.p[i].N : maxN;
-    maxM = batch.p[i].M > maxM ? batch.p[i].M : maxM;
-    maxK = batch.p[i].K > maxK ? batch.p[i].K : maxK;
-  }
-  if (maxM <= 4) return launch_fewrows_cfg<4>(batch, maxN, maxK, stream, cell);
-  if (maxM <= 8) return launch_fewrows_cfg<8>(batch, maxN, maxK, stream, cell);
-  if (maxM <= 12) return launch_fewrows_cfg<12>(batch, maxN, maxK, stream, cell);
-  return launch_fewrows_cfg<16>(batch, maxN, maxK, stream, cell);
+  const BatchExtent x = batch_extent(batch);
+  if (x.maxM <= 4) return launch_fewrows_cfg<4>(batch, x.maxN, x.maxK, stream, cell);
+  if (x.maxM <= 8) return launch_fewrows_cfg<8>(batch, x.maxN, x.maxK, stream, cell);
+  if (x.maxM <= 12) return launch_fewrows_cfg<12>(batch, x.maxN, x.maxK, stream, cell);
+  return launch_fewrows_cfg<16>(batch, x.maxN, x.maxK, stream, cell);
+}
+
+// The matrix-vector shape: at most FEWROWS_MAX_M rows, every K long enough to split over a wave's lanes, and the rows of A
+// (rounded up to a multiple of 4) of the longest K within the kernel's LDS.
+static bool fewrows_shape(const BatchExtent& x) {
+  return options().gemm_splitk != 0 && x.maxM <= FEWROWS_MAX_M && x.minK >= 1024 && x.maxN >= 64 &&
+         (size_t)((x.maxM + 3) & ~3) * x.maxK * sizeof(float) <= FEWROWS_MAX_LDS;
 }
 
 // The matrix-vector kernel with the LSTM cell of the step below as its epilogue (back-propagation through time at the
 // reference's training batch); false when the shape is not this kernel's.
 bool gemm_fewrows_applicable(int M, int N, int K) {
-  return options().gemm_splitk != 0 && M <= FEWROWS_MAX_M && K >= 1024 && K % 4 == 0 && N >= 64 &&
-         (size_t)((M + 3) & ~3) * K * sizeof(float) <= FEWROWS_MAX_LDS;
+  BatchExtent x;
+  x.maxM = M; x.maxN = N; x.minK = x.maxK = K;
+  return K % 4 == 0 && fewrows_shape(x);
 }
 hipError_t launch_gemm_fewrows_cell(const GemmProb& p, const LstmCellBwdArgs& cell, hipStream_t stream) {
   GemmBatch b;
@@ -970,341 +713,23 @@ hipError_t launch_gemm_fewrows_cell(const GemmProb& p, const LstmCellBwdArgs& ce
   return launch_fewrows(b, stream, &cell);
 }
 
-// ---------------------------------------------------------------------------------------------------------------
-// The two recurrent-product kernels above for a wavefront step of back-propagation through time (kernels.h RecBatch):
-// up to two problems per launch, each a sum over up to two K segments, each followed by its own LSTM cell.  The
-// arithmetic of a problem with ONE segment is that of the single-problem kernels (same slices, same order).
-// ---------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void rec_ksplit_kernel(RecBatch b, float* partial, int tiles, int s_max) {
-  using namespace ks;
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* sA = sm;
-  float* sW = sm + BT * LDK;
-  const RecProb& p = b.p[blockIdx.z];
-  const int M = p.M, N = p.N;
-  const int nt_n = (N + BT - 1) / BT;
-  const int tile = blockIdx.x, m0 = (tile / nt_n) * BT, n0 = (tile % nt_n) * BT;
-  // slice -> (segment, k0): the slices of segment 0 first
-  const int s0 = (p.seg[0].K + KS - 1) / KS;
-  const int s_tot = s0 + (p.nseg > 1 ? (p.seg[1].K + KS - 1) / KS : 0);
-  if ((int)blockIdx.y >= s_tot) return;
-  const bool second = (int)blockIdx.y >= s0;
-  const RecSeg& sg = p.seg[second ? 1 : 0];
-  const int k0 = ((int)blockIdx.y - (second ? s0 : 0)) * KS, K = sg.K;
-  const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  {
-    f32x4 va[16], vw[16];
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int i = tid + u * 256, r = i >> 6, c = (i & 63) * 4;
-      const bool kin = k0 + c < K;   // K % 4 == 0
-      va[u] = kin ? *reinterpret_cast<const f32x4*>(sg.A + (size_t)min(m0 + r, M - 1) * sg.lda + k0 + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-      vw[u] = kin ? *reinterpret_cast<const f32x4*>(sg.W + (size_t)min(n0 + r, N - 1) * sg.ldw + k0 + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-#pragma unroll
-    for (int u = 0; u < 16; ++u) {
-      const int i = tid + u * 256, r = i >> 6, c = (i & 63) * 4;
-      *reinterpret_cast<f32x4*>(sA + r * LDK + c) = va[u];
-      *reinterpret_cast<f32x4*>(sW + r * LDK + c) = vw[u];
-    }
-  }
-  __syncthreads();
-  const int mq = (wave >> 1) * 32, nq = (wave & 1) * 32;
-  f32x16 acc;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-  const float* ar = sA + (mq + l31) * LDK + lh * 4;
-  const float* wr = sW + (nq + l31) * LDK + lh * 4;
-#pragma unroll 8
-  for (int g = 0; g < KS / 8; ++g) {
-    const f32x4 fa = *reinterpret_cast<const f32x4*>(ar + g * 8);
-    const f32x4 fb = *reinterpret_cast<const f32x4*>(wr + g * 8);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[e], fb[e], acc, 0, 0, 0);
-  }
-  // [problem][slice][tile][wave][reg][lane]
-  float* pt = partial + ((((size_t)blockIdx.z * s_max + blockIdx.y) * tiles + tile) * 4 + wave) * 1024;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) pt[r * 64 + lane] = acc[r];
-}
-
-__global__ __launch_bounds__(256) void rec_ksplit_reduce_kernel(RecBatch b, const float* partial, int tiles, int s_max,
-                                                                LstmCellBwdArgs cell0, LstmCellBwdArgs cell1) {
-  using namespace ks;
-  const RecProb& p = b.p[blockIdx.y];
-  const LstmCellBwdArgs& cell = blockIdx.y == 0 ? cell0 : cell1;
-  const int M = p.M, N = p.N;
-  const int nt_n = (N + BT - 1) / BT;
-  const int S = (p.seg[0].K + KS - 1) / KS + (p.nseg > 1 ? (p.seg[1].K + KS - 1) / KS : 0);
-  const size_t idx = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= (size_t)tiles * 4096) return;
-  const float* base = partial + (size_t)blockIdx.y * s_max * tiles * 4096 + idx;
-  float ps[KSPLIT_MAX_S];
-#pragma unroll
-  for (int s2 = 0; s2 < KSPLIT_MAX_S; ++s2) ps[s2] = s2 < S ? base[(size_t)s2 * tiles * 4096] : 0.f;
-  float v = 0.f;
-#pragma unroll
-  for (int s2 = 0; s2 < KSPLIT_MAX_S; ++s2) v += ps[s2];
-  const int tile = (int)(idx >> 12), wave = (int)(idx >> 10) & 3, r = (int)(idx >> 6) & 15, lane = (int)idx & 63;
-  const int m0 = (tile / nt_n) * BT, n0 = (tile % nt_n) * BT;
-  const int mq = (wave >> 1) * 32, nq = (wave & 1) * 32, l31 = lane & 31, lh = lane >> 5;
-  const int row = m0 + mq + (r & 3) + 8 * (r >> 2) + 4 * lh, n = n0 + nq + l31;
-  if (row >= M || n >= N) return;
-  float y = v;
-  if (p.resid) y += p.resid[(size_t)row * p.ldr + n];
-  lstm_cell_bwd_elem(cell, row * cell.H + n, y);
-}
-
-size_t rec_ksplit_workspace_floats(int M, int N, int K_total_max, int count) {
-  const size_t tiles = (size_t)((M + ks::BT - 1) / ks::BT) * ((N + ks::BT - 1) / ks::BT);
-  const size_t S = (K_total_max + ks::KS - 1) / ks::KS;
-  return (size_t)count * tiles * S * 4096 + 64;
-}
-
-hipError_t launch_rec_ksplit(const RecBatch& b, const LstmCellBwdArgs* cells, float* workspace, hipStream_t stream) {
-  int tiles = 0, s_max = 0;
-  for (int i = 0; i < b.count; ++i) {
-    const RecProb& p = b.p[i];
-    int s = 0;
-    for (int g = 0; g < p.nseg; ++g) {
-      if (p.seg[g].K % ks::KS != 0) return hipErrorInvalidValue;
-      s += p.seg[g].K / ks::KS;
-    }
-    if (s > KSPLIT_MAX_S || p.nseg < 1 || p.nseg > 2) return hipErrorInvalidValue;
-    s_max = s > s_max ? s : s_max;
-    const int t = ((p.M + ks::BT - 1) / ks::BT) * ((p.N + ks::BT - 1) / ks::BT);
-    if (i > 0 && t != tiles) return hipErrorInvalidValue;   // the problems of a wavefront step share M and N
-    tiles = t;
-  }
-  if (hipError_t e = launch_lds(rec_ksplit_kernel, dim3(tiles, s_max, b.count), dim3(256), ks::LDS_BYTES, stream, b, workspace,
-                                tiles, s_max))
-    return e;
-  hipLaunchKernelGGL(rec_ksplit_reduce_kernel, dim3(tiles * 16, b.count), dim3(256), 0, stream, b, (const float*)workspace,
-                     tiles, s_max, cells[0], cells[b.count > 1 ? 1 : 0]);
-  return hipGetLastError();
-}
-
-template <int MB>
-__global__ __launch_bounds__(256) void rec_fewrows_kernel(RecBatch b, LstmCellBwdArgs cell0, LstmCellBwdArgs cell1) {
-  extern __shared__ __attribute__((aligned(16))) float arow[];   // [MB][K of the segment]
-  const RecProb& p = b.p[blockIdx.y];
-  const LstmCellBwdArgs& cell = blockIdx.y == 0 ? cell0 : cell1;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int n = blockIdx.x * 4 + wave;
-  const int M = p.M, N = p.N;
-  constexpr int WMAX = 8;   // a segment's K <= 64 lanes x 4 x 8 = 2048
-  // lane m finishes row m: what the cell's reverse reads besides dh is fetched now, under the product (same arithmetic
-  // as lstm_cell_bwd_elem: rows past their length read valid addresses, their values are not used)
-  LstmCellBwdPre pre{};
-  const bool fin = n < N && lane < M;
-  float res = 0.f;
-  if (fin) {
-    pre = lstm_cell_bwd_load(cell, lane * cell.H + n);
-    if (p.resid) res = p.resid[(size_t)lane * p.ldr + n];
-  }
-  float acc[MB];
-#pragma unroll
-  for (int m = 0; m < MB; ++m) acc[m] = 0.f;
-  for (int g = 0; g < p.nseg; ++g) {
-    const RecSeg& sg = p.seg[g];
-    const int K = sg.K, k4n = K >> 2;
-    if (g > 0) __syncthreads();   // every wave is done with the previous segment's rows
-    // this wave's weight row first: its 16-byte pieces are in flight while the rows of A are staged
-    const float* __restrict__ wrow = sg.W + (size_t)(n < N ? n : N - 1) * sg.ldw;
-    f32x4 w[WMAX];
-#pragma unroll
-    for (int j = 0; j < WMAX; ++j) {
-      const int k4 = j * 256 + lane * 4;
-      w[j] = k4 < K ? *reinterpret_cast<const f32x4*>(wrow + k4) : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
-    {
-      const float* __restrict__ A = sg.A;
-      constexpr int SB = 12;    // 12 rows x 2048 floats are two rounds of 12 loads per thread
-      int m = (int)threadIdx.x / k4n, c = (int)threadIdx.x - m * k4n;   // k4n >= 256: a step of 256 wraps at most once
-      for (int i0 = threadIdx.x; i0 < MB * k4n; i0 += 256 * SB) {
-        f32x4 v[SB];
-        int mu[SB], cu[SB];
-#pragma unroll
-        for (int u = 0; u < SB; ++u) {
-          mu[u] = m; cu[u] = c;
-          const int mr = m < M ? m : M - 1;
-          v[u] = *reinterpret_cast<const f32x4*>(A + (size_t)mr * sg.lda + (c < k4n ? c : 0) * 4);
-          if (m >= M) v[u] = f32x4{0.f, 0.f, 0.f, 0.f};
-          c += 256;
-          if (c >= k4n) { c -= k4n; ++m; }
-        }
-#pragma unroll
-        for (int u = 0; u < SB; ++u)
-          if (mu[u] < MB) *reinterpret_cast<f32x4*>(arow + (size_t)mu[u] * K + cu[u] * 4) = v[u];
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < WMAX; ++j) {
-      const int k4 = j * 256 + lane * 4;
-      const int kk = k4 < K ? k4 : 0;
-#pragma unroll
-      for (int m = 0; m < MB; ++m) {
-        const f32x4 a = *reinterpret_cast<const f32x4*>(arow + (size_t)m * K + kk);
-        acc[m] = __builtin_fmaf(a[3], w[j][3], __builtin_fmaf(a[2], w[j][2], __builtin_fmaf(a[1], w[j][1], __builtin_fmaf(a[0], w[j][0], acc[m]))));
-      }
-    }
-  }
-  if (n >= N) return;
-  float out = 0.f;   // lane m ends up with row m
-#pragma unroll
-  for (int m = 0; m < MB; ++m) {
-    float v = acc[m];
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    if (lane == m) out = v;
-  }
-  if (fin) lstm_cell_bwd_finish(cell, lane * cell.H + n, pre, out + res);
-}
-
-// Round 5: the same product with the K range split over the four waves and BOTH operands in registers.  The kernel above
-// stages the M rows of A in LDS (98 KB per segment at 12 rows x 2048) and every wave re-reads all of them for its one
-// column: a 12-window BPTT step spent its time waiting for that staging and on LDS reads (4 per 16 multiply-adds).  Here
-// wave w owns the quarter [w K / 4, (w + 1) K / 4) of every segment for all four columns of the workgroup: a lane loads
-// its 16-byte pieces of the M rows and of the 4 weight rows once (all loads of a segment in flight together), 4 M
-// accumulators per lane; the sums over the 64 lanes are a reduce-scatter (each step halves what a lane carries: 51 lane
-// exchanges for 48 sums instead of 288), the four waves' sums meet in LDS and are added in wave order.  Needs K % 16 == 0.
-template <int MB>
-__global__ __launch_bounds__(256) void rec_fewrows_reg_kernel(RecBatch b, LstmCellBwdArgs cell0, LstmCellBwdArgs cell1) {
-  __shared__ float wsum[4][4 * MB + 4];
-  const RecProb& p = b.p[blockIdx.y];
-  const LstmCellBwdArgs& cell = blockIdx.y == 0 ? cell0 : cell1;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int n0 = blockIdx.x * 4;
-  const int M = p.M, N = p.N;
-  // thread (column c, row m) finishes element (m, n0 + c): what the cell's reverse reads besides dh is fetched now
-  const int f_c = tid / MB, f_m = tid - f_c * MB;
-  const bool fin = tid < 4 * MB && f_m < M && n0 + f_c < N;
-  LstmCellBwdPre pre{};
-  float res = 0.f;
-  if (fin) {
-    pre = lstm_cell_bwd_load(cell, f_m * cell.H + n0 + f_c);
-    if (p.resid) res = p.resid[(size_t)f_m * p.ldr + n0 + f_c];
-  }
-  float v[64];
-#pragma unroll
-  for (int i = 0; i < 4 * MB; ++i) v[i] = 0.f;
-  for (int g = 0; g < p.nseg; ++g) {
-    const RecSeg& sg = p.seg[g];
-    const int Kq = sg.K >> 2;                      // this wave's quarter: Kq <= 512 floats, a multiple of 4
-    const int kbase = wave * Kq;
-    f32x4 a[MB][2], w[4][2];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int kl = j * 256 + lane * 4;
-      const bool in = kl < Kq;
-      const int k = kbase + (in ? kl : 0);
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(sg.W + (size_t)min(n0 + c, N - 1) * sg.ldw + k);
-        w[c][j] = in ? x : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-#pragma unroll
-      for (int m = 0; m < MB; ++m) {
-        const f32x4 x = *reinterpret_cast<const f32x4*>(sg.A + (size_t)min(m, M - 1) * sg.lda + k);
-        a[m][j] = (in && m < M) ? x : f32x4{0.f, 0.f, 0.f, 0.f};
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int m = 0; m < MB; ++m) {
-          float t = v[c * MB + m];
-          t = __builtin_fmaf(a[m][j][0], w[c][j][0], t);
-          t = __builtin_fmaf(a[m][j][1], w[c][j][1], t);
-          t = __builtin_fmaf(a[m][j][2], w[c][j][2], t);
-          t = __builtin_fmaf(a[m][j][3], w[c][j][3], t);
-          v[c * MB + m] = t;
-        }
-  }
-  int base = 0, count = 0;
-  LaneReduceScatter<4 * MB, 32, 64>::run(v, lane, base, count);
-#pragma unroll
-  for (int i = 0; i < 4; ++i)          // (count <= 3 for the instantiated row counts; lanes that hold the same sums write the same)
-    if (i < count) wsum[wave][base + i] = v[i];
-  __syncthreads();
-  if (fin) {
-    const float out = ((wsum[0][tid] + wsum[1][tid]) + wsum[2][tid]) + wsum[3][tid];
-    lstm_cell_bwd_finish(cell, f_m * cell.H + n0 + f_c, pre, out + res);
-  }
-}
-
-template <int MB>
-static hipError_t launch_rec_fewrows_cfg(const RecBatch& b, const LstmCellBwdArgs* cells, int maxN, int maxK,
-                                         hipStream_t stream) {
-  const size_t lds = (size_t)MB * maxK * sizeof(float);   // arow[MB][K of the widest segment]
-  if (lds > FEWROWS_MAX_LDS) return hipErrorInvalidValue;
-  bool k16 = true;
-  for (int i = 0; i < b.count; ++i)
-    for (int g = 0; g < b.p[i].nseg; ++g) k16 = k16 && b.p[i].seg[g].K % 16 == 0;
-  if (k16) {      // both operands in registers, K split over the waves
-    hipLaunchKernelGGL(rec_fewrows_reg_kernel<MB>, dim3((maxN + 3) / 4, b.count), dim3(256), 0, stream, b, cells[0],
-                       cells[b.count > 1 ? 1 : 0]);
-    return hipGetLastError();
-  }
-  return launch_lds(rec_fewrows_kernel<MB>, dim3((maxN + 3) / 4, b.count), dim3(256), lds, stream, b, cells[0],
-                    cells[b.count > 1 ? 1 : 0]);
-}
-
-hipError_t launch_rec_fewrows(const RecBatch& b, const LstmCellBwdArgs* cells, hipStream_t stream) {
-  int maxN = 0, maxM = 0, maxK = 0;
-  for (int i = 0; i < b.count; ++i) {
-    const RecProb& p = b.p[i];
-    if (p.nseg < 1 || p.nseg > 2) return hipErrorInvalidValue;
-    for (int g = 0; g < p.nseg; ++g) {
-      if (p.seg[g].K < 1024 || p.seg[g].K > 2048 || p.seg[g].K % 4 != 0) return hipErrorInvalidValue;
-      maxK = p.seg[g].K > maxK ? p.seg[g].K : maxK;
-    }
-    maxN = p.N > maxN ? p.N : maxN;
-    maxM = p.M > maxM ? p.M : maxM;
-  }
-  if (maxM > FEWROWS_MAX_M) return hipErrorInvalidValue;
-  if (maxM <= 4) return launch_rec_fewrows_cfg<4>(b, cells, maxN, maxK, stream);
-  if (maxM <= 8) return launch_rec_fewrows_cfg<8>(b, cells, maxN, maxK, stream);
-  if (maxM <= 12) return launch_rec_fewrows_cfg<12>(b, cells, maxN, maxK, stream);
-  return launch_rec_fewrows_cfg<16>(b, cells, maxN, maxK, stream);
-}
-
 enum GemmPick { PICK_S11, PICK_S12, PICK_S21, PICK_WIDE, PICK_LARGE, PICK_SPLITK, PICK_FEWROWS };
 
 static GemmPick pick_gemm(const GemmBatch& batch) {
-  int maxM = 0, maxN = 0;
-  for (int i = 0; i < batch.count; ++i) {
-    maxM = batch.p[i].M > maxM ? batch.p[i].M : maxM;
-    maxN = batch.p[i].N > maxN ? batch.p[i].N : maxN;
-  }
+  const BatchExtent x = batch_extent(batch);
   // Narrow outputs (heads: 66 / 10 columns) and short batches take the smaller tiles; everything else the large ones,
   // unless that would leave most of the 256 CUs without a block.
-  const bool narrow = maxN <= 64;
-  const bool shortm = maxM <= 64;
+  const bool narrow = x.maxN <= 64;
+  const bool shortm = x.maxM <= 64;
   auto nblocks = [&](int bm, int bn) {
     long t = 0;
     for (int i = 0; i < batch.count; ++i)
       t += (long)((batch.p[i].M + bm - 1) / bm) * ((batch.p[i].N + bn - 1) / bn);
     return t;
   };
+  if (fewrows_shape(x)) return PICK_FEWROWS;
   // few 32 x 32 tiles in total and a K worth splitting: one tile per workgroup, K over its four waves
-  const bool splitk_on = options().gemm_splitk != 0;
-  int minK = 1 << 30;
-  for (int i = 0; i < batch.count; ++i) minK = batch.p[i].K < minK ? batch.p[i].K : minK;
-  {   // matrix-vector shape
-    int maxK = 0;
-    for (int i = 0; i < batch.count; ++i) maxK = batch.p[i].K > maxK ? batch.p[i].K : maxK;
-    if (splitk_on && maxM <= FEWROWS_MAX_M && minK >= 1024 && maxN >= 64 &&
-        (size_t)((maxM + 3) & ~3) * maxK * sizeof(float) <= FEWROWS_MAX_LDS)
-      return PICK_FEWROWS;
-  }
-  if (splitk_on && minK >= 64 && nblocks(32, 32) <= SPLITK_MAX_TILES) return PICK_SPLITK;
+  if (options().gemm_splitk != 0 && x.minK >= 64 && nblocks(32, 32) <= SPLITK_MAX_TILES) return PICK_SPLITK;
   if (shortm && narrow) return PICK_S11;
   if (shortm) return PICK_S12;
   if (narrow) return PICK_S21;
@@ -1342,156 +767,6 @@ hipError_t launch_gemm_train(const TrainGemmArgs& t, int amode, int emode, hipSt
   // per 8192 x 512 x 512 launch than the plain tile even with the transform switched off at run time)
   if (amode == 0) return emode == 1 ? launch_cfg<CfgS12, 4>(b, stream) : launch_cfg<CfgS12, 0>(b, stream);
   return launch_cfg<CfgS12, 2>(b, stream);
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// The train-mode layer products of LARGE batches on three bf16 pieces per operand (bf16x3.h; round 6): y = a W^T + b with the
-// statistics epilogue, and dA = dY W with the dyh epilogue -- what launch_gemm_train runs on the fp32 MFMA instruction
-// (CfgS12, ROLE 2 / 3).  Structure of the fused inference MLP (mlp_fused_x3.hip): a workgroup stages its 64 rows of A
-// (all of K <= 512, fp32) in LDS once; its four waves take 64 rows x 64 columns each (2 x 2 tiles), read 8 consecutive fp32
-// of a k-step per row tile from LDS and split them into pieces in registers, and stream the weight pieces -- split ONCE per
-// optimiser step by pack_x3_kernel, fragment order [k-step][32-column tile][piece] -> 1 KB -- from L2 into a register ring;
-// the accumulators then go through the SAME train_epilogue as the fp32 kernels (same C/D layout).  One workgroup per CU
-// (132 KB of LDS), stores only after the K loop (bf16_hazard_repro.md).
-// ---------------------------------------------------------------------------------------------------------------------
-namespace gx {
-constexpr int BM = 64, BN = 256, NT = 256;
-constexpr int LDA = FUSED_MAX_WIDTH + 4;
-constexpr size_t LDS_BYTES = (size_t)BM * LDA * sizeof(float) + 64;
-constexpr int RING = 3;
-}  // namespace gx
-
-// W [N][ldw] (K columns used) -> pieces in fragment order: [k-step of 16][32-column tile][piece][lane][8], lane
-// (n = lane & 31, half = lane >> 5) owns W[tile * 32 + n][ks * 16 + half * 8 .. + 7]; rows >= N and columns >= K are zero.
-__global__ __launch_bounds__(256) void pack_x3_kernel(const float* __restrict__ W, int ldw, int N, int K,
-                                                      unsigned short* __restrict__ out) {
-  const int KS = (K + 15) / 16, NT32 = (N + 31) / 32;
-  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (long)KS * NT32 * 64) return;
-  const int lane = (int)(i & 63), tile = (int)((i >> 6) % NT32), ks = (int)((i >> 6) / NT32);
-  const int n = tile * 32 + (lane & 31), k0 = ks * 16 + (lane >> 5) * 8;
-  float v[8];
-#pragma unroll
-  for (int e = 0; e < 8; ++e) v[e] = (n < N && k0 + e < K) ? W[(size_t)n * ldw + k0 + e] : 0.f;
-  const Pieces q = split8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
-  unsigned short* o = out + (((size_t)ks * NT32 + tile) * 3) * 512 + lane * 8;
-#pragma unroll
-  for (int pc = 0; pc < 3; ++pc) *reinterpret_cast<u32x4_t*>(o + pc * 512) = q.p[pc];
-}
-
-size_t pack_x3_elems(int N, int K) { return (size_t)((K + 15) / 16) * ((N + 31) / 32) * 3 * 512; }
-
-hipError_t launch_pack_x3(const float* W, int ldw, int N, int K, unsigned short* out, hipStream_t stream) {
-  const long n = (long)((K + 15) / 16) * ((N + 31) / 32) * 64;
-  hipLaunchKernelGGL(pack_x3_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, W, ldw, N, K, out);
-  return hipGetLastError();
-}
-
-template <bool BWD>
-__global__ __launch_bounds__(gx::NT) void gemm_train_x3_kernel(GemmProb p, const unsigned short* __restrict__ wfrag) {
-  X3_EXCLUSIVE_SIMD();
-  using namespace gx;
-  extern __shared__ __attribute__((aligned(16))) float act[];
-  const int M = p.M, N = p.N, K = p.K;
-  const int tiles_n = (N + BN - 1) / BN;
-  const int m0 = ((int)blockIdx.x / tiles_n) * BM, n0 = ((int)blockIdx.x % tiles_n) * BN;
-  const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int KS = (K + 15) / 16, NT32 = (N + 31) / 32;
-  {   // the block's rows of A, columns [0, 16 KS) (zero past K; rows past M repeat row M - 1 and are never stored)
-    const int c4n = KS * 4;
-    for (int i = tid; i < BM * c4n; i += NT) {
-      const int r = i / c4n, c = (i % c4n) * 4;
-      const int row = m0 + r < M ? m0 + r : M - 1;
-      f32x4 v = {0.f, 0.f, 0.f, 0.f};
-      if (c < K) v = *reinterpret_cast<const f32x4*>(p.A + (size_t)row * p.lda + c);   // K % 4 == 0
-      *reinterpret_cast<f32x4*>(act + r * LDA + c) = v;
-    }
-  }
-  __syncthreads();
-  // the wave's two column tiles (a tile past the matrix reads the last one; the epilogue drops its columns)
-  int ct[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) { const int t = n0 / 32 + wave * 2 + j; ct[j] = t < NT32 ? t : NT32 - 1; }
-  x3_gptr_t wb = (x3_gptr_t)wfrag + lane * 8;
-  const float* a_rd = act + l31 * LDA + lh * 8;
-
-  f32x16 acc[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  u32x4_t fb[RING][2][3];
-  Pieces ap[2][2];
-  auto bload = [&](u32x4_t (&b)[2][3], int ks) {
-    const int kc = ks < KS ? ks : KS - 1;
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int pc = 0; pc < 3; ++pc) b[j][pc] = *(x3_gvec_t)(wb + (((size_t)kc * NT32 + ct[j]) * 3 + pc) * 512);
-  };
-  auto asplit = [&](Pieces (&a)[2], int ks) {
-    const int kc = ks < KS ? ks : KS - 1;
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const f32x4 lo = *reinterpret_cast<const f32x4*>(a_rd + i * 32 * LDA + kc * 16);
-      const f32x4 hi = *reinterpret_cast<const f32x4*>(a_rd + i * 32 * LDA + kc * 16 + 4);
-      a[i] = split8(lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]);
-    }
-  };
-  auto mma = [&](const Pieces (&a)[2], const u32x4_t (&b)[2][3]) {
-#pragma unroll
-    for (int t = 0; t < 6; ++t)
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[i].p[X3_PA[t]]),
-                                                              __builtin_bit_cast(bf16x8_t, b[j][X3_PB[t]]), acc[i][j], 0, 0, 0);
-  };
-  bload(fb[0], 0);
-  bload(fb[1], 1);
-  asplit(ap[0], 0);
-  // k-steps in groups of six (the ring rotates with period 3, the A pieces with period 2), then the tail below
-  int ks = 0;
-  for (; ks + 6 <= KS; ks += 6) {
-    bload(fb[2], ks + 2); asplit(ap[1], ks + 1); mma(ap[0], fb[0]);
-    bload(fb[0], ks + 3); asplit(ap[0], ks + 2); mma(ap[1], fb[1]);
-    bload(fb[1], ks + 4); asplit(ap[1], ks + 3); mma(ap[0], fb[2]);
-    bload(fb[2], ks + 5); asplit(ap[0], ks + 4); mma(ap[1], fb[0]);
-    bload(fb[0], ks + 6); asplit(ap[1], ks + 5); mma(ap[0], fb[1]);
-    bload(fb[1], ks + 7); asplit(ap[0], ks + 6); mma(ap[1], fb[2]);
-  }
-  // tail (at most five steps): the same rotation, each step guarded by a wave-uniform test
-  if (ks < KS) { bload(fb[2], ks + 2); asplit(ap[1], ks + 1); mma(ap[0], fb[0]); }
-  if (ks + 1 < KS) { bload(fb[0], ks + 3); asplit(ap[0], ks + 2); mma(ap[1], fb[1]); }
-  if (ks + 2 < KS) { bload(fb[1], ks + 4); asplit(ap[1], ks + 3); mma(ap[0], fb[2]); }
-  if (ks + 3 < KS) { bload(fb[2], ks + 5); asplit(ap[0], ks + 4); mma(ap[1], fb[0]); }
-  if (ks + 4 < KS) { asplit(ap[1], ks + 5); mma(ap[0], fb[1]); }
-
-  train_epilogue<2, 2, BWD>(p, acc, m0, n0 + wave * 64, l31, lh);
-}
-
-bool gemm_train_x3_applicable(int M, int N, int K) {
-  return M >= 1024 && N % 64 == 0 && N >= 256 && K % 4 == 0 && K >= 16 && K <= FUSED_MAX_WIDTH;
-}
-
-hipError_t launch_gemm_train_x3(const TrainGemmArgs& t, const unsigned short* wfrag, int emode, hipStream_t stream) {
-  if (emode > 2 || !wfrag || !gemm_train_x3_applicable(t.M, t.N, t.K)) return hipErrorInvalidValue;
-  GemmProb g{};
-  g.A = t.A; g.lda = t.lda; g.W = nullptr; g.ldw = 0; g.C = t.C; g.ldc = t.ldc; g.M = t.M; g.N = t.N; g.K = t.K;
-  g.scale = nullptr; g.shift = t.bias; g.resid = nullptr; g.ldr = 0; g.act = 0; g.slope = 0.f;
-  if (emode >= 1) g.stat_part = t.part;
-  if (emode == 2) {
-    g.e_y = t.e_y; g.ld_ey = t.ld_ey; g.e_s = t.e_s; g.e_t = t.e_t; g.e_mean = t.e_mean; g.e_rstd = t.e_rstd;
-    g.e_slope = t.e_slope;
-  }
-  const dim3 grid((unsigned)(((t.M + gx::BM - 1) / gx::BM) * ((t.N + gx::BN - 1) / gx::BN)));
-  return emode == 2 ? launch_lds(gemm_train_x3_kernel<true>, grid, dim3(gx::NT), gx::LDS_BYTES, stream, g, wfrag)
-                    : launch_lds(gemm_train_x3_kernel<false>, grid, dim3(gx::NT), gx::LDS_BYTES, stream, g, wfrag);
 }
 
 // Name (as a profiler prints it) of the kernel `launch_gemm` runs for `count` problems of this shape.

@@ -140,29 +140,29 @@ struct GemmProb {
 };
 struct GemmBatch { GemmProb p[2]; int count; int role = 0; int xcd_swizzle = 1; };  // role 1 = update-net hidden layer (profiling name only)
 
-// The same product with K split over workgroups (a few hundred rows, long K, small output: the recurrent products of
-// back-propagation through time); `workspace`: gemm_ksplit_workspace_floats floats.  Deterministic (partials added in
-// slice order by a second kernel).
-bool gemm_ksplit_applicable(int M, int N, int K);
-size_t gemm_ksplit_workspace_floats(int M, int N, int K);
+// At most FEWROWS_MAX_M rows against a long K: the matrix-vector kernel of gemm_f32.hip (launch_gemm picks it by itself).
+// With `cell` (back-propagation through time, layer after layer): the product is dh of the step below (N = H, one value per
+// (row, unit)), and the kernel runs that step's cell on it instead of storing C.
+constexpr int FEWROWS_MAX_M = 16;
 struct LstmCellBwdArgs;
-// `cell` (back-propagation through time): the product is dh of the step below (N = H, one value per (row, unit)); the
-// reduce kernel runs that step's cell on it instead of storing C.
-hipError_t launch_gemm_ksplit(const GemmProb& p, float* workspace, hipStream_t stream, const LstmCellBwdArgs* cell = nullptr);
-// At most 16 rows: the matrix-vector kernel, same epilogue.
 bool gemm_fewrows_applicable(int M, int N, int K);
 hipError_t launch_gemm_fewrows_cell(const GemmProb& p, const LstmCellBwdArgs& cell, hipStream_t stream);
 
-// Back-propagation through time as a wavefront over the layers: one launch forms the incoming hidden-state cotangent
-// of up to two (layer, step) units and runs their cells.  A unit's product may have two K segments with their own
-// operands -- dh0_t = dG0_{t+1} . W_hh0 + dG1_t . W_ih1 is one K = 8H product over the rows [dG0_{t+1} | dG1_t] that
-// are never concatenated in memory.  C = sum_seg A_seg . W_seg^T (+ resid); the unit's cell consumes it.
+// The recurrent products of back-propagation through time (gemm_rec.hip): one launch forms the incoming hidden-state
+// cotangent of up to two (layer, step) units and runs their cells on it.  A unit's product may have two K segments with
+// their own operands -- in the wavefront over two layers, dh0_t = dG0_{t+1} . W_hh0 + dG1_t . W_ih1 is one K = 8H product
+// over the rows [dG0_{t+1} | dG1_t] that are never concatenated in memory.  C = sum_seg A_seg . W_seg^T (+ resid); the
+// unit's cell consumes it, nothing is stored.  The layer-after-layer form launches one unit of one segment.
 struct RecSeg { const float* A; int lda; const float* W; int ldw; int K; };   // A [M][lda], W [N][ldw], K % 4 == 0
 struct RecProb { RecSeg seg[2]; int nseg; int M, N; const float* resid; int ldr; };
 struct RecBatch { RecProb p[2]; int count; };
+// K split over workgroups (more than FEWROWS_MAX_M rows, long K, small output; at most 16 slices of 256 per unit, a
+// segment's last slice may be partial): whether one segment of K is this kernel pair's shape, and the floats of `workspace`
+// for `count` units of K_total_max in all.  Deterministic: the partial tiles are added in slice order by a second kernel.
+bool rec_ksplit_applicable(int M, int N, int K);
 size_t rec_ksplit_workspace_floats(int M, int N, int K_total_max, int count);
-// K-split tiles (a few hundred rows; every segment's K a multiple of 256) / matrix-vector kernel (<= 16 rows, every
-// segment's K in [1024, 2048]); cells[i] is the cell of problem i.
+// cells[i] is the cell of unit i.  launch_rec_fewrows: at most FEWROWS_MAX_M rows, every segment's K a multiple of 16 in
+// [1024, 2048].
 hipError_t launch_rec_ksplit(const RecBatch& b, const LstmCellBwdArgs* cells, float* workspace, hipStream_t stream);
 hipError_t launch_rec_fewrows(const RecBatch& b, const LstmCellBwdArgs* cells, hipStream_t stream);
 
@@ -247,7 +247,7 @@ struct TrainGemmArgs {       // C[M][N] = A'[M][K] . W[N][K]^T (+ bias), 64 x 12
   const float* e_slope;
 };
 hipError_t launch_gemm_train(const TrainGemmArgs& p, int amode, int emode, hipStream_t stream);
-// The same products (amode 0) on three bf16 pieces per operand for large batches (gemm_f32.hip, gemm_train_x3_kernel):
+// The same products (amode 0) on three bf16 pieces per operand for large batches (gemm_train_x3.hip, gemm_train_x3_kernel):
 // `wfrag` = the weight matrix W [N][K] as pieces in fragment order, made by launch_pack_x3 once per optimiser step.
 bool gemm_train_x3_applicable(int M, int N, int K);
 hipError_t launch_gemm_train_x3(const TrainGemmArgs& p, const unsigned short* wfrag, int emode, hipStream_t stream);

@@ -1,6 +1,11 @@
 // One element (batch row b, hidden unit j) of a step of back-propagation through time of an LSTM layer (see the comment of
-// lstm_cell_bwd_kernel in train.hip).  Shared by that kernel and by the reduce kernel of the K-split recurrent product
-// (gemm_f32.hip), which feeds the dh it has just formed straight into the next step's cell instead of storing it.
+// lstm_cell_bwd_kernel in train.hip).  Shared by that kernel and by the recurrent products of gemm_rec.hip and the
+// matrix-vector kernel of gemm_f32.hip, which feed the dh they have just formed straight into the next step's cell
+// instead of storing it.
+// The formulas stand twice on purpose: lstm_cell_bwd_elem for a caller that has dh at hand, lstm_cell_bwd_load +
+// lstm_cell_bwd_finish for one that fetches under its product.  Writing the first as the second of the other two was
+// tried and changes the bits: the compiler then contracts 1 - tc * tc into one fused multiply-add where it now multiplies
+// and subtracts (profiles/r10_gemm_family_resources.txt).  A change to one copy belongs in the other.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,7 +14,7 @@
 namespace empose {
 
 // Everything the element reads that does not depend on the incoming dh: fetched BEFORE the recurrent product that forms dh
-// (rec_fewrows_kernel), so that the step's tail is arithmetic and stores only.
+// (rec_fewrows_reg_kernel), so that the step's tail is arithmetic and stores only.
 struct LstmCellBwdPre {
   float dc_in, gi, gf, gg, go, tc, c_prev, dy;
   int live;

@@ -4,11 +4,18 @@ through the C ABI: what the pieces shared by the two forms of the reverse pass -
 batched tail -- must keep, whichever recurrence runs.  Ragged lengths and a carried state throughout.
 
 The shapes are the smallest that take each branch of the reverse pass (carve_train_lstm in api_lstm.hip,
-gemm_ksplit_applicable / gemm_fewrows_applicable in gemm_f32.hip; B rows, 4H = 1024 deep recurrent products of H columns):
-  wavefront, matrix-vector   L = 2, B <= 16 and 1024 <= 4H <= 2048
+rec_ksplit_applicable in gemm_rec.hip / gemm_fewrows_applicable in gemm_f32.hip; B rows, 4H = 1024 deep recurrent products
+of H columns):
+  wavefront, matrix-vector   L = 2, B <= 16 and 1024 <= 4H <= 2048 (rec_fewrows_reg_kernel)
   wavefront, K-split         L = 2, B > 16, 4 slices of 256 x (2 x 4 tiles of 64 x 64) = 32 workgroups, the lower bound
-  layer form, the same two   L = 1 (the wavefront needs two layers): matrix-vector product fused with the cell, K-split + cell
+                             (rec_ksplit_kernel + rec_ksplit_reduce_kernel, two units of one and two K segments)
+  layer form, the same two   L = 1 (the wavefront needs two layers): gemm_fewrows_kernel fused with the cell; the same
+                             K-split kernel pair with one unit of one segment
+  layer form, partial slice  H = 260 (4H is no multiple of 256, so no wavefront either): K = 1040 is five slices, the last
+                             16 wide; five column tiles, the last 4 wide; a second row tile of one row -- the slice mask and
+                             both tile edges of the K-split pair
   layer form, plain GEMM     4H = 64: one K slice and fewer than 1024 deep, neither special product applies
+Every output of every case is also held to torch.nn.LSTM in float64 (test_every_output_matches_float64_lstm).
 """
 import ctypes as C
 import functools
@@ -25,6 +32,7 @@ CASES = [pytest.param(5, 4, 8, 256, 2, id='wavefront_matrix_vector'),
          pytest.param(65, 3, 8, 256, 2, id='wavefront_ksplit'),
          pytest.param(5, 4, 8, 256, 1, id='layers_fused_matrix_vector_cell'),
          pytest.param(65, 3, 8, 256, 1, id='layers_ksplit_cell'),
+         pytest.param(65, 3, 8, 260, 1, id='layers_ksplit_partial_slice'),
          pytest.param(3, 4, 8, 16, 3, id='layers_plain_gemm')]
 PLANES = 7      # of [B][F][H] per layer in the save buffer: gates x 4, cell state, incoming hidden state, layer output
 WEIGHT_KEYS = ('w_ih', 'w_hh', 'b_ih', 'b_hh')
@@ -145,3 +153,44 @@ def test_wavefront_stays_within_tolerance_of_layer_after_layer(B, F, K, H, L):
     for key, a in layers.items():
         assert torch.isfinite(wave[key]).all(), key
         torch.testing.assert_close(wave[key], a, atol=2e-5 * max(1.0, float(a.abs().max())), rtol=1e-4, msg=key)
+
+
+@functools.lru_cache(maxsize=None)
+def float64_lstm(B, F, K, H, L):
+    """torch.nn.LSTM in float64 on the CPU from the same inputs: packed sequences, the carried state with requires_grad,
+    the loss (y * dy).sum() (the construction of test_hip_round5.py's training test).  Keys as in forward() / backward()."""
+    inp = inputs(B, F, K, H, L)
+    cpu64 = lambda t: t.double().cpu()
+    ref = torch.nn.LSTM(K, H, L, batch_first=True).double()
+    names = ('weight_ih_l%d', 'weight_hh_l%d', 'bias_ih_l%d', 'bias_hh_l%d')
+    with torch.no_grad():
+        for l in range(L):
+            for k, name in enumerate(names):
+                getattr(ref, name % l).copy_(cpu64(inp['weights'][4 * l + k]))
+    x, h0, c0 = (cpu64(inp[k]).requires_grad_(True) for k in ('x', 'h0', 'c0'))
+    packed = torch.nn.utils.rnn.pack_padded_sequence(x, inp['lens'].cpu().long(), batch_first=True, enforce_sorted=False)
+    out, (h_n, c_n) = ref(packed, (h0, c0))
+    y, _ = torch.nn.utils.rnn.pad_packed_sequence(out, batch_first=True, total_length=F)
+    (y * cpu64(inp['dy'])).sum().backward()
+    want = dict(y=y.detach(), h_n=h_n.detach(), c_n=c_n.detach(), dx=x.grad, d_h0=h0.grad, d_c0=c0.grad)
+    for l in range(L):
+        for key, name in zip(WEIGHT_KEYS, names):
+            want['%s%d' % (key, l)] = getattr(ref, name % l).grad
+    return want
+
+
+@pytest.mark.parametrize('B,F,K,H,L', CASES)
+def test_every_output_matches_float64_lstm(B, F, K, H, L):
+    """y, h_n, c_n, dx, d_h0, d_c0 and every dW / db of the first run against torch.nn.LSTM in float64, whichever recurrence
+    ran: at most 2e-5 * max(1, max |reference|) per tensor, the bound of
+    test_hip_round5.py::test_lstm_training_forward_of_a_few_rows_and_its_reverse_equal_the_small_batch_kernels.
+    (Measured when the test was written: the worst tensor, dW_ih of layer 0, uses 2.1 % of its bound.)"""
+    fwd, bwd = first_run(B, F, K, H, L)
+    got = dict(bwd, **{k: fwd[k] for k in ('y', 'h_n', 'c_n')})
+    want = float64_lstm(B, F, K, H, L)
+    assert got.keys() == want.keys()
+    for key, b in want.items():
+        err = float((got[key].double().cpu() - b).abs().max())
+        bound = 2e-5 * max(1.0, float(b.abs().max()))
+        print('%s: worst error %.3e, bound %.3e' % (key, err, bound))
+        assert err < bound, key
