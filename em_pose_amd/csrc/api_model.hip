@@ -1,6 +1,7 @@
 // C ABI (include/empose_hip.h), the LGD model: weight packing, empose_model_create, the SMPL / update-net / LGD
 // workspaces and the launch sequence of the LGD loop; the stand-alone SMPL and update-net entry points.
 #include "api_internal.h"
+#include "f16pair.h"
 
 #include <cmath>
 
@@ -183,11 +184,50 @@ int pack_fragments_x3_16_raw(std::vector<void*>& allocs, const float* weight, in
   }), out);
 }
 
-// Both instruction shapes' orders are packed here, at creation: the options choose between them at run time, and the
-// library does not allocate after creation (12 bytes per weight together).
+// The weights as TWO f16 pieces each (f16pair.h) in the same order: [k-step of 32][16-column tile][piece] -> 1 KB, 2 KB
+// per tile and step.  Output column n's pieces are those of W[n][:] 2^e(n), e(n) from the column's largest magnitude;
+// inv[n] = 2^-e(n) is what the kernel's epilogue multiplies the accumulator by.  Zero padding as above.
+int pack_fragments_pair16_raw(std::vector<void*>& allocs, const float* weight, int N, int K, float** out, float** inv_out) {
+  const int KS = (K + 31) / 32, NT = (N + 15) / 16;
+  const int KS2 = (KS + 1) & ~1;
+  std::vector<unsigned short> buf((size_t)KS2 * NT * 2 * FRAG, 0);
+  std::vector<float> inv(N, 1.f), sc(N, 1.f);
+  for (int n = 0; n < N; ++n) {
+    unsigned m = 0u;
+    for (int k = 0; k < K; ++k) {
+      const unsigned b = pair16::finite_abs_bits(weight[(size_t)n * K + k]);
+      m = b > m ? b : m;
+    }
+    const int e = pair16::scale_exp(m);
+    sc[n] = pair16::pow2(e);
+    inv[n] = pair16::pow2(-e);
+  }
+  for (int ks = 0; ks < KS; ++ks)
+    for (int nt = 0; nt < NT; ++nt)
+      for (int lane = 0; lane < 64; ++lane) {
+        const int n = nt * 16 + (lane & 15);
+        if (n >= N) continue;
+        for (int e = 0; e < 8; ++e) {
+          const int k = ks * 32 + (lane >> 4) * 8 + e;
+          if (k >= K) continue;
+          const float x = weight[(size_t)n * K + k] * sc[n];
+          const _Float16 hi = (_Float16)x;                       // round to nearest even
+          const _Float16 lo = (_Float16)(x - (float)hi);
+          const size_t at = ((size_t)ks * NT + nt) * 2 * FRAG + (size_t)lane * 8 + e;
+          buf[at] = __builtin_bit_cast(unsigned short, hi);
+          buf[at + FRAG] = __builtin_bit_cast(unsigned short, lo);
+        }
+      }
+  TRY(upload_bf16(allocs, buf, out));
+  return upload(allocs, inv.data(), inv.size(), inv_out);
+}
+
+// Every kernel's order is packed here, at creation: the options choose between them at run time, and the library does
+// not allocate after creation (16 bytes per weight together).
 int pack_fragments(std::vector<void*>& allocs, const empose_dense_desc& d, Dense* out) {
   TRY(pack_fragments_x3_raw(allocs, d.weight, d.out_dim, d.in_dim, &out->wp3));
   TRY(pack_fragments_x3_16_raw(allocs, d.weight, d.out_dim, d.in_dim, &out->wp3_16));
+  TRY(pack_fragments_pair16_raw(allocs, d.weight, d.out_dim, d.in_dim, &out->wp2_16, &out->wp2_16_inv));
   return pack_fragments_raw(allocs, d.weight, d.out_dim, d.in_dim, &out->wp);
 }
 
@@ -250,13 +290,15 @@ struct MlpRun {
 // x3: fp32 products from three bf16 pieces per operand on the bf16 matrix path (mlp_fused_x3.hip; fp32-equivalent, 2.7
 // times the fp32 instruction's rate): needs every hidden width to be whole quads of k-steps of the next layer.
 // shape16: that kernel on the 16x16x32 form of the instruction (option mlp_fused16; the kernel of mlp_x3 = 1 only).
-struct MlpPlan { bool one_launch, x3, shape16; };
+// pair16: the shape16 kernel's place taken by the one on two f16 pieces per operand (option mlp_pair16).
+struct MlpPlan { bool one_launch, x3, shape16, pair16; };
 MlpPlan plan_mlps(const MlpRun& r) {
   const int L = r.nets[0]->n_layers;
   MlpPlan p;
   p.one_launch = options().mlp_fused != 0 && L <= FUSED_MAX_LAYERS && (long)((r.T + 63) / 64) * r.n_nets >= 256;
   p.x3 = options().mlp_x3 != 0;
   p.shape16 = options().mlp_x3 == 1 && options().mlp_fused16 != 0;
+  p.pair16 = options().mlp_pair16 != 0;
   for (int i = 0; i < r.n_nets; ++i) {
     const Mlp& net = *r.nets[i];
     if (net.skip || net.layers[0].in_dim > FUSED_MAX_WIDTH) p.one_launch = false;   // no room for a block input
@@ -265,10 +307,12 @@ MlpPlan plan_mlps(const MlpRun& r) {
       if (d.out_dim > FUSED_MAX_WIDTH || d.act > 1) p.one_launch = false;
       if (l + 1 < L && (d.out_dim % 64 != 0 || !d.wp3)) p.x3 = false;
       if (!d.wp3_16) p.shape16 = false;
+      if (!d.wp2_16 || !d.wp2_16_inv) p.pair16 = false;
     }
   }
   p.x3 = p.x3 && p.one_launch;
   p.shape16 = p.shape16 && p.x3;
+  p.pair16 = p.pair16 && p.shape16;
   return p;
 }
 
@@ -283,12 +327,14 @@ int run_mlps_one_launch(const MlpRun& r, const MlpPlan& plan, hipStream_t stream
     for (int l = 0; l < fn.n_layers; ++l) {
       const Dense& d = r.nets[i]->layers[l];
       FusedLayer& fl = fn.layer[l];
-      fl.W = plan.shape16 ? d.wp3_16 : x3 ? d.wp3 : d.wp; fl.K = d.in_dim; fl.N = d.out_dim; fl.scale = d.scale; fl.shift = d.shift;
+      fl.W = plan.pair16 ? d.wp2_16 : plan.shape16 ? d.wp3_16 : x3 ? d.wp3 : d.wp;
+      fl.wexp = plan.pair16 ? d.wp2_16_inv : nullptr;
+      fl.K = d.in_dim; fl.N = d.out_dim; fl.scale = d.scale; fl.shift = d.shift;
       fl.slope = d.slope; fl.act = d.act;
     }
   }
   prof_mark(r.init_net ? P_INIT_MLP : P_MLP_FUSED, stream);
-  HIP_CHECK(x3 ? launch_mlp_fused_x3(fa, plan.shape16, stream) : launch_mlp_fused(fa, stream), "fused mlp launch");
+  HIP_CHECK(x3 ? launch_mlp_fused_x3(fa, plan.shape16, stream, plan.pair16) : launch_mlp_fused(fa, stream), "fused mlp launch");
   prof_mark(P_END, stream);   // close the dominant kernel's interval at its completion, not at the next launch
   return EMPOSE_OK;
 }

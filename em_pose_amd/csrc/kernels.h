@@ -82,6 +82,10 @@ namespace empose {
   X(mlp_fused16, 1)    /* fused update MLPs with mlp_x3 = 1: the products on v_mfma_f32_16x16x32_bf16 (mlp_fused_x3_kernel<16>, \
                              weights in the [k-step of 32][16-column tile][piece] order); 0: v_mfma_f32_32x32x16_bf16 \
                              (mlp_fused_x3_kernel<32>).  Equal to rounding, not to the bit */ \
+  X(mlp_pair16, 1)     /* fused update MLPs with mlp_x3 = 1 and mlp_fused16 != 0: every fp32 product from TWO f16 pieces per \
+                             operand under per-row / per-column power-of-two scales, three v_mfma_f32_16x16x32_f16 instead of six \
+                             of the bf16 instruction (mlp_fused_x3_kernel<PAIR16>, f16pair.h); 0: the three bf16 pieces of \
+                             mlp_fused_x3_kernel<16>.  Equal to rounding, not to the bit */ \
   X(lstm_chain16, 1)   /* large-batch LSTM steps with lstm_x3 = 1: lstm_chain16_x3.hip (v_mfma_f32_16x16x32_bf16) where the model \
                              has the LSTM_MID16 weight order; 0: lstm_chain_x3_kernel (32x32x16) */
 
@@ -306,6 +310,7 @@ struct FusedLayer {
   const float* W; int K, N;              // weights in fragment order (api_model.hip pack_fragments), K % 4 == 0, N <= FUSED_MAX_WIDTH
   const float* scale; const float* shift;
   float slope; int act;                  // 0 none, 1 PReLU
+  const float* wexp = nullptr;           // pair16 only: [N] the inverse of the power-of-two scale W's columns were packed with
 };
 struct FusedNet {
   const float* x; int ldx;
@@ -317,8 +322,10 @@ struct FusedMlpArgs { FusedNet net[2]; int count; int M; };
 hipError_t launch_mlp_fused(const FusedMlpArgs& args, hipStream_t stream);
 // The same launch with FusedLayer::W = three bf16 pieces per weight in bf16-MFMA fragment order (api_model.hip
 // pack_fragments_x3_raw): mlp_fused_x3.hip.  Hidden widths must be multiples of 64.  shape16: the kernel on
-// v_mfma_f32_16x16x32_bf16, W then in the order of pack_fragments_x3_16_raw.
-hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, bool shape16, hipStream_t stream);
+// v_mfma_f32_16x16x32_bf16, W then in the order of pack_fragments_x3_16_raw.  pair16: the kernel on two f16 pieces per
+// operand (f16pair.h; three v_mfma_f32_16x16x32_f16 per product instead of six), W in the order of
+// pack_fragments_pair16_raw with FusedLayer::wexp set.
+hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, bool shape16, hipStream_t stream, bool pair16 = false);
 // One linear layer C = A . W^T with A's row block resident in LDS and W (fragment order) streamed from L2.
 bool gemm_rows_applicable(int M, int N, int K);
 hipError_t launch_gemm_rows(const float* A, int lda, const float* Wp, float* C, int ldc, int M, int N, int K,

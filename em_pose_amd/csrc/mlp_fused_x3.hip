@@ -24,7 +24,10 @@
 //     k-steps deep; 12 KB per wave and k-step.
 //   * one wave per SIMD (132 KB of LDS per workgroup), as everything in this tree that issues the bf16 32x32x16 MFMA
 //     (scripts/dev/bf16_hazard_repro.md).
+// The default form since option mlp_pair16 is p16_layer below: TWO f16 pieces per operand under power-of-two scales
+// (f16pair.h), three products instead of six, the same workgroup.
 #include "bf16x3.h"
+#include "f16pair.h"
 #include "gemm_epilogue.h"
 #include "stage_block.h"
 
@@ -630,6 +633,342 @@ __device__ __forceinline__ void x16_layer(const FusedNet& net, const FusedLayer&
   }
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The same layer with every fp32 product formed from TWO f16 pieces per operand (f16pair.h; option mlp_pair16): three
+// v_mfma_f32_16x16x32_f16 per accumulator and k-step instead of six of the bf16 instruction -- same shape, rate and
+// fragment layout as x16_layer's, half the executed matrix work.  x16_layer's skeleton (64 rows, four waves, column split
+// for wide layers, K split up to 128 columns, weights from L2 into registers, no barrier in the K loop, results through
+// LDS, the last layer out by the coalesced copy), and what differs:
+//   * a (hi, lo) pair is 4 bytes, the size of the fp32 it replaces, so the activation buffer holds FINISHED pieces: two
+//     f16 planes [64][PLD], a lane's A fragment of a piece is one ds_read_b128 and the K loop has no split, no VALU at
+//     all.  PLD = 528 halves: a row is 66 16-byte slots, and 66 = 2 (mod 16) spreads each of the ds_read_b128's lane
+//     groups (rows 0-3, 12-15 of one k quarter with rows 4-11 of the next) over all 16 slots of a bank row: conflict-free;
+//   * the pieces of a row need the row's scale, the scale the row's largest magnitude: the epilogue keeps its results in
+//     registers, reduces the maxima (in the lane, over the 16 lanes of a row, over the four waves by an LDS atomic on a
+//     64-word array), and writes the pieces after ONE more barrier than x16_layer has.  The K-split layers need neither the
+//     atomic nor the barrier: their reduction already has a row's columns in 16 adjacent lanes.  Two arrays of maxima
+//     alternate by layer: the scale a layer's input was packed with is undone in that layer's epilogue;
+//   * two adjacent lanes exchange half of their values, so that each writes (column, column + 1) of two rows as one word:
+//     as many LDS writes as x16_layer's fp32 results took;
+//   * weights in the order of api_model.hip pack_fragments_pair16_raw: [k-step of 32][16-column tile][piece] -> 1 KB, with
+//     the columns' inverse scales beside them (FusedLayer::wexp).  A chunk is one column tile's 12 MFMAs with one A
+//     fragment of the next step and the two weight fragments of the tile just finished, for the step AFTER the next: the
+//     registers the third piece and the raw values gave back hold a second set of weights, so a fragment is asked for
+//     1 7/8 steps (~2,900 cycles, as before) ahead of its use although a step is half as long;
+//   * the last layer leaves fp32 results in the same memory at x16_layer's stride.
+namespace fx {
+constexpr int PLD = FUSED_MAX_WIDTH + 16;                       // halves per row of a piece plane
+constexpr int PLANE_BYTES = BM * PLD * 2;
+constexpr size_t LDS_BYTES_P = (size_t)2 * PLANE_BYTES + 2 * BM * sizeof(unsigned);   // + the two arrays of row maxima
+static_assert((size_t)2 * PLANE_BYTES >= (size_t)BM * LDA * sizeof(float), "the last layer's fp32 results fit");
+static_assert((size_t)2 * PLANE_BYTES >= (size_t)4 * BM * 128 * sizeof(float), "the K-split partial sums fit");
+}  // namespace fx
+
+// A lane's four scaled values of one (row tile, column tile) -- rows e = 0 .. 3 of column c -- go out as pieces: the even
+// lane takes rows 0, 1 and the odd lane rows 2, 3 of the columns (c & ~1, c | 1) of both.  `row_base`: the lane's row 0.
+__device__ __forceinline__ void p16_put4(char* lds, int row_base, int col, float v0, float v1, float v2, float v3) {
+  const bool odd = col & 1;
+  const float r0 = __shfl_xor(odd ? v0 : v2, 1), r1 = __shfl_xor(odd ? v1 : v3, 1);
+  unsigned h0, l0, h1, l1;
+  pair16::split_pair(odd ? r0 : v0, odd ? v2 : r0, h0, l0);
+  pair16::split_pair(odd ? r1 : v1, odd ? v3 : r1, h1, l1);
+  char* p = lds + ((row_base + (odd ? 2 : 0)) * fx::PLD + (col & ~1)) * 2;
+  *reinterpret_cast<unsigned*>(p) = h0;
+  *reinterpret_cast<unsigned*>(p + fx::PLANE_BYTES) = l0;
+  *reinterpret_cast<unsigned*>(p + fx::PLD * 2) = h1;
+  *reinterpret_cast<unsigned*>(p + fx::PLD * 2 + fx::PLANE_BYTES) = l1;
+}
+
+// Layer 0's input: row-major x[M][ldx], rows m0 .. m0 + 63, columns [0, K0) -> the piece planes, columns [K0, kpad) zero;
+// rows past M - 1 repeat row M - 1 (never stored).  16 lanes share a row (256-byte runs), a thread holds its 4 rows x
+// kpad / 64 chunks of 16 bytes in registers -- all loads in flight (stage_block.h) -- until the row maxima are known.
+__device__ __forceinline__ void p16_stage(const float* x, int ldx, int m0, int M, int K0, int kpad, char* lds, unsigned* mx) {
+  const int tid = threadIdx.x, l15 = tid & 15, rg = tid >> 4;
+  const int k4 = K0 >> 2, nu = kpad >> 6;       // nu <= 8: kpad <= FUSED_MAX_WIDTH
+  const int r_max = M - 1 - m0;
+  const stage::gbyte_t xb = (stage::gbyte_t)(x + (size_t)m0 * ldx);
+  const unsigned ldx4 = (unsigned)ldx * 4u;
+  f32x4 v[4][8];
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    const int row = rg + 16 * rr, rc = row < r_max ? row : r_max;
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (u < nu) {                             // wave-uniform
+        const int c = l15 + 16 * u, cc = c < k4 ? c : k4 - 1;
+        v[rr][u] = *(stage::gvec_t)(xb + ((unsigned)rc * ldx4 + (unsigned)cc * 16u));
+      }
+  }
+#pragma unroll
+  for (int rr = 0; rr < 4; ++rr) {
+    const int row = rg + 16 * rr;
+    unsigned m = 0u;
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (u < nu) {
+        if (l15 + 16 * u >= k4) v[rr][u] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const unsigned b = pair16::finite_abs_bits(v[rr][u][e]);
+          m = b > m ? b : m;
+        }
+      }
+    m = pair16::max16(m);
+    if (l15 == 0) mx[row] = m;
+    const float s = pair16::pow2(pair16::scale_exp(m));
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (u < nu) {
+        typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+        unsigned h0, l0, h1, l1;
+        pair16::split_pair(v[rr][u][0] * s, v[rr][u][1] * s, h0, l0);
+        pair16::split_pair(v[rr][u][2] * s, v[rr][u][3] * s, h1, l1);
+        char* p = lds + (row * fx::PLD + (l15 + 16 * u) * 4) * 2;
+        *reinterpret_cast<u32x2_t*>(p) = u32x2_t{h0, h1};
+        *reinterpret_cast<u32x2_t*>(p + fx::PLANE_BYTES) = u32x2_t{l0, l1};
+      }
+  }
+}
+
+// `lds`: the two piece planes, columns [0, 32 KS2) of the layer's input valid or zero; `mx_in`: the row maxima that input
+// was scaled by, `mx_out`: those of this layer's results (left for the next layer).
+template <int NCT, bool KSPLIT>
+__device__ __forceinline__ void p16_layer(const FusedNet& net, const FusedLayer& L, int M, int m0, char* lds,
+                                          const unsigned* mx_in, unsigned* mx_out, int wave, bool last) {
+  constexpr int RT = 4, NCHUNK = 8;
+  static_assert(NCT >= 1 && NCT <= 8, "a wave owns up to 128 columns");
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int l15 = lane & 15, lq = lane >> 4;
+  const int K = L.K, N = L.N;
+  const int NT16 = (N + 15) / 16;
+  const int KS2 = ((K + 31) / 32 + 1) & ~1;                 // k-steps of the packed weights (zero-padded to whole pairs)
+  const int col_tile0 = KSPLIT ? 0 : wave * NCT;
+  const int g0 = KSPLIT ? wave : 0, gs = KSPLIT ? 4 : 1;
+  const int n_w = KSPLIT ? (KS2 - wave + 3) / 4 : (col_tile0 < NT16 ? KS2 : 0);
+  auto gk = [&](int i) { const int g = g0 + i * gs; return g < KS2 ? g : KS2 - 1; };   // (look-ahead past the end: clamped)
+  const unsigned b_lane = (unsigned)lane * 16u;
+  auto tile_off = [&](int j) { return (size_t)(col_tile0 + j < NT16 ? col_tile0 + j : NT16 - 1) * 2048; };
+  fx_gbyte_t wb = (fx_gbyte_t)L.W;
+  const size_t step_bytes = (size_t)NT16 * 2048;
+  const char* a_rd = lds + (l15 * fx::PLD + lq * 8) * 2;
+  float* const act = reinterpret_cast<float*>(lds);         // the same memory as fp32, once the K loop has read its last
+  constexpr int lda = fx::LDA;
+
+  if (tid < fx::BM) mx_out[tid] = 0u;                       // (last read before the previous layer's final barrier)
+
+  f32x4 acc[RT][NCT];
+  u32x4_t ap[2][RT][2];            // A pieces of the step being multiplied and of the next one, in flight from LDS
+  u32x4_t fb[2][NCT][2];           // weight pieces of two steps: tile j multiplied in chunk j, asked for again in chunk j + 1
+
+  auto bload = [&](u32x4_t (&b)[2], int g, int j) {
+    fx_gbyte_t p = wb + (size_t)g * step_bytes + tile_off(j) + b_lane;
+    b[0] = *(x3_gvec_t)p;
+    b[1] = *(x3_gvec_t)(p + 1024);
+  };
+  auto aread = [&](u32x4_t (&a)[RT][2], int g, int c) {     // slot c = (row tile c / 2, piece c % 2) of step g
+    a[c / 2][c % 2] = *reinterpret_cast<const u32x4_t*>(a_rd + (c / 2) * 16 * fx::PLD * 2 + (c % 2) * fx::PLANE_BYTES + g * 64);
+  };
+  // the wave's step number i: multiplies ap_cur by fb_cur, fetches ap_nxt; fb_oth holds the next step's weights
+  auto step = [&](int i, const u32x4_t (&ap_cur)[RT][2], u32x4_t (&ap_nxt)[RT][2], u32x4_t (&fb_cur)[NCT][2],
+                  u32x4_t (&fb_oth)[NCT][2]) {
+    const int g1 = gk(i + 1), g2 = gk(i + 2);
+#pragma unroll
+    for (int c = 0; c < NCHUNK; ++c) {
+      if (c == 0) {
+        if constexpr (NCT == 8) bload(fb_oth[NCT - 1], g1, NCT - 1);   // (the previous step's last tile)
+      } else if (c - 1 < NCT) {
+        bload(fb_cur[c - 1 < NCT ? c - 1 : 0], g2, c - 1 < NCT ? c - 1 : 0);
+      }
+      aread(ap_nxt, g1, c);
+      if (c < NCT) {
+        const int j = c < NCT ? c : 0;
+#pragma unroll
+        for (int mm = 0; mm < 3 * RT; ++mm) {
+          const int t = mm / RT, r = mm % RT;
+          acc[r][j] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8_t, ap_cur[r][pair16::PA[t]]),
+                                                             __builtin_bit_cast(f16x8_t, fb_cur[j][pair16::PB[t]]), acc[r][j], 0, 0, 0);
+        }
+#pragma unroll
+        for (int mm = 0; mm < 3 * RT; ++mm) { SGB(SG_MFMA, 1); if (mm < 3) SGB(SG_VMEM_RD | SG_DS_RD, 1); }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+
+#pragma unroll
+  for (int r = 0; r < RT; ++r)
+#pragma unroll
+    for (int j = 0; j < NCT; ++j) acc[r][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  // ---- prologue: the weights of the first two steps (but the tile the first chunk asks for), the A pieces of the first
+#pragma unroll
+  for (int j = 0; j < NCT; ++j) bload(fb[0][j], gk(0), j);
+#pragma unroll
+  for (int j = 0; j < (NCT == 8 ? NCT - 1 : NCT); ++j) bload(fb[1][j], gk(1), j);
+#pragma unroll
+  for (int c = 0; c < NCHUNK; ++c) aread(ap[0], gk(0), c);
+  // the first pair is peeled so that the loop header merges two states with the same outstanding loads (mlp_fused.hip)
+  int i = 0;
+  if (n_w >= 2) {
+    step(0, ap[0], ap[1], fb[0], fb[1]);
+    step(1, ap[1], ap[0], fb[1], fb[0]);
+    i = 2;
+  }
+  for (; i + 2 <= n_w; i += 2) {
+    step(i, ap[0], ap[1], fb[0], fb[1]);
+    step(i + 1, ap[1], ap[0], fb[1], fb[0]);
+  }
+  if (i < n_w) step(i, ap[0], ap[1], fb[0], fb[1]);
+
+  const float e_slope = L.act == 1 ? L.slope : 1.f;         // slope 1: no activation (exact identity)
+  const float* const scale = L.scale;
+  const float* const shift = L.shift;
+  const float* const wexp = L.wexp;
+  if constexpr (!KSPLIT) {
+    float e_ci[NCT], e_sc[NCT], e_sh[NCT];
+#pragma unroll
+    for (int j = 0; j < NCT; ++j) {
+      const int n = (col_tile0 + j) * 16 + l15;
+      const bool real = n < N;
+      const int nc = real ? n : N - 1;
+      e_ci[j] = wexp[nc];
+      e_sc[j] = real ? (scale ? scale[nc] : 1.f) : 0.f;
+      e_sh[j] = real ? (shift ? shift[nc] : 0.f) : 0.f;
+    }
+    const bool mine = col_tile0 < NT16;                     // (wave-uniform; a tile past N gives zeros: e_sc, e_sh)
+    unsigned m[RT][4];
+#pragma unroll
+    for (int r = 0; r < RT; ++r)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float ri = pair16::pow2(-pair16::scale_exp(mx_in[r * 16 + 4 * lq + e]));
+        m[r][e] = 0u;
+#pragma unroll
+        for (int j = 0; j < NCT; ++j) {
+          const float y = ((acc[r][j][e] * e_ci[j]) * ri) * e_sc[j] + e_sh[j];
+          acc[r][j][e] = y >= 0.f ? y : y * e_slope;
+          const unsigned b = pair16::finite_abs_bits(acc[r][j][e]);
+          m[r][e] = b > m[r][e] ? b : m[r][e];
+        }
+      }
+    __syncthreads();   // every wave has read its last A pieces: the buffer may be overwritten
+    if (last) {
+      if (mine) {
+#pragma unroll
+        for (int j = 0; j < NCT; ++j) {
+          if (col_tile0 + j >= NT16) continue;
+          const int n = (col_tile0 + j) * 16 + l15;
+#pragma unroll
+          for (int r = 0; r < RT; ++r)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) act[(r * 16 + 4 * lq + e) * lda + n] = acc[r][j][e];
+        }
+      }
+    } else {
+      if (mine) {
+#pragma unroll
+        for (int r = 0; r < RT; ++r)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const unsigned mr = pair16::max16(m[r][e]);
+            if (l15 == 0) atomicMax(&mx_out[r * 16 + 4 * lq + e], mr);
+          }
+      }
+      __syncthreads();   // the rows' maxima are complete
+      if (mine) {
+#pragma unroll
+        for (int r = 0; r < RT; ++r) {
+          float s[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) s[e] = pair16::pow2(pair16::scale_exp(mx_out[r * 16 + 4 * lq + e]));
+#pragma unroll
+          for (int j = 0; j < NCT; ++j)
+            p16_put4(lds, r * 16 + 4 * lq, (col_tile0 + j) * 16 + l15, acc[r][j][0] * s[0], acc[r][j][1] * s[1],
+                     acc[r][j][2] * s[2], acc[r][j][3] * s[3]);
+        }
+      }
+    }
+  } else {
+    constexpr int NC = NCT * 16;   // partial sums [wave][64][NC]
+    __syncthreads();   // every wave has read its last A pieces: the buffer is free for the partial sums
+    {
+      float* pw = act + ((size_t)wave * fx::BM + 4 * lq) * NC + l15;
+#pragma unroll
+      for (int j = 0; j < NCT; ++j)
+#pragma unroll
+        for (int r = 0; r < RT; ++r)
+#pragma unroll
+          for (int e = 0; e < 4; ++e) pw[(r * 16 + e) * NC + j * 16] = acc[r][j][e];
+    }
+    __syncthreads();
+    // thread (c16 = tid & 15, r16 = tid >> 4) takes column c16 of every column tile and rows r16, r16 + 16, ..: a row's
+    // columns lie in 16 adjacent lanes
+    const int c16 = tid & 15, r16 = tid >> 4;
+    float y[NCT][4];
+    unsigned m[4] = {0u, 0u, 0u, 0u};
+    float ri[4];
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) ri[rr] = pair16::pow2(-pair16::scale_exp(mx_in[r16 + 16 * rr]));
+#pragma unroll
+    for (int j = 0; j < NCT; ++j) {
+      const int n = j * 16 + c16;
+      const bool real = n < N;
+      const int nc = real ? n : N - 1;
+      const float ci = wexp[nc];
+      const float sc = real ? (scale ? scale[nc] : 1.f) : 0.f, sh = real ? (shift ? shift[nc] : 0.f) : 0.f;
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        const float* ps = act + (r16 + 16 * rr) * NC + n;
+        const float sum = ((ps[0] + ps[fx::BM * NC]) + ps[2 * fx::BM * NC]) + ps[3 * fx::BM * NC];
+        const float v = ((sum * ci) * ri[rr]) * sc + sh;
+        y[j][rr] = v >= 0.f ? v : v * e_slope;
+        const unsigned b = pair16::finite_abs_bits(y[j][rr]);
+        m[rr] = b > m[rr] ? b : m[rr];
+      }
+    }
+    __syncthreads();   // the partial sums are read: the results take their place
+    if (last) {
+#pragma unroll
+      for (int j = 0; j < NCT; ++j)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) act[(r16 + 16 * rr) * lda + j * 16 + c16] = y[j][rr];
+    } else {
+      float s[4];
+#pragma unroll
+      for (int rr = 0; rr < 4; ++rr) {
+        m[rr] = pair16::max16(m[rr]);
+        if (c16 == 0) mx_out[r16 + 16 * rr] = m[rr];
+        s[rr] = pair16::pow2(pair16::scale_exp(m[rr]));
+      }
+      // (lane pairs as in p16_put4, the four values of a lane now 16 rows apart)
+      const bool odd = c16 & 1;
+#pragma unroll
+      for (int j = 0; j < NCT; ++j) {
+        const float v0 = y[j][0] * s[0], v1 = y[j][1] * s[1], v2 = y[j][2] * s[2], v3 = y[j][3] * s[3];
+        const float q0 = __shfl_xor(odd ? v0 : v2, 1), q1 = __shfl_xor(odd ? v1 : v3, 1);
+        unsigned h0, l0, h1, l1;
+        pair16::split_pair(odd ? q0 : v0, odd ? v2 : q0, h0, l0);
+        pair16::split_pair(odd ? q1 : v1, odd ? v3 : q1, h1, l1);
+        char* p = lds + ((r16 + (odd ? 32 : 0)) * fx::PLD + j * 16 + (c16 & ~1)) * 2;
+        *reinterpret_cast<unsigned*>(p) = h0;
+        *reinterpret_cast<unsigned*>(p + fx::PLANE_BYTES) = l0;
+        *reinterpret_cast<unsigned*>(p + 16 * fx::PLD * 2) = h1;
+        *reinterpret_cast<unsigned*>(p + 16 * fx::PLD * 2 + fx::PLANE_BYTES) = l1;
+      }
+    }
+  }
+  __syncthreads();
+  if (last) {          // (no MFMA of the workgroup is in flight: every accumulator was read before the barrier)
+    float* const out = net.out;
+    const int ld_out = net.ld_out;
+    const int rows = M - m0 < fx::BM ? M - m0 : fx::BM;
+    for (int idx = tid; idx < rows * N; idx += fx::NT) {
+      const int r = idx / N, n = idx - r * N;
+      out[(size_t)(m0 + r) * ld_out + n] = act[r * lda + n];
+    }
+  }
+}
+
 __global__ __launch_bounds__(fx::NT) void mlp_fused_x3c_kernel(FusedMlpArgs args) {
   X3_EXCLUSIVE_SIMD();
   using namespace fx;
@@ -652,17 +991,41 @@ __global__ __launch_bounds__(fx::NT) void mlp_fused_x3c_kernel(FusedMlpArgs args
   }
 }
 
-// SHAPE: the bf16 MFMA the products run on -- 32: v_mfma_f32_32x32x16_bf16 (x3_layer), 16: v_mfma_f32_16x16x32_bf16
-// (x16_layer); each with its own order of the packed weights.  One name for both, as the profile readers know it.
+// SHAPE: the MFMA the products run on -- 32: v_mfma_f32_32x32x16_bf16 (x3_layer), 16: v_mfma_f32_16x16x32_bf16
+// (x16_layer), PAIR16: v_mfma_f32_16x16x32_f16 on two f16 pieces (p16_layer); each with its own order of the packed
+// weights.  One name for all, as the profile readers know it.
+constexpr int PAIR16 = 2;
 template <int SHAPE>
 __global__ __launch_bounds__(fx::NT) void mlp_fused_x3_kernel(FusedMlpArgs args) {
   X3_EXCLUSIVE_SIMD();
   using namespace fx;
-  static_assert(SHAPE == 32 || SHAPE == 16, "the two shapes of the bf16 MFMA");
+  static_assert(SHAPE == 32 || SHAPE == 16 || SHAPE == PAIR16, "the two shapes of the bf16 MFMA, or f16 pairs");
   extern __shared__ __attribute__((aligned(16))) float act[];
   const FusedNet& net = args.net[blockIdx.y];
   const int M = args.M, m0 = blockIdx.x * BM;
   const int tid = threadIdx.x;
+  if constexpr (SHAPE == PAIR16) {
+    char* const lds = reinterpret_cast<char*>(act);
+    unsigned* const mx = reinterpret_cast<unsigned*>(lds + 2 * PLANE_BYTES);   // [2][64] row maxima, alternating by layer
+    {
+      const int K0 = net.layer[0].K;          // K0 % 4 == 0
+      p16_stage(net.x, net.ldx, m0, M, K0, (K0 + 63) / 64 * 64, lds, mx);
+    }
+    __syncthreads();
+    for (int l = 0; l < net.n_layers; ++l) {
+      const FusedLayer& L = net.layer[l];
+      const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+      const bool last = l == net.n_layers - 1;
+      const unsigned* mx_in = mx + (l & 1) * BM;
+      unsigned* mx_out = mx + ((l + 1) & 1) * BM;
+      if (L.N <= 16) p16_layer<1, true>(net, L, M, m0, lds, mx_in, mx_out, wave, last);
+      else if (L.N <= 64) p16_layer<4, true>(net, L, M, m0, lds, mx_in, mx_out, wave, last);
+      else if (L.N <= 80) p16_layer<5, true>(net, L, M, m0, lds, mx_in, mx_out, wave, last);
+      else if (L.N <= 128) p16_layer<8, true>(net, L, M, m0, lds, mx_in, mx_out, wave, last);
+      else p16_layer<8, false>(net, L, M, m0, lds, mx_in, mx_out, wave, last);
+    }
+    return;
+  }
   {
     const int K0 = net.layer[0].K;          // K0 % 4 == 0
     const int kpad = (K0 + 63) / 64 * 64;   // whole quads of k-steps of 16 = whole pairs of k-steps of 32
@@ -687,11 +1050,12 @@ __global__ __launch_bounds__(fx::NT) void mlp_fused_x3_kernel(FusedMlpArgs args)
   }
 }
 
-hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, bool shape16, hipStream_t stream) {
+hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, bool shape16, hipStream_t stream, bool pair16) {
   dim3 grid((args.M + fx::BM - 1) / fx::BM, args.count);
   if (options().mlp_x3 >= 2) {   // opt-in: the cooperative split (measured slower, see x3c_layer)
     return launch_lds(mlp_fused_x3c_kernel, grid, dim3(fx::NT), fx::LDS_BYTES_C, stream, args);
   }
+  if (pair16) return launch_lds(mlp_fused_x3_kernel<PAIR16>, grid, dim3(fx::NT), fx::LDS_BYTES_P, stream, args);
   if (shape16) return launch_lds(mlp_fused_x3_kernel<16>, grid, dim3(fx::NT), fx::LDS_BYTES, stream, args);
   return launch_lds(mlp_fused_x3_kernel<32>, grid, dim3(fx::NT), fx::LDS_BYTES, stream, args);
 }

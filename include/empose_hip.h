@@ -73,7 +73,11 @@ const char* empose_arch(void);
  * variant, measured slower; 3 = force the kernel on the 16x16x32 form of the bf16 instruction), "lstm_chain16" (those
  * steps with lstm_x3 = 1 on the 16x16x32 form of the bf16 instruction -- equal to the 32x32x16 form to rounding, not to the
  * bit; measured 3 to 6 % faster per launch: 1 [default]; 0 = the 32x32x16 form), "mlp_fused16" (the same choice for the
- * fused update MLPs with mlp_x3 = 1; measured 4 to 8 % faster per launch: 1 [default]; 0 = the 32x32x16 form), "rows_x3" (the
+ * fused update MLPs with mlp_x3 = 1; measured 4 to 8 % faster per launch: 1 [default]; 0 = the 32x32x16 form), "mlp_pair16"
+ * (the fused update MLPs with mlp_x3 = 1 and mlp_fused16 != 0 form every fp32 product from TWO f16 pieces per operand
+ * under a power-of-two scale per activation row and per weight column -- three f16 matrix-core products instead of six
+ * bf16 ones, as accurate against float64, equal to rounding and not to the bit; measured 17 % faster per launch:
+ * 1 [default]; 0 = the three bf16 pieces), "rows_x3" (the
  * same arithmetic for the row-block products with fused prologue / epilogue: the blend products of the frame-per-lane
  * SMPL path and the stacked init heads; 0 = the fp32 MFMA instruction), "train_cols" (training at up to 512 rows: a
  * layer's product + BatchNorm + PReLU as one launch, forward and backward, both update networks side by side -- see

@@ -8,12 +8,14 @@ from em_pose_amd.helpers.configuration import lgd_config
 from em_pose_amd.nn.models import create_model
 dev = torch.device('cuda:0')
 T = int(os.environ.get('T', 32768))
+AB_OPTION = os.environ.get('AB_OPTION', 'mlp_fused16')   # the option --ab alternates between 0 and 1
 torch.manual_seed(0)
 net = create_model(lgd_config(12, True, 4), SMPLLayer(synthetic.make_model())).to(dev).eval()
 h = net._ensure_handle(dev)
 lib = _lib.lib()
 if '--ab' in sys.argv:
-    # Interleaved A/B over option mlp_fused16 (the 16x16x32 against the 32x32x16 form of the bf16 MFMA) on RANDOM inputs --
+    # Interleaved A/B over one option (default mlp_fused16: the 16x16x32 against the 32x32x16 form of the bf16 MFMA;
+    # AB_OPTION=mlp_pair16: two f16 pieces against three bf16 pieces) on RANDOM inputs --
     # zeros hide the clock the chip holds under matrix load: rounds of 50 back-to-back launches per arm, arms alternating.
     x = torch.randn(T, 296, device=dev)
     dp, ds = torch.empty(T, 66, device=dev), torch.empty(T, 10, device=dev)
@@ -24,7 +26,7 @@ if '--ab' in sys.argv:
     us = {0: [], 1: []}
     for rnd in range(9):
         for arm in ((0, 1) if rnd % 2 == 0 else (1, 0)):
-            _lib.check(lib.empose_set_option(b'mlp_fused16', arm))
+            _lib.check(lib.empose_set_option(AB_OPTION.encode(), arm))
             for _ in range(5): run()
             e0.record()
             for _ in range(50): run()
@@ -34,7 +36,7 @@ if '--ab' in sys.argv:
     lib.empose_reset_options()
     for arm in (0, 1):
         v = sorted(us[arm])
-        print('mlp_fused16=%d T=%d: median %.1f us/launch (min %.1f, max %.1f, %d rounds of 50)'
+        print(AB_OPTION + '=%d T=%d: median %.1f us/launch (min %.1f, max %.1f, %d rounds of 50)'
               % (arm, T, v[len(v) // 2], v[0], v[-1], len(v)))
     sys.exit(0)
 flush = torch.empty(160 * 1024 * 1024, device=dev)  # 640 MB: evicts L2 and the 256 MB Infinity Cache
