@@ -136,11 +136,8 @@ int upload_bf16(std::vector<void*>& allocs, const std::vector<unsigned short>& b
 struct Dense {
   int in_dim = 0, out_dim = 0;
   float* w = nullptr;      // [out][in]
-  float* wp = nullptr;     // the same weights in MFMA fragment order (mlp_fused.hip), only for MLP layers
-  float* wp3 = nullptr;    // ... and as three bf16 pieces per weight in bf16-MFMA fragment order (mlp_fused_x3.hip)
-  float* wp3_16 = nullptr; // ... and the same pieces in the order of the 16x16x32 instruction (mlp_fused_x3_kernel<16>)
-  float* wp2_16 = nullptr; // ... and as two scaled f16 pieces per weight in that order (mlp_fused_x3_kernel<PAIR16>, f16pair.h)
-  float* wp2_16_inv = nullptr; // [out] the inverse of the power-of-two scale each output column's pieces carry
+  float* frag[FUSED_FORMS] = {};   // the same weights in the fragment order of each FusedForm (kernels.h), only for MLP layers
+  float* wexp = nullptr;   // [out] the inverse of the power-of-two scale each output column's pair16 pieces carry
   float* scale = nullptr;  // nullptr => 1
   float* shift = nullptr;  // bias (and folded BN)
   int act = 0;

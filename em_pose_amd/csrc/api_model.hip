@@ -153,44 +153,47 @@ int pack_fragments_raw(std::vector<void*>& allocs, const float* weight, int N, i
   return upload(allocs, buf.data(), buf.size(), out);
 }
 
-// The same weights as three bf16 pieces each (split3) in the order v_mfma_f32_32x32x16_bf16 consumes them
-// (mlp_fused_x3.hip): for every k-step of 16, every 32-column tile and every piece one 1 KB wave fragment -- lane
-// (n = lane & 31, half = lane >> 5) owns piece[tile * 32 + n][ks * 16 + half * 8 .. + 7]; k-steps padded with zeros to a
-// multiple of four (the kernel walks quads).  6 bytes per weight.
+// The order the piece kernels of mlp_fused_x3.hip consume their weights in: fragment f = ks * NT + tile of
+// [k-steps of S][tiles of C columns], and in it lane owns row[tile * C + (lane mod C)], k0 = ks * S + (lane / C) * 8 .. + 7.
+// C, S = 32, 16 for v_mfma_f32_32x32x16_bf16 and 16, 32 for the 16x16x32 instructions.  The k-steps are padded with zeros
+// to a multiple of PAD (the steps the kernel's loop walks at a time: the padding starts past K, so nothing is written
+// there); columns past N and k past K are zero too, so a wave's fragment is one coalesced 1 KB read per piece and ragged
+// K needs no masking on this operand.
+struct FragOrder {
+  int C, S, N, K, NT, KSP;
+  FragOrder(int C_, int S_, int PAD, int N_, int K_)
+      : C(C_), S(S_), N(N_), K(K_), NT((N_ + C_ - 1) / C_), KSP(((K_ + S_ - 1) / S_ + PAD - 1) & ~(PAD - 1)) {}
+  size_t n_frag() const { return (size_t)KSP * NT; }
+  bool owns(size_t f, int lane, int* n, int* k0) const {
+    *n = (int)(f % NT) * C + lane % C;
+    *k0 = (int)(f / NT) * S + lane / C * 8;
+    return *n < N;
+  }
+};
+// The weights as three bf16 pieces each (split3) in that order: [fragment][piece] -> 1 KB, 6 bytes per weight.
+int pack_x3_order(std::vector<void*>& allocs, const float* weight, const FragOrder& o, float** out) {
+  return upload_bf16(allocs, pack_fragments_x3(o.n_frag(), o.K, [&](size_t f, int lane, const float** row, int* k0) {
+    int n;
+    if (!o.owns(f, lane, &n, k0)) return false;
+    *row = weight + (size_t)n * o.K;
+    return true;
+  }), out);
+}
+// ... for v_mfma_f32_32x32x16_bf16 (mlp_fused_x3_kernel<32>, whose loop walks quads of k-steps; also x3_rows_layer's)
 int pack_fragments_x3_raw(std::vector<void*>& allocs, const float* weight, int N, int K, float** out) {
-  const int KS = (K + 15) / 16, NT = (N + 31) / 32;
-  const int KS4 = (KS + 3) & ~3;
-  return upload_bf16(allocs, pack_fragments_x3((size_t)KS4 * NT, K, [&](size_t f, int lane, const float** row, int* k0) {
-    const int ks = (int)(f / NT), n = (int)(f % NT) * 32 + (lane & 31);
-    if (n >= N) return false;
-    *row = weight + (size_t)n * K;
-    *k0 = ks * 16 + (lane >> 5) * 8;      // (the padding k-steps start past K: nothing written)
-    return true;
-  }), out);
+  return pack_x3_order(allocs, weight, FragOrder(32, 16, 4, N, K), out);
 }
-
-// The same pieces in the order v_mfma_f32_16x16x32_bf16 consumes them (mlp_fused_x3_kernel<16>): for every k-step of 32,
-// every 16-column tile and every piece one 1 KB wave fragment -- lane (n = lane & 15, q = lane >> 4) owns
-// piece[tile * 16 + n][ks * 32 + q * 8 .. + 7]; k-steps padded with zeros to an even count (the kernel walks pairs).
+// ... and for v_mfma_f32_16x16x32_bf16 (mlp_fused_x3_kernel<16>, whose loop walks pairs)
 int pack_fragments_x3_16_raw(std::vector<void*>& allocs, const float* weight, int N, int K, float** out) {
-  const int KS = (K + 31) / 32, NT = (N + 15) / 16;
-  const int KS2 = (KS + 1) & ~1;
-  return upload_bf16(allocs, pack_fragments_x3((size_t)KS2 * NT, K, [&](size_t f, int lane, const float** row, int* k0) {
-    const int ks = (int)(f / NT), n = (int)(f % NT) * 16 + (lane & 15);
-    if (n >= N) return false;
-    *row = weight + (size_t)n * K;
-    *k0 = ks * 32 + (lane >> 4) * 8;      // (k past K, the padding k-step included: nothing written)
-    return true;
-  }), out);
+  return pack_x3_order(allocs, weight, FragOrder(16, 32, 2, N, K), out);
 }
 
-// The weights as TWO f16 pieces each (f16pair.h) in the same order: [k-step of 32][16-column tile][piece] -> 1 KB, 2 KB
-// per tile and step.  Output column n's pieces are those of W[n][:] 2^e(n), e(n) from the column's largest magnitude;
-// inv[n] = 2^-e(n) is what the kernel's epilogue multiplies the accumulator by.  Zero padding as above.
+// The weights as TWO f16 pieces each (f16pair.h) in the order of the 16x16x32 instruction: [fragment][piece] -> 1 KB.
+// Output column n's pieces are those of W[n][:] 2^e(n), e(n) from the column's largest magnitude; inv[n] = 2^-e(n) is
+// what the kernel's epilogue multiplies the accumulator by.
 int pack_fragments_pair16_raw(std::vector<void*>& allocs, const float* weight, int N, int K, float** out, float** inv_out) {
-  const int KS = (K + 31) / 32, NT = (N + 15) / 16;
-  const int KS2 = (KS + 1) & ~1;
-  std::vector<unsigned short> buf((size_t)KS2 * NT * 2 * FRAG, 0);
+  const FragOrder o(16, 32, 2, N, K);
+  std::vector<unsigned short> buf(o.n_frag() * 2 * FRAG, 0);
   std::vector<float> inv(N, 1.f), sc(N, 1.f);
   for (int n = 0; n < N; ++n) {
     unsigned m = 0u;
@@ -202,33 +205,31 @@ int pack_fragments_pair16_raw(std::vector<void*>& allocs, const float* weight, i
     sc[n] = pair16::pow2(e);
     inv[n] = pair16::pow2(-e);
   }
-  for (int ks = 0; ks < KS; ++ks)
-    for (int nt = 0; nt < NT; ++nt)
-      for (int lane = 0; lane < 64; ++lane) {
-        const int n = nt * 16 + (lane & 15);
-        if (n >= N) continue;
-        for (int e = 0; e < 8; ++e) {
-          const int k = ks * 32 + (lane >> 4) * 8 + e;
-          if (k >= K) continue;
-          const float x = weight[(size_t)n * K + k] * sc[n];
-          const _Float16 hi = (_Float16)x;                       // round to nearest even
-          const _Float16 lo = (_Float16)(x - (float)hi);
-          const size_t at = ((size_t)ks * NT + nt) * 2 * FRAG + (size_t)lane * 8 + e;
-          buf[at] = __builtin_bit_cast(unsigned short, hi);
-          buf[at + FRAG] = __builtin_bit_cast(unsigned short, lo);
-        }
+  for (size_t f = 0; f < o.n_frag(); ++f)
+    for (int lane = 0; lane < 64; ++lane) {
+      int n, k0;
+      if (!o.owns(f, lane, &n, &k0)) continue;
+      for (int e = 0; e < 8 && k0 + e < K; ++e) {
+        const float x = weight[(size_t)n * K + k0 + e] * sc[n];
+        const _Float16 hi = (_Float16)x;                       // round to nearest even
+        const _Float16 lo = (_Float16)(x - (float)hi);
+        const size_t at = f * 2 * FRAG + (size_t)lane * 8 + e;
+        buf[at] = __builtin_bit_cast(unsigned short, hi);
+        buf[at + FRAG] = __builtin_bit_cast(unsigned short, lo);
       }
+    }
   TRY(upload_bf16(allocs, buf, out));
   return upload(allocs, inv.data(), inv.size(), inv_out);
 }
 
-// Every kernel's order is packed here, at creation: the options choose between them at run time, and the library does
+// Every form's order is packed here, at creation: the options choose between them at run time, and the library does
 // not allocate after creation (16 bytes per weight together).
 int pack_fragments(std::vector<void*>& allocs, const empose_dense_desc& d, Dense* out) {
-  TRY(pack_fragments_x3_raw(allocs, d.weight, d.out_dim, d.in_dim, &out->wp3));
-  TRY(pack_fragments_x3_16_raw(allocs, d.weight, d.out_dim, d.in_dim, &out->wp3_16));
-  TRY(pack_fragments_pair16_raw(allocs, d.weight, d.out_dim, d.in_dim, &out->wp2_16, &out->wp2_16_inv));
-  return pack_fragments_raw(allocs, d.weight, d.out_dim, d.in_dim, &out->wp);
+  auto frag = [&](FusedForm f) { return &out->frag[(int)f]; };
+  TRY(pack_fragments_x3_raw(allocs, d.weight, d.out_dim, d.in_dim, frag(FusedForm::x3_32)));
+  TRY(pack_fragments_x3_16_raw(allocs, d.weight, d.out_dim, d.in_dim, frag(FusedForm::x3_16)));
+  TRY(pack_fragments_pair16_raw(allocs, d.weight, d.out_dim, d.in_dim, frag(FusedForm::pair16), &out->wexp));
+  return pack_fragments_raw(allocs, d.weight, d.out_dim, d.in_dim, frag(FusedForm::fp32));
 }
 
 int pack_mlp(std::vector<void*>& allocs, const empose_mlp_desc& d, Mlp* out, int* hidden_max, int* any_skip) {
@@ -287,37 +288,32 @@ struct MlpRun {
 
 // Large batches: every layer of both nets in ONE launch (mlp_fused.hip); a workgroup keeps 128 rows through all the
 // layers. Needs enough row panels to fill the chip and layers no wider than the four 128-column waves.
-// x3: fp32 products from three bf16 pieces per operand on the bf16 matrix path (mlp_fused_x3.hip; fp32-equivalent, 2.7
-// times the fp32 instruction's rate): needs every hidden width to be whole quads of k-steps of the next layer.
-// shape16: that kernel on the 16x16x32 form of the instruction (option mlp_fused16; the kernel of mlp_x3 = 1 only).
-// pair16: the shape16 kernel's place taken by the one on two f16 pieces per operand (option mlp_pair16).
-struct MlpPlan { bool one_launch, x3, shape16, pair16; };
+// form (FusedForm, kernels.h): each piece form rests on the one before it --
+//   x3_32 (option mlp_x3): fp32 products from three bf16 pieces per operand on the bf16 matrix path (mlp_fused_x3.hip;
+//          fp32-equivalent, 2.7 times the fp32 instruction's rate): needs every hidden width to be whole quads of k-steps
+//          of the next layer;
+//   x3_16 (option mlp_fused16): that kernel on the 16x16x32 form of the instruction;
+//   pair16 (option mlp_pair16): its place taken by the kernel on two f16 pieces per operand.
+struct MlpPlan { bool one_launch; FusedForm form; };
 MlpPlan plan_mlps(const MlpRun& r) {
   const int L = r.nets[0]->n_layers;
-  MlpPlan p;
-  p.one_launch = options().mlp_fused != 0 && L <= FUSED_MAX_LAYERS && (long)((r.T + 63) / 64) * r.n_nets >= 256;
-  p.x3 = options().mlp_x3 != 0;
-  p.shape16 = options().mlp_x3 == 1 && options().mlp_fused16 != 0;
-  p.pair16 = options().mlp_pair16 != 0;
+  bool one_launch = options().mlp_fused != 0 && L <= FUSED_MAX_LAYERS && (long)((r.T + 63) / 64) * r.n_nets >= 256;
+  bool x3 = options().mlp_x3 != 0, shape16 = options().mlp_fused16 != 0, pair16 = options().mlp_pair16 != 0;
   for (int i = 0; i < r.n_nets; ++i) {
     const Mlp& net = *r.nets[i];
-    if (net.skip || net.layers[0].in_dim > FUSED_MAX_WIDTH) p.one_launch = false;   // no room for a block input
+    if (net.skip || net.layers[0].in_dim > FUSED_MAX_WIDTH) one_launch = false;   // no room for a block input
     for (int l = 0; l < L; ++l) {
       const Dense& d = net.layers[l];
-      if (d.out_dim > FUSED_MAX_WIDTH || d.act > 1) p.one_launch = false;
-      if (l + 1 < L && (d.out_dim % 64 != 0 || !d.wp3)) p.x3 = false;
-      if (!d.wp3_16) p.shape16 = false;
-      if (!d.wp2_16 || !d.wp2_16_inv) p.pair16 = false;
+      if (d.out_dim > FUSED_MAX_WIDTH || d.act > 1) one_launch = false;
+      if (l + 1 < L && (d.out_dim % 64 != 0 || !d.frag[(int)FusedForm::x3_32])) x3 = false;
+      if (!d.frag[(int)FusedForm::x3_16]) shape16 = false;
+      if (!d.frag[(int)FusedForm::pair16] || !d.wexp) pair16 = false;
     }
   }
-  p.x3 = p.x3 && p.one_launch;
-  p.shape16 = p.shape16 && p.x3;
-  p.pair16 = p.pair16 && p.shape16;
-  return p;
+  return {one_launch, !x3 ? FusedForm::fp32 : !shape16 ? FusedForm::x3_32 : !pair16 ? FusedForm::x3_16 : FusedForm::pair16};
 }
 
-int run_mlps_one_launch(const MlpRun& r, const MlpPlan& plan, hipStream_t stream) {
-  const bool x3 = plan.x3;
+int run_mlps_one_launch(const MlpRun& r, FusedForm form, hipStream_t stream) {
   FusedMlpArgs fa;
   fa.count = r.n_nets; fa.M = r.T;
   for (int i = 0; i < r.n_nets; ++i) {
@@ -327,14 +323,14 @@ int run_mlps_one_launch(const MlpRun& r, const MlpPlan& plan, hipStream_t stream
     for (int l = 0; l < fn.n_layers; ++l) {
       const Dense& d = r.nets[i]->layers[l];
       FusedLayer& fl = fn.layer[l];
-      fl.W = plan.pair16 ? d.wp2_16 : plan.shape16 ? d.wp3_16 : x3 ? d.wp3 : d.wp;
-      fl.wexp = plan.pair16 ? d.wp2_16_inv : nullptr;
+      fl.W = d.frag[(int)form];
+      fl.wexp = form == FusedForm::pair16 ? d.wexp : nullptr;
       fl.K = d.in_dim; fl.N = d.out_dim; fl.scale = d.scale; fl.shift = d.shift;
       fl.slope = d.slope; fl.act = d.act;
     }
   }
   prof_mark(r.init_net ? P_INIT_MLP : P_MLP_FUSED, stream);
-  HIP_CHECK(x3 ? launch_mlp_fused_x3(fa, plan.shape16, stream, plan.pair16) : launch_mlp_fused(fa, stream), "fused mlp launch");
+  HIP_CHECK(form == FusedForm::fp32 ? launch_mlp_fused(fa, stream) : launch_mlp_fused_x3(fa, form, stream), "fused mlp launch");
   prof_mark(P_END, stream);   // close the dominant kernel's interval at its completion, not at the next launch
   return EMPOSE_OK;
 }
@@ -385,7 +381,7 @@ int run_mlps(const MlpRun& r, const UpdWs& ws, int hidden_max, hipStream_t strea
   for (int i = 1; i < r.n_nets; ++i)
     if (r.nets[i]->n_layers != r.nets[0]->n_layers) return fail(EMPOSE_EINVAL, "paired MLPs must have the same depth");
   const MlpPlan p = plan_mlps(r);
-  return p.one_launch ? run_mlps_one_launch(r, p, stream) : run_mlps_layers(r, ws, hidden_max, stream);
+  return p.one_launch ? run_mlps_one_launch(r, p.form, stream) : run_mlps_layers(r, ws, hidden_max, stream);
 }
 
 // Where the residual gradient of one SMPL evaluation goes.

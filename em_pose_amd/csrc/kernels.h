@@ -67,9 +67,8 @@ namespace empose {
                              instead of the whole-sequence kernel / lstm_small_kernel (0: those; they share their bits) */ \
   X(mlp_x3, 1)         /* fused update MLPs: fp32 products as six bf16-MFMA products of three bf16 pieces per operand \
                              (mlp_fused_x3.hip: fp32-equivalent accuracy, measured equal to the fp32 instruction's against \
-                             float64); 0: the fp32 MFMA instruction (mlp_fused.hip); 2: the variant whose waves share the \
-                             A-side split through LDS (a barrier per k-step; measured 9 % slower).  Which instruction kernel 1 \
-                             issues is mlp_fused16's choice */ \
+                             float64); 0: the fp32 MFMA instruction (mlp_fused.hip); any other value is on.  Which \
+                             instruction and how many pieces is mlp_fused16's and mlp_pair16's choice */ \
   X(last_pass_joints, 1) /* LGD forward, frame-per-lane path: an SMPL evaluation nobody asks sensor outputs of (the last pass \
                              without histories) multiplies only the rest-joint column tiles of the blend matrix and runs the \
                              chain alone (smpl_tile_kernel, CHAIN_ONLY); 0: the whole sub-mesh, as for every other pass */ \
@@ -79,10 +78,10 @@ namespace empose {
   X(lstm_skip_dead, 1) /* chain step kernels (lstm_x3 = 1 / 3): work whose result nobody reads is left out, same bits -- the \
                              recurrent k-steps of a unit whose h_{t-1} is the zero state of a new sequence, and without \
                              seq_lengths (lstm_state_direct path) the fp32 h_prev loads / h_next stores; 0: all of it runs */ \
-  X(mlp_fused16, 1)    /* fused update MLPs with mlp_x3 = 1: the products on v_mfma_f32_16x16x32_bf16 (mlp_fused_x3_kernel<16>, \
+  X(mlp_fused16, 1)    /* fused update MLPs with mlp_x3 != 0: the products on v_mfma_f32_16x16x32_bf16 (mlp_fused_x3_kernel<16>, \
                              weights in the [k-step of 32][16-column tile][piece] order); 0: v_mfma_f32_32x32x16_bf16 \
                              (mlp_fused_x3_kernel<32>).  Equal to rounding, not to the bit */ \
-  X(mlp_pair16, 1)     /* fused update MLPs with mlp_x3 = 1 and mlp_fused16 != 0: every fp32 product from TWO f16 pieces per \
+  X(mlp_pair16, 1)     /* fused update MLPs with mlp_x3 != 0 and mlp_fused16 != 0: every fp32 product from TWO f16 pieces per \
                              operand under per-row / per-column power-of-two scales, three v_mfma_f32_16x16x32_f16 instead of six \
                              of the bf16 instruction (mlp_fused_x3_kernel<PAIR16>, f16pair.h); 0: the three bf16 pieces of \
                              mlp_fused_x3_kernel<16>.  Equal to rounding, not to the bit */ \
@@ -320,12 +319,17 @@ struct FusedNet {
 };
 struct FusedMlpArgs { FusedNet net[2]; int count; int M; };
 hipError_t launch_mlp_fused(const FusedMlpArgs& args, hipStream_t stream);
-// The same launch with FusedLayer::W = three bf16 pieces per weight in bf16-MFMA fragment order (api_model.hip
-// pack_fragments_x3_raw): mlp_fused_x3.hip.  Hidden widths must be multiples of 64.  shape16: the kernel on
-// v_mfma_f32_16x16x32_bf16, W then in the order of pack_fragments_x3_16_raw.  pair16: the kernel on two f16 pieces per
-// operand (f16pair.h; three v_mfma_f32_16x16x32_f16 per product instead of six), W in the order of
-// pack_fragments_pair16_raw with FusedLayer::wexp set.
-hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, bool shape16, hipStream_t stream, bool pair16 = false);
+// The form the products of that launch take, and with it the order FusedLayer::W is packed in (api_model.hip
+// pack_fragments keeps one table per form):
+//   fp32    the fp32 MFMA instruction (mlp_fused.hip, launch_mlp_fused);
+//   x3_32   three bf16 pieces per operand on v_mfma_f32_32x32x16_bf16, six products (mlp_fused_x3_kernel<32>);
+//   x3_16   the same pieces on v_mfma_f32_16x16x32_bf16 (mlp_fused_x3_kernel<16>);
+//   pair16  two f16 pieces per operand under power-of-two scales on v_mfma_f32_16x16x32_f16, three products
+//           (mlp_fused_x3_kernel<PAIR16>, f16pair.h), FusedLayer::wexp set.
+enum class FusedForm { fp32, x3_32, x3_16, pair16 };
+constexpr int FUSED_FORMS = 4;
+// The same launch in one of the piece forms (mlp_fused_x3.hip; `form` is not fp32).  Hidden widths must be multiples of 64.
+hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, FusedForm form, hipStream_t stream);
 // One linear layer C = A . W^T with A's row block resident in LDS and W (fragment order) streamed from L2.
 bool gemm_rows_applicable(int M, int N, int K);
 hipError_t launch_gemm_rows(const float* A, int lda, const float* Wp, float* C, int ldc, int M, int N, int K,

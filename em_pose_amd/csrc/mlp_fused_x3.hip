@@ -107,32 +107,6 @@ __device__ __forceinline__ void x3_layer(const FusedNet& net, const FusedLayer& 
 #pragma unroll
     for (int i = 0; i < WM; ++i) q[i] = fx_split8(a[i][0], a[i][1]);
   };
-  // the six products of a k-step, the small ones first so that they meet in the accumulator before the large one rounds;
-  // consecutive MFMAs go to different accumulator tiles
-  auto mma = [&](const Pieces (&a)[WM], const u32x4_t (&b)[WN][3]) {
-#pragma unroll
-    for (int t = 0; t < 6; ++t)
-#pragma unroll
-      for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[i].p[X3_PA[t]]),
-                                                              __builtin_bit_cast(bf16x8_t, b[j][X3_PB[t]]), acc[i][j], 0, 0, 0);
-  };
-  // one k-step: its MFMAs with the next step's split (VALU), the weight loads of step s + 3 and the LDS reads of step s + 2
-  // spread between them
-  auto pattern = [&]() {
-    constexpr int NM = WM * WN * 6, NV = 48 * WM, NVM = 3 * WN, NDS = 2 * WM;
-    constexpr int vper = (NV + NM - 1) / NM;
-    static_assert(NVM + NDS <= NM, "k-step too small for its memory operations");
-#pragma unroll
-    for (int q = 0; q < NM; ++q) {
-      SGB(SG_MFMA, 1);
-      if (q < NVM) SGB(SG_VMEM_RD, 1);
-      else if (q < NVM + NDS) SGB(SG_DS_RD, 1);
-      SGB(SG_VALU, vper);
-    }
-  };
   // One k-step as NCH chunks, each fenced by a scheduling barrier: 48 / NCH of the step's MFMAs, the split of ONE pair of the
   // next step's A values (11 VALU) and 16 / NCH of the step's memory operations (the weight loads of step s + 3, the LDS
   // reads of step s + 2).  Left to itself over a whole step (or four), the scheduler emits the split as one dependent
@@ -238,193 +212,71 @@ __device__ __forceinline__ void x3_layer(const FusedNet& net, const FusedLayer& 
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// The same layer with the A-side split done ONCE per element instead of once per wave: the four waves each split a quarter
-// of the k-step's 64 x 16 block (16 rows: one fp32 ds_read_b128 and 22 VALU per lane instead of 88) and leave the pieces
-// in a small LDS stage in FRAGMENT order ([piece][row tile] -> 1 KB, so a wave's A fragment is one conflict-free
-// ds_read_b128); one workgroup barrier per k-step hands them over.  Pieces of step k: raw read at the start of step k - 2,
-// split + written at its end, barrier at the start of step k - 1, fragments read right after it, multiplied in step k.
-// Two stages of 6 KB behind the activation buffer.  Every wave runs the loop, also one that owns no column of a narrow
-// layer (it still splits its rows and meets the barriers).
-// MEASURED (T = 32768, two nets, scripts/dev/fused_x3_lab.hip): 853-879 us per launch against 780-798 us for the kernel above
-// -- the 66 VALU per lane and k-step it saves cost less than the barrier per k-step that replaces them (the four waves then
-// run in lock step: every stall of one is a stall of all; split early or late in the step, raw values read one or two steps
-// ahead: within 3 %).  Opt-in (option mlp_x3 = 2); kept for what it shows.
-namespace fx {
-constexpr int STAGE_U32 = 3 * 2 * 64 * 4;                          // one k-step's pieces: [piece][row tile][lane][4 x u32]
-constexpr int ACT_FLOATS = BM * LDA + 16;
-constexpr size_t LDS_BYTES_C = ((size_t)ACT_FLOATS + 2 * STAGE_U32) * sizeof(float);   // 144,448 bytes
-}  // namespace fx
+// What the two layers on the 16x16x32 instructions share (x16_layer: three bf16 pieces, p16_layer: two f16 pieces; their
+// schedules are described there).  Each takes the caller's tid / l15 / lq / wave: re-derived from threadIdx.x here, they
+// are computed twice.
+// What they do NOT share although it reads alike: the wave's plan (col_tile0 .. step_bytes), the peeled pair loop and the
+// L.N ladder of the kernel body.  Written once, each of the three changes the K loops the compiler emits (the waits at
+// the head of p16_layer's loop, a last step of its own in x16_layer) and cost 1 to 2 us per launch where the parent's
+// runs lay within 2 (profiles/mlp_scaffold_ab_parent_vs_head.txt); with what is below, every block of the two kernels that
+// holds MFMAs has the parent's size.  A change to the plan or to the loop is made in both layers.
+namespace l16 {
+constexpr int RT = 4, NCHUNK = 8;   // a wave's 64 rows are four row tiles; a step is eight chunks, one per column tile
 
-template <int WM, int WN>
-__device__ __forceinline__ void x3c_layer(const FusedNet& net, const FusedLayer& L, int M, int m0, float* act, int lda,
-                                          int row_tile0, int col_tile0, bool last) {
-  using namespace fx;
-  const int lane = threadIdx.x & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int l31 = lane & 31, lh = lane >> 5;
-  const int K = L.K, N = L.N;
-  const int NT32 = (N + 31) / 32;
-  const int KS4 = ((K + 15) / 16 + 3) & ~3;
-  const bool active = col_tile0 < NT32;     // wave-uniform
-  unsigned* stage = reinterpret_cast<unsigned*>(act + ACT_FLOATS);
-  unsigned b_voff[WN];
-#pragma unroll
-  for (int j = 0; j < WN; ++j)
-    b_voff[j] = (unsigned)((col_tile0 + j < NT32 ? col_tile0 + j : NT32 - 1) * 3072 + lane * 16);
-  fx_gbyte_t wb = (fx_gbyte_t)L.W;
-  // producer side: this lane's four raw values of a k-step and where their pieces go
-  const int p_row = wave * 16 + (lane >> 2), p_k4 = (lane & 3) * 4;
-  const float* p_rd = act + p_row * lda + p_k4;
-  const int p_wr = ((p_row >> 5) * 64 + (p_row & 31) + 32 * (p_k4 >> 3)) * 4 + ((p_k4 >> 2) & 1) * 2;   // u32 index in a piece plane
-  // consumer side: fragment (piece pc, row tile i) of a stage = 64 lanes x 16 bytes
-  const int c_rd = (row_tile0 * 64 + lane) * 4;
-
-  float e_sc[WN], e_sh[WN];
-  const float e_slope = L.act == 1 ? L.slope : 1.f;
-  const bool slope_unit = e_slope >= 0.f && e_slope <= 1.f;
-#pragma unroll
-  for (int j = 0; j < WN; ++j) {
-    const int n = (col_tile0 + j) * 32 + l31;
-    const bool real = n < N;
-    const int nc = real ? n : N - 1;
-    e_sc[j] = real ? (L.scale ? L.scale[nc] : 1.f) : 0.f;
-    e_sh[j] = real ? (L.shift ? L.shift[nc] : 0.f) : 0.f;
-  }
-
-  f32x16 acc[WM][WN];
-  f32x4 raw[2];                    // this lane's raw values of k-steps s + 2 (split in step s) and s + 3: read TWO steps
-                                   // before their split, so that the split has its data at the start of the step
-  Pieces ap[2][WM];                // fragments of k-steps s (multiplied) and s + 1 (in flight from the stage)
-  u32x4_t fb[RING][WN][3];
-
-  auto rawread = [&](int ks, f32x4& r) {
-    const int kc = ks < KS4 ? ks : KS4 - 1;
-    r = *reinterpret_cast<const f32x4*>(p_rd + kc * 16);
-  };
-  auto produce = [&](int ks, const f32x4& r) {     // split r (the raw values of k-step ks) into stage ks & 1
-    unsigned h0, m0_, l0, h1, m1, l1;
-    split_pair(r[0], r[1], h0, m0_, l0);
-    split_pair(r[2], r[3], h1, m1, l1);
-    unsigned* st = stage + (ks & 1) * STAGE_U32 + p_wr;
-    typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-    *reinterpret_cast<u32x2_t*>(st) = u32x2_t{h0, h1};
-    *reinterpret_cast<u32x2_t*>(st + 2 * 64 * 4) = u32x2_t{m0_, m1};
-    *reinterpret_cast<u32x2_t*>(st + 2 * 2 * 64 * 4) = u32x2_t{l0, l1};
-  };
-  auto fetch = [&](int ks, Pieces (&q)[WM]) {   // fragments of k-step ks out of its stage
-    const unsigned* st = stage + (ks & 1) * STAGE_U32 + c_rd;
-#pragma unroll
-    for (int i = 0; i < WM; ++i)
-#pragma unroll
-      for (int pc = 0; pc < 3; ++pc) q[i].p[pc] = *reinterpret_cast<const u32x4_t*>(st + (pc * 2 + i) * 64 * 4);
-  };
-  auto bload = [&](u32x4_t (&b)[WN][3], int ks) {
-    const int kc = ks < KS4 ? ks : KS4 - 1;
-    fx_gbyte_t p = wb + (size_t)kc * NT32 * 3072;
-#pragma unroll
-    for (int j = 0; j < WN; ++j)
-#pragma unroll
-      for (int q = 0; q < 3; ++q) b[j][q] = *(x3_gvec_t)(p + b_voff[j] + q * 1024);
-  };
-  auto mma = [&](const Pieces (&a)[WM], const u32x4_t (&b)[WN][3]) {
-#pragma unroll
-    for (int t = 0; t < 6; ++t)
-#pragma unroll
-      for (int i = 0; i < WM; ++i)
-#pragma unroll
-        for (int j = 0; j < WN; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, a[i].p[X3_PA[t]]),
-                                                              __builtin_bit_cast(bf16x8_t, b[j][X3_PB[t]]), acc[i][j], 0, 0, 0);
-  };
-  auto pattern = [&]() {
-    constexpr int NM = WM * WN * 6, NVM = 3 * WN, NDS = 3 * WM + 1;
-    if constexpr (NM >= 48) {      // (the narrow output layers are left to the compiler's own order)
-      // the split of step s + 2 and its three LDS writes FIRST (they must have landed long before the next barrier, which
-      // waits for this wave's LDS operations), then the fragment reads, then the weight loads
-#pragma unroll
-      for (int q = 0; q < 12; ++q) { SGB(SG_MFMA, 1); SGB(SG_VALU, 2); }
-#pragma unroll
-      for (int q = 0; q < 3; ++q) { SGB(SG_MFMA, 1); SGB(0x200, 1); }
-#pragma unroll
-      for (int q = 0; q < NDS; ++q) { SGB(SG_MFMA, 1); SGB(SG_DS_RD, 1); }
-#pragma unroll
-      for (int q = 0; q < NVM; ++q) { SGB(SG_MFMA, 1); SGB(SG_VMEM_RD, 1); }
-      SGB(SG_MFMA, NM - 15 - NDS - NVM);
-    }
-  };
-  // step s: barrier (stage (s + 1) & 1 is complete) | split + write of s + 2 | fragments of s + 1, raw of s + 3 | weights of
-  // s + 3 | MFMAs of s
-  auto step = [&](int s, const Pieces (&ap_cur)[WM], Pieces (&ap_nxt)[WM], const u32x4_t (&b_cur)[WN][3],
-                  u32x4_t (&b_free)[WN][3], f32x4& r) {
-    __syncthreads();
-    produce(s + 2, r);             // (r holds k-step s + 2, read during step s - 2; stage s & 1 was last read in step s - 1)
-    fetch(s + 1, ap_nxt);
-    rawread(s + 4, r);
-    if (active) {
-      bload(b_free, s + 3);
-      mma(ap_cur, b_cur);
-      pattern();
-    }
-  };
-  auto quad = [&](int g) {
-    step(g, ap[0], ap[1], fb[0], fb[3], raw[0]);
-    step(g + 1, ap[1], ap[0], fb[1], fb[0], raw[1]);
-    step(g + 2, ap[0], ap[1], fb[2], fb[1], raw[0]);
-    step(g + 3, ap[1], ap[0], fb[3], fb[2], raw[1]);
-  };
-
-#pragma unroll
-  for (int i = 0; i < WM; ++i)
-#pragma unroll
-    for (int j = 0; j < WN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
-
-  // ---- prologue: pieces of steps 0 and 1 into their stages, fragments of step 0 into registers, raw of steps 2, 3 in flight
-  if (active) {
-    bload(fb[0], 0);
-    bload(fb[1], 1);
-    bload(fb[2], 2);
-  }
-  rawread(0, raw[0]);
-  rawread(1, raw[1]);
-  produce(0, raw[0]);
-  produce(1, raw[1]);
-  rawread(2, raw[0]);
-  rawread(3, raw[1]);
-  __syncthreads();
-  fetch(0, ap[0]);
-  quad(0);
-  for (int g = 4; g < KS4; g += 4) quad(g);
-
-  __syncthreads();   // every wave has read its last raw values and fragments: the buffer may be overwritten
-  if (active) {
-    if (last) {
-      GemmProb p;
-      p.C = net.out; p.ldc = net.ld_out;
-      p.M = M; p.N = N; p.K = K;
-      p.scale = L.scale; p.shift = L.shift; p.resid = nullptr; p.ldr = 0;
-      p.act = L.act; p.slope = L.slope;
-      p.A = nullptr; p.W = nullptr; p.lda = 0; p.ldw = 0;
-      epilogue<WM, WN>(p, acc, m0 + row_tile0 * 32, col_tile0 * 32, l31, lh);
-    } else {
-#pragma unroll
-      for (int j = 0; j < WN; ++j) {
-        const int n = (col_tile0 + j) * 32 + l31;
-        if (col_tile0 + j >= NT32) continue;
-#pragma unroll
-        for (int i = 0; i < WM; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int row = (row_tile0 + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            const float y = acc[i][j][r] * e_sc[j] + e_sh[j];
-            act[row * lda + n] = slope_unit ? fmaxf(y, y * e_slope) : (y >= 0.f ? y : y * e_slope);
-          }
-      }
-    }
-  }
-  __syncthreads();
+// Output column n's epilogue constants; a column past N gives zeros.  Returns the column to read further constants of.
+__device__ __forceinline__ int col_consts(const float* scale, const float* shift, int n, int N, float& sc, float& sh) {
+  const bool real = n < N;
+  const int nc = real ? n : N - 1;
+  sc = real ? (scale ? scale[nc] : 1.f) : 0.f;
+  sh = real ? (shift ? shift[nc] : 0.f) : 0.f;
+  return nc;
 }
+
+// K-split layers: every wave's partial sums go to the (then free) activation buffer as [wave][64][NC] ...
+template <int NCT>
+__device__ __forceinline__ void ksplit_spill(float* act, const f32x4 (&acc)[RT][NCT], int wave, int l15, int lq) {
+  constexpr int NC = NCT * 16;
+  float* pw = act + ((size_t)wave * fx::BM + 4 * lq) * NC + l15;
+#pragma unroll
+  for (int j = 0; j < NCT; ++j)
+#pragma unroll
+    for (int r = 0; r < RT; ++r)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) pw[(r * 16 + e) * NC + j * 16] = acc[r][j][e];
+}
+// ... and, a barrier later, are added in wave order: thread (c16 = tid & 15, r16 = tid >> 4) takes column c16 of every
+// column tile and rows r16, r16 + 16, .. -- shifts and masks only (a division by NC here is loop-invariant, gets hoisted
+// out of the layer loop and lives through every K loop); a row's columns lie in 16 adjacent lanes.
+// `fin(j, rr, nc, sum, sc, sh)` is what the layer does with the sum of (column tile j, row r16 + 16 rr).
+template <int NCT, typename Fin>
+__device__ __forceinline__ void ksplit_sum(const float* act, int tid, int N, const float* scale, const float* shift, Fin fin) {
+  constexpr int NC = NCT * 16;
+  const int c16 = tid & 15, r16 = tid >> 4;
+#pragma unroll
+  for (int j = 0; j < NCT; ++j) {
+    const int n = j * 16 + c16;
+    float sc, sh;
+    const int nc = col_consts(scale, shift, n, N, sc, sh);
+#pragma unroll
+    for (int rr = 0; rr < 4; ++rr) {
+      const float* ps = act + (r16 + 16 * rr) * NC + n;
+      fin(j, rr, nc, ((ps[0] + ps[fx::BM * NC]) + ps[2 * fx::BM * NC]) + ps[3 * fx::BM * NC], sc, sh);
+    }
+  }
+}
+
+// The last layer's results, fp32 [64][lda] in LDS, go out to global memory by all threads, coalesced, after the layer's
+// final barrier: no global store while any MFMA of the workgroup is in flight (bf16x3.h).
+__device__ __forceinline__ void copy_out(const FusedNet& net, const float* act, int lda, int M, int m0, int N, int tid) {
+  float* const out = net.out;
+  const int ld_out = net.ld_out;
+  const int rows = M - m0 < fx::BM ? M - m0 : fx::BM;
+  for (int idx = tid; idx < rows * N; idx += fx::NT) {
+    const int r = idx / N, n = idx - r * N;
+    out[(size_t)(m0 + r) * ld_out + n] = act[r * lda + n];
+  }
+}
+}  // namespace l16
 
 // ---------------------------------------------------------------------------------------------------------------------
 // The same layer on v_mfma_f32_16x16x32_bf16 (option mlp_fused16): same workgroup, same single fp32 activation buffer, same
@@ -454,7 +306,7 @@ __device__ __forceinline__ void x3c_layer(const FusedNet& net, const FusedLayer&
 template <int NCT, bool KSPLIT>
 __device__ __forceinline__ void x16_layer(const FusedNet& net, const FusedLayer& L, int M, int m0, float* act, int lda,
                                           int wave, bool last) {
-  constexpr int RT = 4, NCHUNK = 8;
+  using namespace l16;
   static_assert(NCT >= 1 && NCT <= 8, "a wave owns up to 128 columns");
   const int tid = threadIdx.x, lane = tid & 63;
   const int l15 = lane & 15, lq = lane >> 4;
@@ -564,13 +416,7 @@ __device__ __forceinline__ void x16_layer(const FusedNet& net, const FusedLayer&
   if constexpr (!KSPLIT) {
     float e_sc[NCT], e_sh[NCT];
 #pragma unroll
-    for (int j = 0; j < NCT; ++j) {
-      const int n = (col_tile0 + j) * 16 + l15;
-      const bool real = n < N;
-      const int nc = real ? n : N - 1;
-      e_sc[j] = real ? (scale ? scale[nc] : 1.f) : 0.f;
-      e_sh[j] = real ? (shift ? shift[nc] : 0.f) : 0.f;
-    }
+    for (int j = 0; j < NCT; ++j) col_consts(scale, shift, (col_tile0 + j) * 16 + l15, N, e_sc[j], e_sh[j]);
     __syncthreads();   // every wave has read its last A values: the buffer may be overwritten
 #pragma unroll
     for (int j = 0; j < NCT; ++j) {
@@ -585,36 +431,15 @@ __device__ __forceinline__ void x16_layer(const FusedNet& net, const FusedLayer&
         }
     }
   } else {
-    constexpr int NC = NCT * 16;   // partial sums [wave][64][NC]
     __syncthreads();   // every wave has read its last A values: the buffer is free for the partial sums
-    {
-      float* pw = act + ((size_t)wave * fx::BM + 4 * lq) * NC + l15;
-#pragma unroll
-      for (int j = 0; j < NCT; ++j)
-#pragma unroll
-        for (int r = 0; r < RT; ++r)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) pw[(r * 16 + e) * NC + j * 16] = acc[r][j][e];
-    }
+    ksplit_spill<NCT>(act, acc, wave, l15, lq);
     __syncthreads();
-    // thread (c16 = tid & 15, r16 = tid >> 4) takes column c16 of every column tile and rows r16, r16 + 16, ..: shifts and
-    // masks only (a division by NC here is loop-invariant, gets hoisted out of the layer loop and lives through every K loop)
     const int c16 = tid & 15, r16 = tid >> 4;
     float y[NCT][4];
-#pragma unroll
-    for (int j = 0; j < NCT; ++j) {
-      const int n = j * 16 + c16;
-      const bool real = n < N;
-      const int nc = real ? n : N - 1;
-      const float sc = real ? (scale ? scale[nc] : 1.f) : 0.f, sh = real ? (shift ? shift[nc] : 0.f) : 0.f;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const float* ps = act + (r16 + 16 * rr) * NC + n;
-        const float sum = ((ps[0] + ps[fx::BM * NC]) + ps[2 * fx::BM * NC]) + ps[3 * fx::BM * NC];
-        const float v = sum * sc + sh;
-        y[j][rr] = v >= 0.f ? v : v * e_slope;
-      }
-    }
+    ksplit_sum<NCT>(act, tid, N, scale, shift, [&](int j, int rr, int, float sum, float sc, float sh) {
+      const float v = sum * sc + sh;
+      y[j][rr] = v >= 0.f ? v : v * e_slope;
+    });
     __syncthreads();   // the partial sums are read: the activations take their place
 #pragma unroll
     for (int j = 0; j < NCT; ++j)
@@ -622,15 +447,7 @@ __device__ __forceinline__ void x16_layer(const FusedNet& net, const FusedLayer&
       for (int rr = 0; rr < 4; ++rr) act[(r16 + 16 * rr) * lda + j * 16 + c16] = y[j][rr];
   }
   __syncthreads();
-  if (last) {          // (no MFMA of the workgroup is in flight: every accumulator was read before the barrier)
-    float* const out = net.out;
-    const int ld_out = net.ld_out;
-    const int rows = M - m0 < fx::BM ? M - m0 : fx::BM;
-    for (int idx = tid; idx < rows * N; idx += fx::NT) {
-      const int r = idx / N, n = idx - r * N;
-      out[(size_t)(m0 + r) * ld_out + n] = act[r * lda + n];
-    }
-  }
+  if (last) copy_out(net, act, lda, M, m0, N, tid);   // (no MFMA of the workgroup is in flight: every accumulator was read)
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -638,7 +455,7 @@ __device__ __forceinline__ void x16_layer(const FusedNet& net, const FusedLayer&
 // v_mfma_f32_16x16x32_f16 per accumulator and k-step instead of six of the bf16 instruction -- same shape, rate and
 // fragment layout as x16_layer's, half the executed matrix work.  x16_layer's skeleton (64 rows, four waves, column split
 // for wide layers, K split up to 128 columns, weights from L2 into registers, no barrier in the K loop, results through
-// LDS, the last layer out by the coalesced copy), and what differs:
+// LDS, the last layer out by the coalesced copy: namespace l16 above), and what differs:
 //   * a (hi, lo) pair is 4 bytes, the size of the fp32 it replaces, so the activation buffer holds FINISHED pieces: two
 //     f16 planes [64][PLD], a lane's A fragment of a piece is one ds_read_b128 and the K loop has no split, no VALU at
 //     all.  PLD = 528 halves: a row is 66 16-byte slots, and 66 = 2 (mod 16) spreads each of the ds_read_b128's lane
@@ -735,7 +552,7 @@ __device__ __forceinline__ void p16_stage(const float* x, int ldx, int m0, int M
 template <int NCT, bool KSPLIT>
 __device__ __forceinline__ void p16_layer(const FusedNet& net, const FusedLayer& L, int M, int m0, char* lds,
                                           const unsigned* mx_in, unsigned* mx_out, int wave, bool last) {
-  constexpr int RT = 4, NCHUNK = 8;
+  using namespace l16;
   static_assert(NCT >= 1 && NCT <= 8, "a wave owns up to 128 columns");
   const int tid = threadIdx.x, lane = tid & 63;
   const int l15 = lane & 15, lq = lane >> 4;
@@ -828,12 +645,8 @@ __device__ __forceinline__ void p16_layer(const FusedNet& net, const FusedLayer&
     float e_ci[NCT], e_sc[NCT], e_sh[NCT];
 #pragma unroll
     for (int j = 0; j < NCT; ++j) {
-      const int n = (col_tile0 + j) * 16 + l15;
-      const bool real = n < N;
-      const int nc = real ? n : N - 1;
+      const int nc = col_consts(scale, shift, (col_tile0 + j) * 16 + l15, N, e_sc[j], e_sh[j]);
       e_ci[j] = wexp[nc];
-      e_sc[j] = real ? (scale ? scale[nc] : 1.f) : 0.f;
-      e_sh[j] = real ? (shift ? shift[nc] : 0.f) : 0.f;
     }
     const bool mine = col_tile0 < NT16;                     // (wave-uniform; a tile past N gives zeros: e_sc, e_sh)
     unsigned m[RT][4];
@@ -889,43 +702,21 @@ __device__ __forceinline__ void p16_layer(const FusedNet& net, const FusedLayer&
       }
     }
   } else {
-    constexpr int NC = NCT * 16;   // partial sums [wave][64][NC]
     __syncthreads();   // every wave has read its last A pieces: the buffer is free for the partial sums
-    {
-      float* pw = act + ((size_t)wave * fx::BM + 4 * lq) * NC + l15;
-#pragma unroll
-      for (int j = 0; j < NCT; ++j)
-#pragma unroll
-        for (int r = 0; r < RT; ++r)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) pw[(r * 16 + e) * NC + j * 16] = acc[r][j][e];
-    }
+    ksplit_spill<NCT>(act, acc, wave, l15, lq);
     __syncthreads();
-    // thread (c16 = tid & 15, r16 = tid >> 4) takes column c16 of every column tile and rows r16, r16 + 16, ..: a row's
-    // columns lie in 16 adjacent lanes
     const int c16 = tid & 15, r16 = tid >> 4;
     float y[NCT][4];
     unsigned m[4] = {0u, 0u, 0u, 0u};
     float ri[4];
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) ri[rr] = pair16::pow2(-pair16::scale_exp(mx_in[r16 + 16 * rr]));
-#pragma unroll
-    for (int j = 0; j < NCT; ++j) {
-      const int n = j * 16 + c16;
-      const bool real = n < N;
-      const int nc = real ? n : N - 1;
-      const float ci = wexp[nc];
-      const float sc = real ? (scale ? scale[nc] : 1.f) : 0.f, sh = real ? (shift ? shift[nc] : 0.f) : 0.f;
-#pragma unroll
-      for (int rr = 0; rr < 4; ++rr) {
-        const float* ps = act + (r16 + 16 * rr) * NC + n;
-        const float sum = ((ps[0] + ps[fx::BM * NC]) + ps[2 * fx::BM * NC]) + ps[3 * fx::BM * NC];
-        const float v = ((sum * ci) * ri[rr]) * sc + sh;
-        y[j][rr] = v >= 0.f ? v : v * e_slope;
-        const unsigned b = pair16::finite_abs_bits(y[j][rr]);
-        m[rr] = b > m[rr] ? b : m[rr];
-      }
-    }
+    ksplit_sum<NCT>(act, tid, N, scale, shift, [&](int j, int rr, int nc, float sum, float sc, float sh) {
+      const float v = ((sum * wexp[nc]) * ri[rr]) * sc + sh;
+      y[j][rr] = v >= 0.f ? v : v * e_slope;
+      const unsigned b = pair16::finite_abs_bits(y[j][rr]);
+      m[rr] = b > m[rr] ? b : m[rr];
+    });
     __syncthreads();   // the partial sums are read: the results take their place
     if (last) {
 #pragma unroll
@@ -958,37 +749,7 @@ __device__ __forceinline__ void p16_layer(const FusedNet& net, const FusedLayer&
     }
   }
   __syncthreads();
-  if (last) {          // (no MFMA of the workgroup is in flight: every accumulator was read before the barrier)
-    float* const out = net.out;
-    const int ld_out = net.ld_out;
-    const int rows = M - m0 < fx::BM ? M - m0 : fx::BM;
-    for (int idx = tid; idx < rows * N; idx += fx::NT) {
-      const int r = idx / N, n = idx - r * N;
-      out[(size_t)(m0 + r) * ld_out + n] = act[r * lda + n];
-    }
-  }
-}
-
-__global__ __launch_bounds__(fx::NT) void mlp_fused_x3c_kernel(FusedMlpArgs args) {
-  X3_EXCLUSIVE_SIMD();
-  using namespace fx;
-  extern __shared__ __attribute__((aligned(16))) float act[];
-  const FusedNet& net = args.net[blockIdx.y];
-  const int M = args.M, m0 = blockIdx.x * BM;
-  const int tid = threadIdx.x;
-  {
-    const int K0 = net.layer[0].K;
-    stage::rows<BM, NT>(net.x, net.ldx, m0, M, K0, (K0 + 63) / 64 * 64, act, LDA);
-  }
-  __syncthreads();
-  for (int l = 0; l < net.n_layers; ++l) {
-    const FusedLayer& L = net.layer[l];
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool last = l == net.n_layers - 1;
-    if (L.N <= 32) x3c_layer<1, 1>(net, L, M, m0, act, LDA, wave & 1, wave >> 1, last);
-    else if (L.N <= 128) x3c_layer<1, 2>(net, L, M, m0, act, LDA, wave & 1, (wave >> 1) * 2, last);
-    else x3c_layer<2, 4>(net, L, M, m0, act, LDA, 0, wave * 4, last);
-  }
+  if (last) copy_out(net, act, lda, M, m0, N, tid);   // (no MFMA of the workgroup is in flight: every accumulator was read)
 }
 
 // SHAPE: the MFMA the products run on -- 32: v_mfma_f32_32x32x16_bf16 (x3_layer), 16: v_mfma_f32_16x16x32_bf16
@@ -1050,14 +811,15 @@ __global__ __launch_bounds__(fx::NT) void mlp_fused_x3_kernel(FusedMlpArgs args)
   }
 }
 
-hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, bool shape16, hipStream_t stream, bool pair16) {
+hipError_t launch_mlp_fused_x3(const FusedMlpArgs& args, FusedForm form, hipStream_t stream) {
   dim3 grid((args.M + fx::BM - 1) / fx::BM, args.count);
-  if (options().mlp_x3 >= 2) {   // opt-in: the cooperative split (measured slower, see x3c_layer)
-    return launch_lds(mlp_fused_x3c_kernel, grid, dim3(fx::NT), fx::LDS_BYTES_C, stream, args);
+  switch (form) {
+    case FusedForm::pair16: return launch_lds(mlp_fused_x3_kernel<PAIR16>, grid, dim3(fx::NT), fx::LDS_BYTES_P, stream, args);
+    case FusedForm::x3_16: return launch_lds(mlp_fused_x3_kernel<16>, grid, dim3(fx::NT), fx::LDS_BYTES, stream, args);
+    case FusedForm::x3_32: return launch_lds(mlp_fused_x3_kernel<32>, grid, dim3(fx::NT), fx::LDS_BYTES, stream, args);
+    case FusedForm::fp32: break;   // (mlp_fused.hip's launch)
   }
-  if (pair16) return launch_lds(mlp_fused_x3_kernel<PAIR16>, grid, dim3(fx::NT), fx::LDS_BYTES_P, stream, args);
-  if (shape16) return launch_lds(mlp_fused_x3_kernel<16>, grid, dim3(fx::NT), fx::LDS_BYTES, stream, args);
-  return launch_lds(mlp_fused_x3_kernel<32>, grid, dim3(fx::NT), fx::LDS_BYTES, stream, args);
+  return hipErrorInvalidValue;
 }
 
 }  // namespace empose

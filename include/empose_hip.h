@@ -67,14 +67,13 @@ const char* empose_arch(void);
  * gradients: whole-tile / whole-chunk products on a branch-free interior kernel, bit-identical; 0 = the general kernel),
  * "mlp_x3" (the fused update MLPs form every fp32 product from three bf16 pieces per operand -- six bf16 matrix-core
  * products with fp32 accumulation, fp32-equivalent and 2.7 times the fp32 instruction's rate -- when every hidden width
- * is a multiple of 64: 1 [default]; 0 = the fp32 MFMA instruction; 2 = a variant whose waves share the operand split
- * through LDS, measured slower), "lstm_x3" (the same arithmetic for the LSTM steps of batches above 256 rows, inference,
+ * is a multiple of 64: 1 [default]; 0 = the fp32 MFMA instruction; any other value is on, like 1), "lstm_x3" (the same arithmetic for the LSTM steps of batches above 256 rows, inference,
  * uni-directional stacks with a hidden size of whole 32s: 1 [default]; 0 = the fp32 MFMA instruction; 2 = a row-split
  * variant, measured slower; 3 = force the kernel on the 16x16x32 form of the bf16 instruction), "lstm_chain16" (those
  * steps with lstm_x3 = 1 on the 16x16x32 form of the bf16 instruction -- equal to the 32x32x16 form to rounding, not to the
  * bit; measured 3 to 6 % faster per launch: 1 [default]; 0 = the 32x32x16 form), "mlp_fused16" (the same choice for the
- * fused update MLPs with mlp_x3 = 1; measured 4 to 8 % faster per launch: 1 [default]; 0 = the 32x32x16 form), "mlp_pair16"
- * (the fused update MLPs with mlp_x3 = 1 and mlp_fused16 != 0 form every fp32 product from TWO f16 pieces per operand
+ * fused update MLPs with mlp_x3 != 0; measured 4 to 8 % faster per launch: 1 [default]; 0 = the 32x32x16 form), "mlp_pair16"
+ * (the fused update MLPs with mlp_x3 != 0 and mlp_fused16 != 0 form every fp32 product from TWO f16 pieces per operand
  * under a power-of-two scale per activation row and per weight column -- three f16 matrix-core products instead of six
  * bf16 ones, as accurate against float64, equal to rounding and not to the bit; measured 17 % faster per launch:
  * 1 [default]; 0 = the three bf16 pieces), "rows_x3" (the

@@ -104,10 +104,7 @@ int main(int argc, char** argv) {
            hipGetErrorString(hipGetLastError()));
   };
   time_it("fp32 mfma", [&] { return launch_mlp_fused(a32, 0); });
-  options().mlp_x3 = 2;
-  time_it("3 x bf16 (cooperative split)", [&] { return launch_mlp_fused_x3(ax3, false, 0); });
-  options().mlp_x3 = 1;
-  time_it("3 x bf16 (every wave splits)", [&] { return launch_mlp_fused_x3(ax3, false, 0); });
+  time_it("3 x bf16 (32x32x16)", [&] { return launch_mlp_fused_x3(ax3, FusedForm::x3_32, 0); });
 
   // accuracy on sampled rows
   std::vector<int> rows;
