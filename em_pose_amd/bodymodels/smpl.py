@@ -11,6 +11,8 @@ the saved poses and betas; single backward only).  Otherwise the call is the pla
 orientation and position (reference smpl.py:112-119) with the root-frame kernel (csrc/root_frame.hip) in front of the mesh
 kernels; under autograd it is a node of its own in front of the mesh node, with empose_root_frame_vjp as its backward.
 `sub_mesh(vertex_ids)` gives the same layer on the vertices the virtual sensors at `vertex_ids` read (`SubMeshLayer`).
+`vertex_error(...)` is not in the reference: the per-frame sums of the per-vertex distance between two bodies and of its
+square, from one fused kernel that writes neither mesh (csrc/mesh_err.hip; eval/mesh_metrics.py turns them into PVE).
 Differences to the reference, on purpose:
   * `normalize_root=True`: the exponential map follows `rodrigues_convention`, the logarithm is accurate up to pi, and
     the backward is the derivative of the exact maps, finite at the first frame, where the reference's acos-based
@@ -264,6 +266,34 @@ class SMPLLayer(nn.Module):
                                                   _lib.dptr(joints), _lib.dptr(ws), ws_bytes, _lib.current_stream()))
         return joints[:, :C.N_JOINTS + 1].contiguous()
 
+    def vertex_error(self, poses_body, betas, poses_body_hat, betas_hat, poses_root=None, poses_root_hat=None,
+                     trans=None, trans_hat=None):
+        """Per-vertex error between the body (poses_body, betas, poses_root, trans) and the body (`*_hat`), N frames
+        each, without writing either mesh (empose_mesh_vertex_error, csrc/mesh_err.hip): `sums` (N, 2) float64 on the
+        device, per frame the sum over this layer's vertices of |v - v_hat| (metres) and of |v - v_hat|^2; a frame's
+        mean per-vertex error is `sums[:, 0] / n_vertices`.  The inputs are packed as `forward` packs them (betas
+        broadcast, the first 63 body columns, `num_betas` shape coefficients).  No autograd: the inputs are detached and
+        the result never carries a `grad_fn`.  fp32 on the fp32 matrix cores whatever `arithmetic` the layer has;
+        deterministic, and a frame's row depends on that frame alone."""
+        if not (poses_body.is_cuda and poses_body_hat.is_cuda):
+            raise _lib.EmposeError('SMPLLayer needs GPU tensors; there is no CPU fallback')
+        if poses_body_hat.shape[0] != poses_body.shape[0]:
+            raise ValueError('both bodies need the same number of frames')
+        det = lambda t: t.detach() if t is not None else None
+        pa, ba, ta = self._pack(det(poses_body), det(betas), det(poses_root), det(trans))
+        pb, bb, tb = self._pack(det(poses_body_hat), det(betas_hat), det(poses_root_hat), det(trans_hat))
+        n, dev = pa.shape[0], pa.device
+        lib = _lib.lib()
+        with torch.cuda.device(dev):
+            handle = self._mesh_handle(dev)
+            sums = torch.empty(n, 2, dtype=torch.float64, device=dev)
+            ws_bytes = lib.empose_mesh_vertex_error_workspace_bytes(handle, n)
+            ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            _lib.check(lib.empose_mesh_vertex_error(handle, n, _lib.dptr(pa), _lib.dptr(ba), _lib.dptr(ta), _lib.dptr(pb),
+                                                    _lib.dptr(bb), _lib.dptr(tb), _lib.dptr(sums), _lib.dptr(ws),
+                                                    ws_bytes, _lib.current_stream()))
+        return sums
+
     def fk(self, poses_body, betas, poses_root=None, trans=None, normalize_root=False, window_size=None):
         # The reference slices long inputs into windows to bound memory (smpl.py:124-144); the HIP entry point already
         # processes slabs of 2048 frames internally, so `window_size` only has to be accepted.
@@ -350,6 +380,7 @@ class SubMeshLayer(object):
     _release, __del__ = SMPLLayer._release, SMPLLayer.__del__
     _fk, _pack, _fk_packed, _vjp_packed = SMPLLayer._fk, SMPLLayer._pack, SMPLLayer._fk_packed, SMPLLayer._vjp_packed
     fk_joints, fk = SMPLLayer.fk_joints, SMPLLayer.fk
+    vertex_error = SMPLLayer.vertex_error   # the error over the sub-mesh vertices (`needed`), on this object's handle
 
     def forward(self, *args, **kwargs):
         return self.fk(*args, **kwargs)

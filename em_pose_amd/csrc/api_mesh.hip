@@ -479,6 +479,59 @@ int empose_mesh_vjp(const empose_mesh_t* mesh, int T, const float* poses, const 
   return EMPOSE_OK;
 }
 
+// ---- per-vertex error between two bodies -------------------------------------------------------------------------
+// Scratch for a slab of S frames: the forward's for each body, the posed joints the chain writes on its way to the
+// transforms (not returned), and the pair kernel's per-tile partials.
+struct MeshErrWs { MeshWs a, b; float *joints, *part; };
+static MeshErrWs carve_mesh_err(Carver& c, const empose_mesh* mesh, size_t S) {
+  MeshErrWs w;
+  w.a = carve_mesh(c, mesh, S);
+  w.b = carve_mesh(c, mesh, S);
+  w.joints = c.f(S * (size_t)mesh->n_joints * 3);
+  w.part = c.f(S * (size_t)((mesh->V + 31) / 32) * 2);
+  return w;
+}
+
+size_t empose_mesh_vertex_error_workspace_bytes(const empose_mesh_t* mesh, int T) {
+  if (!mesh || T <= 0) return 0;
+  return Carver::measure([&](Carver& c) { carve_mesh_err(c, mesh, T < MESH_SLAB ? T : MESH_SLAB); });
+}
+
+int empose_mesh_vertex_error(const empose_mesh_t* mesh, int T, const float* poses_a, const float* betas_a,
+                             const float* trans_a, const float* poses_b, const float* betas_b, const float* trans_b,
+                             double* sums, void* workspace, size_t workspace_bytes, empose_stream_t stream_) {
+  if (!mesh) return fail(EMPOSE_EINVAL, "mesh is NULL");
+  if (!poses_a) return fail(EMPOSE_EINVAL, "poses_a is NULL");
+  if (!betas_a) return fail(EMPOSE_EINVAL, "betas_a is NULL");
+  if (!poses_b) return fail(EMPOSE_EINVAL, "poses_b is NULL");
+  if (!betas_b) return fail(EMPOSE_EINVAL, "betas_b is NULL");
+  if (!sums) return fail(EMPOSE_EINVAL, "sums is NULL");
+  if (!workspace) return fail(EMPOSE_EINVAL, "workspace is NULL");
+  if (T <= 0) return fail(EMPOSE_EINVAL, "T must be positive");
+  if (workspace_bytes < empose_mesh_vertex_error_workspace_bytes(mesh, T))
+    return fail(EMPOSE_ENOMEM, "workspace too small (empose_mesh_vertex_error_workspace_bytes)");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const int S = T < MESH_SLAB ? T : MESH_SLAB;
+  const int n_tiles = (mesh->V + 31) / 32;
+  Carver c(workspace);
+  const MeshErrWs w = carve_mesh_err(c, mesh, (size_t)S);
+  for (int t0 = 0; t0 < T; t0 += S) {
+    const int n = (T - t0) < S ? (T - t0) : S;
+    const float* tra = trans_a ? trans_a + (size_t)t0 * 3 : nullptr;
+    const float* trb = trans_b ? trans_b + (size_t)t0 * 3 : nullptr;
+    TRY(mesh_slab_prologue(mesh, w.a, poses_a, betas_a, t0, n, tra, w.joints, stream));
+    TRY(mesh_slab_prologue(mesh, w.b, poses_b, betas_b, t0, n, trb, w.joints, stream));
+    MeshPairErrorArgs pa;
+    pa.feat_a = w.a.feat; pa.xf_a = w.a.xf; pa.trans_a = tra;
+    pa.feat_b = w.b.feat; pa.xf_b = w.b.xf; pa.trans_b = trb;
+    pa.skin_idx = mesh->skin_idx; pa.skin_w = mesh->skin_w; pa.kb = mesh->kb; pa.T = n; pa.V = mesh->V;
+    pa.wc_frag = mesh->wc_frag; pa.skin_idx4 = mesh->skin_idx4; pa.skin_w4 = mesh->skin_w4; pa.part = w.part;
+    HIP_CHECK(launch_mesh_pair_error(pa, stream), "mesh pair error kernel");
+    HIP_CHECK(launch_mesh_err_sum(w.part, n_tiles, n, sums + (size_t)t0 * 2, stream), "mesh error sum kernel");
+  }
+  return EMPOSE_OK;
+}
+
 // ---- root normalisation -----------------------------------------------------------------------------------------
 static int root_frame_args_ok(int T, int seg_len, int rodrigues, int ld_root, int flags) {
   if (T <= 0 || seg_len <= 0) return fail(EMPOSE_EINVAL, "T and seg_len must be positive");

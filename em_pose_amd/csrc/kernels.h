@@ -806,6 +806,23 @@ constexpr int MESH_SKIN_BF16_TILE_BYTES = 2 * 2 * 1024;
 hipError_t launch_mesh_rows_x3(const MeshSkinArgs& a, bool overlap, hipStream_t stream);
 constexpr int MESH_X3_TILE_BYTES = 13 * 9 * 1024;
 
+// Per-vertex error between two bodies (mesh_err.hip): both bodies of a frame are evaluated in the same lanes on the fp32
+// MFMA instruction and only their distances are kept -- part [T][tiles][2] = the sums of |v_A - v_B| and of its square
+// over the 32 vertices of a tile (vertices past V count as an exact 0), tiles = ceil(V / 32).  launch_mesh_err_sum adds a
+// frame's partials in ascending tile order in double: out [T][2].  Fixed-order sums only; a frame's result depends on
+// nothing but that frame.
+struct MeshPairErrorArgs {
+  const float *feat_a, *xf_a, *trans_a;   // body A: [T][200], [T][22][3][4], [T][3] or nullptr
+  const float *feat_b, *xf_b, *trans_b;   // body B likewise
+  const int* skin_idx; const float* skin_w; int kb;
+  int T, V;
+  const float* wc_frag;                   // as MeshSkinArgs
+  const int* skin_idx4; const float* skin_w4;
+  float* part;
+};
+hipError_t launch_mesh_pair_error(const MeshPairErrorArgs& a, hipStream_t stream);
+hipError_t launch_mesh_err_sum(const float* part, int n_tiles, int T, double* out, hipStream_t stream);
+
 // Full-mesh vector-Jacobian product (mesh_vjp.hip): the two vertex sweeps of the reverse for a cotangent dV [T][V][3].
 //   feat sweep: d_feat[t][k] = sum_v,c dvp[t][v][c] wc[3v+c][k], dvp_v = sum_b w_vb (A_b^R)^T dV_v   -> out [T][200]
 //   bone sweep: dA_b[t][r][c] = sum_v w_vb dV_v[r] [vp_v; 1][c]                                       -> out [T][22][12]

@@ -102,12 +102,13 @@ def get_model_config(model_id):
     return Configuration.from_json(os.path.join(model_dir, 'config.json')), model_dir
 
 
-def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, device=None):
+def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, device=None, vertex_engine=None):
     """
     Losses and metrics over a hold-out set (reference eval/helpers.py:51-111): every batch is normalised as a whole,
     cut into temporal chunks (`window_size`, single-recording `RealBatch`es only, as in the reference), preprocessed,
     run through the model with the LSTM state carried over the chunks, and fed to the metrics engine with the shape of
-    the first chunk.
+    the first chunk.  `vertex_engine` (optional, eval/mesh_metrics.py `VertexErrorEngine`) is reset and fed beside the
+    metrics engine, with the same tensors and the first chunk's shape: the per-vertex error of the same frames.
     :return: dict of loss values averaged over the samples of the set.
     """
     device = C.DEVICE if device is None else device
@@ -116,6 +117,8 @@ def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, 
     net.keep_history = True            # the loss values are computed from the iteration histories
     agg, n_samples = defaultdict(float), 0
     metrics_engine.reset()
+    if vertex_engine is not None:
+        vertex_engine.reset()
     try:
         with torch.no_grad():
             for b, abatch in enumerate(data_loader):
@@ -132,6 +135,10 @@ def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, 
                         first_shape_hat = out['shape_hat'][:, 0] if out['shape_hat'] is not None else None
                     metrics_engine.compute(chunk.poses_body, chunk.shapes, pose_hat, first_shape_hat, chunk.seq_lengths,
                                            chunk.poses_root, out['root_ori_hat'], frame_mask=chunk.marker_masks)
+                    if vertex_engine is not None:
+                        vertex_engine.compute(chunk.poses_body, chunk.shapes, pose_hat, first_shape_hat,
+                                              chunk.seq_lengths, chunk.poses_root, out['root_ori_hat'],
+                                              frame_mask=chunk.marker_masks)
                     n_chunks, bs = i + 1, chunk.batch_size
                 for k, v in seq_vals.items():
                     agg[k] += v / n_chunks * bs
@@ -141,16 +148,24 @@ def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, 
     return {k: v / n_samples for k, v in agg.items()}
 
 
-def compute_loss_and_metrics(data_loader, net, preprocess_fn, model_id, smpl_model=None, device=None):
-    """reference eval/helpers.py:114-128"""
+def compute_loss_and_metrics(data_loader, net, preprocess_fn, model_id, smpl_model=None, device=None,
+                             vertex_error=False):
+    """reference eval/helpers.py:114-128.  `vertex_error` (not in the reference): also accumulate the per-vertex error
+    (eval/mesh_metrics.py) and print it as a second table line; the returned values are the same either way."""
     if smpl_model is None:
         from em_pose_amd.bodymodels.smpl import create_default_smpl_model
         smpl_model = create_default_smpl_model(device)
     me = MetricsEngine(smpl_model)
-    losses = evaluate(data_loader, net, preprocess_fn, me, device=device)
+    ve = None
+    if vertex_error:
+        from em_pose_amd.eval.mesh_metrics import VertexErrorEngine
+        ve = VertexErrorEngine(smpl_model)
+    losses = evaluate(data_loader, net, preprocess_fn, me, device=device, vertex_engine=ve)
     print('[LOSS] loss: {:.6f}'.format(losses['total_loss']))
     metrics = me.get_metrics()
     print(me.to_pretty_string(metrics, model_id))
+    if ve is not None:
+        print(ve.to_pretty_string(ve.get_metrics(), model_id))
     return losses, metrics
 
 

@@ -782,6 +782,23 @@ int empose_mesh_vjp(const empose_mesh_t* mesh, int T, const float* poses, const 
                     const float* d_joints, float* g_poses, float* g_betas, float* g_trans, void* workspace,
                     size_t workspace_bytes, empose_stream_t stream);
 
+/* Per-vertex error between two bodies on the same mesh handle (PVE / MPVPE; this project's addition, the reference has no
+ * such metric): body A (poses_a, betas_a, trans_a: the ground truth) and body B (the estimate) with the layouts of
+ * empose_mesh_vertices_fwd, trans_a / trans_b each [T][3] or NULL.  sums [T][2] (double) receives per frame the sum over
+ * the handle's V vertices of |v_A - v_B| and of |v_A - v_B|^2, in metres and square metres; the mean per-vertex error of a
+ * frame is sums[t][0] / V.  No mesh is written: both bodies of a frame are evaluated in the same lanes (csrc/mesh_err.hip,
+ * fp32 operands on the fp32 MFMA instruction whatever arithmetic the handle's forward uses) and only per-tile partial
+ * sums, 8 bytes per frame and 32 vertices, go through the workspace.  Deterministic, and a frame's two numbers depend on
+ * that frame alone: not on T, on the frame's position in the call or on the other frames.
+ * Workspace: empose_mesh_vertex_error_workspace_bytes(mesh, T), for a slab of min(T, 16384) frames twice the forward's
+ * scratch, the posed joints and the partials (about 8.9 KB per frame for SMPL-H); 0 for a NULL handle or T <= 0.
+ * Before any GPU work: EMPOSE_EINVAL for a NULL mesh, poses_a, betas_a, poses_b, betas_b, sums or workspace and for
+ * T <= 0, EMPOSE_ENOMEM for a workspace that is too small; empose_last_error() names the argument. */
+size_t empose_mesh_vertex_error_workspace_bytes(const empose_mesh_t* mesh, int T);
+int empose_mesh_vertex_error(const empose_mesh_t* mesh, int T, const float* poses_a, const float* betas_a,
+                             const float* trans_a, const float* poses_b, const float* betas_b, const float* trans_b,
+                             double* sums, void* workspace, size_t workspace_bytes, empose_stream_t stream);
+
 /* ---- root normalisation (reference bodymodels/smpl.py:112-119, data/transforms.py:247-254) ----------------------- */
 /* T frames in segments of seg_len consecutive rows (T % seg_len == 0): a sequence is re-expressed in the frame of the
  * first root orientation of its segment, R_0 = exp(root[first]):

@@ -170,6 +170,10 @@ def train_on_amass(args, dev, rank, world):
         print('Model created with {} trainable parameters'.format(count_parameters(net)))
         print('Saving checkpoints to {}'.format(checkpoint))
     me = MetricsEngine(smpl)
+    ve = None
+    if args.valid_vertex_error:
+        from em_pose_amd.eval.mesh_metrics import VertexErrorEngine
+        ve = VertexErrorEngine(smpl)
     step, best, done, skipped = 0, float('inf'), False, 0
     for epoch in range(args.n_epochs):
         for i, abatch in enumerate(train_loader):
@@ -211,12 +215,15 @@ def train_on_amass(args, dev, rank, world):
                       ' elapsed: {:.3f} secs'.format(time.perf_counter() - t0))
             step += 1
             if step % args.eval_every == 0 or step == args.steps:
-                losses = evaluate(valid_loader, net, fn_valid, me, device=dev)     # every rank: same held-out set
+                losses = evaluate(valid_loader, net, fn_valid, me, device=dev,     # every rank: same held-out set
+                                  vertex_engine=ve)
                 if rank == 0:
                     better = losses['total_loss'] < best
                     print('[VALID {:0>5d} | {:0>3d}] '.format(i + 1, epoch + 1) +
                           ' '.join('{}: {:.6f}'.format(k, v) for k, v in losses.items()) + (' ***' if better else ''))
                     print(me.to_pretty_string(me.get_metrics(), 'VALID'))
+                    if ve is not None:
+                        print(ve.to_pretty_string(ve.get_metrics(), 'VALID'))
                     if better:
                         best = losses['total_loss']
                         torch.save({'iteration': i, 'epoch': epoch, 'global_step': step,
@@ -279,6 +286,9 @@ def main():
     p.add_argument('--n_epochs', type=int, default=1)
     p.add_argument('--eval_every', type=int, default=200)
     p.add_argument('--valid_fraction', type=float, default=0.1)
+    p.add_argument('--valid_vertex_error', action='store_true',
+                   help='the periodic validation also reports the mean per-vertex error (PVE) of the body surface, a second '
+                        'table line (eval/mesh_metrics.py); default off')
     p.add_argument('--offset_noise_level', type=int, default=0)
     # sensor-noise augmentation (reference configuration.py: the same five flags; data/noise_functions.py)
     p.add_argument('--noise_num_markers', type=int, default=1, help='how many sensors the sensor noise affects')
