@@ -186,10 +186,15 @@ struct Lstm {   // unit u = layer * dirs + direction
   float* w_hh[8] = {};
   float* bias[8] = {};   // b_ih + b_hh
   LstmW3 w3[LSTM_N_LAYOUTS];   // uni-directional stacks with H % 32 == 0 only, else null
+  // lstm_chain16_pair_kernel (LSTM_MID16 order, three-piece stride; same stacks): per gate column n one power-of-two scale
+  // s_n from the column of [W_ih | W_hh].  pair: two f16 pieces of w s_n -- W_hh, and W_ih of layers >= 1; wide: three
+  // bf16 pieces of w s_n 2^14 -- W_ih of layer 0, and every W_hh for the step that consumes a caller's h0
+  LstmW3 w_pair, w_wide;
+  float* inv_scale[8] = {};    // [4H] 2^-14 / s_n
 };
 
 // Uploads an LSTM stack (api_lstm.hip): fp32 weights, summed biases and, for uni-directional stacks with H % 32 == 0, the
-// three-piece bf16 weights in every layout of the table above.
+// three-piece bf16 weights in every layout of the table above and the scaled pieces of lstm_chain16_pair_kernel.
 int pack_lstm(std::vector<void*>& allocs, const empose_lstm_desc& r, int dirs, const float* const* w_ih,
               const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, Lstm* out);
 
@@ -198,7 +203,8 @@ int pack_lstm(std::vector<void*>& allocs, const empose_lstm_desc& r, int dirs, c
 // whole-sequence kernels get buffers (persist and seq by shape alone, midseq by shape and options); the cooperative
 // launches to try, in order -- each may report done = false at run time (its workgroups cannot all be resident) -- and
 // the step kernel that runs when none finished, with its weight layout and how it treats the state of new sequences.
-enum class LstmStep { wave, chain_x3, rows_x3, mid_x3, mid16_x3, chain16_x3 };   // wave: lstm_wave (fp32); else three bf16 pieces
+// wave: lstm_wave (fp32); chain16_pair: two f16 pieces where the operand is the kernel's own; else three bf16 pieces
+enum class LstmStep { wave, chain_x3, rows_x3, mid_x3, mid16_x3, chain16_x3, chain16_pair };
 enum class LstmCoop { persist, seq, midseq };   // lstm_persist_kernel (small), lstm_seq_kernel (large), lstm_midseq_x3.hip
 struct LstmPlan {
   bool persist = false;   // exchange words of lstm_persist_kernel

@@ -1,8 +1,11 @@
 // C ABI (include/empose_hip.h), LSTM, host code only.  Inference: plan_lstm decides what a call does (api_internal.h
 // LstmPlan), carve_lstm_of hands out the buffers the plan names, LstmRun walks it, one function per path.  Packing: the
-// three-piece bf16 weights in every layout of LSTM_LAYOUTS.  Training (empose_lstm_train_*): the forward saves what LstmSave
+// three-piece bf16 weights in every layout of LSTM_LAYOUTS and the scaled pieces of lstm_chain16_pair_kernel.  Training (empose_lstm_train_*): the forward saves what LstmSave
 // lays out; back-propagation through time (Bptt) is two recurrences over one cell builder and one batched tail.
 #include "api_internal.h"
+#include "f16pair.h"
+
+#include <algorithm>
 
 using namespace empose;
 using namespace empose::api;
@@ -21,7 +24,13 @@ bool has_layout(const Lstm& r, LstmLayout y) {
 struct X3Step { hipError_t (*launch)(const LstmX3Args&, hipStream_t); LstmLayout layout; };
 const X3Step X3_STEPS[] = {{nullptr, LSTM_CHAIN}, {launch_lstm_chain_x3, LSTM_CHAIN}, {launch_lstm_rows_x3, LSTM_CHAIN},
                            {launch_lstm_mid_x3, LSTM_MID}, {launch_lstm_mid16_x3, LSTM_MID16},
-                           {launch_lstm_chain16_x3, LSTM_MID16}};
+                           {launch_lstm_chain16_x3, LSTM_MID16}, {launch_lstm_chain16_pair, LSTM_MID16}};
+// the scaled pieces of lstm_chain16_pair_kernel (pack_lstm_pair16)
+bool has_pair16(const Lstm& r) {
+  for (int l = 0; l < r.num_layers; ++l)
+    if (!r.w_pair.hh[l] || !r.w_wide.hh[l] || !r.inv_scale[l] || !(l == 0 ? r.w_wide.ih[l] : r.w_pair.ih[l])) return false;
+  return true;
+}
 // medium batches step on lstm_mid_x3.hip from 17 rows (below: lstm_persist_kernel / lstm_fewrows_kernel), and from 9 with the
 // 4-unit tiles of lstm_mid16_x3.hip (7.0 us per step against 7.8 - 10.7 of lstm_fewrows_kernel at 9 - 16 rows)
 constexpr int LSTM_MID16_MIN_B = 9;
@@ -52,6 +61,8 @@ LstmPlan plan_lstm(const Lstm& r, int B, int F, bool fresh_state) {
     // the same step on the 16x16x32 instruction: what the default takes (lstm_chain16), and what lstm_x3 = 3 forces
     const bool want16 = o.lstm_x3 == 3 || (o.lstm_x3 == 1 && o.lstm_chain16 != 0);
     if (want16 && has_layout(r, LSTM_MID16)) p.step = LstmStep::chain16_x3;
+    // ... and within that kernel, how many pieces (lstm_pair16, as mlp_pair16 within mlp_fused16)
+    if (p.step == LstmStep::chain16_x3 && o.lstm_pair16 != 0 && has_pair16(r)) p.step = LstmStep::chain16_pair;
   }
   else if (mid && B >= (tiles16 ? LSTM_MID16_MIN_B : LSTM_PERSIST_B + 1) && B < LSTM_SEQ_MIN_B)
     p.step = tiles16 ? LstmStep::mid16_x3 : LstmStep::mid_x3;
@@ -64,7 +75,7 @@ LstmPlan plan_lstm(const Lstm& r, int B, int F, bool fresh_state) {
     if (p.midseq) p.coop[p.n_coop++] = LstmCoop::midseq;
   }
   p.zero_planes = p.step != LstmStep::wave && fresh_state && o.lstm_state_direct != 0;
-  const bool chain = p.step == LstmStep::chain_x3 || p.step == LstmStep::chain16_x3;
+  const bool chain = p.step == LstmStep::chain_x3 || p.step == LstmStep::chain16_x3 || p.step == LstmStep::chain16_pair;
   p.state_direct = p.zero_planes && chain;
   p.skip_dead = chain && o.lstm_skip_dead != 0;
   return p;
@@ -223,6 +234,16 @@ struct LstmRun {
         const bool last_step = p.state_direct && t == F - 1;
         xu.h_final = last_step && h_n ? h_n + l * bh() : nullptr;
         xu.c_final = last_step && c_n ? c_n + l * bh() : nullptr;
+        if (p.step == LstmStep::chain16_pair) {
+          // Pair steps for what the kernel wrote itself: the layer below's h_t, and h_{t-1} from the second step on (a
+          // new sequence's zero planes are zero in either format).  Wide steps for the stored input and for a caller's
+          // h0, which split_state left as three bf16 pieces: neither is bounded by 1.
+          xu.in_pair = l > 0;
+          xu.rec_pair = !(h0 && t == 0);
+          xu.w3_ih = xu.in_pair ? r.w_pair.ih[l] : r.w_wide.ih[l];
+          xu.w3_hh = xu.rec_pair ? r.w_pair.hh[l] : r.w_wide.hh[l];
+          xu.inv_scale = r.inv_scale[l];
+        }
       }
       xa.units_per_block = tiles >= 192 ? xa.n_units : 1;
       prof_mark(P_LSTM_STEP, stream);
@@ -301,6 +322,52 @@ int pack_lstm_x3(std::vector<void*>& allocs, LstmLayout layout, const float* w, 
     *k0 = ks * d.k_width + lane / cols * 8;
     return true;
   }), out);
+}
+
+// The weights of lstm_chain16_pair_kernel for one layer, in the mid16 order at the three-piece stride.  Gate column n has
+// one scale s_n = 2^e(n), e from the largest finite magnitude of row n of [W_ih | W_hh] (pair16::scale_exp; at most 2^100,
+// so that 2^-14 / s_n stays a normal number).  pair: hi, lo = the two f16 pieces of w s_n, third slot zero; wide: the three
+// bf16 pieces of w s_n 2^14 -- scaling by a power of two before the split is exact.  inv: [4H] 2^-14 / s_n.
+int pack_lstm_pair16(std::vector<void*>& allocs, int l, const float* w_ih, const float* w_hh, int H, int K_in, Lstm* out) {
+  const int N = 4 * H;
+  std::vector<float> sc(N), inv(N);
+  for (int n = 0; n < N; ++n) {
+    unsigned m = 0u;
+    for (int k = 0; k < K_in; ++k) m = std::max(m, pair16::finite_abs_bits(w_ih[(size_t)n * K_in + k]));
+    for (int k = 0; k < H; ++k) m = std::max(m, pair16::finite_abs_bits(w_hh[(size_t)n * H + k]));
+    const int e = std::min(pair16::scale_exp(m), 100);
+    sc[n] = pair16::pow2(e);
+    inv[n] = pair16::pow2(-e - pair16::EXP_TOP);
+  }
+  auto wide = [&](const float* w, int K, unsigned short** dst) {
+    std::vector<float> ws((size_t)N * K);
+    for (int n = 0; n < N; ++n)
+      for (int k = 0; k < K; ++k) ws[(size_t)n * K + k] = w[(size_t)n * K + k] * sc[n] * pair16::pow2(pair16::EXP_TOP);
+    return pack_lstm_x3(allocs, LSTM_MID16, ws.data(), H, K, dst);
+  };
+  auto pair = [&](const float* w, int K, unsigned short** dst) {
+    const LstmLayoutDesc d = LSTM_LAYOUTS[LSTM_MID16];
+    const int KS = (K + d.k_width - 1) / d.k_width, JB = H / d.units, cols = 512 / d.k_width;
+    std::vector<unsigned short> buf((size_t)KS * JB * 3 * FRAG, 0);
+    for (int ks = 0; ks < KS; ++ks)
+      for (int jb = 0; jb < JB; ++jb)
+        for (int lane = 0; lane < 64; ++lane) {
+          const int c = lane % cols, n = (c / d.units) * H + jb * d.units + c % d.units, k0 = ks * d.k_width + lane / cols * 8;
+          for (int e = 0; e < 8 && k0 + e < K; ++e) {
+            const float x = w[(size_t)n * K + k0 + e] * sc[n];
+            const _Float16 hi = (_Float16)x;                       // round to nearest even
+            const _Float16 lo = (_Float16)(x - (float)hi);
+            const size_t at = ((size_t)ks * JB + jb) * 3 * FRAG + (size_t)lane * 8 + e;
+            buf[at] = __builtin_bit_cast(unsigned short, hi);
+            buf[at + FRAG] = __builtin_bit_cast(unsigned short, lo);
+          }
+        }
+    return upload_bf16(allocs, buf, dst);
+  };
+  TRY(l == 0 ? wide(w_ih, K_in, &out->w_wide.ih[l]) : pair(w_ih, K_in, &out->w_pair.ih[l]));
+  TRY(pair(w_hh, H, &out->w_pair.hh[l]));
+  TRY(wide(w_hh, H, &out->w_wide.hh[l]));
+  return upload(allocs, inv.data(), inv.size(), &out->inv_scale[l]);
 }
 
 // ---- training ---------------------------------------------------------------------------------------------------------
@@ -585,6 +652,7 @@ int pack_lstm(std::vector<void*>& allocs, const empose_lstm_desc& r, int dirs, c
         TRY(pack_lstm_x3(allocs, (LstmLayout)y, w_ih[u], r.hidden_size, k_in, &out->w3[y].ih[u]));
         TRY(pack_lstm_x3(allocs, (LstmLayout)y, w_hh[u], r.hidden_size, r.hidden_size, &out->w3[y].hh[u]));
       }
+      TRY(pack_lstm_pair16(allocs, l, w_ih[u], w_hh[u], r.hidden_size, k_in, out));
     }
   return EMPOSE_OK;
 }

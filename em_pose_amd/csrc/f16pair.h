@@ -1,4 +1,5 @@
-// fp32 values as TWO f16 pieces under a power-of-two scale, the operand format of mlp_fused_x3_kernel<PAIR16>:
+// fp32 values as TWO f16 pieces under a power-of-two scale, the operand format of mlp_fused_x3_kernel<PAIR16> and of
+// lstm_chain16_pair_kernel:
 //   hi = rn_f16(x s),  lo = rn_f16(x s - float(hi))          11 + 11 mantissa bits, 2^-24 relative: fp32's own roundoff
 //   x w ~= (lo_x hi_w + hi_x lo_w + hi_x hi_w) / (s_x s_w)   three v_mfma_f32_16x16x32_f16 products, the small ones first;
 // what is dropped (lo_x lo_w) is at 2^-24 of the product.  The three-piece bf16 format (bf16x3.h) needs six products for
@@ -9,6 +10,11 @@
 // 2^-24 of the largest still has a (subnormal) hi piece.  An all-zero row has e = 0; floor(log2 m) is clamped to
 // +-EXP_CLAMP, which keeps s and 1 / s normal fp32 numbers.  A row that holds inf or NaN keeps its finite scale: its
 // pieces, and with them its results, are non-finite, and no other row sees it.
+// A second user with a FIXED scale: lstm_chain16_pair_kernel (lstm_chain16_x3.hip).  Its A operand is the hidden state
+// h = o tanh(c) in [-1, 1]: s = 2^EXP_TOP for every row, no maximum to find (h s <= 2^14 cannot overflow; an element below
+// 2^-24 of 1 has lost its lo piece, which is 2^-24 of what a gate sum is compared with).  Its weight columns are scaled as
+// above, over the concatenated [W_ih | W_hh]; an operand that is not bounded (the raw input, a caller's h0) stays on three
+// bf16 pieces against weights packed as the pieces of w s 2^EXP_TOP and adds into the same accumulator.
 // Conversions are round to nearest (v_cvt_pk_f16_f32), never the round-toward-zero pack: truncated pieces are four times
 // less accurate.  Internal, gfx950 only.
 #pragma once

@@ -86,7 +86,14 @@ namespace empose {
                              of the bf16 instruction (mlp_fused_x3_kernel<PAIR16>, f16pair.h); 0: the three bf16 pieces of \
                              mlp_fused_x3_kernel<16>.  Equal to rounding, not to the bit */ \
   X(lstm_chain16, 1)   /* large-batch LSTM steps with lstm_x3 = 1: lstm_chain16_x3.hip (v_mfma_f32_16x16x32_bf16) where the model \
-                             has the LSTM_MID16 weight order; 0: lstm_chain_x3_kernel (32x32x16) */
+                             has the LSTM_MID16 weight order; 0: lstm_chain_x3_kernel (32x32x16) */ \
+  X(lstm_pair16, 1)    /* large-batch LSTM steps on the 16x16x32 chain kernel (lstm_x3 = 3, or 1 with lstm_chain16 on): every \
+                             operand the kernel itself produced -- h_{t-1} and the layer below's h_t, both in [-1, 1] -- as TWO \
+                             f16 pieces under the fixed scale 2^14, weights under per-column power-of-two scales, three \
+                             v_mfma_f32_16x16x32_f16 instead of six of the bf16 instruction (lstm_chain16_pair_kernel, \
+                             f16pair.h); the raw input of layer 0 and a caller's h0 stay on three bf16 pieces and share the \
+                             accumulator; 0: three bf16 pieces throughout (lstm_chain16_x3_kernel).  Equal to rounding, not to \
+                             the bit */
 
 struct Options {
 #define EMPOSE_OPTION_FIELD(name, default_value) int name = default_value;
@@ -410,6 +417,11 @@ struct LstmX3Unit {
   // the layer's slices of h_n / c_n ([B][H]) on the launch of its last step, else nullptr: a second copy of what goes to
   // h_next / c (the chain kernels only; the other step kernels ignore them and the caller copies the state out)
   float* h_final = nullptr; float* c_final = nullptr;
+  // lstm_chain16_pair_kernel only.  A part (input / recurrent) is walked in pair steps -- its planes hold two f16 pieces of
+  // h 2^14, its weights (w3_ih / w3_hh) two f16 pieces of w s_n, both at the three-piece stride -- or in wide steps: three
+  // bf16 pieces of the operand as it is, weights those of w s_n 2^14.  inv_scale: [4H] 2^-14 / s_n, applied to the gate sums
+  int in_pair = 0, rec_pair = 0;
+  const float* inv_scale = nullptr;
 };
 struct LstmX3Args {
   LstmX3Unit unit[4];
@@ -423,6 +435,8 @@ struct LstmX3Args {
 hipError_t launch_lstm_chain_x3(const LstmX3Args& a, hipStream_t stream);
 // the same step on v_mfma_f32_16x16x32_bf16, weights in the LSTM_MID16 order (lstm_chain16_x3.hip; option lstm_x3 = 3)
 hipError_t launch_lstm_chain16_x3(const LstmX3Args& a, hipStream_t stream);
+// ... with the operands the kernel produced itself on two f16 pieces (LstmX3Unit::in_pair / rec_pair; option lstm_pair16)
+hipError_t launch_lstm_chain16_pair(const LstmX3Args& a, hipStream_t stream);
 // the same step with the waves splitting ROWS, the weight block of a k-step shared through LDS and the cell update in
 // registers (lstm_rows_x3.hip; option lstm_x3 = 2): one unit per workgroup, `units_per_block` unused
 hipError_t launch_lstm_rows_x3(const LstmX3Args& a, hipStream_t stream);

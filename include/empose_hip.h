@@ -76,7 +76,9 @@ const char* empose_arch(void);
  * (the fused update MLPs with mlp_x3 != 0 and mlp_fused16 != 0 form every fp32 product from TWO f16 pieces per operand
  * under a power-of-two scale per activation row and per weight column -- three f16 matrix-core products instead of six
  * bf16 ones, as accurate against float64, equal to rounding and not to the bit; measured 17 % faster per launch:
- * 1 [default]; 0 = the three bf16 pieces), "rows_x3" (the
+ * 1 [default]; 0 = the three bf16 pieces), "lstm_pair16" (the same choice for the LSTM steps on the 16x16x32 form: the
+ * hidden states the kernel itself produced, which lie in [-1, 1], go as two f16 pieces under the fixed scale 2^14; the raw
+ * input of layer 0 and a caller's h0 stay on three bf16 pieces: 1 [default]; 0 = three bf16 pieces throughout), "rows_x3" (the
  * same arithmetic for the row-block products with fused prologue / epilogue: the blend products of the frame-per-lane
  * SMPL path and the stacked init heads; 0 = the fp32 MFMA instruction), "train_cols" (training at up to 512 rows: a
  * layer's product + BatchNorm + PReLU as one launch, forward and backward, both update networks side by side -- see
