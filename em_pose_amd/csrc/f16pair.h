@@ -54,14 +54,55 @@ __device__ __forceinline__ void split_pair(float x0, float x1, unsigned& hi, uns
   hi = __builtin_bit_cast(unsigned, h);
   lo = __builtin_bit_cast(unsigned, l);
 }
-// the maximum of an integer over the 16 lanes of a row group
+// The same order without a compare per value, for the epilogues that look at every accumulator: the magnitude bits shifted
+// left by one (the sign leaves) plus 2^24, in unsigned arithmetic -- ONE v_lshl_add_u32.  A finite magnitude lands in
+// [KEY_ZERO, 2^32) in its own order; inf and NaN wrap to [0, KEY_ZERO) and lose every maximum that starts from KEY_ZERO,
+// the key of 0.  key_bits undoes it, once per row: key_bits(max of keys) == max of finite_abs_bits.
+constexpr unsigned KEY_ZERO = 0x01000000u;
+__host__ __device__ inline unsigned finite_key(float y) { return (__builtin_bit_cast(unsigned, y) << 1) + KEY_ZERO; }
+__host__ __device__ inline unsigned key_bits(unsigned key) { return (key - KEY_ZERO) >> 1; }
+
+// A row group -- 16 adjacent lanes -- is a DPP row: a lane reads another's register in the instruction that uses it.
+constexpr int DPP_XOR1 = 0xB1, DPP_XOR2 = 0x4E;                  // quad_perm:[1,0,3,2], quad_perm:[2,3,0,1]
+constexpr int DPP_HALF_MIRROR = 0x141, DPP_MIRROR = 0x140;       // row_half_mirror (7 - i of 8), row_mirror (15 - i of 16)
+// (Every lane of a row is written -- all four patterns are permutations, the users run with all lanes on -- so the `old`
+// value is never seen; 0, a maximum's identity, is what lets the compiler fold the move into the v_max_u32 that uses it.)
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp(unsigned v) {
+  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xf, 0xf, false);
+}
+template <int CTRL>
+__device__ __forceinline__ unsigned dpp_max(unsigned m) {
+  const unsigned o = dpp<CTRL>(m);
+  return o > m ? o : m;
+}
+// the maximum of an integer over the 16 lanes of a row group, in every lane: four v_max_u32_dpp
 __device__ __forceinline__ unsigned max16(unsigned m) {
+  return dpp_max<DPP_MIRROR>(dpp_max<DPP_HALF_MIRROR>(dpp_max<DPP_XOR2>(dpp_max<DPP_XOR1>(m))));
+}
+// The maxima of SIXTEEN integers over the 16 lanes of a row group as a reduce-scatter (lane_reduce.h): every step halves
+// what a lane carries -- it keeps the half its lane bit selects and takes the partner's maximum of the same half -- and
+// lane l15 returns the group's maximum of v[l15] (v is used up): 15 exchanges instead of 64.  The mirrors come first: a
+// mirror's partner differs in the lower lane bits too, and has to hold the same half still.
+__device__ __forceinline__ unsigned max16_scatter(unsigned (&v)[16], int l15) {
+  const bool b3 = l15 & 8, b2 = l15 & 4, b1 = l15 & 2, b0 = l15 & 1;
 #pragma unroll
-  for (int d = 1; d < 16; d <<= 1) {
-    const unsigned o = (unsigned)__shfl_xor((int)m, d);
-    m = o > m ? o : m;
+  for (int i = 0; i < 8; ++i) {
+    const unsigned keep = b3 ? v[i + 8] : v[i], send = b3 ? v[i] : v[i + 8], got = dpp<DPP_MIRROR>(send);
+    v[i] = got > keep ? got : keep;
   }
-  return m;
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const unsigned keep = b2 ? v[i + 4] : v[i], send = b2 ? v[i] : v[i + 4], got = dpp<DPP_HALF_MIRROR>(send);
+    v[i] = got > keep ? got : keep;
+  }
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const unsigned keep = b1 ? v[i + 2] : v[i], send = b1 ? v[i] : v[i + 2], got = dpp<DPP_XOR2>(send);
+    v[i] = got > keep ? got : keep;
+  }
+  const unsigned keep = b0 ? v[1] : v[0], send = b0 ? v[0] : v[1], got = dpp<DPP_XOR1>(send);
+  return got > keep ? got : keep;
 }
 }  // namespace pair16
 }  // namespace empose

@@ -26,6 +26,8 @@
 //     (scripts/dev/bf16_hazard_repro.md).
 // The default form since option mlp_pair16 is p16_layer below: TWO f16 pieces per operand under power-of-two scales
 // (f16pair.h), three products instead of six, the same workgroup.
+#include <type_traits>
+
 #include "bf16x3.h"
 #include "f16pair.h"
 #include "gemm_epilogue.h"
@@ -461,12 +463,14 @@ __device__ __forceinline__ void x16_layer(const FusedNet& net, const FusedLayer&
 //     all.  PLD = 528 halves: a row is 66 16-byte slots, and 66 = 2 (mod 16) spreads each of the ds_read_b128's lane
 //     groups (rows 0-3, 12-15 of one k quarter with rows 4-11 of the next) over all 16 slots of a bank row: conflict-free;
 //   * the pieces of a row need the row's scale, the scale the row's largest magnitude: the epilogue keeps its results in
-//     registers, reduces the maxima (in the lane, over the 16 lanes of a row, over the four waves by an LDS atomic on a
-//     64-word array), and writes the pieces after ONE more barrier than x16_layer has.  The K-split layers need neither the
-//     atomic nor the barrier: their reduction already has a row's columns in 16 adjacent lanes.  Two arrays of maxima
-//     alternate by layer: the scale a layer's input was packed with is undone in that layer's epilogue;
-//   * two adjacent lanes exchange half of their values, so that each writes (column, column + 1) of two rows as one word:
-//     as many LDS writes as x16_layer's fp32 results took;
+//     registers, reduces the maxima (in the lane; over the 16 lanes of a row, which are a DPP row: no LDS trip, and as a
+//     reduce-scatter of the lane's 16 rows that leaves one row per lane; over the four waves by ONE LDS atomic of all lanes
+//     on a 64-word array), and writes the pieces after ONE more barrier than x16_layer has.  Nothing in it compares: 128
+//     select masks per wave did not fit the scalar registers (p16_activation, pair16::finite_key).  The K-split layers
+//     need neither the atomic nor the barrier: their reduction already has a row's columns in 16 adjacent lanes.  Two
+//     arrays of maxima alternate by layer: the scale a layer's input was packed with is undone in that layer's epilogue;
+//   * two adjacent lanes exchange half of their values (DPP again), so that each writes (column, column + 1) of two rows
+//     as one word: as many LDS writes as x16_layer's fp32 results took;
 //   * weights in the order of api_model.hip pack_fragments_pair16_raw: [k-step of 32][16-column tile][piece] -> 1 KB, with
 //     the columns' inverse scales beside them (FusedLayer::wexp).  A chunk is one column tile's 12 MFMAs with one A
 //     fragment of the next step and the two weight fragments of the tile just finished, for the step AFTER the next: the
@@ -481,19 +485,45 @@ static_assert((size_t)2 * PLANE_BYTES >= (size_t)BM * LDA * sizeof(float), "the 
 static_assert((size_t)2 * PLANE_BYTES >= (size_t)4 * BM * 128 * sizeof(float), "the K-split partial sums fit");
 }  // namespace fx
 
+typedef __attribute__((address_space(3))) char* p16_lds_t;
+// a value of the lane next door (lane ^ 1)
+__device__ __forceinline__ float p16_swap1(float v) {
+  const int b = __builtin_bit_cast(int, v);                 // (`old` = the source: no register to set up, f16pair.h)
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(b, b, pair16::DPP_XOR1, 0xf, 0xf, false));
+}
 // A lane's four scaled values of one (row tile, column tile) -- rows e = 0 .. 3 of column c -- go out as pieces: the even
-// lane takes rows 0, 1 and the odd lane rows 2, 3 of the columns (c & ~1, c | 1) of both.  `row_base`: the lane's row 0.
-__device__ __forceinline__ void p16_put4(char* lds, int row_base, int col, float v0, float v1, float v2, float v3) {
-  const bool odd = col & 1;
-  const float r0 = __shfl_xor(odd ? v0 : v2, 1), r1 = __shfl_xor(odd ? v1 : v3, 1);
+// lane takes rows 0, 1 and the odd lane rows 2, 3 of the columns (c & ~1, c | 1) of both; the two trade through DPP.
+// `p_hi`, `p_lo`: where the lane's first piece pair goes in either plane (PLANE_BYTES apart is past a ds_write's 16-bit
+// offset: one address register per plane, everything else an immediate `off`); `row2`: bytes to its second pair.
+__device__ __forceinline__ void p16_put4(p16_lds_t p_hi, p16_lds_t p_lo, int off, int row2, bool odd, float v0, float v1,
+                                         float v2, float v3) {
+  const float r0 = p16_swap1(odd ? v0 : v2), r1 = p16_swap1(odd ? v1 : v3);
   unsigned h0, l0, h1, l1;
   pair16::split_pair(odd ? r0 : v0, odd ? v2 : r0, h0, l0);
   pair16::split_pair(odd ? r1 : v1, odd ? v3 : r1, h1, l1);
-  char* p = lds + ((row_base + (odd ? 2 : 0)) * fx::PLD + (col & ~1)) * 2;
-  *reinterpret_cast<unsigned*>(p) = h0;
-  *reinterpret_cast<unsigned*>(p + fx::PLANE_BYTES) = l0;
-  *reinterpret_cast<unsigned*>(p + fx::PLD * 2) = h1;
-  *reinterpret_cast<unsigned*>(p + fx::PLD * 2 + fx::PLANE_BYTES) = l1;
+  typedef __attribute__((address_space(3))) unsigned* word_t;
+  *(word_t)(p_hi + off) = h0;
+  *(word_t)(p_lo + off) = l0;
+  *(word_t)(p_hi + off + row2) = h1;
+  *(word_t)(p_lo + off + row2) = l1;
+}
+// The address of a lane's first store in either plane, each in a register of its own (left to itself the compiler keeps
+// one and adds the planes' distance, which no immediate holds, before every second store).
+__device__ __forceinline__ void p16_planes(char* p, p16_lds_t& p_hi, p16_lds_t& p_lo) {
+  unsigned a = (unsigned)(size_t)(p16_lds_t)p, b = a + (unsigned)fx::PLANE_BYTES;
+  asm volatile("" : "+v"(a), "+v"(b));
+  p_hi = (p16_lds_t)(size_t)a;
+  p_lo = (p16_lds_t)(size_t)b;
+}
+
+// y >= 0 ? y : y slope.  For a slope in (0, 1] (UNIT) that is the larger of y and y slope, bit for bit: both zeros keep
+// their sign (-0 slope = -0), +-inf and NaN come out as they do from the select.  One v_max_f32 and no compare mask: 128 of
+// those per wave and layer did not fit the scalar registers.  Slope 0 is not UNIT: -inf x 0 is NaN, which a maximum drops.
+// `ys`: y slope, the caller's (packed) multiply.
+template <bool UNIT>
+__device__ __forceinline__ float p16_activation(float y, float ys) {
+  if constexpr (UNIT) return fmaxf(y, ys);
+  else return y >= 0.f ? y : ys;
 }
 
 // Layer 0's input: row-major x[M][ldx], rows m0 .. m0 + 63, columns [0, K0) -> the piece planes, columns [K0, kpad) zero;
@@ -516,33 +546,36 @@ __device__ __forceinline__ void p16_stage(const float* x, int ldx, int m0, int M
         v[rr][u] = *(stage::gvec_t)(xb + ((unsigned)rc * ldx4 + (unsigned)cc * 16u));
       }
   }
+  p16_lds_t p_hi, p_lo;
+  p16_planes(lds + (rg * fx::PLD + l15 * 4) * 2, p_hi, p_lo);
 #pragma unroll
   for (int rr = 0; rr < 4; ++rr) {
     const int row = rg + 16 * rr;
-    unsigned m = 0u;
+    unsigned key = pair16::KEY_ZERO;
 #pragma unroll
     for (int u = 0; u < 8; ++u)
       if (u < nu) {
         if (l15 + 16 * u >= k4) v[rr][u] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const unsigned b = pair16::finite_abs_bits(v[rr][u][e]);
-          m = b > m ? b : m;
+          const unsigned b = pair16::finite_key(v[rr][u][e]);
+          key = b > key ? b : key;
         }
       }
-    m = pair16::max16(m);
+    const unsigned m = pair16::key_bits(pair16::max16(key));
     if (l15 == 0) mx[row] = m;
     const float s = pair16::pow2(pair16::scale_exp(m));
 #pragma unroll
     for (int u = 0; u < 8; ++u)
       if (u < nu) {
         typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
+        typedef __attribute__((address_space(3))) u32x2_t* pair_t;
         unsigned h0, l0, h1, l1;
         pair16::split_pair(v[rr][u][0] * s, v[rr][u][1] * s, h0, l0);
         pair16::split_pair(v[rr][u][2] * s, v[rr][u][3] * s, h1, l1);
-        char* p = lds + (row * fx::PLD + (l15 + 16 * u) * 4) * 2;
-        *reinterpret_cast<u32x2_t*>(p) = u32x2_t{h0, h1};
-        *reinterpret_cast<u32x2_t*>(p + fx::PLANE_BYTES) = u32x2_t{l0, l1};
+        const int off = (16 * rr * fx::PLD + 16 * u * 4) * 2;
+        *(pair_t)(p_hi + off) = u32x2_t{h0, h1};
+        *(pair_t)(p_lo + off) = u32x2_t{l0, l1};
       }
   }
 }
@@ -638,6 +671,7 @@ __device__ __forceinline__ void p16_layer(const FusedNet& net, const FusedLayer&
   if (i < n_w) step(i, ap[0], ap[1], fb[0], fb[1]);
 
   const float e_slope = L.act == 1 ? L.slope : 1.f;         // slope 1: no activation (exact identity)
+  const bool slope_unit = e_slope > 0.f && e_slope <= 1.f;  // (wave-uniform) the activation is then a maximum, p16_activation
   const float* const scale = L.scale;
   const float* const shift = L.shift;
   const float* const wexp = L.wexp;
@@ -649,21 +683,36 @@ __device__ __forceinline__ void p16_layer(const FusedNet& net, const FusedLayer&
       e_ci[j] = wexp[nc];
     }
     const bool mine = col_tile0 < NT16;                     // (wave-uniform; a tile past N gives zeros: e_sc, e_sh)
-    unsigned m[RT][4];
+    unsigned key[RT * 4];                                   // pair16::finite_key maxima of the lane's rows (r, e)
+    auto finish = [&](auto unit) {
+      // (rows in pairs, spelled as vectors: the multiplies and the fused multiply-add are packed instructions, which the
+      // compiler no longer finds by itself once the activation, which has no packed form, is a maximum)
 #pragma unroll
-    for (int r = 0; r < RT; ++r)
+      for (int r = 0; r < RT; ++r)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float ri = pair16::pow2(-pair16::scale_exp(mx_in[r * 16 + 4 * lq + e]));
-        m[r][e] = 0u;
+        for (int e = 0; e < 4; e += 2) {
+          const f32x2_t ri = {pair16::pow2(-pair16::scale_exp(mx_in[r * 16 + 4 * lq + e])),
+                              pair16::pow2(-pair16::scale_exp(mx_in[r * 16 + 4 * lq + e + 1]))};
+          unsigned k0 = pair16::KEY_ZERO, k1 = pair16::KEY_ZERO;
 #pragma unroll
-        for (int j = 0; j < NCT; ++j) {
-          const float y = ((acc[r][j][e] * e_ci[j]) * ri) * e_sc[j] + e_sh[j];
-          acc[r][j][e] = y >= 0.f ? y : y * e_slope;
-          const unsigned b = pair16::finite_abs_bits(acc[r][j][e]);
-          m[r][e] = b > m[r][e] ? b : m[r][e];
+          for (int j = 0; j < NCT; ++j) {
+            const f32x2_t a = {acc[r][j][e], acc[r][j][e + 1]};
+            const f32x2_t y = __builtin_elementwise_fma((a * e_ci[j]) * ri, f32x2_t{e_sc[j], e_sc[j]}, f32x2_t{e_sh[j], e_sh[j]});
+            const f32x2_t z = y * e_slope;
+            acc[r][j][e] = p16_activation<decltype(unit)::value>(y[0], z[0]);
+            acc[r][j][e + 1] = p16_activation<decltype(unit)::value>(y[1], z[1]);
+            const unsigned b0 = pair16::finite_key(acc[r][j][e]), b1 = pair16::finite_key(acc[r][j][e + 1]);
+            k0 = b0 > k0 ? b0 : k0;
+            k1 = b1 > k1 ? b1 : k1;
+          }
+          key[r * 4 + e] = k0;
+          key[r * 4 + e + 1] = k1;
         }
-      }
+    };
+    if (slope_unit) finish(std::true_type{});
+    else finish(std::false_type{});
+    unsigned mr = 0u;                                       // lane l15 of a row group: the maximum of the group's row l15
+    if (!last && mine) mr = pair16::key_bits(pair16::max16_scatter(key, l15));
     __syncthreads();   // every wave has read its last A pieces: the buffer may be overwritten
     if (last) {
       if (mine) {
@@ -678,26 +727,24 @@ __device__ __forceinline__ void p16_layer(const FusedNet& net, const FusedLayer&
         }
       }
     } else {
-      if (mine) {
-#pragma unroll
-        for (int r = 0; r < RT; ++r)
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const unsigned mr = pair16::max16(m[r][e]);
-            if (l15 == 0) atomicMax(&mx_out[r * 16 + 4 * lq + e], mr);
-          }
-      }
+      // one ds_max_u32 of all 64 lanes: lane l15 = 4 r + e holds row (r, e) of its group's sixteen
+      if (mine) atomicMax(&mx_out[(l15 >> 2) * 16 + 4 * lq + (l15 & 3)], mr);
       __syncthreads();   // the rows' maxima are complete
       if (mine) {
+        const bool odd = l15 & 1;
+        p16_lds_t p_hi, p_lo;
+        p16_planes(lds + ((4 * lq + (odd ? 2 : 0)) * fx::PLD + col_tile0 * 16 + (l15 & ~1)) * 2, p_hi, p_lo);
 #pragma unroll
         for (int r = 0; r < RT; ++r) {
           float s[4];
 #pragma unroll
           for (int e = 0; e < 4; ++e) s[e] = pair16::pow2(pair16::scale_exp(mx_out[r * 16 + 4 * lq + e]));
 #pragma unroll
-          for (int j = 0; j < NCT; ++j)
-            p16_put4(lds, r * 16 + 4 * lq, (col_tile0 + j) * 16 + l15, acc[r][j][0] * s[0], acc[r][j][1] * s[1],
-                     acc[r][j][2] * s[2], acc[r][j][3] * s[3]);
+          for (int j = 0; j < NCT; ++j) {
+            const f32x2_t v01 = f32x2_t{acc[r][j][0], acc[r][j][1]} * f32x2_t{s[0], s[1]};
+            const f32x2_t v23 = f32x2_t{acc[r][j][2], acc[r][j][3]} * f32x2_t{s[2], s[3]};
+            p16_put4(p_hi, p_lo, (r * 16 * fx::PLD + j * 16) * 2, fx::PLD * 2, odd, v01[0], v01[1], v23[0], v23[1]);
+          }
         }
       }
     }
@@ -707,16 +754,25 @@ __device__ __forceinline__ void p16_layer(const FusedNet& net, const FusedLayer&
     __syncthreads();
     const int c16 = tid & 15, r16 = tid >> 4;
     float y[NCT][4];
-    unsigned m[4] = {0u, 0u, 0u, 0u};
+    unsigned key[4] = {pair16::KEY_ZERO, pair16::KEY_ZERO, pair16::KEY_ZERO, pair16::KEY_ZERO};
     float ri[4];
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) ri[rr] = pair16::pow2(-pair16::scale_exp(mx_in[r16 + 16 * rr]));
     ksplit_sum<NCT>(act, tid, N, scale, shift, [&](int j, int rr, int nc, float sum, float sc, float sh) {
-      const float v = ((sum * wexp[nc]) * ri[rr]) * sc + sh;
-      y[j][rr] = v >= 0.f ? v : v * e_slope;
-      const unsigned b = pair16::finite_abs_bits(y[j][rr]);
-      m[rr] = b > m[rr] ? b : m[rr];
+      y[j][rr] = ((sum * wexp[nc]) * ri[rr]) * sc + sh;
     });
+    auto finish = [&](auto unit) {
+#pragma unroll
+      for (int j = 0; j < NCT; ++j)
+#pragma unroll
+        for (int rr = 0; rr < 4; ++rr) {
+          y[j][rr] = p16_activation<decltype(unit)::value>(y[j][rr], y[j][rr] * e_slope);
+          const unsigned b = pair16::finite_key(y[j][rr]);
+          key[rr] = b > key[rr] ? b : key[rr];
+        }
+    };
+    if (slope_unit) finish(std::true_type{});
+    else finish(std::false_type{});
     __syncthreads();   // the partial sums are read: the results take their place
     if (last) {
 #pragma unroll
@@ -727,25 +783,17 @@ __device__ __forceinline__ void p16_layer(const FusedNet& net, const FusedLayer&
       float s[4];
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
-        m[rr] = pair16::max16(m[rr]);
-        if (c16 == 0) mx_out[r16 + 16 * rr] = m[rr];
-        s[rr] = pair16::pow2(pair16::scale_exp(m[rr]));
+        const unsigned m = pair16::key_bits(pair16::max16(key[rr]));
+        if (c16 == 0) mx_out[r16 + 16 * rr] = m;
+        s[rr] = pair16::pow2(pair16::scale_exp(m));
       }
-      // (lane pairs as in p16_put4, the four values of a lane now 16 rows apart)
+      // (lane pairs as in the wide layers, the four values of a lane now 16 rows apart)
       const bool odd = c16 & 1;
+      p16_lds_t p_hi, p_lo;
+      p16_planes(lds + ((r16 + (odd ? 32 : 0)) * fx::PLD + (c16 & ~1)) * 2, p_hi, p_lo);
 #pragma unroll
-      for (int j = 0; j < NCT; ++j) {
-        const float v0 = y[j][0] * s[0], v1 = y[j][1] * s[1], v2 = y[j][2] * s[2], v3 = y[j][3] * s[3];
-        const float q0 = __shfl_xor(odd ? v0 : v2, 1), q1 = __shfl_xor(odd ? v1 : v3, 1);
-        unsigned h0, l0, h1, l1;
-        pair16::split_pair(odd ? q0 : v0, odd ? v2 : q0, h0, l0);
-        pair16::split_pair(odd ? q1 : v1, odd ? v3 : q1, h1, l1);
-        char* p = lds + ((r16 + (odd ? 32 : 0)) * fx::PLD + j * 16 + (c16 & ~1)) * 2;
-        *reinterpret_cast<unsigned*>(p) = h0;
-        *reinterpret_cast<unsigned*>(p + fx::PLANE_BYTES) = l0;
-        *reinterpret_cast<unsigned*>(p + 16 * fx::PLD * 2) = h1;
-        *reinterpret_cast<unsigned*>(p + 16 * fx::PLD * 2 + fx::PLANE_BYTES) = l1;
-      }
+      for (int j = 0; j < NCT; ++j)
+        p16_put4(p_hi, p_lo, j * 16 * 2, 16 * fx::PLD * 2, odd, y[j][0] * s[0], y[j][1] * s[1], y[j][2] * s[2], y[j][3] * s[3]);
     }
   }
   __syncthreads();
