@@ -218,14 +218,9 @@ def tanh_finish(z):
     return (1 - t * t) * (z.abs() + 2) * U + 3 * U
 
 
-def lstm_step_reference(w_ih, w_hh, bias, x, h, c, gamma, e_x=None, e_h=None, e_c=None):
-    """One LSTM step in float64 from (x, h, c) and its allowance.  The pre-activations get the GEMM bound
-    gamma u (|W_ih| |x| + |W_hh| |h| + |b|) plus propagate(e_x, W_ih) + propagate(e_h, W_hh); the gates Lipschitz 1/4 (sigmoid)
-    and 1 (tanh) plus the finish terms of the approximate __expf / rcp (sigmoid_finish, tanh_finish -- stated, not folded
-    into gamma); then
-        e_c' = |f| e_c + |c| e_f + |g| e_i + |i| e_g + gamma u (|f c| + |i g|)
-        e_h' = |tanh c'| e_o + |o| (e_c' + tanh_finish(c')) + gamma u |h'|.
-    Returns (h', c', e_h', e_c') in float64."""
+def _lstm_step(w_ih, w_hh, bias, x, h, c, gamma, e_x=None, e_h=None, e_c=None):
+    """The one body of `lstm_step_reference` and `lstm_gates_reference`: (h', c', e_h', e_c', gates, e_gates), the gates
+    activated, i | f | g | o along the columns."""
     x, h, c = (t.detach().double() for t in (x, h, c))
     w_ih, w_hh, bias = (t.detach().double().to(x.device) for t in (w_ih, w_hh, bias))
     H = w_hh.shape[1]
@@ -246,7 +241,132 @@ def lstm_step_reference(w_ih, w_hh, bias, x, h, c, gamma, e_x=None, e_h=None, e_
     tc = torch.tanh(c_new)
     h_new = o * tc
     e_h_new = tc.abs() * eo + o.abs() * (e_c_new + tanh_finish(c_new)) + gamma * U * h_new.abs()
-    return h_new, c_new, e_h_new, e_c_new
+    return h_new, c_new, e_h_new, e_c_new, torch.cat([i, f, g, o], dim=1), torch.cat([ei, ef, eg, eo], dim=1)
+
+
+def lstm_step_reference(w_ih, w_hh, bias, x, h, c, gamma, e_x=None, e_h=None, e_c=None):
+    """One LSTM step in float64 from (x, h, c) and its allowance.  The pre-activations get the GEMM bound
+    gamma u (|W_ih| |x| + |W_hh| |h| + |b|) plus propagate(e_x, W_ih) + propagate(e_h, W_hh); the gates Lipschitz 1/4 (sigmoid)
+    and 1 (tanh) plus the finish terms of the approximate __expf / rcp (sigmoid_finish, tanh_finish -- stated, not folded
+    into gamma); then
+        e_c' = |f| e_c + |c| e_f + |g| e_i + |i| e_g + gamma u (|f c| + |i g|)
+        e_h' = |tanh c'| e_o + |o| (e_c' + tanh_finish(c')) + gamma u |h'|.
+    Returns (h', c', e_h', e_c') in float64."""
+    return _lstm_step(w_ih, w_hh, bias, x, h, c, gamma, e_x, e_h, e_c)[:4]
+
+
+def lstm_gates_reference(w_ih, w_hh, bias, x, h, c, gamma):
+    """`lstm_step_reference` from an exact state, with what the training forward saves for the reverse pass returned as
+    well: (h', c', e_h', e_c', gates, e_gates), the activated gates i | f | g | o as (rows, 4H) and their allowances."""
+    return _lstm_step(w_ih, w_hh, bias, x, h, c, gamma)
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# Training LSTM: the save buffer of empose_lstm_train_fwd and back-propagation through time from it
+LSTM_SAVE_PLANES = 7
+
+
+def lstm_save_planes(save, L, B, F, H):
+    """Views into the save buffer (csrc/api_lstm.hip, LstmSave), per layer: `gates` [B][F][4H] activated i | f | g | o,
+    `c` [B][F][H] after every step, `hprev` [B][F][H] the hidden state before every step, `y` [B][F][H] the layer's output
+    (the top layer's goes to the caller's y; its plane is never written)."""
+    bfh = B * F * H
+    rec = save.reshape(L, LSTM_SAVE_PLANES * bfh)
+    return [dict(gates=rec[l, :4 * bfh].view(B, F, 4 * H), c=rec[l, 4 * bfh:5 * bfh].view(B, F, H),
+                 hprev=rec[l, 5 * bfh:6 * bfh].view(B, F, H), y=rec[l, 6 * bfh:].view(B, F, H)) for l in range(L)]
+
+
+def lstm_bptt_reference(weights, x, lens, c0, save, dy, gamma):
+    """The reverse sweep of the training LSTM (empose_lstm_train_bwd) in float64 FROM THE SAVED PLANES, and one allowance
+    per output element.  `weights`: (w_ih, w_hh, b_ih, b_hh) per layer, flat; x [B][F][K]; `lens` [B] or None; `c0`
+    [L][B][H] or None; `save` the flat save buffer; dy [B][F][H] the cotangent of the top layer's output.  The planes are
+    exactly what the kernels read (activated gates, c after every step, hprev, the output of the layer below as layer
+    input), converted to float64: the forward's error is no part of this, the sweep is linear in dy, and what remains is
+    the roundoff of the reverse kernels alone.
+    Returns (values, allowances), dicts with keys dx [B][F][K], d_h0, d_c0 [L][B][H], w_ih<l>, w_hh<l>, b_ih<l>, b_hh<l>.
+
+    The allowance is a running bound, u = 2^-24, P = `propagate` (root-sum-square through the products), the local term of
+    every product the worst case gamma u |A| |W|.  Per layer, top down, t = F-1 .. 0 (rows with t >= len: dG = 0 exactly,
+    e = 0, dc unchanged):
+        dh  = dy_l[t] + dG[t+1] W_hh        e_dh = e_dy_l[t] + P(e_dG[t+1], W_hh^T) + gamma u |dG[t+1]| |W_hh| + u |dh|
+        tc  = tanh(c_t)  e_tc = 4 u (tanhf) s2 = 1 - tc^2,  e_s2 = 2 |tc| e_tc + 2 u
+        d_o = dh tc                         e_do = |tc| e_dh + |dh| e_tc + u |d_o|
+        dc  = dc_in + dh o s2               e_dc = e_dc_in + |o s2| e_dh + |dh o| e_s2 + 3 u |dh o s2| + u |dc|
+        dG_i = dc g i (1 - i)               e = |g i (1 - i)| e_dc + u |dc g i| + 4 u |dG_i|
+        dG_f = dc c_prev f (1 - f)          e = |c_prev f (1 - f)| e_dc + u |dc c_prev f| + 4 u |dG_f|
+        dG_g = dc i (1 - g^2)               e = |i (1 - g^2)| e_dc + 2 u |dc i| + 4 u |dG_g|
+        dG_o = d_o o (1 - o)                e = |o (1 - o)| e_do + u |d_o o| + 4 u |dG_o|
+        dc_in <- dc f                       e <- |f| e_dc + u |dc f|
+    (c_prev = c0 at t = 0, 0 without one; the u |.| terms beside the 4 u |dG| are the rounding of 1 - i, 1 - f, 1 - g^2 and
+    1 - o, each at most u, or 2 u with the square, times what multiplies it.)  After the loop, over the rows (b, t):
+        dW   = dG^T In        e = sqrt((e_dG^2)^T In^2) + gamma u |dG|^T |In|   (In = x, the y plane below, or hprev)
+        db   = sum dG         e = sqrt(sum e_dG^2) + gamma u sum |dG|            (b_ih and b_hh both)
+        dx_l = dG W_ih        e = P(e_dG, W_ih^T) + gamma u |dG| |W_ih|          (the e_dy of the layer below)
+        d_h0 = dG[0] W_hh     the same form;      d_c0 = the final dc_in with its e."""
+    L = len(weights) // 4
+    B, F, _ = x.shape
+    H = dy.shape[2]
+    dev = x.device
+    d64 = lambda t: t.detach().double().to(dev)
+    gu = gamma * U
+    lens = torch.full((B,), F, dtype=torch.long, device=dev) if lens is None else lens.to(dev).long()
+    planes = lstm_save_planes(save, L, B, F, H)
+    dy_l, e_dy_l = d64(dy), torch.zeros(B, F, H, dtype=torch.float64, device=dev)
+    val, tol = {}, {}
+    val['d_h0'], tol['d_h0'] = (torch.zeros(L, B, H, dtype=torch.float64, device=dev) for _ in range(2))
+    val['d_c0'], tol['d_c0'] = (torch.zeros(L, B, H, dtype=torch.float64, device=dev) for _ in range(2))
+    for l in range(L - 1, -1, -1):
+        w_ih, w_hh = d64(weights[4 * l]), d64(weights[4 * l + 1])
+        gates, c_all, hprev = (d64(planes[l][k]) for k in ('gates', 'c', 'hprev'))
+        layer_in = d64(x) if l == 0 else d64(planes[l - 1]['y'])
+        dG = torch.zeros(B, F, 4 * H, dtype=torch.float64, device=dev)
+        e_dG = torch.zeros_like(dG)
+        dc_in = torch.zeros(B, H, dtype=torch.float64, device=dev)
+        e_dc_in = torch.zeros_like(dc_in)
+        product = lambda g, e, w: (g @ w, propagate(e, w.t()) + gu * (g.abs() @ w.abs()))
+        for t in range(F - 1, -1, -1):
+            live = (t < lens)[:, None]
+            dh, e_dh = dy_l[:, t], e_dy_l[:, t]
+            if t + 1 < F:
+                rec, e_rec = product(dG[:, t + 1], e_dG[:, t + 1], w_hh)
+                dh, e_dh = dh + rec, e_dh + e_rec
+            e_dh = e_dh + U * dh.abs()
+            i, f, g, o = (gates[:, t, k * H:(k + 1) * H] for k in range(4))
+            c_prev = c_all[:, t - 1] if t > 0 else (torch.zeros_like(dc_in) if c0 is None else d64(c0[l]))
+            tc = torch.tanh(c_all[:, t])
+            e_tc = 4 * U
+            s2 = 1 - tc * tc
+            e_s2 = 2 * tc.abs() * e_tc + 2 * U
+            d_o = dh * tc
+            e_do = tc.abs() * e_dh + dh.abs() * e_tc + U * d_o.abs()
+            dc = dc_in + dh * o * s2
+            e_dc = e_dc_in + (o * s2).abs() * e_dh + (dh * o).abs() * e_s2 + 3 * U * (dh * o * s2).abs() + U * dc.abs()
+            dGi = dc * g * i * (1 - i)
+            dGf = dc * c_prev * f * (1 - f)
+            dGg = dc * i * (1 - g * g)
+            dGo = d_o * o * (1 - o)
+            e_i = (g * i * (1 - i)).abs() * e_dc + U * (dc * g * i).abs() + 4 * U * dGi.abs()
+            e_f = (c_prev * f * (1 - f)).abs() * e_dc + U * (dc * c_prev * f).abs() + 4 * U * dGf.abs()
+            e_g = (i * (1 - g * g)).abs() * e_dc + 2 * U * (dc * i).abs() + 4 * U * dGg.abs()
+            e_o = (o * (1 - o)).abs() * e_do + U * (d_o * o).abs() + 4 * U * dGo.abs()
+            zero = torch.zeros_like(dc)
+            dG[:, t] = torch.cat([torch.where(live, v, zero) for v in (dGi, dGf, dGg, dGo)], dim=1)
+            e_dG[:, t] = torch.cat([torch.where(live, v, zero) for v in (e_i, e_f, e_g, e_o)], dim=1)
+            dc_in, e_dc_in = torch.where(live, dc * f, dc_in), torch.where(live, f.abs() * e_dc + U * (dc * f).abs(), e_dc_in)
+        val['d_c0'][l], tol['d_c0'][l] = dc_in, e_dc_in
+        val['d_h0'][l], tol['d_h0'][l] = product(dG[:, 0], e_dG[:, 0], w_hh)
+        rows, e_rows = dG.reshape(B * F, 4 * H), e_dG.reshape(B * F, 4 * H)
+        for key, a in (('w_ih', layer_in), ('w_hh', hprev)):
+            a = a.reshape(B * F, -1)
+            val['%s%d' % (key, l)] = rows.t() @ a
+            tol['%s%d' % (key, l)] = torch.sqrt((e_rows * e_rows).t() @ (a * a)) + gu * (rows.abs().t() @ a.abs())
+        for key in ('b_ih', 'b_hh'):
+            val['%s%d' % (key, l)] = rows.sum(0)
+            tol['%s%d' % (key, l)] = torch.sqrt((e_rows * e_rows).sum(0)) + gu * rows.abs().sum(0)
+        dx_l, e_dx_l = product(rows, e_rows, w_ih)
+        dy_l, e_dy_l = dx_l.view(B, F, -1), e_dx_l.view(B, F, -1)
+    val['dx'], tol['dx'] = dy_l, e_dy_l
+    return val, tol
 
 
 # ----------------------------------------------------------------------------------------------------------------------

@@ -39,15 +39,20 @@ WEIGHT_KEYS = ('w_ih', 'w_hh', 'b_ih', 'b_hh')
 
 
 @functools.lru_cache(maxsize=None)
-def inputs(B, F, K, H, L):
+def inputs(B, F, K, H, L, lens='ragged', state=True, dev=DEV):
+    """The tensors of a case, the same draws whatever the options.  `lens`: 'ragged' (row 0 reaches F), 'short' (no row
+    does: at most F - 1) or None (no seq_lengths); `state` False: neither h0 nor c0; `dev`: where the tensors live."""
     g = torch.Generator().manual_seed(1000 * B + 100 * F + H + L)
     rnd = lambda *shape: torch.randn(*shape, generator=g)
-    lens = torch.randint(1, F + 1, (B,), generator=g, dtype=torch.int32)
-    lens[0] = F
-    weights = [(rnd(*shape) / H ** 0.5).to(DEV) for l in range(L)
+    drawn = torch.randint(1, F + 1, (B,), generator=g, dtype=torch.int32)
+    drawn[0] = F
+    if lens == 'short':
+        drawn = torch.clamp(drawn, max=F - 1)
+    weights = [(rnd(*shape) / H ** 0.5).to(dev) for l in range(L)
                for shape in ((4 * H, K if l == 0 else H), (4 * H, H), (4 * H,), (4 * H,))]
-    return dict(B=B, F=F, K=K, H=H, L=L, x=rnd(B, F, K).to(DEV), lens=lens.to(DEV), h0=(0.5 * rnd(L, B, H)).to(DEV),
-                c0=(0.5 * rnd(L, B, H)).to(DEV), dy=rnd(B, F, H).to(DEV), weights=weights)
+    x, h0, c0, dy = rnd(B, F, K), 0.5 * rnd(L, B, H), 0.5 * rnd(L, B, H), rnd(B, F, H)
+    return dict(B=B, F=F, K=K, H=H, L=L, x=x.to(dev), lens=None if lens is None else drawn.to(dev),
+                h0=h0.to(dev) if state else None, c0=c0.to(dev) if state else None, dy=dy.to(dev), weights=weights)
 
 
 def _params(inp):
@@ -70,7 +75,7 @@ def forward(inp):
     out = dict(y=torch.empty(B, F, H, device=DEV), h_n=torch.empty(L, B, H, device=DEV), c_n=torch.empty(L, B, H, device=DEV),
                save=torch.zeros(lib.empose_lstm_train_save_floats(L, B, F, H), device=DEV))
     ws, nbytes = _workspace(p, B, F)
-    _lib.check(lib.empose_lstm_train_fwd(C.byref(p), B, F, _lib.dptr(inp['x']), K, _lib.dptr(inp['lens']),
+    _lib.check(lib.empose_lstm_train_fwd(C.byref(p), B, F, _lib.dptr(inp['x']), inp.get('ldx', K), _lib.dptr(inp['lens']),
                                          _lib.dptr(inp['h0']), _lib.dptr(inp['c0']), _lib.dptr(out['y']), _lib.dptr(out['h_n']),
                                          _lib.dptr(out['c_n']), _lib.dptr(out['save']), _lib.dptr(ws), nbytes,
                                          _lib.current_stream()))
@@ -93,7 +98,8 @@ def backward(inp, save, optional=True):
         for l in range(L):
             g.d_h0[l], g.d_c0[l] = out['d_h0'][l].data_ptr(), out['d_c0'][l].data_ptr()
     ws, nbytes = _workspace(p, B, F)
-    _lib.check(lib.empose_lstm_train_bwd(C.byref(p), B, F, _lib.dptr(inp['x']), K, _lib.dptr(inp['lens']), _lib.dptr(inp['c0']),
+    _lib.check(lib.empose_lstm_train_bwd(C.byref(p), B, F, _lib.dptr(inp['x']), inp.get('ldx', K), _lib.dptr(inp['lens']),
+                                         _lib.dptr(inp['c0']),
                                          _lib.dptr(save), _lib.dptr(inp['dy']), _lib.dptr(out.get('dx')), C.byref(g),
                                          _lib.dptr(ws), nbytes, _lib.current_stream()))
     torch.cuda.synchronize()
