@@ -370,6 +370,311 @@ def lstm_bptt_reference(weights, x, lens, c0, save, dy, gamma):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
+# Training update MLPs: the save buffer and the stash of empose_mlp_train_fwd / _bwd*, and both sweeps from them
+#
+# Roundings of elementwise operations are counted one by one, each as v = 2 u = 2^-23, one unit in the last place of its
+# result: twice what a correctly rounded fp32 operation can be off by.  A float32 evaluation with correctly rounded
+# operations (the control of tests/test_train_mlp_bounds.py) therefore stays within half of such an allowance by
+# construction and not by luck -- with u per operation a quantity that is ONE rounding away from its inputs (s = weight
+# rstd) sits at up to 1.0 of its allowance in the control --, and an operation the device evaluates to one unit and not
+# half of one (v_rcp_f32, v_rsq_f32, v_sqrt_f32, where a compiler picks them for a quotient or a root) is covered.  Products
+# and column sums keep gamma u |A| |W|, gamma = GAMMA_GEMM.
+ULP = 2.0 * U
+def mlp_train_save_planes(save, layout, L, M, H):
+    """Views into the save buffer of one network (csrc/api_train.hip, MlpPlan), one dict per hidden layer (L dense layers,
+    L - 1 hidden):
+        layout 1 (passes, one-launch layers)   pre = z [M][H] | a [M][H] | mean [H] | rstd [H]
+        layout 2 (fused)                       pre = y [M][H] | mean | rstd | s | t
+        layout 3 (epi)                         pre = y [M][H] | a [M][H] | mean | rstd | s | t
+    `pre` is the layer's product + bias (called z in layout 1, y in the others), `a` its activation after BatchNorm and
+    PReLU, s = gamma rstd and t = beta - mean s the affine form of the BatchNorm."""
+    n_planes = 1 if layout == 2 else 2
+    vecs = ('mean', 'rstd') if layout == 1 else ('mean', 'rstd', 's', 't')
+    rec = save.reshape(L - 1, n_planes * M * H + len(vecs) * H)
+    out = []
+    for l in range(L - 1):
+        d = {'pre': rec[l, :M * H].view(M, H)}
+        if layout != 2:
+            d['a'] = rec[l, M * H:2 * M * H].view(M, H)
+        for k, name in enumerate(vecs):
+            d[name] = rec[l, n_planes * M * H + k * H:n_planes * M * H + (k + 1) * H]
+        out.append(d)
+    return out
+
+
+def mlp_train_stash_planes(stash, L, M, H, out_dim):
+    """Views into the stash of one application (deferred weight gradients): dZ_l [M][H] of every hidden layer, then the
+    copy of d_out [M][(out_dim + 3) & ~3]."""
+    op = (out_dim + 3) & ~3
+    return [stash[l * M * H:(l + 1) * M * H].view(M, H) for l in range(L - 1)] + \
+        [stash[(L - 1) * M * H:(L - 1) * M * H + M * op].view(M, op)]
+
+
+def _f32(v):
+    """A host float as the kernels receive it (eps and momentum travel as float)."""
+    return float(torch.tensor(float(v), dtype=torch.float32))
+
+
+def _mlp_layer_input(layers, x, planes, layout, l):
+    """(h, e_h): what layer l's product and its weight gradient read, in float64 from the saved numbers.  x for layer 0
+    and the saved activation plane in layouts 1 and 3, both exact (e_h None).  Layout 2 stores no activation: every consumer
+    re-forms a = PReLU(s y + t) in fp32 from the saved y, s, t; here in float64 with
+        e_h = max(1, |slope|) v (|s y| + |s y + t|) + v |a|
+    (the product and the sum round once each, the slope product once; PReLU is continuous, so an element whose fp32 sign
+    differs still moves by at most its Lipschitz constant times the error)."""
+    if l == 0:
+        return x.detach().double(), None
+    p = planes[l - 1]
+    if layout != 2:
+        return p['a'].detach().double(), None
+    slope = layers[l - 1]['slope'].detach().double().to(x.device)
+    sy = p['s'].detach().double() * p['pre'].detach().double()
+    yh = sy + p['t'].detach().double()
+    a = _prelu(yh, slope)
+    return a, torch.clamp(slope.abs(), min=1.0) * ULP * (sy.abs() + yh.abs()) + ULP * a.abs()
+
+
+def _bn_statistics(z, eps, gamma):
+    """mean, biased variance and rstd of the columns of a float64 plane, with the allowances of `train_mlp_reference` for
+    an exact plane (e_z = 0): e_mu = gamma u rowmean(|z|); half the variance's, the bracket of |dr| / r there,
+    h = |mean| e_mu + gamma u rowmean(z^2).
+    The three-pass BatchNorm of large batches (csrc/bn_prelu.hip, bn_stats_fwd_kernel / bn_combine_fwd_kernel) sums the
+    plane SHIFTED by its first row, k = z[0]: d = sum(z - k) / M, mean = k + d, var = sum((z - k)^2) / M - d^2.  That is
+    the same one-pass form on z - k, so its allowances are the same expressions on z - k (plus one rounding for k + d):
+    e_mu' = gamma u rowmean(|z - k|) + v |mean|,  h' = |d| gamma u rowmean(|z - k|) + gamma u rowmean((z - k)^2).  Where the
+    first row of a column lies far from the column's mean these exceed e_mu and h (measured on the MI355X at 1064 x 152 x 64:
+    one rstd element at 1.005 of r^3 h + 3 v r); each statistic gets the larger of its two forms, which covers both paths.
+    Returns (mean, var, r, e_mu, h)."""
+    gu = gamma * U
+    mean, var = z.mean(0), z.var(0, unbiased=False)
+    e_mu = gu * z.abs().mean(0)
+    half = mean.abs() * e_mu + gu * (z * z).mean(0)
+    zk = z - z[0]
+    e_d = gu * zk.abs().mean(0)
+    half_k = (mean - z[0]).abs() * e_d + gu * (zk * zk).mean(0)
+    return mean, var, 1.0 / torch.sqrt(var + eps), torch.maximum(e_mu, e_d + ULP * mean.abs()), torch.maximum(half, half_k)
+
+
+def mlp_train_fwd_reference(layers, x, save, layout, gamma, eps=1e-5, momentum=0.1, running=None):
+    """Everything the training forward of one update MLP writes (empose_mlp_train_fwd / _fwd_pair), each quantity in
+    float64 FROM THE SAVED QUANTITIES THE KERNEL COMPUTED IT FROM, and one allowance per element: the error of the layers
+    below is no part of a layer's check.  `layers`: dicts of w, b, bn = (weight, bias) or None, slope, as
+    `train_mlp_reference`; `save` the flat save buffer in `layout`; `running`: per hidden layer (running_mean,
+    running_var) as they were BEFORE the call, or None.  Returns (values, allowances), dicts with keys pre<l>, mean<l>,
+    rstd<l>, s<l>, t<l> (layouts 2, 3), a<l> (layouts 1, 3), running_mean<l>, running_var<l> per hidden layer l, and out.
+    num_batches_tracked is the caller's: exactly + 1.
+
+    u = 2^-24, v = 2 u (above), P = `propagate`, r = 1 / sqrt(var + eps), in the order of a layer:
+        pre   = h W^T + b                       e = gamma u (|h| |W|^T + |b|) + P(e_h, W)     (h, e_h: `_mlp_layer_input`)
+        mean, var of the SAVED pre plane z      e_mu = gamma u rowmean(|z|)
+                                                e_var = 2 h,  h = |mean| e_mu + gamma u rowmean(z^2)
+                                                (each the larger of this and its form on the plane shifted by its first row,
+                                                `_bn_statistics`)
+        rstd  = r                               e = r^3 h + 3 v r              (the sum with eps, the root and the quotient)
+        s     = weight rstd                     e = v |s|                                     (from the saved rstd)
+        t     = bias - mean s                   e = |mean| e_s + v (|mean s| + |t|)           (from the saved mean and rstd)
+        a     = PReLU(y), with y recomputed from the saved plane and the saved statistics as the kernel does:
+                layout 1: y = weight ((z - mean) rstd) + bias     e_y = v (3 |weight xh| + |y|) + |weight| rstd u |mean|
+                          (xh = (z - mean) rstd: the difference, two products, the sum.  The last term: bn_prelu_fwd_kernel
+                          holds mean = sum (1 / M) in a register, and the compiler contracts that product into the
+                          difference, z - sum (1 / M) with ONE rounding: the forward's mean is the unrounded product, up to
+                          u |mean| from the saved one, the same for all rows of a column.  Measured on the MI355X without
+                          the term: a few elements with |y| << |weight xh| of the pass kernels at M = 100, 200, 384, 700
+                          up to 44 times over, columns apart, none at M = 512 and 1024 where 1 / M is a power of two and the
+                          product exact.  The reverse kernels read the saved mean: their branch value has no such term.)
+                layout 3: y = s z + t                             e_y = v (|s z| + |y|)
+                                                e = max(1, |slope|) e_y + v |a|
+        out   = h W^T + b  from the last saved activation, as pre
+        running_mean' = (1 - m) running_mean + m mean             e = v (2 |(1 - m) running_mean| + |m mean| + |.'|)
+        running_var'  = (1 - m) running_var + m var M / (M - 1)   e = m M / (M - 1) e_var + v (2 |(1 - m) running_var| +
+                        3 |m var M / (M - 1)| + |.'|)
+    (the fp32 difference 1 - m and its product round once each, m times the statistic once, the sum once; the unbiased
+    variance two more; mean is the saved one, var the float64 one of the saved plane.)"""
+    dev = x.device
+    d64 = lambda t: t.detach().double().to(dev)
+    gu = gamma * U
+    L, M, H = len(layers), x.shape[0], layers[0]['w'].shape[0]
+    eps, mom = _f32(eps), _f32(momentum)
+    planes = mlp_train_save_planes(save, layout, L, M, H)
+    val, tol = {}, {}
+    for l in range(L):
+        h, e_h = _mlp_layer_input(layers, x, planes, layout, l)
+        w, b = d64(layers[l]['w']), d64(layers[l]['b'])
+        key = 'out' if l == L - 1 else 'pre%d' % l
+        val[key] = h @ w.t() + b
+        tol[key] = gu * linear_magnitude(h, w, b) + (0 if e_h is None else propagate(e_h, w))
+        if l == L - 1:
+            break
+        p = planes[l]
+        z, ms, rs = d64(p['pre']), d64(p['mean']), d64(p['rstd'])
+        bw, bb = (d64(t) for t in layers[l]['bn'])
+        slope = d64(layers[l]['slope'])
+        mean, var, r, e_mu, half = _bn_statistics(z, eps, gamma)
+        val['mean%d' % l], tol['mean%d' % l] = mean, e_mu
+        val['rstd%d' % l], tol['rstd%d' % l] = r, r ** 3 * half + 3 * ULP * r
+        if layout != 1:
+            s = bw * rs
+            t = bb - ms * s
+            val['s%d' % l], tol['s%d' % l] = s, ULP * s.abs()
+            val['t%d' % l], tol['t%d' % l] = t, ms.abs() * ULP * s.abs() + ULP * ((ms * s).abs() + t.abs())
+        if layout != 2:
+            if layout == 1:
+                gx = bw * ((z - ms) * rs)
+                y = gx + bb
+                e_y = ULP * (3 * gx.abs() + y.abs()) + bw.abs() * rs * U * ms.abs()
+            else:
+                sy = d64(p['s']) * z
+                y = sy + d64(p['t'])
+                e_y = ULP * (sy.abs() + y.abs())
+            a = _prelu(y, slope)
+            val['a%d' % l], tol['a%d' % l] = a, torch.clamp(slope.abs(), min=1.0) * e_y + ULP * a.abs()
+        if running is not None:
+            rm0, rv0 = (d64(t) for t in running[l])
+            fac = M / (M - 1.0) if M > 1 else 1.0
+            keep, new_m, new_v = 1.0 - mom, mom * ms, mom * var * fac
+            val['running_mean%d' % l] = keep * rm0 + new_m
+            tol['running_mean%d' % l] = ULP * (2 * (keep * rm0).abs() + new_m.abs() + val['running_mean%d' % l].abs())
+            val['running_var%d' % l] = keep * rv0 + new_v
+            tol['running_var%d' % l] = mom * fac * 2 * half + ULP * (2 * (keep * rv0).abs() + 3 * new_v.abs()
+                                                                    + val['running_var%d' % l].abs())
+    return val, tol
+
+
+def mlp_train_wgrad_reference(rows, gamma, init=None):
+    """dW = dY^T In and db = sum dY of one layer over the rows of every application in `rows`, a list of (dY, e_dY, In,
+    e_In or None) -- float64 values and their allowances -- with
+        e_dW = sqrt((e_dY^2)^T In^2) + sqrt((dY^2)^T e_In^2) + gamma u |dY|^T |In|
+        e_db = sqrt(sum e_dY^2) + gamma u sum |dY|
+    (sums over rows whose errors are independent from row to row: root-sum-square, the local term the worst case, as
+    `lstm_bptt_reference` has them).  `init` = (dW0, db0): accumulate onto these, one more rounding, v |result|.
+    Returns (dW, e_dW, db, e_db)."""
+    gu = gamma * U
+    dY, e_dY, a = (torch.cat([r[k] for r in rows], dim=0) for k in range(3))
+    dW = dY.t() @ a
+    e_dW = torch.sqrt((e_dY * e_dY).t() @ (a * a)) + gu * (dY.abs().t() @ a.abs())
+    if rows[0][3] is not None:
+        e_a = torch.cat([r[3] for r in rows], dim=0)
+        e_dW = e_dW + torch.sqrt((dY * dY).t() @ (e_a * e_a))
+    db = dY.sum(0)
+    e_db = torch.sqrt((e_dY * e_dY).sum(0)) + gu * dY.abs().sum(0)
+    if init is not None:
+        dW, db = dW + init[0].detach().double().to(dW.device), db + init[1].detach().double().to(dW.device)
+        e_dW, e_db = e_dW + ULP * dW.abs(), e_db + ULP * db.abs()
+    return dW, e_dW, db, e_db
+
+
+def mlp_train_bwd_reference(layers, x, save, layout, d_out, gamma, init=None, rows_only=False):
+    """The reverse sweep of one training update MLP (empose_mlp_train_bwd / _bwd_deferred / _bwd_deferred_pair, and the
+    products of empose_mlp_train_wgrad) in float64 FROM THE SAVED PLANES and d_out, with a running allowance per element.
+    `d_out` [M][(out + 3) & ~3], its padding columns zero; `init`: {key: tensor} of the gradients' values before the call
+    when it accumulates, else None.  Returns (values, allowances, info): keys d_out (the stash copy, exact), dZ<l>
+    (the stash slots), dgamma<l>, dbeta<l>, dslope<l> per hidden layer, dW<l>, db<l> per layer; info['undecided'] the
+    share of undecided PReLU branches per hidden layer, info['rows'] per layer the (dY, e_dY, In, e_In) that
+    `mlp_train_wgrad_reference` takes (`rows_only`: no dW / db formed here: several applications).  There is no dx.
+
+    Top down, dY = d_out with e = 0; per layer l (P = `propagate`, u = 2^-24, v = 2 u as above):
+        dW_l, db_l        `mlp_train_wgrad_reference` from dY_l and the layer's input (`_mlp_layer_input`)
+        dA = dY_l W_l     e_dA = P(e_dY, W_l^T) + gamma u |dY_l| |W_l|
+    then the PReLU and BatchNorm reverse of layer j = l - 1 from its saved plane z, mean, rstd (and s, t):
+        xh = (z - mean) rstd                    e_xh = 2 v |xh|                               (difference, product)
+        the branch value, as the kernels recompute it in fp32 (layout 1 and the one-launch layers: csrc/bn_prelu.hip,
+        csrc/train_cols.hip; layouts 2 and 3: csrc/train_epilogue.h):
+          layout 1:    y = weight xh + bias     e_y = v (3 |weight xh| + |y|)
+          layouts 2, 3: y = s z + t             e_y = v (|s z| + |y|)
+        UNDECIDED where |y| <= e_y: the fp32 value may lie on the other side.  No element is left out:
+        dy = dA (y > 0) or slope dA             e_dy = lip e_dA + v |dy| + [undecided] |1 - slope| |dA|,
+                                                lip = 1 / |slope| by the branch, max(1, |slope|) where undecided
+        dslope = sum_{y <= 0} dA y              per term |y| e_dA + |dA| e_y + v |dA y| (undecided: |dA| (|y| + e_y) more,
+                                                the term either way); the sum over all M H terms as below
+        dbeta  = sum dy                         e = sqrt(sum e_dy^2) + gamma u sum |dy|
+        dgamma = sum dy xh                      per term |xh| e_dy + |dy| e_xh + v |dy xh|; e = sqrt(sum e^2) + gamma u sum |dy xh|
+        dZ_j = weight rstd (dy - dbeta / M - xh dgamma / M)
+    The kernels form dZ in two ways: k (M dy - dbeta - xh dgamma) with k = weight rstd / M (layout 1), and
+    c1 dyh + c3 z + c0 with per-column coefficients on the UNCENTRED plane, c1 = weight rstd, c3 = -weight rstd^2 dgamma /
+    M, c0 = -c1 dbeta / M - c3 mean (layouts 2, 3).  One allowance from magnitudes covers both, with
+    sp = rstd (|z| + |mean|) >= |xh| where the second form does not centre:
+        e_dZ = |weight| rstd (e_dy + e_dbeta / M + sp e_dgamma / M + |dgamma| e_xh / M)
+               + 8 v |weight| rstd (|dy| + |dbeta| / M + sp |dgamma| / M)
+    8: the longest chain of roundings on one term, c3 mean in c0 (four in c3, the product, the difference in c0, two sums);
+    the first form has at most 6 (k two, M dy, xh dgamma, two differences -- and the product with k).
+    Column sums are over M rows of errors that are independent from row to row: root-sum-square plus gamma u sum |.|.  The
+    bias in front of a train-mode BatchNorm has a mathematically zero gradient; db_j's allowance is exactly that sum.
+    Accumulating adds the initial value with one rounding, v |result|."""
+    dev = x.device
+    d64 = lambda t: t.detach().double().to(dev)
+    gu = gamma * U
+    L, M, H = len(layers), x.shape[0], layers[0]['w'].shape[0]
+    out_dim = layers[-1]['w'].shape[0]
+    planes = mlp_train_save_planes(save, layout, L, M, H)
+    val, tol = {'d_out': d64(d_out)}, {'d_out': torch.zeros(d_out.shape, dtype=torch.float64, device=dev)}
+    info = {'undecided': [0.0] * (L - 1), 'undecided_count': [0] * (L - 1), 'rows': [None] * L}
+
+    def put(key, v, e):
+        if init is not None and key in init:
+            v = v + d64(init[key])
+            e = e + ULP * v.abs()
+        val[key], tol[key] = v, e
+
+    dY = d64(d_out)[:, :out_dim]
+    e_dY = torch.zeros_like(dY)
+    for l in range(L - 1, -1, -1):
+        h, e_h = _mlp_layer_input(layers, x, planes, layout, l)
+        info['rows'][l] = (dY, e_dY, h, e_h)
+        if not rows_only:
+            seed = None if init is None or 'dW%d' % l not in init else (init['dW%d' % l], init['db%d' % l])
+            val['dW%d' % l], tol['dW%d' % l], val['db%d' % l], tol['db%d' % l] = \
+                mlp_train_wgrad_reference([info['rows'][l]], gamma, seed)
+        if l == 0:
+            break
+        w = d64(layers[l]['w'])
+        dA = dY @ w
+        e_dA = propagate(e_dY, w.t()) + gu * (dY.abs() @ w.abs())
+        j = l - 1
+        p = planes[j]
+        z, ms, rs = d64(p['pre']), d64(p['mean']), d64(p['rstd'])
+        bw, bb = (d64(t) for t in layers[j]['bn'])
+        slope = d64(layers[j]['slope'])
+        xh = (z - ms) * rs
+        e_xh = 2 * ULP * xh.abs()
+        if layout == 1:
+            gx = bw * xh
+            y = gx + bb
+            e_y = ULP * (3 * gx.abs() + y.abs())
+        else:
+            sy = d64(p['s']) * z
+            y = sy + d64(p['t'])
+            e_y = ULP * (sy.abs() + y.abs())
+        undecided = y.abs() <= e_y
+        pos = y > 0
+        info['undecided_count'][j] = int(undecided.sum())
+        info['undecided'][j] = info['undecided_count'][j] / float(y.numel())
+        one, zero = torch.ones_like(y), torch.zeros_like(y)
+        dy = torch.where(pos, dA, slope * dA)
+        lip = torch.where(undecided, torch.clamp(slope.abs(), min=1.0) * one, torch.where(pos, one, slope.abs() * one))
+        e_dy = lip * e_dA + ULP * dy.abs() + torch.where(undecided, (1 - slope).abs() * dA.abs(), zero)
+        term = torch.where(pos, zero, dA * y)
+        e_term = y.abs() * e_dA + dA.abs() * e_y + ULP * (dA * y).abs()
+        e_term = torch.where(undecided, e_term + dA.abs() * (y.abs() + e_y), torch.where(pos, zero, e_term))
+        put('dslope%d' % j, term.sum().reshape(1), (torch.sqrt((e_term * e_term).sum()) + gu * term.abs().sum()).reshape(1))
+        dbeta = dy.sum(0)
+        e_dbeta = torch.sqrt((e_dy * e_dy).sum(0)) + gu * dy.abs().sum(0)
+        prod = dy * xh
+        e_prod = xh.abs() * e_dy + dy.abs() * e_xh + ULP * prod.abs()
+        dgamma = prod.sum(0)
+        e_dgamma = torch.sqrt((e_prod * e_prod).sum(0)) + gu * prod.abs().sum(0)
+        put('dbeta%d' % j, dbeta, e_dbeta)
+        put('dgamma%d' % j, dgamma, e_dgamma)
+        k = (bw * rs).abs()
+        sp = rs * (z.abs() + ms.abs())
+        dZ = bw * rs * (dy - dbeta / M - xh * dgamma / M)
+        e_dZ = k * (e_dy + e_dbeta / M + sp * e_dgamma / M + dgamma.abs() * e_xh / M) \
+            + 8 * ULP * k * (dy.abs() + dbeta.abs() / M + sp * dgamma.abs() / M)
+        val['dZ%d' % j], tol['dZ%d' % j] = dZ, e_dZ
+        dY, e_dY = dZ, e_dZ
+    return val, tol, info
+
+
+# ----------------------------------------------------------------------------------------------------------------------
 # Full mesh: x3 against the fp32-instruction kernel
 def mesh_magnitude(bm, pose_body, betas, root, trans=None):
     """Per vertex coordinate (n, V, 3), float64:

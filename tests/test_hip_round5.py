@@ -321,11 +321,14 @@ def _mlp_pair(in_dim, hidden, seed):
     return [n.to(DEV).train() for n in nets]
 
 
-def _run_mlp_train(nets, x, d_outs, M, pair, deferred=True, saves_from=None, after_forward=None):
+def _run_mlp_train(nets, x, d_outs, M, pair, deferred=True, saves_from=None, after_forward=None, accumulate=0,
+                   grads_init=None):
     """forward + reverse sweep of both networks through the C ABI; returns everything they write.  `saves_from`: the
     reverse sweep reads these saved activations instead of its own forward's (same PReLU branch decisions for two
     reverse paths under comparison: an activation within rounding of zero flips one element's branch otherwise).
-    `after_forward`: called between the forward and the reverse sweep (tests/test_train_mlp_layout.py flips options there)."""
+    `after_forward`: called between the forward and the reverse sweep (tests/test_train_mlp_layout.py flips options there).
+    `accumulate`, `grads_init`: the reverse sweep adds to these gradient tensors (per network, in the order of
+    `_MlpView.parameter_list`) instead of writing into zeroed ones (tests/test_train_mlp_elementwise.py)."""
     import ctypes as C
     from em_pose_amd.nn.train_engine import _MlpView
     lib = _lib.lib()
@@ -343,7 +346,7 @@ def _run_mlp_train(nets, x, d_outs, M, pair, deferred=True, saves_from=None, aft
     saves = [torch.zeros(lib.empose_mlp_train_save_floats(C.byref(p), M), device=DEV) for p in ps]
     nbytes = max(lib.empose_mlp_train_pair_workspace_bytes(C.byref(ps[0]), C.byref(ps[1]), M), 16)
     ws = torch.empty(nbytes // 4 + 4, device=DEV)
-    grads = [[torch.zeros_like(p) for p in v.parameter_list()] for v in views]
+    grads = [[torch.zeros_like(p) for p in v.parameter_list()] for v in views] if grads_init is None else grads_init
     gs = [v.grads(g) for v, g in zip(views, grads)]
     stashes = [torch.zeros(lib.empose_mlp_train_stash_floats(C.byref(p), M), device=DEV) for p in ps]
     lds = [d.shape[1] for d in d_outs]
@@ -359,7 +362,7 @@ def _run_mlp_train(nets, x, d_outs, M, pair, deferred=True, saves_from=None, aft
                 t.copy_(src)
         _lib.check(lib.empose_mlp_train_bwd_deferred_pair(
             C.byref(ps[0]), C.byref(ps[1]), M, _lib.dptr(x), ldx, _lib.dptr(d_outs[0]), lds[0], _lib.dptr(d_outs[1]), lds[1],
-            _lib.dptr(saves[0]), _lib.dptr(saves[1]), C.byref(gs[0]), C.byref(gs[1]), 0, _lib.dptr(stashes[0]),
+            _lib.dptr(saves[0]), _lib.dptr(saves[1]), C.byref(gs[0]), C.byref(gs[1]), accumulate, _lib.dptr(stashes[0]),
             _lib.dptr(stashes[1]), _lib.dptr(ws), nbytes, stream))
     else:
         for i in (0, 1):
@@ -374,11 +377,11 @@ def _run_mlp_train(nets, x, d_outs, M, pair, deferred=True, saves_from=None, aft
         for i in (0, 1):
             if deferred:
                 _lib.check(lib.empose_mlp_train_bwd_deferred(C.byref(ps[i]), M, _lib.dptr(x), ldx, _lib.dptr(d_outs[i]), lds[i],
-                                                             _lib.dptr(saves[i]), C.byref(gs[i]), 0, _lib.dptr(stashes[i]),
+                                                             _lib.dptr(saves[i]), C.byref(gs[i]), accumulate, _lib.dptr(stashes[i]),
                                                              _lib.dptr(ws), nbytes, stream))
             else:
                 _lib.check(lib.empose_mlp_train_bwd(C.byref(ps[i]), M, _lib.dptr(x), ldx, _lib.dptr(d_outs[i]), lds[i],
-                                                    _lib.dptr(saves[i]), C.byref(gs[i]), 0, _lib.dptr(ws), nbytes, stream))
+                                                    _lib.dptr(saves[i]), C.byref(gs[i]), accumulate, _lib.dptr(ws), nbytes, stream))
     torch.cuda.synchronize()
     _lib.check(lib.empose_async_status())
     res = {'out': outs, 'save': saves if saves_from is None else fwd_saves, 'stash': stashes, 'grads': grads, 'views': views}

@@ -26,15 +26,19 @@ def _set(lib, opts):
         _lib.check(lib.empose_set_option(name.encode(), value))
 
 
-def _wgrad(res, x, M):
-    """dW, db of both networks from what the deferred sweep left (one application), through the views it was run with."""
+def _wgrad(res, x, M, accumulate=0, more=()):
+    """dW, db of both networks from what the deferred sweep left (one application), through the views it was run with.
+    `more`: further applications of the same networks, (their result, their x) each: one call over all of them;
+    `accumulate`: added to the gradients in `res` instead of written."""
     lib = _lib.lib()
-    for view, save, stash, grads in zip(res['views'], res['save'], res['stash'], res['grads']):
+    for i, (view, save, stash, grads) in enumerate(zip(res['views'], res['save'], res['stash'], res['grads'])):
         p, g = view.params(), view.grads(grads)
-        arr = lambda t: (C.c_void_p * 1)(_lib.dptr(t))
-        nbytes = lib.empose_mlp_train_wgrad_workspace_bytes(C.byref(p), 1, M)
+        apps = [(x, save, stash)] + [(xk, rk['save'][i], rk['stash'][i]) for rk, xk in more]
+        n = len(apps)
+        arr = lambda k: (C.c_void_p * n)(*[_lib.dptr(app[k]) for app in apps])
+        nbytes = lib.empose_mlp_train_wgrad_workspace_bytes(C.byref(p), n, M)
         ws = torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=DEV)
-        _lib.check(lib.empose_mlp_train_wgrad(C.byref(p), 1, M, arr(x), x.shape[1], arr(save), arr(stash), C.byref(g), 0,
+        _lib.check(lib.empose_mlp_train_wgrad(C.byref(p), n, M, arr(0), x.shape[1], arr(1), arr(2), C.byref(g), accumulate,
                                               _lib.dptr(ws), nbytes, _lib.current_stream()))
     torch.cuda.synchronize()
     _lib.check(lib.empose_async_status())
