@@ -117,6 +117,18 @@ class MeshDesc(C.Structure):
                 ('n_joints', C.c_int), ('rodrigues', C.c_int), ('with_bf16x3', C.c_int)]
 
 
+class FitIO(C.Structure):        # empose_fit_io
+    _fields_ = [('B', C.c_int), ('F', C.c_int), ('K', C.c_int),
+                ('tgt', C.c_void_p), ('ld_tgt', C.c_int), ('seq_lengths', C.c_void_p), ('marker_masks', C.c_void_p),
+                ('offset_r', C.c_void_p), ('offset_t', C.c_void_p),
+                ('pose_init', C.c_void_p), ('shape_init', C.c_void_p), ('pose_prior', C.c_void_p),
+                ('lr', C.c_float), ('lr_decay', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float),
+                ('eps', C.c_float), ('lambda_pose', C.c_float), ('lambda_shape', C.c_float),
+                ('lambda_smooth', C.c_float), ('shape_per_window', C.c_int), ('keep_best', C.c_int),
+                ('pose', C.c_void_p), ('shape', C.c_void_p), ('joints', C.c_void_p), ('pos', C.c_void_p),
+                ('ori', C.c_void_p), ('objective', C.c_void_p), ('energy', C.c_void_p)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests check against the header.
 SIGNATURES = {
     'empose_last_error': (C.c_char_p, []),
@@ -286,6 +298,11 @@ SIGNATURES = {
     # thigh_a, thigh_b, mask_value; pos, ori, normal and their outputs; stream)
     'empose_sensor_noise': (C.c_int, [C.c_int] * 6 + [C.c_void_p] * 7 + [C.c_float, C.c_int, C.c_int, C.c_float] +
                                      [C.c_void_p] * 7),
+    'empose_sensor_fit_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int, C.c_int]),
+    'empose_sensor_fit': (C.c_int, [C.c_void_p, C.POINTER(FitIO), C.c_void_p, C.c_size_t, C.c_void_p]),
+    # (model, io, k; theta, beta, g_theta, g_beta, pos, ori, s; the four moments; theta_next, beta_next; energy, J; best_J,
+    # best_theta, best_beta; stream)
+    'empose_sensor_fit_step': (C.c_int, [C.c_void_p, C.POINTER(FitIO), C.c_int] + [C.c_void_p] * 18 + [C.c_void_p]),
 }
 
 _lib = None

@@ -1,4 +1,4 @@
-// What the pieces of the C ABI (api.hip, api_model.hip, api_lstm.hip, api_train.hip, api_mesh.hip) share: the error
+// What the pieces of the C ABI (api.hip, api_model.hip, api_lstm.hip, api_train.hip, api_mesh.hip, api_fit.hip) share: the error
 // state, the profiler, workspace carving and upload, the packed model, and the LSTM dispatcher.  Host code only.
 #pragma once
 #include "../../include/empose_hip.h"
@@ -237,6 +237,14 @@ LstmWs carve_lstm_of(Carver& c, const Lstm& r, int B, int F);
 // State layout of h0/c0/h_n/c_n: [num_layers * dirs][B][H], unit u = layer * dirs + direction (PyTorch's order).
 int run_lstm(const Lstm& r, int B, int F, const float* x, int ldx, const int* seq_lengths, const float* h0,
              const float* c0, float* y, float* h_n, float* c_n, const LstmWs& ws, hipStream_t stream);
+
+// What empose_smpl_sensors_fwd_bwd runs once its arguments are checked (api_model.hip): plan_smpl for this T and request, then
+// run_smpl_eval.  The sensor fit (api_fit.hip) evaluates through it, so its residual gradient has the bits of the public
+// call at the same T.  tgt == nullptr: forward only.  workspace: empose_smpl_workspace_bytes(m, T).
+int smpl_sensors_eval(const empose_model* m, int T, int F, const float* theta, int ld_theta, const float* beta, int ld_beta,
+                      const float* offset_r, const float* offset_t, const float* tgt, int ld_tgt, const float* frame_scale,
+                      float* pos, float* ori, float* joints, float* g_theta, int ld_g, float* g_beta, int ld_gb,
+                      void* workspace, hipStream_t stream);
 
 // Frames per pass of the virtual-sensor reverse (api_mesh.hip), shared by empose_sample_sensors_vjp (api_sample.hip).
 int sensors_vjp_slab(int T, int M);

@@ -648,6 +648,33 @@ size_t smpl_vjp_bytes(const empose_model* m, int T) {
 
 }  // namespace
 
+namespace empose {
+namespace api {
+
+int smpl_sensors_eval(const empose_model* m, int T, int F, const float* theta, int ld_theta, const float* beta, int ld_beta,
+                      const float* offset_r, const float* offset_t, const float* tgt, int ld_tgt, const float* frame_scale,
+                      float* pos, float* ori, float* joints, float* g_theta, int ld_g, float* g_beta, int ld_gb,
+                      void* workspace, hipStream_t stream) {
+  Carver c(workspace);
+  const SmplWs ws = carve_smpl(c, m, T);
+  const GradOut go{g_theta, ld_g, g_beta, ld_gb, nullptr, nullptr};
+  SmplEval rq;
+  rq.update = plain_feat_args(theta, ld_theta, beta, ld_beta);
+  rq.offset_r = offset_r; rq.offset_t = offset_t;
+  rq.pos = pos; rq.ori = ori; rq.joints = joints;
+  rq.tgt = tgt; rq.ld_tgt = ld_tgt; rq.frame_scale = frame_scale;
+  if (tgt) rq.grad = &go;
+  const SmplPlan plan = plan_smpl(m, T, rq);
+  if (tgt && plan.tile) {
+    HIP_CHECK(launch_rows_to_tile(tgt, ld_tgt, 12 * m->n_markers, ws.tgt_t, T, stream), "tile transpose");
+    rq.tgt_t = ws.tgt_t;
+  }
+  return run_smpl_eval(m, T, F, ws, plan, rq, stream);
+}
+
+}  // namespace api
+}  // namespace empose
+
 extern "C" {
 
 void empose_model_destroy(empose_model_t* model) {
@@ -825,22 +852,8 @@ int empose_smpl_sensors_fwd_bwd(const empose_model_t* m, int T, int F, const flo
   if (T <= 0 || F <= 0 || T % F != 0) return fail(EMPOSE_EINVAL, "T must be a positive multiple of F");
   if (tgt && (!frame_scale || !g_theta || !g_beta)) return fail(EMPOSE_EINVAL, "gradient outputs missing");
   if (workspace_bytes < empose_smpl_workspace_bytes(m, T)) return fail(EMPOSE_ENOMEM, "workspace too small");
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
-  Carver c(workspace);
-  const SmplWs ws = carve_smpl(c, m, T);
-  const GradOut go{g_theta, ld_g, g_beta, ld_gb, nullptr, nullptr};
-  SmplEval rq;
-  rq.update = plain_feat_args(theta, ld_theta, beta, ld_beta);
-  rq.offset_r = offset_r; rq.offset_t = offset_t;
-  rq.pos = pos; rq.ori = ori; rq.joints = joints;
-  rq.tgt = tgt; rq.ld_tgt = ld_tgt; rq.frame_scale = frame_scale;
-  if (tgt) rq.grad = &go;
-  const SmplPlan plan = plan_smpl(m, T, rq);
-  if (tgt && plan.tile) {
-    HIP_CHECK(launch_rows_to_tile(tgt, ld_tgt, 12 * m->n_markers, ws.tgt_t, T, stream), "tile transpose");
-    rq.tgt_t = ws.tgt_t;
-  }
-  return run_smpl_eval(m, T, F, ws, plan, rq, stream);
+  return smpl_sensors_eval(m, T, F, theta, ld_theta, beta, ld_beta, offset_r, offset_t, tgt, ld_tgt, frame_scale, pos, ori,
+                           joints, g_theta, ld_g, g_beta, ld_gb, workspace, static_cast<hipStream_t>(stream_));
 }
 
 int empose_smpl_sensors_vjp(const empose_model_t* m, int T, int F, const float* theta, int ld_theta, const float* beta,

@@ -911,6 +911,68 @@ int empose_sensor_noise(int mode, int N, int F, int M, int K, int window_len, co
 int empose_metrics_rows(int T, const float* joints_gt, const float* joints_hat, const float* pose_gt,
                         const float* pose_hat, const int* parents_host, double* rows, empose_stream_t stream);
 
+/* ---- model-free sensor fitting (new in this library) ------------------------------------------- */
+/* A pose per frame and a shape per window (or per frame) from sensor readings alone: K steps of Adam on, per window w
+ * of F frames with live_t = [t < seq_length],
+ *   J_w = sum_t s_t E_t + lambda_pose / 2 sum_{t live} |theta_t[3:66] - p_t[3:66]|^2 + lambda_shape / 2 |beta_w|^2
+ *         + lambda_smooth / 2 sum_{t >= 1, live} |theta_t - theta_{t-1}|^2.
+ * E_t is the reconstruction energy of empose_smpl_sensors_fwd_bwd (sum over the model's sensors of |pos - target| and
+ * |ori - target|_F, reference loss.py:23-41) and s_t = live_t * [every sensor the model reads has mask 1 in the frame]:
+ * the weight of a frame is 1, not F / len.  The root orientation theta[0:3] is not regularised towards the prior.  With
+ * one shape per frame the shape term is summed over the live frames.  The reference has no such optimiser; its learned
+ * loop (models.py:547-600) is this one with the step replaced by two networks.
+ *   tgt [B*F][ld_tgt]       the rows empose_pack_inputs writes for the model's sensors (12 * n_markers columns read)
+ *   seq_lengths [B] int32 or NULL (= F), marker_masks [B*F][12] or NULL, offset_r [B][12][3][3], offset_t [B][12][3]
+ *   pose_init [B*F][66], shape_init [B*F][10] or NULL (zeros; one shape per window: the row of the window's first
+ *   frame); pose_prior p [B*F][66] or NULL (zeros)
+ *   iterate k + 1 = iterate k - lr lr_decay^k c1 m / (sqrt(c2 v) + eps), m and v the Adam moments with beta1, beta2 and
+ *   c1 = 1 / (1 - beta1^(k+1)), c2 = 1 / (1 - beta2^(k+1)); the three k-dependent factors are computed in double on the
+ *   host and rounded to float once.  Padded frames keep their init.  One shape per window: the gradient is the sum over
+ *   the window's live frames and every row of `shape` holds the window's shape.
+ *   keep_best: what is returned is, per window, the iterate of 0 .. K with the smallest J_w (the earliest of equal
+ *   ones); otherwise iterate K.
+ *   outputs: pose [B*F][66], shape [B*F][10], and joints [B*F][66], pos [B*F][36], ori [B*F][108] of what is returned
+ *   (the bits of empose_smpl_sensors_fwd_bwd on it at T = B*F); objective [K + 2][B] or NULL: J_w of the iterates
+ *   0 .. K, then of what is returned; energy [B*F] or NULL: s_t E_t of what is returned.
+ * K + 2 SMPL evaluations (K with the reverse pass) through the path of empose_smpl_sensors_fwd_bwd at T = B*F, one
+ * launch of csrc/sensor_fit.hip after each.  No host synchronisation, no allocation, no copy from the host: the call is
+ * asynchronous on `stream` and may be captured in a HIP graph.  Every sum runs in a fixed order and nothing is
+ * accumulated atomically: the same inputs give the same bits.  K = 0 returns the init with its outputs and J.
+ * Returns, before any GPU work, EMPOSE_EINVAL for a NULL model, io, workspace, tgt, offset_r, offset_t, pose, shape,
+ * joints, pos or ori, B or F <= 0 (or B * F above 2^24), K < 0, ld_tgt < 12 * n_markers, lr or lr_decay not finite or
+ * not positive, beta1 or beta2 outside [0, 1), eps not finite or negative, or a negative or non-finite lambda;
+ * EMPOSE_ENOMEM for a workspace below empose_sensor_fit_workspace_bytes (0 for a NULL model or B, F <= 0);
+ * empose_last_error() names the field. */
+typedef struct {
+  int B, F, K;
+  const float* tgt; int ld_tgt;
+  const int* seq_lengths; const float* marker_masks;
+  const float* offset_r; const float* offset_t;
+  const float* pose_init; const float* shape_init; const float* pose_prior;
+  float lr, lr_decay, beta1, beta2, eps, lambda_pose, lambda_shape, lambda_smooth;
+  int shape_per_window, keep_best;
+  float* pose; float* shape; float* joints; float* pos; float* ori;
+  float* objective; float* energy;
+} empose_fit_io;
+size_t empose_sensor_fit_workspace_bytes(const empose_model_t* model, int B, int F);
+int empose_sensor_fit(const empose_model_t* model, const empose_fit_io* io, void* workspace, size_t workspace_bytes,
+                      empose_stream_t stream);
+/* What one iteration does after its SMPL evaluation, as exactly one launch on the caller's buffers (the unit tests drive
+ * it; empose_sensor_fit is K of these between evaluations).  From `io`: B, F, tgt, ld_tgt, seq_lengths, pose_prior, the
+ * step sizes, betas, eps, lambdas and shape_per_window; everything else of it is ignored.  k >= 0 is the iteration.
+ *   theta, beta: iterate k; g_theta [B*F][66], g_beta [B*F][10], pos, ori: what empose_smpl_sensors_fwd_bwd gave for it
+ *   with frame_scale = s; s [B*F] the frame weights
+ *   m_theta, v_theta [B*F][66], m_beta, v_beta [B*F][10]: Adam moments, updated in place on live frames (one shape per
+ *   window: the window's first row only)
+ *   theta_next, beta_next: iterate k + 1, buffers other than theta and beta
+ *   energy [B*F] (s_t E_t at iterate k) or NULL, J [B] (J_w at iterate k)
+ *   best_J [B], best_theta, best_beta: where J_w is below best_J, iterate k and J_w are copied there; all three or none. */
+int empose_sensor_fit_step(const empose_model_t* model, const empose_fit_io* io, int k, const float* theta,
+                           const float* beta, const float* g_theta, const float* g_beta, const float* pos,
+                           const float* ori, const float* s, float* m_theta, float* v_theta, float* m_beta,
+                           float* v_beta, float* theta_next, float* beta_next, float* energy, float* J, float* best_J,
+                           float* best_theta, float* best_beta, empose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
