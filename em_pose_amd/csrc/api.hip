@@ -98,6 +98,7 @@ namespace {
 unsigned* g_timeout_host = nullptr;   // host-mapped, device-visible (fine-grained): written by kernels, read here
 unsigned* g_timeout_dev = nullptr;
 }  // namespace
+int poll_spin_limit(int kernel_default) { return options().spin_limit > 0 ? options().spin_limit : kernel_default; }
 unsigned* poll_timeout_word() {
   static std::once_flag once;
   std::call_once(once, [] {

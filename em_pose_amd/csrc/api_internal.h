@@ -199,13 +199,20 @@ int pack_lstm(std::vector<void*>& allocs, const empose_lstm_desc& r, int dirs, c
               const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, Lstm* out);
 
 // ---- the LSTM dispatcher (api_lstm.hip) ------------------------------------------------------------------------
-// What one call does, decided in ONE place (plan_lstm) from the stack, the shape and the options of the moment: which
-// whole-sequence kernels get buffers (persist and seq by shape alone, midseq by shape and options); the cooperative
-// launches to try, in order -- each may report done = false at run time (its workgroups cannot all be resident) -- and
-// the step kernel that runs when none finished, with its weight layout and how it treats the state of new sequences.
-// wave: lstm_wave (fp32); chain16_pair: two f16 pieces where the operand is the kernel's own; else three bf16 pieces
+// What one call does, decided in ONE place (plan_lstm, over plan_lstm_f32 for the fp32 kernels) from the stack, the shape
+// and the options of the moment: which whole-sequence kernels get buffers (persist and seq by shape alone, midseq by shape
+// and options); the cooperative launches to try, in order -- listed only where the kernel covers the shape and would
+// really be tried; each may still report done = false at run time (its workgroups cannot all be resident) -- and the step
+// kernel that runs when none finished, with its weight layout and how it treats the state of new sequences.
+// wave: fp32, the kernel LstmPlan::wave names; chain16_pair: two f16 pieces where the operand is the kernel's own; else
+// three bf16 pieces
 enum class LstmStep { wave, chain_x3, rows_x3, mid_x3, mid16_x3, chain16_x3, chain16_pair };
+// the fp32 step kernels: lstm_small_kernel, lstm_fewrows_kernel (lstm_fewrows.hip), lstm_mid_kernel, lstm_chain_kernel
+enum class LstmWave { small, fewrows, mid, chain };
 enum class LstmCoop { persist, seq, midseq };   // lstm_persist_kernel (small), lstm_seq_kernel (large), lstm_midseq_x3.hip
+// What the fp32 kernels are chosen by: the units of one launch (a stacked wavefront's layers, or the two directions of a
+// bidirectional layer) and the width of each one's input
+struct LstmShape { int B, F, H, n_units; int in_k[4]; bool stacked; };
 struct LstmPlan {
   bool persist = false;   // exchange words of lstm_persist_kernel
   bool seq = false;       // third hidden buffers + counters of lstm_seq_kernel
@@ -213,6 +220,10 @@ struct LstmPlan {
   bool x3 = false;        // the bf16 piece planes of the inputs and hidden states (a three-piece step kernel or midseq)
   int n_coop = 0; LstmCoop coop[3];
   LstmStep step = LstmStep::wave; LstmLayout layout = LSTM_CHAIN;   // (the layout of the three-piece step kernel)
+  LstmWave wave = LstmWave::chain;   // the fp32 step kernel (step == wave)
+  // lstm_chain_kernel and the three-piece chain kernels: a workgroup walks all active units (the tiles alone fill the CUs:
+  // equal work per workgroup) instead of one
+  bool chain_all_units = false;
   // three-piece steps on new sequences (option lstm_state_direct): the zero hidden-state planes by one fill, and on the
   // chain kernels h_n / c_n stored by the last step of each layer
   bool zero_planes = false, state_direct = false;

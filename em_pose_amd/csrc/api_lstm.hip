@@ -4,6 +4,7 @@
 // lays out; back-propagation through time (Bptt) is two recurrences over one cell builder and one batched tail.
 #include "api_internal.h"
 #include "f16pair.h"
+#include "lstm_wave.h"
 
 #include <algorithm>
 
@@ -20,7 +21,7 @@ bool has_layout(const Lstm& r, LstmLayout y) {
     if (!r.w3[y].ih[l] || !r.w3[y].hh[l]) return false;
   return true;
 }
-// The step kernels by LstmStep (wave: fp32, none of this).  A new one is an entry here, one in the enum, a line in plan_lstm.
+// The three-piece step kernels by LstmStep (wave: fp32, none of this).  A new one is an entry here, one in the enum, a line in plan_lstm.
 struct X3Step { hipError_t (*launch)(const LstmX3Args&, hipStream_t); LstmLayout layout; };
 const X3Step X3_STEPS[] = {{nullptr, LSTM_CHAIN}, {launch_lstm_chain_x3, LSTM_CHAIN}, {launch_lstm_rows_x3, LSTM_CHAIN},
                            {launch_lstm_mid_x3, LSTM_MID}, {launch_lstm_mid16_x3, LSTM_MID16},
@@ -36,19 +37,56 @@ bool has_pair16(const Lstm& r) {
 constexpr int LSTM_MID16_MIN_B = 9;
 constexpr int LSTM_MIDSEQ_MIN_B = 4, LSTM_MIDSEQ_MAX_B = 64;   // (up to 3 rows: lstm_persist_kernel)
 
-// The only reader of the LSTM options and shapes; `fresh_state`: new sequences (no h0, no c0).
-LstmPlan plan_lstm(const Lstm& r, int B, int F, bool fresh_state) {
+// fp32 steps: up to LSTM_SMALL_B rows the weight-streaming kernels of lstm_fewrows.hip, up to LSTM_MID_B lstm_mid_kernel, above
+// lstm_chain_kernel -- lstm_mid_kernel against lstm_chain_kernel, us per wavefront step of the 2 x 512 stack
+// (scripts/dev/bench_lstm_mid.py): B = 17..128: 17 vs 36, B = 256: 22 vs 37, B = 512: 44 vs 37.
+constexpr int LSTM_SMALL_B = 16, LSTM_MID_B = 256;
+static_assert(LSTM_MID_B + 1 == LSTM_SEQ_MIN_B, "lstm_seq_kernel takes over where lstm_chain_kernel does");
+
+// The fp32 part of a plan, from the shape alone (inference, the layers of a bidirectional stack and the training forward
+// alike): the step kernel, the buffers of the whole-sequence kernels and whether they are tried.  With plan_lstm below
+// the only reader of the LSTM dispatch options.
+LstmPlan plan_lstm_f32(const LstmShape& s) {
   const Options& o = options();
   LstmPlan p;
-  if (r.dirs != 1) return p;   // bidirectional: layer after layer on lstm_wave
+  const int B = s.B, n_k = s.n_units < 4 ? s.n_units : 4;   // (in_k has four entries; deeper stacks are refused at run time)
+  if (B > LSTM_MID_B) p.wave = LstmWave::chain;
+  else if (B > LSTM_SMALL_B) p.wave = LstmWave::mid;
+  // from 4 rows all threads of a workgroup split K (reduce-scatter), below a wave per hidden unit
+  else if (o.lstm_fewrows != 0 && B >= LSTM_FEWROWS_MIN_B && lstm_fewrows_shape_ok(B, s.H, n_k, s.in_k)) p.wave = LstmWave::fewrows;
+  else p.wave = LstmWave::small;
+  // Chain all units in one block (equal work per block) once the tiles alone fill the CUs; spread them otherwise.
+  p.chain_all_units = ((s.H + lc::BU - 1) / lc::BU) * ((B + lc::BM - 1) / lc::BM) >= 192;
+  if (!s.stacked) return p;   // bidirectional: layer after layer, step launches only
+  // the whole-sequence kernels get their buffers by shape alone (the options gate their launches below)
+  p.persist = B <= LSTM_PERSIST_B;
+  p.seq = B >= LSTM_SEQ_MIN_B && s.n_units <= 4;
+  // the whole sequence in one cooperative launch, from 4 steps; tried in this order
+  if (s.F >= 4 && s.n_units <= 4) {
+    // (from 4 rows on a step launch of lstm_fewrows_kernel is faster than polling B x H exchange words per layer and step)
+    if (p.persist && o.lstm_persist != 0 && (o.lstm_fewrows == 0 || B < LSTM_FEWROWS_MIN_B) &&
+        lstm_persist_shape_ok(B, s.H, s.n_units, s.in_k))
+      p.coop[p.n_coop++] = LstmCoop::persist;
+    if (p.seq && o.lstm_seq != 0 && lstm_seq_shape_ok(s.H, s.n_units, s.in_k)) p.coop[p.n_coop++] = LstmCoop::seq;
+  }
+  return p;
+}
+LstmShape stacked_shape(int L, int input_size, int H, int B, int F) {
+  LstmShape s{B, F, H, L, {}, true};
+  for (int l = 0; l < L && l < 4; ++l) s.in_k[l] = l == 0 ? input_size : H;
+  return s;
+}
+
+// With plan_lstm_f32 the only reader of the LSTM options and shapes; `fresh_state`: new sequences (no h0, no c0).
+LstmPlan plan_lstm(const Lstm& r, int B, int F, bool fresh_state) {
+  const Options& o = options();
+  if (r.dirs != 1) return LstmPlan();   // bidirectional: no buffers; LstmRun::bidirectional plans each layer's steps
+  LstmPlan p = plan_lstm_f32(stacked_shape(r.num_layers, r.input_size, r.H, B, F));
   const bool x3 = o.lstm_x3 != 0 && r.num_layers <= 4 && r.H % 32 == 0 && r.input_size % 4 == 0;
   const bool mid = x3 && o.lstm_mid_x3 != 0 && has_layout(r, LSTM_MID);
   // ... up to 64 rows with half the tile, on all 256 CUs (lstm_mid16_x3.hip)
   const bool tiles16 = mid && o.lstm_mid16 != 0 && lstm_mid16_shape_ok(B, r.H) && has_layout(r, LSTM_MID16);
-  // the whole-sequence kernels get their buffers by shape alone (the options gate their launches below) ...
-  p.persist = B <= LSTM_PERSIST_B;
-  p.seq = B >= LSTM_SEQ_MIN_B && r.num_layers <= 4;
-  // ... lstm_midseq_x3.hip by shape and options (it needs the 8-unit-block weight order too)
+  // lstm_midseq_x3.hip gets its buffers by shape and options (it needs the 8-unit-block weight order too)
   if (mid && o.lstm_midseq != 0 && B >= LSTM_MIDSEQ_MIN_B && B <= LSTM_MIDSEQ_MAX_B) {
     int ks_in[4];
     for (int l = 0; l < r.num_layers; ++l) ks_in[l] = l == 0 ? (r.input_size + 15) / 16 : r.H / 16;
@@ -68,12 +106,8 @@ LstmPlan plan_lstm(const Lstm& r, int B, int F, bool fresh_state) {
     p.step = tiles16 ? LstmStep::mid16_x3 : LstmStep::mid_x3;
   p.layout = X3_STEPS[(int)p.step].layout;
   p.x3 = p.step != LstmStep::wave || p.midseq;
-  // the whole sequence in one cooperative launch, from 4 steps; tried in this order
-  if (F >= 4) {
-    if (p.persist && o.lstm_persist != 0) p.coop[p.n_coop++] = LstmCoop::persist;
-    if (p.seq && o.lstm_seq != 0) p.coop[p.n_coop++] = LstmCoop::seq;
-    if (p.midseq) p.coop[p.n_coop++] = LstmCoop::midseq;
-  }
+  // the whole sequence in one cooperative launch, from 4 steps; tried after those of plan_lstm_f32
+  if (F >= 4 && p.midseq) p.coop[p.n_coop++] = LstmCoop::midseq;
   p.zero_planes = p.step != LstmStep::wave && fresh_state && o.lstm_state_direct != 0;
   const bool chain = p.step == LstmStep::chain_x3 || p.step == LstmStep::chain16_x3 || p.step == LstmStep::chain16_pair;
   p.state_direct = p.zero_planes && chain;
@@ -115,11 +149,16 @@ LstmWaveArgs stacked_wave_args(int L, int input_size, int H, const float* const*
   }
   return a;
 }
-int wave_steps(LstmWaveArgs& a, int n_steps, bool mark, hipStream_t stream) {
+// the fp32 steps on the kernel the plan names, one launch per wavefront step
+int wave_steps(LstmWaveArgs& a, const LstmPlan& p, int n_steps, bool mark, hipStream_t stream) {
+  const int units_per_block = p.wave == LstmWave::chain && p.chain_all_units ? a.n_units : 1;
   for (int s = 0; s < n_steps; ++s) {
     a.s = s;
+    lstm_build_chain(a, units_per_block);
     if (mark) prof_mark(P_LSTM_STEP, stream);
-    HIP_CHECK(launch_lstm_wave(a, stream), "lstm step");
+    HIP_CHECK(p.wave == LstmWave::chain ? launch_lstm_chain(a, units_per_block, stream)
+              : p.wave == LstmWave::mid ? launch_lstm_mid(a, stream)
+              : p.wave == LstmWave::fewrows ? launch_lstm_fewrows(a, stream) : launch_lstm_small(a, stream), "lstm step");
   }
   return EMPOSE_OK;
 }
@@ -212,7 +251,6 @@ struct LstmRun {
       }
     }
     if (e != hipSuccess) return fail(EMPOSE_EHIP, "lstm operand split: %s", hipGetErrorString(e));
-    const int tiles = (H / 32) * ((B + 63) / 64);
     for (int s = 0; s < F + L - 1; ++s) {
       LstmX3Args xa;
       xa.n_units = 0; xa.seq_lengths = seq_lengths; xa.B = B; xa.F = F; xa.H = H;
@@ -245,7 +283,7 @@ struct LstmRun {
           xu.inv_scale = r.inv_scale[l];
         }
       }
-      xa.units_per_block = tiles >= 192 ? xa.n_units : 1;
+      xa.units_per_block = p.chain_all_units ? xa.n_units : 1;
       prof_mark(P_LSTM_STEP, stream);
       HIP_CHECK(X3_STEPS[(int)p.step].launch(xa, stream), "lstm step (bf16 pieces)");
     }
@@ -258,14 +296,15 @@ struct LstmRun {
     LstmWaveArgs a;
     a.seq_lengths = seq_lengths; a.B = B; a.F = F; a.H = H; a.n_units = 2;
     for (int l = 0; l < L; ++l) {
+      const int in_k = l == 0 ? r.input_size : 2 * H;
       for (int d = 0; d < 2; ++d) {
         LstmUnitArgs& ua = a.unit[d];
         fill_unit(ua, r.w_ih[l * 2 + d], r.w_hh[l * 2 + d], r.bias[l * 2 + d], ws, l * 2 + d);
-        ua.in_k = (l == 0) ? r.input_size : 2 * H;
+        ua.in_k = in_k;
         ua.in_seq = l == 0 ? x : ws.yb[(l - 1) & 1]; ua.in_ld = l == 0 ? ldx : 2 * H; ua.reverse = d;
         ua.y = l == L - 1 ? y : ws.yb[l & 1]; ua.y_ld = 2 * H; ua.y_col = d * H;
       }
-      TRY(wave_steps(a, F, true, stream));
+      TRY(wave_steps(a, plan_lstm_f32(LstmShape{B, F, H, 2, {in_k, in_k}, false}), F, true, stream));
     }
     return EMPOSE_OK;
   }
@@ -290,7 +329,7 @@ struct LstmRun {
         TRY(coop(p.coop[i], a, &done));
         seq_done = done && p.coop[i] == LstmCoop::seq;
       }
-      if (!done && p.step == LstmStep::wave) TRY(wave_steps(a, F + r.num_layers - 1, true, stream));
+      if (!done && p.step == LstmStep::wave) TRY(wave_steps(a, p, F + r.num_layers - 1, true, stream));
       if (!done && p.step != LstmStep::wave) {
         TRY(x3_steps());
         if (p.state_direct) return EMPOSE_OK;   // the last step of each layer has stored h_n / c_n itself
@@ -758,10 +797,12 @@ int empose_lstm_train_fwd(const empose_lstm_params* p, int B, int F, const float
   }
   // Small batches (the reference's training batch of 12 windows): the whole sequence in one cooperative launch with the
   // weights in registers, as in inference -- the step-by-step kernel streams 13.8 MB of weights per wavefront step.
+  // (the plan of the fp32 kernels, as in inference; lstm_seq_kernel saves nothing for the reverse pass)
+  const LstmPlan plan = plan_lstm_f32(stacked_shape(L, p->input_size, H, B, F));
   bool done = false;
-  if (w.st.xch && F >= 4 && options().lstm_persist != 0)
+  if (plan.n_coop > 0 && plan.coop[0] == LstmCoop::persist)
     HIP_CHECK(launch_lstm_persist(a, w.st.xch, stream, &done), "lstm sequence kernel");
-  if (!done) TRY(wave_steps(a, F + L - 1, false, stream));
+  if (!done) TRY(wave_steps(a, plan, F + L - 1, false, stream));
   for (int l = 0; l < L; ++l) {
     if (h_n) HIP_TRY(hipMemcpyAsync(h_n + l * bh, w.st.h[l][F & 1], bh * sizeof(float), hipMemcpyDeviceToDevice, stream));
     if (c_n) HIP_TRY(hipMemcpyAsync(c_n + l * bh, w.st.c[l], bh * sizeof(float), hipMemcpyDeviceToDevice, stream));

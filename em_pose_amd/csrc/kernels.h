@@ -113,6 +113,7 @@ Options& options();
 unsigned* poll_timeout_word();          // device-visible address of the counter
 unsigned poll_timeouts_take();          // host: read and clear
 unsigned poll_timeouts_peek();          // host: read
+int poll_spin_limit(int kernel_default);   // option "spin_limit" where it is set, else the polling kernel's own limit
 constexpr size_t LDS_BYTES_PER_CU = 160 * 1024;
 hipError_t allow_dynamic_lds(const void* fn, size_t bytes);
 // A launch of a kernel with a large dynamic-LDS request: raises the limit of `fn` (above), launches, returns the launch's
@@ -379,12 +380,20 @@ struct LstmWaveArgs {
   const int* seq_lengths;    // [B] or nullptr (required for reverse units)
   int B, F, H;
   int s;                     // launch index
-  // set by launch_lstm_wave: blockIdx.z walks through the segments [z_beg[z], z_beg[z] + z_cnt[z]) (two per active unit)
+  // set by lstm_build_chain (lstm_wave.h): blockIdx.z walks through the segments [z_beg[z], z_beg[z] + z_cnt[z]) (two per active unit)
   LstmSeg seg[8];
   int z_beg[4], z_cnt[4];
 };
-hipError_t launch_lstm_wave(const LstmWaveArgs& a, hipStream_t stream);
-// Whole sequence of a stacked uni-directional LSTM on a LARGE batch (B > 256) in one cooperative launch (lstm.hip,
+// The fp32 step kernels, one launcher each; plan_lstm (api_lstm.hip) picks, the launchers take no decisions.  All expect the
+// segment table built (lstm_build_chain, lstm_wave.h): one unit per slice, lstm_chain_kernel `units_per_block`.  A shape
+// outside a kernel's ..._shape_ok is hipErrorInvalidValue.
+hipError_t launch_lstm_chain(const LstmWaveArgs& a, int units_per_block, hipStream_t stream);   // lstm_chain.hip
+hipError_t launch_lstm_mid(const LstmWaveArgs& a, hipStream_t stream);                          // lstm_mid.hip
+bool lstm_small_shape_ok(int B);                                                                 // lstm_fewrows.hip
+bool lstm_fewrows_shape_ok(int B, int H, int n_units, const int* in_k);
+hipError_t launch_lstm_small(const LstmWaveArgs& a, hipStream_t stream);
+hipError_t launch_lstm_fewrows(const LstmWaveArgs& a, hipStream_t stream);
+// Whole sequence of a stacked uni-directional LSTM on a LARGE batch in one cooperative launch (lstm_seq.hip,
 // lstm_seq_kernel): the units' hidden states rotate through three buffers (h[0], h[1] of the unit + a third one), the
 // workgroups of a 64-row group synchronise through `counters` (lstm_seq_counter_uints(B) unsigned, zeroed by the launcher).
 struct LstmSeqArgs {
@@ -474,11 +483,14 @@ hipError_t launch_lstm_split_rows(const float* src, long row_stride, long z_stri
                                   unsigned short* dst, long dst_z_stride, hipStream_t stream);
 constexpr int LSTM_SEQ_MIN_B = 257;   // below: lstm_mid_kernel / the small-batch kernels
 size_t lstm_seq_counter_uints(int B);
+bool lstm_seq_shape_ok(int H, int n_units, const int* in_k);   // enough K tiles per unit (per-unit input widths in_k)
 hipError_t launch_lstm_seq(const LstmWaveArgs& a, float* const* h_third, unsigned* counters, hipStream_t stream, bool* done);
-// Whole sequence of a stacked uni-directional LSTM in one cooperative launch (B <= 16); *done = false: not covered.
+// Whole sequence of a stacked uni-directional LSTM in one cooperative launch (lstm_persist.hip, B <= 16); *done = false:
+// its workgroups cannot all be resident here.
 constexpr int LSTM_PERSIST_B = 16;   // largest batch of the whole-sequence kernel
 constexpr int LSTM_FEWROWS_MIN_B = 4;   // from here to 16 rows a step launch of lstm_fewrows_kernel beats it (option lstm_fewrows)
 size_t lstm_persist_xch_floats(int n_units, int B, int H);   // its exchange buffer (8-byte aligned)
+bool lstm_persist_shape_ok(int B, int H, int n_units, const int* in_k);   // H, in_k <= 512 in 16-byte pieces, rows within LDS
 hipError_t launch_lstm_persist(const LstmWaveArgs& a, float* xch, hipStream_t stream, bool* done);
 
 // ---------------------------------------------------------------------------------------------------------------

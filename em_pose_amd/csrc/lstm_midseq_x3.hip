@@ -263,7 +263,7 @@ hipError_t launch_lstm_midseq_x3(const LstmMidSeqArgs& a_in, hipStream_t stream,
   int ks_in[4];
   for (int u = 0; u < a.n_units && u < 4; ++u) ks_in[u] = a.unit[u].ks_in;
   if (!lstm_midseq_shape_ok(a.B, a.H, a.n_units, ks_in)) return hipSuccess;
-  a.spin_limit = options().spin_limit > 0 ? options().spin_limit : 1 << 20;
+  a.spin_limit = poll_spin_limit(1 << 20);
   a.timeouts = poll_timeout_word();
   if (!a.timeouts) return hipErrorOutOfMemory;
   if (hipError_t e = hipMemsetAsync(a.flags, 0, lstm_midseq_flag_uints(a.n_units, a.H) * sizeof(unsigned), stream)) return e;

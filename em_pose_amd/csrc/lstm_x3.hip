@@ -1,4 +1,4 @@
-// The LSTM wavefront step of large batches (lstm.hip, lstm_chain_kernel: reference nn/layers.py:133-157) with every fp32
+// The LSTM wavefront step of large batches (lstm_chain.hip, lstm_chain_kernel: reference nn/layers.py:133-157) with every fp32
 // product formed on the bf16 matrix path from three bf16 pieces per operand (bf16x3.h): fp32-equivalent arithmetic, six
 // v_mfma_f32_32x32x16_bf16 per 16 k instead of 64 v_mfma_f32_16x16x4_f32-quarters.
 //

@@ -383,7 +383,7 @@ hipError_t launch_cols(ColsArgs a, int mode, hipStream_t stream) {
   const int T16 = (a.M + 15) / 16;
   a.R = T16 < 4 ? T16 : 4;
   a.tiles_per_part = (T16 + a.R - 1) / a.R;
-  a.spin_limit = options().spin_limit > 0 ? options().spin_limit : 1 << 20;
+  a.spin_limit = poll_spin_limit(1 << 20);
   a.timeouts = poll_timeout_word();
   if (!a.timeouts) return hipErrorOutOfMemory;
   int n_max = 0;

@@ -1,5 +1,5 @@
 """Dev: the stand-alone LSTM entry point (2 x 512, input 60) on medium batches: us per wavefront step
-(B <= 256: lstm_mid_kernel, above: lstm_chain_kernel; the threshold constant LSTM_MID_B in csrc/lstm.hip was set from
+(B <= 256: lstm_mid_kernel, above: lstm_chain_kernel; the threshold constant LSTM_MID_B of plan_lstm_f32 in csrc/api_lstm.hip was set from
 this sweep run with either kernel forced)."""
 import sys, time
 sys.path.insert(0, '.')

@@ -4,7 +4,7 @@ sys.path.insert(0, '.')
 import torch
 from em_pose_amd import _lib
 if os.environ.get('EMPOSE_LIB_PATH'):
-    _lib.LIB_PATH = os.environ['EMPOSE_LIB_PATH']   # dev: a lab build of the library (scripts/dev/persist_lab.sh)
+    _lib.LIB_PATH = os.environ['EMPOSE_LIB_PATH']   # dev: another build of the library
 from em_pose_amd.nn.layers import RNNLayer
 dev = 'cuda:0'
 layer = RNNLayer(60, 512, 2).eval().to(dev)

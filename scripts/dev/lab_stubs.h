@@ -19,6 +19,7 @@ hipError_t coresident_blocks(const void* fn, int threads, size_t lds, int* block
   return e;
 }
 unsigned* poll_timeout_word() { static unsigned* p = nullptr; if (!p) (void)hipMalloc(&p, 64); return p; }
+int poll_spin_limit(int kernel_default) { return options().spin_limit > 0 ? options().spin_limit : kernel_default; }
 unsigned poll_timeouts_take() { return 0; }
 unsigned poll_timeouts_peek() { return 0; }
 }  // namespace empose

@@ -1,7 +1,7 @@
 // Dev lab: one wavefront launch of the LSTM kernel (both layers active) at the bench shape, with phase stamps.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iem_pose_amd/csrc scripts/dev/lstm_lab.hip -o /tmp/lstm_lab && /tmp/lstm_lab
 #define EMPOSE_LSTM_TRACE 1
-#include "../../em_pose_amd/csrc/lstm.hip"
+#include "../../em_pose_amd/csrc/lstm_chain.hip"
 #include "lab_stubs.h"
 
 #include <cstdio>
@@ -23,6 +23,7 @@ static float* dev_rand(size_t n, unsigned seed, float scale) {
 
 int main(int argc, char** argv) {
   const int B = argc > 1 ? atoi(argv[1]) : 1024, F = 32, H = 512, IN = 144, LDX = 296;
+  const int UPB = ((H + 31) / 32) * ((B + 63) / 64) >= 192 ? 2 : 1;   // units per workgroup, as plan_lstm_f32 (api_lstm.hip)
   LstmWaveArgs a;
   a.n_units = 2; a.seq_lengths = nullptr; a.B = B; a.F = F; a.H = H;
   float* x = dev_rand((size_t)B * F * LDX, 1, 1.f);
@@ -42,12 +43,12 @@ int main(int argc, char** argv) {
   hipEvent_t e0, e1; (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
   for (int variant = 0; variant < 2; ++variant) {
     a.s = 5;
-    for (int i = 0; i < 5; ++i) { a.s = 5 + i; (void)launch_lstm_wave(a, 0); }
+    for (int i = 0; i < 5; ++i) { a.s = 5 + i; lstm_build_chain(a, UPB); (void)launch_lstm_chain(a, UPB, 0); }
     (void)hipDeviceSynchronize();
     float best = 1e9f;
     for (int r = 0; r < 3; ++r) {
       (void)hipEventRecord(e0);
-      for (int i = 0; i < 20; ++i) { a.s = 3 + i; (void)launch_lstm_wave(a, 0); }
+      for (int i = 0; i < 20; ++i) { a.s = 3 + i; lstm_build_chain(a, UPB); (void)launch_lstm_chain(a, UPB, 0); }
       (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
       float ms; (void)hipEventElapsedTime(&ms, e0, e1);
       best = ms / 20 < best ? ms / 20 : best;

@@ -446,7 +446,7 @@ def test_one_launch_train_layers_equal_the_layer_by_layer_path(M, in_dim, hidden
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# LSTM steps of a few rows (csrc/lstm.hip, lstm_fewrows_kernel; csrc/gemm_rec.hip, rec_fewrows_reg_kernel)
+# LSTM steps of a few rows (csrc/lstm_fewrows.hip, lstm_fewrows_kernel; csrc/gemm_rec.hip, rec_fewrows_reg_kernel)
 @pytest.mark.parametrize('B,F,In,H,L,bi', [(12, 32, 144, 512, 2, False), (4, 9, 60, 512, 2, False), (16, 7, 72, 64, 3, False),
                                           (6, 11, 60, 128, 2, True), (9, 5, 144, 256, 1, False)])
 def test_lstm_steps_of_a_few_rows_equal_the_small_batch_kernels(B, F, In, H, L, bi):

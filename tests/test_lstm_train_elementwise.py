@@ -11,8 +11,8 @@ t = len - 1.
 Reverse: every element of every output against the float64 sweep from that forward's own save buffer (so the forward's
 error is no part of it).
 
-Cases: the smallest shapes that take each branch; the id names the forward kernel (launch_lstm_wave / launch_lstm_persist
-in csrc/lstm.hip, by B and F) and the form of the reverse pass (carve_train_lstm / Bptt in csrc/api_lstm.hip,
+Cases: the smallest shapes that take each branch; the id names the forward kernel (plan_lstm_f32 in
+csrc/api_lstm.hip, by B and F) and the form of the reverse pass (carve_train_lstm / Bptt in csrc/api_lstm.hip,
 rec_ksplit_applicable in csrc/gemm_rec.hip, gemm_fewrows_applicable in csrc/gemm_f32.hip), read off the dispatch code:
   forward   B <= 3 and F >= 4: lstm_persist_kernel (whole sequence, cooperative); else B <= 4 / 8 / 12 / 16:
             lstm_fewrows_kernel<4,2> / <8,2> / <12,2> / <16,1>; B <= 256: lstm_mid_kernel (32-row tiles: B = 17 is a second
