@@ -13,7 +13,7 @@ struct empose_mesh {
   int n_joints = 22;            // posed joints returned (22 body, or all 52 of SMPL-H)
   int rod_conv = 0;             // EMPOSE_RODRIGUES_*
   float* wc = nullptr;
-  float* wc_frag = nullptr;     // vertex rows of wc in matrix-core fragment order, per 32-vertex tile (mesh.hip)
+  float* wc_frag = nullptr;     // vertex rows of wc in matrix-core fragment order, per 32-vertex tile (mesh_rows.hip)
   int* skin_idx = nullptr;
   float* skin_w = nullptr;
   int* skin_idx4 = nullptr;     // first four bones / weights per vertex, padded to whole tiles
@@ -77,7 +77,7 @@ int pack_mesh_tiles_x3(empose_mesh* m, const empose_mesh_desc* d) {
 
 // Tables of mesh_rows_bf16_kernel: per 32-vertex tile, k-step of 16, coordinate plane and (hi, lo) piece, lane
 // (v = lane & 31, half = lane >> 5) owns the eight values k = kstep * 16 + half * 8 .. + 7 of row (tile * 32 + v) * 3 + c.
-// Columns (mesh.hip): 0..188 pose, (hi, lo) = (w0, w1); 189..199 shape/template, (b0, b2); 200..210 the same
+// Columns (mesh_bf16.hip): 0..188 pose, (hi, lo) = (w0, w1); 189..199 shape/template, (b0, b2); 200..210 the same
 // coefficients again, (b1, b0); zero up to 223.
 int pack_mesh_tiles_bf16(empose_mesh* m, const empose_mesh_desc* d) {
   const int V = d->n_vertices, NT = (V + 31) / 32, K = 200, KS = 14;
@@ -103,7 +103,7 @@ int pack_mesh_tiles_bf16(empose_mesh* m, const empose_mesh_desc* d) {
     }
   TRY(upload_bf16(m->allocs, buf, &m->wc_bf16));
   // The skin weights as a dense [32 bone slots][32 vertices] block per tile for the bone blend on the matrix cores
-  // (mesh.hip mesh_rows_bf16s_kernel): k-step ks, piece p, lane (vertex = lane & 31, half = lane >> 5) holds the eight
+  // (mesh_bf16.hip mesh_rows_bf16s_kernel): k-step ks, piece p, lane (vertex = lane & 31, half = lane >> 5) holds the eight
   // weights of bones 16 ks + 8 half + 0..7 -- hi = bf16(w), lo = bf16(w - hi); bones a vertex does not have, and the
   // slots past the 22 body bones, are zero.  Weights of the same bone listed twice add up.
   {

@@ -1,4 +1,4 @@
-// The per-frame bodies of the pose / shape update + Rodrigues + feature row (update_feat_kernel, smpl.hip) and of the
+// The per-frame bodies of the pose / shape update + Rodrigues + feature row (update_feat_kernel, smpl_rows.hip) and of the
 // Rodrigues reverse in tile layout (rodrigues_bwd_t_kernel, smpl_tile.hip), shared with the blend-shape GEMMs that
 // carry them as prologue / epilogue (mlp_fused.hip: blend_feat_gemm_kernel, blend_t_gemm_rod_kernel).  One definition,
 // so the stand-alone kernels and the fused ones produce the same bits.  Internal, gfx950 only.

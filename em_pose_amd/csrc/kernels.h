@@ -494,7 +494,7 @@ bool lstm_persist_shape_ok(int B, int H, int n_units, const int* in_k);   // H, 
 hipError_t launch_lstm_persist(const LstmWaveArgs& a, float* xch, hipStream_t stream, bool* done);
 
 // ---------------------------------------------------------------------------------------------------------------
-// Training backward (train.hip)
+// Training backward (gemm_atb.hip, train_glue.hip, train_loss.hip, adam.hip)
 // ---------------------------------------------------------------------------------------------------------------
 constexpr int ATB_MAX_SEG = 8;
 struct AtbArgs {             // C[N][ldc] = A[M][lda]^T . B[M][ldb]  (+ bias[n] = sum_m A[m][n])
@@ -818,7 +818,7 @@ struct MeshSkinArgs {
   int stagger = 1;                 // mesh_rows_x3_kernel: a tile's stores ride in the next tile's K loop, at a per-wave k-step
 };
 hipError_t launch_mesh_rows(const MeshSkinArgs& a, hipStream_t stream);
-// The same evaluation with the blend-shape contraction in split bf16 (mesh.hip); needs MeshSkinArgs::wc_bf16.
+// The same evaluation with the blend-shape contraction in split bf16 (mesh_bf16.hip); needs MeshSkinArgs::wc_bf16.
 hipError_t launch_mesh_rows_bf16(const MeshSkinArgs& a, hipStream_t stream);
 constexpr int MESH_BF16_TILE_BYTES = 14 * 3 * 2 * 1024;
 // ... and with the bone blend as a second contraction on the matrix cores (needs MeshSkinArgs::skin_bf16 too).
@@ -877,7 +877,7 @@ int mesh_vjp_feat_split(int T, int V);
 int mesh_vjp_bone_split(int T, int V);
 hipError_t launch_mesh_vjp_feat(const MeshVjpArgs& a, hipStream_t stream);
 hipError_t launch_mesh_vjp_bone(const MeshVjpArgs& a, hipStream_t stream);
-// Reverse kinematic chain (smpl.hip, beside mesh_chain_kernel): one thread per frame recomputes the 22 global rotations
+// Reverse kinematic chain (mesh_chain.hip, beside mesh_chain_kernel): one thread per frame recomputes the 22 global rotations
 // and takes dA (bone sweep) and the joint cotangents back to d_rot, the rest-joint cotangents and d_trans.
 struct MeshChainBwdArgs {
   const float* rot;            // [T][22][9]

@@ -1,5 +1,5 @@
 // One element (batch row b, hidden unit j) of a step of back-propagation through time of an LSTM layer (see the comment of
-// lstm_cell_bwd_kernel in train.hip).  Shared by that kernel and by the recurrent products of gemm_rec.hip and the
+// lstm_cell_bwd_kernel in train_glue.hip).  Shared by that kernel and by the recurrent products of gemm_rec.hip and the
 // matrix-vector kernel of gemm_f32.hip, which feed the dh they have just formed straight into the next step's cell
 // instead of storing it.
 // The formulas stand twice on purpose: lstm_cell_bwd_elem for a caller that has dh at hand, lstm_cell_bwd_load +

@@ -1,229 +1,25 @@
-// Full-mesh SMPL-H evaluation (reference smpl_torch_batch.py / bodymodels' SMPLLayer forward: v_posed = v_template +
-// shapedirs . beta + posedirs . (R - I), then linear blend skinning of all V vertices), gfx950 only.
-//
-// One workgroup owns 64 frames for the whole launch: their 200 pose/shape features and their 22 relative bone
-// transforms stay in LDS (120 KB), and the workgroup's eight waves walk the 32-vertex tiles of the mesh.  For a tile a
-// wave computes v_posed of 32 vertices x 64 frames on the fp32 matrix cores -- six 32x32 accumulators: two frame
-// tiles x the three coordinate planes, so a lane ends up with x, y and z of the same (frame, vertex) pairs -- and skins
-// them in registers; the (T x 20670) v_posed matrix never exists in memory and the vertices are written once.
-// The coefficient matrix is consumed from L2 in matrix-core fragment order (one coalesced 1 KB read per k-group and
-// coordinate plane, packed by the host when the mesh handle is created) through a five-slot register ring that runs
-// four k-groups ahead and straight across tile boundaries; there is no barrier after the staging.
-// Measured (scripts/dev/mesh_lab.hip, T = 16384): a tile costs a wave 41.1k cycles of K loop (600 MFMAs, 38.4k ideal)
-// plus 11.1k cycles of skinning when it has its SIMD to itself.  The second wave per SIMD hides load and LDS latency
-// but does not overlap the two phases: fp32 vector FMAs and fp32 MFMAs share the SIMD's FMA lanes (the chip's vector
-// and matrix fp32 peaks are the same number), so the cost is the sum of both, and the kernel runs at the power limit
-// (~2.1 GHz).  The skinning is therefore written for the fewest vector instructions: packed FMAs on the halves of
-// each 16-byte transform row.
+// Full-mesh SMPL-H evaluation with the blend-shape contraction in split bf16: mesh_rows_kernel (mesh_rows.hip) on the bf16
+// matrix cores, two opt-in kernels.  Neither is the headline's arithmetic (that is mesh_x3.hip, three pieces on all columns).
 #include <hip/hip_runtime.h>
 #include <type_traits>
 
 #include "bf16x3.h"
 #include "gemm_epilogue.h"
 #include "kernels.h"
+#include "mesh_grid.h"
 
 namespace empose {
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
-namespace mr {
-constexpr int BM = 64;              // frames per workgroup
-constexpr int NW = 8;               // waves per workgroup
-constexpr int K = 200, KG = K / 8;  // 25 k-groups of 8
-constexpr int LDA = K + 4;
-constexpr int RING = 5;             // KG % RING == 0: a k-group's ring slot does not depend on the tile
-constexpr int A_FLOATS = BM * LDA;
-constexpr int XF_FLOATS = BM * NB * 12;
-constexpr int TR_FLOATS = BM * 4;
-constexpr size_t LDS_BYTES = (size_t)(A_FLOATS + XF_FLOATS + TR_FLOATS) * sizeof(float) + 64;
-constexpr int TILE_FLOATS = KG * 3 * 256;   // one 32-vertex tile of the packed coefficients
-static_assert(KG % RING == 0, "ring slots must line up across tiles");
-}  // namespace mr
-
-#ifdef EMPOSE_MESH_TRACE   // dev lab only (scripts/dev/mesh_lab.hip): shader-clock stamps of the waves of block (0,0)
+#ifdef EMPOSE_MESH_TRACE   // dev lab only (scripts/dev/mesh_bf16_lab.hip): shader-clock stamps of the waves of block (0,0)
+// (a lab defines it and includes ONE of mesh_rows.hip / mesh_bf16.hip: a library build with it would define g_mesh_trace twice)
 __device__ long long g_mesh_trace[8 * 32 * 4];
 #define MR_STAMP(tile, i) \
   if (lane == 0 && blockIdx.x == 0 && blockIdx.y == 0) g_mesh_trace[(wave * 32 + (tile)) * 4 + (i)] = clock64();
 #else
 #define MR_STAMP(tile, i)
 #endif
-
-#define MR_SGB(mask, n) __builtin_amdgcn_sched_group_barrier(mask, n, 0);
-#define MR_MFMA 0x008
-#define MR_VMEM_RD 0x020
-#define MR_DS_RD 0x100
-
-template <bool EXTRA>   // EXTRA: body models with more than four bones per vertex (not SMPL-H)
-__global__ __launch_bounds__(mr::NW * 64) void mesh_rows_kernel(MeshSkinArgs a) {
-  using namespace mr;
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  float* As = lds;
-  float* XFs = lds + A_FLOATS;
-  float* TRs = XFs + XF_FLOATS;
-  const int T = a.T, V = a.V;
-  const int f0 = blockIdx.x * BM;
-  const int tid = threadIdx.x, lane = tid & 63, l31 = lane & 31, lh = lane >> 5;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-
-  // ---- staging: features, relative transforms and translations of the block's frames (rows past T repeat row T-1;
-  // their results are never stored)
-  {
-    const float* __restrict__ feat = a.feat;
-    for (int i = tid; i < BM * (K / 4); i += NW * 64) {
-      const int r = i / (K / 4), c = (i % (K / 4)) * 4;
-      const int row = f0 + r < T ? f0 + r : T - 1;
-      *reinterpret_cast<f32x4*>(As + r * LDA + c) = *reinterpret_cast<const f32x4*>(feat + (size_t)row * K + c);
-    }
-    if (tid < BM) *reinterpret_cast<f32x4*>(As + tid * LDA + K) = f32x4{0.f, 0.f, 0.f, 0.f};
-    const float* __restrict__ xf = a.xf;
-    for (int i = tid; i < BM * NB * 3; i += NW * 64) {
-      const int r = i / (NB * 3), c = i % (NB * 3);
-      const int row = f0 + r < T ? f0 + r : T - 1;
-      *reinterpret_cast<f32x4*>(XFs + i * 4) = *reinterpret_cast<const f32x4*>(xf + ((size_t)row * NB * 3 + c) * 4);
-    }
-    if (tid < BM) {
-      const int row = f0 + tid < T ? f0 + tid : T - 1;
-      f32x4 t{0.f, 0.f, 0.f, 0.f};
-      if (a.trans) { t[0] = a.trans[(size_t)row * 3]; t[1] = a.trans[(size_t)row * 3 + 1]; t[2] = a.trans[(size_t)row * 3 + 2]; }
-      *reinterpret_cast<f32x4*>(TRs + tid * 4) = t;
-    }
-  }
-  __syncthreads();
-
-  // ---- this wave's tiles: vt = first + wave, + NW, ... below `end`
-  const int n_tiles = (V + 31) / 32;
-  const int per_block = (n_tiles + gridDim.y - 1) / gridDim.y;
-  const int first = blockIdx.y * per_block;
-  const int end = min(first + per_block, n_tiles);
-  int vt = first + wave;
-  if (vt >= end) return;
-
-  epi_cgbyte_t wbase = (epi_cgbyte_t)a.wc_frag;
-  const unsigned lane16 = (unsigned)lane * 16u;
-  auto tile_base = [&](int t) { return wbase + (size_t)t * (TILE_FLOATS * 4); };
-  auto bload = [&](f32x4 (&dst)[3], epi_cgbyte_t base, int g) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      dst[c] = *(const __attribute__((address_space(1))) f32x4*)(base + ((unsigned)((g * 3 + c) * 1024) + lane16));
-  };
-
-  f32x4 ring[RING][3];
-  {
-    epi_cgbyte_t b0 = tile_base(vt);
-#pragma unroll
-    for (int g = 0; g < RING - 1; ++g) bload(ring[g], b0, g);
-  }
-
-  const float* a_lane = As + l31 * LDA + lh * 4;
-  // A fragments: read one k-group ahead into three slots (k-groups u = 0..4 of a ring pass use slots 0,1,0,1,2, so the
-  // slot being filled is never the one being consumed although a pass has an odd number of k-groups)
-#define FA_SLOT(u) ((u) == RING - 1 ? 2 : ((u) & 1))
-  f32x4 fa[3][2];
-  fa[0][0] = *reinterpret_cast<const f32x4*>(a_lane);
-  fa[0][1] = *reinterpret_cast<const f32x4*>(a_lane + 32 * LDA);
-  epi_gbyte_t vbase = (epi_gbyte_t)a.vertices;
-  const int kb = a.kb;
-  const size_t vrow_bytes = (size_t)V * 12;
-
-  for (int seq = 0; vt < end; vt += NW, ++seq) {
-    MR_STAMP(seq, 0)
-    epi_cgbyte_t bcur = tile_base(vt);
-    // the prefetch runs into the wave's next tile; past the last one it re-reads this tile (never consumed)
-    epi_cgbyte_t bnext = vt + NW < end ? tile_base(vt + NW) : bcur;
-    const int s = vt * 32 + l31;            // this lane's vertex (the packed tables are padded to whole tiles)
-    const int4 bone4 = *reinterpret_cast<const int4*>(a.skin_idx4 + (size_t)s * 4);
-    const f32x4 w4 = *reinterpret_cast<const f32x4*>(a.skin_w4 + (size_t)s * 4);
-
-    f32x16 acc[2][3];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][c][r] = 0.f;
-
-#pragma unroll 1
-    for (int g0 = 0; g0 < KG; g0 += RING) {
-#pragma unroll
-      for (int u = 0; u < RING; ++u) {
-        const int g = g0 + u;
-        {
-          // A fragments of the next k-group (k-group 0 again after the last one: the next tile starts there)
-          const int gn = g + 1 < KG ? g + 1 : 0;
-          f32x4 (&fn)[2] = fa[u + 1 == RING ? 0 : FA_SLOT(u + 1)];
-          fn[0] = *reinterpret_cast<const f32x4*>(a_lane + gn * 8);
-          fn[1] = *reinterpret_cast<const f32x4*>(a_lane + 32 * LDA + gn * 8);
-          const int gp = g + RING - 1;   // k-group to prefetch: this tile's, or the first ones of the next tile
-          epi_cgbyte_t src = gp < KG ? bcur : bnext - (size_t)KG * 3 * 1024;
-          bload(ring[(u + RING - 1) % RING], src, gp);
-        }
-        const f32x4 (&fc)[2] = fa[FA_SLOT(u)];
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-              acc[i][c] = __builtin_amdgcn_mfma_f32_32x32x2f32(fc[i][e], ring[u][c][e], acc[i][c], 0, 0, 0);
-        // 24 MFMAs with the two fragment reads and the three weight loads spread between them
-        MR_SGB(MR_MFMA, 2) MR_SGB(MR_DS_RD, 1) MR_SGB(MR_MFMA, 2) MR_SGB(MR_DS_RD, 1)
-        MR_SGB(MR_MFMA, 2) MR_SGB(MR_VMEM_RD, 1) MR_SGB(MR_MFMA, 2) MR_SGB(MR_VMEM_RD, 1)
-        MR_SGB(MR_MFMA, 2) MR_SGB(MR_VMEM_RD, 1) MR_SGB(MR_MFMA, 14)
-      }
-    }
-
-    MR_STAMP(seq, 1)
-    // ---- skinning of the lane's 32 (frame, vertex) pairs: blended 3x4 transform, then one mat-vec
-    // (reference order: T = sum_k w_k G_k, v = T . [v_posed, 1] + trans).  Addresses are a per-lane part that only
-    // depends on the tile (bones, vertex, lane half) plus a compile-time / wave-uniform part per accumulator element.
-    if (s < V) {
-      const char* xfl = reinterpret_cast<const char*>(XFs) + lh * (4 * NB * 48);
-      const char* xk[4] = {xfl + bone4.x * 48, xfl + bone4.y * 48, xfl + bone4.z * 48, xfl + bone4.w * 48};
-      const f32x2 wp[4] = {{w4[0], w4[0]}, {w4[1], w4[1]}, {w4[2], w4[2]}, {w4[3], w4[3]}};
-      const char* trl = reinterpret_cast<const char*>(TRs) + lh * 64;
-      const unsigned lane_off = ((unsigned)(f0 + 4 * lh) * (unsigned)V + (unsigned)s) * 12u;
-      auto skin = [&](auto full_tag) {
-        constexpr bool FULL = decltype(full_tag)::value;
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int dm = i * 32 + (r & 3) + 8 * (r >> 2);   // frame within the block, less 4 * lh
-            const float vx = acc[i][0][r], vy = acc[i][1][r], vz = acc[i][2][r];
-            const f32x4 tr = *reinterpret_cast<const f32x4*>(trl + dm * 16);
-            float out[3];
-#pragma unroll
-            for (int row = 0; row < 3; ++row) {
-              // (T0, T1) and (T2, T3) as register pairs: two packed FMAs per bone on the halves of the 16-byte read
-              f32x4 gk = *reinterpret_cast<const f32x4*>(xk[0] + dm * (NB * 48) + row * 16);
-              f32x2 Ta = wp[0] * f32x2{gk[0], gk[1]}, Tb = wp[0] * f32x2{gk[2], gk[3]};
-#pragma unroll
-              for (int k = 1; k < 4; ++k) {
-                gk = *reinterpret_cast<const f32x4*>(xk[k] + dm * (NB * 48) + row * 16);
-                Ta = __builtin_elementwise_fma(wp[k], f32x2{gk[0], gk[1]}, Ta);
-                Tb = __builtin_elementwise_fma(wp[k], f32x2{gk[2], gk[3]}, Tb);
-              }
-              if (EXTRA)
-                for (int k = 4; k < kb; ++k) {
-                  const int b = a.skin_idx[(size_t)s * kb + k];
-                  const float wk = a.skin_w[(size_t)s * kb + k];
-                  gk = *reinterpret_cast<const f32x4*>(xfl + b * 48 + dm * (NB * 48) + row * 16);
-                  Ta = __builtin_elementwise_fma(f32x2{wk, wk}, f32x2{gk[0], gk[1]}, Ta);
-                  Tb = __builtin_elementwise_fma(f32x2{wk, wk}, f32x2{gk[2], gk[3]}, Tb);
-                }
-              out[row] = __builtin_fmaf(Ta[0], vx, __builtin_fmaf(Ta[1], vy, __builtin_fmaf(Tb[0], vz, Tb[1]))) + tr[row];
-            }
-            if (FULL || f0 + 4 * lh + dm < T) {
-              epi_gfloat_t o = (epi_gfloat_t)(vbase + (size_t)dm * vrow_bytes + lane_off);
-              o[0] = out[0]; o[1] = out[1]; o[2] = out[2];
-            }
-          }
-      };
-      if (f0 + BM <= T) skin(std::true_type{}); else skin(std::false_type{});
-    }
-    MR_STAMP(seq, 2)
-  }
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // The same kernel with the blend-shape contraction on the bf16 matrix cores ("split bf16", fp32 accumulate): an fp32
@@ -283,6 +79,60 @@ __device__ __forceinline__ unsigned short bf16_rne(float x) {   // round to near
 }
 __device__ __forceinline__ float bf16_f32(unsigned short h) { return __uint_as_float((unsigned)h << 16); }
 
+// What mesh_rows_bf16_kernel and mesh_rows_bf16s_kernel share outside their K loops and skinning bodies; every piece here
+// left the instructions of both kernels as they were.
+namespace mb {
+// staging: the features of the block's frames split into bf16 pieces (column plan above; rows past T repeat row T-1)
+__device__ __forceinline__ void stage_feat_pieces(const float* __restrict__ feat, unsigned short* Ab, int f0, int T, int tid) {
+  for (int i = tid; i < BM * LDA; i += NW * 64) {
+    const int r = i / LDA, c = i - r * LDA;
+    const int row = f0 + r < T ? f0 + r : T - 1;
+    const int src = c < M1 ? c : (c < M2 ? c : c - (M2 - M1));   // both shape groups read columns 189..199
+    const float x = c < KCOLS ? feat[(size_t)row * 200 + src] : 0.f;
+    const unsigned short p0 = bf16_rne(x);
+    const float r1 = x - bf16_f32(p0);
+    const unsigned short p1 = bf16_rne(r1);
+    const unsigned short p2 = bf16_rne(r1 - bf16_f32(p1));
+    Ab[i] = c < M2 ? p0 : p1;                                   // hi: x0 | a0 | a1
+    Ab[A_PIECE_BYTES / 2 + i] = c < M1 ? p1 : (c < M2 ? p2 : p0);   // lo: x1 | a2 | a0
+  }
+}
+// this wave's tiles: vt, vt + NW, ... below `end`, of the grid.y slice of the mesh's n_tiles
+struct TileRange { int n_tiles, end, vt; };
+__device__ __forceinline__ TileRange tile_range(int V, int wave) {
+  TileRange t;
+  t.n_tiles = (V + 31) / 32;
+  const int per_block = (t.n_tiles + gridDim.y - 1) / gridDim.y;
+  const int first = blockIdx.y * per_block;
+  t.end = min(first + per_block, t.n_tiles);
+  t.vt = first + wave;
+  return t;
+}
+// The coefficient table as a raw buffer: a fragment load is one buffer_load_dwordx4 with the lane offset in a VGPR, the
+// tile / k-step offset in an SGPR and the (plane, piece) offset in the instruction -- no address arithmetic in VGPRs
+// (flat global loads made the compiler keep a 64-bit address pair per 4 KB of the 84 KB tile).
+struct CoefTable {
+  __amdgpu_buffer_rsrc_t rsrc;
+  int lane16;
+  __device__ __forceinline__ CoefTable(const void* wc_bf16, int n_tiles, int lane)
+      : rsrc(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(wc_bf16), 0, (int)((size_t)n_tiles * TILE_BYTES), 0x00020000)),
+        lane16(lane * 16) {}
+  __device__ __forceinline__ f32x4 wload(int tile_off, int ks, int c, int p) const {
+    const int f = c * 2 + p;   // fragment of the k-step: the part below 4 KB rides in the instruction's offset field
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsrc, lane16 + (f & 3) * 1024,
+                                                                           tile_off + ks * 6144 + (f >> 2) * 4096, 0));
+  }
+  // B fragments of one k-step: [plane][piece], 1 KB each
+  __device__ __forceinline__ void bload(f32x4 (&dst)[3][2], int tile_off, int ks) const {
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+      for (int p = 0; p < 2; ++p) dst[c][p] = wload(tile_off, ks, c, p);
+  }
+};
+__device__ __forceinline__ int tile_off_of(int t) { return __builtin_amdgcn_readfirstlane(t) * TILE_BYTES; }   // wave-uniform
+}  // namespace mb
+
 template <bool EXTRA>
 __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16_kernel(MeshSkinArgs a) {
   X3_EXCLUSIVE_SIMD();
@@ -298,25 +148,14 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16_kernel(MeshSkinArg
 
   // ---- staging: the features split into bf16 pieces (column plan above), relative transforms, translations
   {
-    const float* __restrict__ feat = a.feat;
-    for (int i = tid; i < BM * LDA; i += NW * 64) {
-      const int r = i / LDA, c = i - r * LDA;
-      const int row = f0 + r < T ? f0 + r : T - 1;
-      const int src = c < M1 ? c : (c < M2 ? c : c - (M2 - M1));   // both shape groups read columns 189..199
-      const float x = c < KCOLS ? feat[(size_t)row * 200 + src] : 0.f;
-      const unsigned short p0 = bf16_rne(x);
-      const float r1 = x - bf16_f32(p0);
-      const unsigned short p1 = bf16_rne(r1);
-      const unsigned short p2 = bf16_rne(r1 - bf16_f32(p1));
-      Ab[i] = c < M2 ? p0 : p1;                                   // hi: x0 | a0 | a1
-      Ab[A_PIECE_BYTES / 2 + i] = c < M1 ? p1 : (c < M2 ? p2 : p0);   // lo: x1 | a2 | a0
-    }
+    stage_feat_pieces(a.feat, Ab, f0, T, tid);
     const float* __restrict__ xf = a.xf;
     for (int i = tid; i < BM * NB * 3; i += NW * 64) {
       const int r = i / (NB * 3), c = i % (NB * 3);
       const int row = f0 + r < T ? f0 + r : T - 1;
       *reinterpret_cast<f32x4*>(XFs + i * 4) = *reinterpret_cast<const f32x4*>(xf + ((size_t)row * NB * 3 + c) * 4);
     }
+    // translation staging: stays duplicated (as a shared function it flips a branch of mesh_rows_bf16_kernel)
     if (tid < BM) {
       const int row = f0 + tid < T ? f0 + tid : T - 1;
       f32x4 t{0.f, 0.f, 0.f, 0.f};
@@ -326,34 +165,15 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16_kernel(MeshSkinArg
   }
   __syncthreads();
 
-  const int n_tiles = (V + 31) / 32;
-  const int per_block = (n_tiles + gridDim.y - 1) / gridDim.y;
-  const int first = blockIdx.y * per_block;
-  const int end = min(first + per_block, n_tiles);
-  int vt = first + wave;
+  const TileRange tiles = tile_range(V, wave);
+  const int n_tiles = tiles.n_tiles, end = tiles.end;
+  int vt = tiles.vt;
   if (vt >= end) return;
 
-  // The coefficient table as a raw buffer: a fragment load is one buffer_load_dwordx4 with the lane offset in a VGPR, the
-  // tile / k-step offset in an SGPR and the (plane, piece) offset in the instruction -- no address arithmetic in VGPRs
-  // (flat global loads made the compiler keep a 64-bit address pair per 4 KB of the 84 KB tile).
-  const __amdgpu_buffer_rsrc_t wtab = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(a.wc_bf16), 0, (int)((size_t)((V + 31) / 32) * TILE_BYTES), 0x00020000);
-  const int lane16 = lane * 16;
-  auto wload = [&](int tile_off, int ks, int c, int p) {
-    const int f = c * 2 + p;   // fragment of the k-step: the part below 4 KB rides in the instruction's offset field
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wtab, lane16 + (f & 3) * 1024,
-                                                                           tile_off + ks * 6144 + (f >> 2) * 4096, 0));
-  };
-  // B fragments of one k-step: [plane][piece], 1 KB each
-  auto bload = [&](f32x4 (&dst)[3][2], int tile_off, int ks) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int p = 0; p < 2; ++p) dst[c][p] = wload(tile_off, ks, c, p);
-  };
-  auto tile_off_of = [&](int t) { return __builtin_amdgcn_readfirstlane(t) * TILE_BYTES; };   // wave-uniform
+  const CoefTable wtab(a.wc_bf16, n_tiles, lane);
   // A fragments of this lane: row l31 (+ 32), 16 bytes at k-step * 32 + lh * 16; [frame tile][piece]
   const char* a_lane = reinterpret_cast<const char*>(Ab) + l31 * (LDA * 2) + lh * 16;
+  // aload: stays duplicated (as a shared function it reorders address arithmetic of mesh_rows_bf16s_kernel)
   auto aload = [&](f32x4 (&dst)[2][2], int ks) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -370,7 +190,7 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16_kernel(MeshSkinArg
   {
     const int b0 = tile_off_of(vt);
 #pragma unroll
-    for (int ks = 0; ks < RING - 1; ++ks) bload(ring[ks], b0, ks);
+    for (int ks = 0; ks < RING - 1; ++ks) wtab.bload(ring[ks], b0, ks);
   }
   aload(fa[0], 0);
 
@@ -410,7 +230,7 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16_kernel(MeshSkinArg
         if (kn < KS) {
 #pragma unroll
           for (int p = 0; p < 2; ++p)
-            bn[prod][p] = wload(bt, kn, prod, p);
+            bn[prod][p] = wtab.wload(bt, kn, prod, p);
         }
         if (prod < 2) {
 #pragma unroll
@@ -429,7 +249,7 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16_kernel(MeshSkinArg
       }
     }
 #pragma unroll
-    for (int ks = 0; ks < RING - 1; ++ks) bload(ring[ks], bnext, ks);
+    for (int ks = 0; ks < RING - 1; ++ks) wtab.bload(ring[ks], bnext, ks);
 
     MR_STAMP(seq, 1)
     // ---- skinning (as mesh_rows_kernel)
@@ -533,19 +353,7 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16s_kernel(MeshSkinAr
 
   // ---- staging: feature pieces (as mesh_rows_bf16_kernel), bone transforms as bf16 pieces, translations
   {
-    const float* __restrict__ feat = a.feat;
-    for (int i = tid; i < BM * LDA; i += NW * 64) {
-      const int r = i / LDA, c = i - r * LDA;
-      const int row = f0 + r < T ? f0 + r : T - 1;
-      const int src = c < M1 ? c : (c < M2 ? c : c - (M2 - M1));
-      const float x = c < KCOLS ? feat[(size_t)row * 200 + src] : 0.f;
-      const unsigned short p0 = bf16_rne(x);
-      const float r1 = x - bf16_f32(p0);
-      const unsigned short p1 = bf16_rne(r1);
-      const unsigned short p2 = bf16_rne(r1 - bf16_f32(p1));
-      Ab[i] = c < M2 ? p0 : p1;
-      Ab[A_PIECE_BYTES / 2 + i] = c < M1 ? p1 : (c < M2 ? p2 : p0);
-    }
+    stage_feat_pieces(a.feat, Ab, f0, T, tid);
     const float* __restrict__ xf = a.xf;
     for (int i = tid; i < BM * NB * 3; i += NW * 64) {   // (frame r, bone b, transform row q): four entries of one row
       const int r = i / (NB * 3), bq = i - r * (NB * 3), b = bq / 3, q = bq - b * 3;
@@ -563,6 +371,7 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16s_kernel(MeshSkinAr
     for (int i = tid; i < 2 * 12 * BM; i += NW * 64)     // the unused bone slots 22, 23 of every row
       *reinterpret_cast<unsigned*>(Gb + i * G_ROW_BYTES + NB * 2) = 0u;
     if (tid < 16) *reinterpret_cast<unsigned*>(Gb + 2 * G_PIECE_BYTES + tid * 4) = 0u;
+    // translation staging: stays duplicated (as a shared function it flips a branch of mesh_rows_bf16_kernel)
     if (tid < BM) {
       const int row = f0 + tid < T ? f0 + tid : T - 1;
       f32x4 t{0.f, 0.f, 0.f, 0.f};
@@ -572,31 +381,17 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16s_kernel(MeshSkinAr
   }
   __syncthreads();
 
-  const int n_tiles = (V + 31) / 32;
-  const int per_block = (n_tiles + gridDim.y - 1) / gridDim.y;
-  const int first = blockIdx.y * per_block;
-  const int end = min(first + per_block, n_tiles);
-  int vt = first + wave;
+  const TileRange tiles = tile_range(V, wave);
+  const int n_tiles = tiles.n_tiles, end = tiles.end;
+  int vt = tiles.vt;
   if (vt >= end) return;
 
-  const __amdgpu_buffer_rsrc_t wtab = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<void*>(a.wc_bf16), 0, (int)((size_t)n_tiles * TILE_BYTES), 0x00020000);
+  const CoefTable wtab(a.wc_bf16, n_tiles, lane);
   const __amdgpu_buffer_rsrc_t stab = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(a.skin_bf16), 0, (int)((size_t)n_tiles * SKIN_TILE_BYTES), 0x00020000);
-  const int lane16 = lane * 16;
-  auto wload = [&](int tile_off, int ks, int c, int p) {
-    const int f = c * 2 + p;
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(wtab, lane16 + (f & 3) * 1024,
-                                                                           tile_off + ks * 6144 + (f >> 2) * 4096, 0));
-  };
-  auto bload = [&](f32x4 (&dst)[3][2], int tile_off, int ks) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-#pragma unroll
-      for (int p = 0; p < 2; ++p) dst[c][p] = wload(tile_off, ks, c, p);
-  };
-  auto tile_off_of = [&](int t) { return __builtin_amdgcn_readfirstlane(t) * TILE_BYTES; };
+  const int lane16 = wtab.lane16;
   const char* a_lane = reinterpret_cast<const char*>(Ab) + l31 * (LDA * 2) + lh * 16;
+  // aload: stays duplicated (as a shared function it reorders address arithmetic of mesh_rows_bf16s_kernel)
   auto aload = [&](f32x4 (&dst)[2][2], int ks) {
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -613,7 +408,7 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16s_kernel(MeshSkinAr
   {
     const int b0 = tile_off_of(vt);
 #pragma unroll
-    for (int ks = 0; ks < RING - 1; ++ks) bload(ring[ks], b0, ks);
+    for (int ks = 0; ks < RING - 1; ++ks) wtab.bload(ring[ks], b0, ks);
   }
   aload(fa[0], 0);
 
@@ -652,7 +447,7 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16s_kernel(MeshSkinAr
       for (int prod = 0; prod < 3; ++prod) {
         if (kn < KS) {
 #pragma unroll
-          for (int p = 0; p < 2; ++p) bn[prod][p] = wload(bt, kn, prod, p);
+          for (int p = 0; p < 2; ++p) bn[prod][p] = wtab.wload(bt, kn, prod, p);
         }
         if (prod < 2) {
 #pragma unroll
@@ -671,7 +466,7 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16s_kernel(MeshSkinAr
       }
     }
 #pragma unroll
-    for (int ks = 0; ks < RING - 1; ++ks) bload(ring[ks], bnext, ks);
+    for (int ks = 0; ks < RING - 1; ++ks) wtab.bload(ring[ks], bnext, ks);
 
     // ---- bone blend on the matrix cores + out = T^R v + T^t on registers
     const char* trl = reinterpret_cast<const char*>(TRs) + lh * 64;
@@ -742,33 +537,14 @@ __global__ __launch_bounds__(mb::NW * 64) void mesh_rows_bf16s_kernel(MeshSkinAr
 
 hipError_t launch_mesh_rows_bf16s(const MeshSkinArgs& a, hipStream_t stream) {
   if (!a.skin_bf16 || !a.wc_bf16) return hipErrorInvalidValue;
-  const int bx = (a.T + mb::BM - 1) / mb::BM;
-  const int n_tiles = (a.V + 31) / 32;
-  int by = bx >= 256 ? 1 : (256 + bx - 1) / bx;
-  const int max_by = (n_tiles + mb::NW - 1) / mb::NW;
-  if (by > max_by) by = max_by;
-  return launch_lds(mesh_rows_bf16s_kernel, dim3(bx, by), dim3(mb::NW * 64), ms::LDS_BYTES, stream, a);
+  const dim3 grid = mesh_rows_grid(a.T, a.V, mb::BM, mb::NW);
+  return launch_lds(mesh_rows_bf16s_kernel, grid, dim3(mb::NW * 64), ms::LDS_BYTES, stream, a);
 }
 
 hipError_t launch_mesh_rows_bf16(const MeshSkinArgs& a, hipStream_t stream) {
-  const int bx = (a.T + mb::BM - 1) / mb::BM;
-  const int n_tiles = (a.V + 31) / 32;
-  int by = bx >= 256 ? 1 : (256 + bx - 1) / bx;
-  const int max_by = (n_tiles + mb::NW - 1) / mb::NW;
-  if (by > max_by) by = max_by;
-  return a.kb <= 4 ? launch_lds(mesh_rows_bf16_kernel<false>, dim3(bx, by), dim3(mb::NW * 64), mb::LDS_BYTES, stream, a)
-                   : launch_lds(mesh_rows_bf16_kernel<true>, dim3(bx, by), dim3(mb::NW * 64), mb::LDS_BYTES, stream, a);
-}
-
-hipError_t launch_mesh_rows(const MeshSkinArgs& a, hipStream_t stream) {
-  const int bx = (a.T + mr::BM - 1) / mr::BM;
-  const int n_tiles = (a.V + 31) / 32;
-  // fewer than one workgroup per CU: split the mesh's tiles over grid.y (at least one tile per wave)
-  int by = bx >= 256 ? 1 : (256 + bx - 1) / bx;
-  const int max_by = (n_tiles + mr::NW - 1) / mr::NW;
-  if (by > max_by) by = max_by;
-  return a.kb <= 4 ? launch_lds(mesh_rows_kernel<false>, dim3(bx, by), dim3(mr::NW * 64), mr::LDS_BYTES, stream, a)
-                   : launch_lds(mesh_rows_kernel<true>, dim3(bx, by), dim3(mr::NW * 64), mr::LDS_BYTES, stream, a);
+  const dim3 grid = mesh_rows_grid(a.T, a.V, mb::BM, mb::NW);
+  return a.kb <= 4 ? launch_lds(mesh_rows_bf16_kernel<false>, grid, dim3(mb::NW * 64), mb::LDS_BYTES, stream, a)
+                   : launch_lds(mesh_rows_bf16_kernel<true>, grid, dim3(mb::NW * 64), mb::LDS_BYTES, stream, a);
 }
 
 }  // namespace empose

@@ -1,7 +1,7 @@
 // Per-vertex error between two posed bodies, sum_v |v_A - v_B| and sum_v |v_A - v_B|^2 per frame (PVE / MPVPE, the
 // surface counterpart of MPJPE; this project's addition, the reference has no such metric), gfx950 only.
 //
-// mesh_pair_error_kernel is mesh_rows_kernel (mesh.hip) with the 64 staged rows used as 32 frames twice: rows 0..31 are
+// mesh_pair_error_kernel is mesh_rows_kernel (mesh_rows.hip) with the 64 staged rows used as 32 frames twice: rows 0..31 are
 // the frames f0 .. f0+31 of body A (the ground truth), rows 32..63 the same frames of body B (the estimate), each body
 // with its own features, bone transforms and translations.  The K loop is the original's -- fp32 matrix cores, packed
 // coefficient tiles from L2 through the five-slot ring -- and since the accumulator layout puts frame

@@ -1,4 +1,4 @@
-// Full-mesh vector-Jacobian product: the two vertex sweeps of the reverse of mesh_rows_kernel (mesh.hip), gfx950 only.
+// Full-mesh vector-Jacobian product: the two vertex sweeps of the reverse of mesh_rows_kernel (mesh_rows.hip), gfx950 only.
 //
 // Forward, per frame: vp = wc[0:3V] . feat (v_posed), v = sum_b w_vb A_b [vp; 1] + trans.  For a cotangent dV:
 //   feat sweep  d_feat = sum_v,c dvp[v][c] wc[3v+c][:] with dvp_v = sum_b w_vb (A_b^R)^T dV_v

@@ -1,8 +1,8 @@
-// Full-mesh SMPL-H evaluation (mesh.hip: v_posed = wc . [pose features, shape, 1], then linear blend skinning of all V
+// Full-mesh SMPL-H evaluation (mesh_rows.hip: v_posed = wc . [pose features, shape, 1], then linear blend skinning of all V
 // vertices; reference bodymodels/smpl.py:81-147) with the blend-shape contraction on the bf16 matrix cores in THREE bf16
 // pieces per operand -- x = x0 + x1 + x2, every piece the round-to-nearest bf16 of what the previous ones leave, six
 // v_mfma_f32_32x32x16_bf16 products per 16 k (x0w0, x0w1, x1w0, x0w2, x1w1, x2w0, the small ones first), fp32 accumulate:
-// the fp32-EQUIVALENT arithmetic of mlp_fused_x3.hip / lstm_x3.hip (bf16x3.h), on ALL 200 columns.  (mesh.hip's
+// the fp32-EQUIVALENT arithmetic of mlp_fused_x3.hip / lstm_x3.hip (bf16x3.h), on ALL 200 columns.  (mesh_bf16.hip's
 // mesh_rows_bf16_kernel keeps two pieces / three products on the 189 pose columns: not fp32-equivalent, opt-in.)
 //
 // Blocking as mesh_rows_kernel: a workgroup owns 64 frames; their features -- split once into three piece planes, 81 KB --
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(mx::NW * 64) void mesh_rows_x3_kernel(MeshSkinArgs 
   int vt = first + wave;
   if (vt >= end) return;
 
-  // The coefficient table as a raw buffer (mesh.hip): lane offset in a VGPR, tile / k-step offset in an SGPR.
+  // The coefficient table as a raw buffer (mesh_bf16.hip): lane offset in a VGPR, tile / k-step offset in an SGPR.
   const __amdgpu_buffer_rsrc_t wtab = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<void*>(a.wc_x3), 0, (int)((size_t)n_tiles * TILE_BYTES), 0x00020000);
   const int lane16 = lane * 16;

@@ -1,5 +1,5 @@
 // Model-free sensor fitting, gfx950 only: Adam on the sensor residual of a body plus priors.  The
-// residual's value and gradient come from the SMPL evaluation (smpl.hip / smpl_tile.hip); the kernels here are what one
+// residual's value and gradient come from the SMPL evaluation (smpl_chain.hip / smpl_tile.hip); the kernels here are what one
 // iteration does besides.  Per window w of F frames, live_t = t < seq_length,
 //   J_w = sum_t s_t E_t + lambda_pose / 2 sum_{t live} |theta_t[3:66] - p_t[3:66]|^2 + lambda_shape / 2 |beta_w|^2
 //         + lambda_smooth / 2 sum_{t >= 1, live} |theta_t - theta_{t-1}|^2,

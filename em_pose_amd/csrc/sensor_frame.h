@@ -1,5 +1,5 @@
 // The local frame of one virtual sensor of one posed mesh, as a device function: the arithmetic of
-// virtual_sensors_kernel (smpl.hip) in its operation order, for kernels that go on computing with the frame instead of
+// virtual_sensors_kernel (virtual_sensors.hip) in its operation order, for kernels that go on computing with the frame instead of
 // storing it (sensor_sample.hip).  Same operations in the same order; which products the compiler contracts with a
 // following sum is decided per kernel, so the last bits may differ (tests/test_sample_sensors.py bounds it).
 #pragma once

@@ -1,4 +1,4 @@
-// Vector-Jacobian product of virtual_sensors_kernel (smpl.hip): the virtual sensors of arbitrary full-mesh vertices
+// Vector-Jacobian product of virtual_sensors_kernel (virtual_sensors.hip): the virtual sensors of arbitrary full-mesh vertices
 // under autograd (data/virtual_sensors.py), gfx950 only.
 //
 // Forward, per (frame, sensor m): n = (sum over the deg_m incident faces of (v1 - v0) x (v2 - v0)) / deg_m, nh = n/|n|,

@@ -1,12 +1,9 @@
-// SMPL-H on the sensor sub-mesh: everything of one body-model evaluation that is not a matrix product.
+// SMPL-H on the sensor sub-mesh, general path: everything of one body-model evaluation between the two blend products.
 //
-//   update_feat    theta/beta update of the LGD step (reference models.py:588-592), Rodrigues per joint
-//                  (angle guard switchable: smplx ||r + 1e-8|| or the so3 clamp), GEMM feature row [vec(R_j - I) | beta | 1]
 //   chain_sensors  22-joint kinematic chain, linear blend skinning of the ~84 needed vertices, vertex normals and
 //                  sensor frames (reference virtual_sensors.py:16-38, utils.py:126-146), sensor offsets
 //                  (reference models.py:478-479), the reconstruction residual (reference loss.py:23-41) and its
 //                  hand-derived reverse pass down to d v_posed, d J and d R (oracle/analytic_np.py is the blueprint)
-//   rodrigues_bwd  d R -> d theta, and the gradient features written into the network input row
 //
 // chain_sensors runs a small tile of frames per workgroup; all per-frame state (rotations, rest joints, global
 // transforms, skinned vertices and their cotangents, per-bone force/moment sums) lives in LDS and every phase is a
@@ -15,186 +12,8 @@
 // dR_j = G_p^T (sum_subtree M_b - F_b (x) t_j) G_j, which needs subtree sums instead of a level-by-level sweep.
 #include "kernels.h"
 #include "smpl_math.h"
-#include "feat_rows.h"
-
-#include <cstdint>
-#include <cstdlib>
 
 namespace empose {
-
-
-// ---------------------------------------------------------------------------------------------------------------
-__global__ void pack_inputs_kernel(PackArgs a) {
-  const int T = a.B * a.F;
-  const int d_in = a.n_markers * 12;
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= T * (d_in + 1)) return;
-  const int t = idx / (d_in + 1), c = idx % (d_in + 1);
-  if (c == d_in) {
-    if (!a.frame_scale) return;
-    const int b = t / a.F, f = t % a.F;
-    const int len = a.seq_lengths ? a.seq_lengths[b] : a.F;
-    // reference: loss / n_frames, then grad * B * F  ->  F / len per valid frame (models.py:578-579, loss.py:36-39);
-    // unpadded mode: every row is treated as a window of its own length (F == len), i.e. weight 1
-    float s = (f < len) ? (a.rows_as_unpadded ? 1.f : (float)a.F / (float)len) : 0.f;
-    if (a.marker_masks) {
-      bool all = true;
-      for (int m = 0; m < 12; ++m) all = all && (a.marker_masks[(size_t)t * 12 + m] != 0.f);
-      if (!all) s = 0.f;
-    }
-    a.frame_scale[t] = s;
-    return;
-  }
-  float v;
-  int marker;
-  if (c < a.n_markers * 3) {
-    const int mi = c / 3, k = c % 3;
-    marker = a.marker_idx[mi];
-    v = a.marker_pos[(size_t)t * 36 + marker * 3 + k];
-  } else {
-    const int cc = c - a.n_markers * 3;
-    const int mi = cc / 9, k = cc % 9;
-    marker = a.marker_idx[mi];
-    v = a.marker_oris[(size_t)t * 108 + marker * 9 + k];
-  }
-  if (a.suppress_missing && a.marker_masks) {   // the reference's arithmetic, so that a NaN reading stays a NaN
-    const bool valid = a.marker_masks[(size_t)t * 12 + marker] == 1.f;
-    v = v * (valid ? 1.f : 0.f) + (0.f + a.mask_value) * (valid ? 0.f : 1.f);
-  }
-  a.x[(size_t)t * a.ldx + c] = v;
-}
-
-// All twelve sensors in their own order and nothing to replace (the headline configuration): the input columns of a frame
-// are its 36 position and 108 orientation values as they lie -- 36 pieces of 16 bytes per frame, no index arithmetic per
-// element; thread 36 of a frame's group writes the frame weight.  (25.6 -> 13 us at 32768 frames.)
-__global__ __launch_bounds__(256) void pack_inputs_all_kernel(PackArgs a) {
-  const int T = a.B * a.F;
-  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
-  const int t = (int)(idx / 37), q = (int)(idx - (long)t * 37);
-  if (t >= T) return;
-  if (q == 36) {
-    if (!a.frame_scale) return;
-    const int b = t / a.F, f = t - b * a.F;
-    const int len = a.seq_lengths ? a.seq_lengths[b] : a.F;
-    float s = (f < len) ? (a.rows_as_unpadded ? 1.f : (float)a.F / (float)len) : 0.f;
-    if (a.marker_masks) {
-      bool all = true;
-      for (int m = 0; m < 12; ++m) all = all && (a.marker_masks[(size_t)t * 12 + m] != 0.f);
-      if (!all) s = 0.f;
-    }
-    a.frame_scale[t] = s;
-    return;
-  }
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  const f4 v = q < 9 ? reinterpret_cast<const f4*>(a.marker_pos + (size_t)t * 36)[q]
-                     : reinterpret_cast<const f4*>(a.marker_oris + (size_t)t * 108)[q - 9];
-  reinterpret_cast<f4*>(a.x + (size_t)t * a.ldx)[q] = v;
-}
-
-hipError_t launch_pack_inputs(const PackArgs& a, hipStream_t stream) {
-  bool plain = a.n_markers == 12 && !(a.suppress_missing && a.marker_masks) && a.ldx % 4 == 0 &&
-               (((uintptr_t)a.marker_pos | (uintptr_t)a.marker_oris | (uintptr_t)a.x) & 15) == 0;
-  for (int i = 0; i < 12; ++i) plain = plain && a.marker_idx[i] == i;
-  if (plain) {
-    const long n37 = (long)a.B * a.F * 37;
-    hipLaunchKernelGGL(pack_inputs_all_kernel, dim3((unsigned)((n37 + 255) / 256)), dim3(256), 0, stream, a);
-    return hipGetLastError();
-  }
-  const long n = (long)a.B * a.F * (a.n_markers * 12 + 1);
-  hipLaunchKernelGGL(pack_inputs_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
-  return hipGetLastError();
-}
-
-// One thread per (frame, slot): slots 0..21 are joints, 22..31 the ten shape coefficients.  The two wide outputs (rot:
-// 198 floats per frame, feat: 200) are assembled in LDS and written out by the whole block as contiguous 8 / 16-byte
-// pieces; a lane writing its nine floats at a 36-byte stride reached 2.9 TB/s.
-constexpr int UF_FRAMES = 8;   // frames per 256-thread block
-__global__ __launch_bounds__(256) void update_feat_kernel(FeatArgs a) {
-  __shared__ __attribute__((aligned(16))) float s_rot[UF_FRAMES * NB * 9];
-  __shared__ __attribute__((aligned(16))) float s_feat[UF_FRAMES * 200];
-  const int t0 = blockIdx.x * UF_FRAMES;
-  const int fl = threadIdx.x >> 5, slot = threadIdx.x & 31;
-  feat_frame(a, t0 + fl, slot, s_feat + fl * 200, s_rot + fl * NB * 9);   // feat_rows.h
-  __syncthreads();
-  // the block's frames are contiguous in both outputs
-  const int nf = min(UF_FRAMES, a.T - t0);
-  if (a.rot) {   // (the frame-per-lane kernel evaluates the rotations itself)
-    const float2* src = reinterpret_cast<const float2*>(s_rot);
-    float2* dst = reinterpret_cast<float2*>(a.rot + (size_t)t0 * NB * 9);   // 198 floats per frame: 8-byte pieces
-    for (int i = threadIdx.x; i < nf * (NB * 9 / 2); i += 256) dst[i] = src[i];
-  }
-  {
-    const float4* src = reinterpret_cast<const float4*>(s_feat);
-    float4* dst = reinterpret_cast<float4*>(a.feat + (size_t)t0 * 200);
-    for (int i = threadIdx.x; i < nf * 50; i += 256) dst[i] = src[i];
-  }
-}
-
-hipError_t launch_update_feat(const FeatArgs& a, hipStream_t stream) {
-  hipLaunchKernelGGL(update_feat_kernel, dim3((unsigned)((a.T + UF_FRAMES - 1) / UF_FRAMES)), dim3(256), 0, stream, a);
-  return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-__global__ void rodrigues_bwd_kernel(RodBwdArgs a) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  const int t = idx >> 5, slot = idx & 31;
-  if (t >= a.T) return;
-  if (slot < NB) {
-    const float* th = a.theta + (size_t)t * a.ld_theta + slot * 3;
-    Rod q; float R[9];
-    rodrigues(th[0], th[1], th[2], a.rod_conv, q, R);
-    float dR[9];
-    const float* dr = a.d_rot + ((size_t)t * NB + slot) * 9;
-#pragma unroll
-    for (int e = 0; e < 9; ++e) dR[e] = dr[e];
-    if (slot >= 1) {
-      const float* df = a.d_feat + (size_t)t * 200 + (slot - 1) * 9;
-#pragma unroll
-      for (int e = 0; e < 9; ++e) dR[e] += df[e];
-    }
-    // K and K^2
-    const float K[9] = {0.f, -q.dz, q.dy, q.dz, 0.f, -q.dx, -q.dy, q.dx, 0.f};
-    const float KK[9] = {-q.dz * q.dz - q.dy * q.dy, q.dx * q.dy, q.dx * q.dz,
-                         q.dx * q.dy, -q.dz * q.dz - q.dx * q.dx, q.dy * q.dz,
-                         q.dx * q.dz, q.dy * q.dz, -q.dy * q.dy - q.dx * q.dx};
-    float ds = 0.f, dc1 = 0.f;
-#pragma unroll
-    for (int e = 0; e < 9; ++e) { ds += dR[e] * K[e]; dc1 += dR[e] * KK[e]; }
-    const float oc = 1.f - q.c;
-    // dK = s dR + (1-c) (dR K^T + K^T dR)
-    float dK[9];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        float m = 0.f;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) m += dR[r * 3 + k] * K[c * 3 + k] + K[k * 3 + r] * dR[k * 3 + c];
-        dK[r * 3 + c] = q.s * dR[r * 3 + c] + oc * m;
-      }
-    const float ddx = dK[7] - dK[5], ddy = dK[2] - dK[6], ddz = dK[3] - dK[1];
-    float da = ds * q.c + dc1 * q.s;
-    da -= (ddx * q.dx + ddy * q.dy + ddz * q.dz) / q.ang;
-    const float g0 = ddx / q.ang + da * q.ux / q.ang;
-    const float g1 = ddy / q.ang + da * q.uy / q.ang;
-    const float g2 = ddz / q.ang + da * q.uz / q.ang;
-    float* g = a.g_theta + (size_t)t * a.ld_g + slot * 3;
-    g[0] = g0; g[1] = g1; g[2] = g2;
-    if (a.trace_g_theta) { float* o = a.trace_g_theta + (size_t)t * 66 + slot * 3; o[0] = g0; o[1] = g1; o[2] = g2; }
-  } else {
-    const int k = slot - NB;
-    const float v = a.d_feat[(size_t)t * 200 + 189 + k];
-    a.g_beta[(size_t)t * a.ld_gb + k] = v;
-    if (a.trace_g_beta) a.trace_g_beta[(size_t)t * 10 + k] = v;
-  }
-}
-
-hipError_t launch_rodrigues_bwd(const RodBwdArgs& a, hipStream_t stream) {
-  const long n = (long)a.T * 32;
-  hipLaunchKernelGGL(rodrigues_bwd_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
-  return hipGetLastError();
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // chain + skinning + sensors (+ reverse)
@@ -733,241 +552,6 @@ static hipError_t launch_chain_cfg(const ChainArgs& a, hipStream_t stream) {
 hipError_t launch_chain_sensors(const ChainArgs& a, hipStream_t stream) {
   if (a.T >= 4096 && chain_lds_bytes(a.tab, 4) <= 64 * 1024) return launch_chain_cfg<4, 256>(a, stream);
   return launch_chain_cfg<2, 192>(a, stream);
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Full mesh (final vertices): chain to relative transforms, then dense skinning of all V vertices.
-// ---------------------------------------------------------------------------------------------------------------
-__global__ void mesh_chain_kernel(MeshChainArgs a) {
-  // one thread per (frame, joint): walks from the root down to its joint with the running transform (3 x 3 | t) in
-  // registers.  (Round 6: a thread per (frame, joint, ROW) before -- three times the threads, each repeating the walk and
-  // the ancestor look-ups for one row: 119 us per 16384 frames, a tenth of the full-mesh evaluation.)  Joints >= NB (the 30
-  // hand joints of SMPL-H) have zero pose on this path (reference smpl.py:99), i.e. identity rotation under either
-  // Rodrigues convention: they only translate along their parent's frame and get no skinning transform of their own
-  // (weights folded into the wrists).
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  const int nj = a.n_joints;
-  // (the parent table in LDS: the walks below are chains of dependent look-ups, ~80 per thread)
-  __shared__ int parents_s[MESH_MAX_JOINTS];
-  for (int i = threadIdx.x; i < nj; i += blockDim.x) parents_s[i] = a.parents[i];
-  __syncthreads();
-  if (idx >= a.T * nj) return;
-  const int t = idx / nj, j = idx % nj;
-  const float* R = a.rot + (size_t)t * NB * 9;
-  const float* J = a.out + (size_t)t * a.ncp + a.j_off;
-  // the joints from the root down to j, without a per-thread array of the path (a dynamically indexed array lives in
-  // scratch memory): the ancestor k levels above j is found by walking up k times -- chains are at most a dozen joints long
-  int n = 0;
-  for (int q = j; q >= 0; q = parents_s[q]) ++n;
-  float G[3][3], tr[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    G[r][0] = R[r * 3 + 0]; G[r][1] = R[r * 3 + 1]; G[r][2] = R[r * 3 + 2];
-    tr[r] = J[r];
-  }
-  int prev = 0;
-  for (int k = n - 2; k >= 0; --k) {
-    int q = j;
-    for (int up = 0; up < k; ++up) q = parents_s[q];
-    const float* Jq = J + q * 3;
-    const float* Jp = J + prev * 3;
-    const float dx = Jq[0] - Jp[0], dy = Jq[1] - Jp[1], dz = Jq[2] - Jp[2];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) tr[r] = G[r][0] * dx + G[r][1] * dy + G[r][2] * dz + tr[r];
-    if (q < NB) {
-      const float* Rq = R + q * 9;
-      float Rv[9];
-#pragma unroll
-      for (int e = 0; e < 9; ++e) Rv[e] = Rq[e];
-#pragma unroll
-      for (int r = 0; r < 3; ++r) {
-        const float n0 = G[r][0] * Rv[0] + G[r][1] * Rv[3] + G[r][2] * Rv[6];
-        const float n1 = G[r][0] * Rv[1] + G[r][1] * Rv[4] + G[r][2] * Rv[7];
-        const float n2 = G[r][0] * Rv[2] + G[r][1] * Rv[5] + G[r][2] * Rv[8];
-        G[r][0] = n0; G[r][1] = n1; G[r][2] = n2;
-      }
-    }
-    prev = q;
-  }
-  if (j < NB) {
-    const float* Jj = J + j * 3;
-    // relative transform, row r: (G^R[r][0..2], A^t[r]) -- one 16-byte read per (bone, row) in the skinning epilogue
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-      *reinterpret_cast<float4*>(a.xf + (((size_t)t * NB + j) * 3 + r) * 4) =
-          make_float4(G[r][0], G[r][1], G[r][2], tr[r] - (G[r][0] * Jj[0] + G[r][1] * Jj[1] + G[r][2] * Jj[2]));
-  }
-#pragma unroll
-  for (int r = 0; r < 3; ++r)
-    a.joints[(size_t)t * nj * 3 + j * 3 + r] = tr[r] + (a.trans ? a.trans[(size_t)t * 3 + r] : 0.f);
-}
-
-hipError_t launch_mesh_chain(const MeshChainArgs& a, hipStream_t stream) {
-  const long n = (long)a.T * a.n_joints;
-  hipLaunchKernelGGL(mesh_chain_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
-  return hipGetLastError();
-}
-
-// Reverse of mesh_chain_kernel (+ the skinning transforms): one thread per frame.  Forward, per joint j with parent p:
-// G_j = G_p R_j (R_j = I for the hand joints), t_j = G_p (J_j - J_p) + t_p, joints_j = t_j + trans, and per body bone
-// A_b = [G_b | t_b - G_b J_b].  The joints are visited from the last to the root, so that dt_j and dG_j are complete when
-// j is reached (children have larger ids):
-//   dR_j = G_p^T dG_j,   dG_p += dG_j R_j^T + dt_j (J_j - J_p)^T,   dt_p += dt_j,
-//   dJ_j = G_p^T dt_j - G_j^T (dt_j - dJoint_j)   (the children's share -G_j^T sum_c dt_c and dA's -G_j^T dA^t_j in one)
-// with dG_j = dA_j^R - dA_j^t J_j^T and dt_j = dJoint_j + dA_j^t to begin with.  A hand joint's G is its body
-// ancestor's, so its dG goes straight there.  Per-frame state in LDS as [item][frame]: 22 G, 22 dG, 52 dt.
-constexpr int MCB_FR = 16;   // frames per block: 35 KB of LDS
-__global__ __launch_bounds__(MCB_FR) void mesh_chain_bwd_kernel(MeshChainBwdArgs a) {
-  __shared__ float G_s[NB * 9][MCB_FR];
-  __shared__ float dG_s[NB * 9][MCB_FR];
-  __shared__ float dt_s[MESH_MAX_JOINTS * 3][MCB_FR];
-  __shared__ int parents_s[MESH_MAX_JOINTS], body_s[MESH_MAX_JOINTS];
-  const int nj = a.n_joints;
-  if (threadIdx.x == 0)
-    for (int j = 0; j < nj; ++j) {
-      parents_s[j] = a.parents[j];
-      body_s[j] = j < NB ? j : body_s[a.parents[j]];   // nearest body ancestor (parents come first)
-    }
-  __syncthreads();
-  const int t = blockIdx.x * MCB_FR + threadIdx.x;
-  if (t >= a.T) return;
-  const int f = threadIdx.x;
-  const float* R = a.rot + (size_t)t * NB * 9;
-  const float* J = a.jrest + (size_t)t * a.ld_j;
-  // global rotations of the body joints
-  for (int j = 0; j < NB; ++j) {
-    const float* Rj = R + j * 9;
-    if (j == 0) {
-      for (int e = 0; e < 9; ++e) G_s[e][f] = Rj[e];
-      continue;
-    }
-    const int p = parents_s[j];
-    float Gp[9];
-    for (int e = 0; e < 9; ++e) Gp[e] = G_s[p * 9 + e][f];
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c)
-        G_s[j * 9 + r * 3 + c][f] = Gp[r * 3] * Rj[c] + Gp[r * 3 + 1] * Rj[3 + c] + Gp[r * 3 + 2] * Rj[6 + c];
-  }
-  const float* dA = a.dA ? a.dA + (size_t)t * MESH_VJP_DA : nullptr;
-  const float* dJ = a.dJ ? a.dJ + (size_t)t * nj * 3 : nullptr;
-  for (int j = 0; j < nj; ++j)
-    for (int r = 0; r < 3; ++r)
-      dt_s[j * 3 + r][f] = (dJ ? dJ[j * 3 + r] : 0.f) + (dA && j < NB ? dA[j * 12 + r * 4 + 3] : 0.f);
-  for (int j = 0; j < NB; ++j)
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c)
-        dG_s[j * 9 + r * 3 + c][f] = dA ? dA[j * 12 + r * 4 + c] - dA[j * 12 + r * 4 + 3] * J[j * 3 + c] : 0.f;
-  float* dR = a.d_rot + (size_t)t * NB * 9;
-  float* dJr = a.d_jrest + (size_t)t * a.ld_dj;
-  for (int j = nj - 1; j >= 0; --j) {
-    const int bj = body_s[j];
-    float Gj[9], dt[3], dtx[3];
-    for (int e = 0; e < 9; ++e) Gj[e] = G_s[bj * 9 + e][f];
-    for (int r = 0; r < 3; ++r) {
-      dt[r] = dt_s[j * 3 + r][f];
-      dtx[r] = dt[r] - (dJ ? dJ[j * 3 + r] : 0.f);   // sum_c dt_c + dA^t_j
-    }
-    if (j == 0) {
-      for (int c = 0; c < 3; ++c) {
-        dJr[c] = dt[c] - (Gj[c] * dtx[0] + Gj[3 + c] * dtx[1] + Gj[6 + c] * dtx[2]);
-        for (int r = 0; r < 3; ++r) dR[r * 3 + c] = dG_s[r * 3 + c][f];
-      }
-      break;
-    }
-    const int p = parents_s[j], bp = body_s[p];
-    float Gp[9];
-    for (int e = 0; e < 9; ++e) Gp[e] = G_s[bp * 9 + e][f];
-    for (int c = 0; c < 3; ++c)
-      dJr[j * 3 + c] = (Gp[c] * dt[0] + Gp[3 + c] * dt[1] + Gp[6 + c] * dt[2]) -
-                       (Gj[c] * dtx[0] + Gj[3 + c] * dtx[1] + Gj[6 + c] * dtx[2]);
-    for (int r = 0; r < 3; ++r) dt_s[p * 3 + r][f] += dt[r];
-    const float rel[3] = {J[j * 3] - J[p * 3], J[j * 3 + 1] - J[p * 3 + 1], J[j * 3 + 2] - J[p * 3 + 2]};
-    float dGp[9];
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 3; ++c) dGp[r * 3 + c] = dt[r] * rel[c];
-    if (j < NB) {
-      const float* Rj = R + j * 9;
-      float dGj[9];
-      for (int e = 0; e < 9; ++e) dGj[e] = dG_s[j * 9 + e][f];
-      for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 3; ++c) {
-          dR[j * 9 + r * 3 + c] = Gp[r] * dGj[c] + Gp[3 + r] * dGj[3 + c] + Gp[6 + r] * dGj[6 + c];   // G_p^T dG_j
-          dGp[r * 3 + c] += dGj[r * 3] * Rj[c * 3] + dGj[r * 3 + 1] * Rj[c * 3 + 1] + dGj[r * 3 + 2] * Rj[c * 3 + 2];
-        }
-    }
-    for (int e = 0; e < 9; ++e) dG_s[bp * 9 + e][f] += dGp[e];
-  }
-  for (int c = nj * 3; c < a.ld_dj; ++c) dJr[c] = 0.f;
-  if (a.g_trans)   // sum_v dV_v (the feat sweep's slices, double) + sum_j dJoint_j, rounded once
-    for (int r = 0; r < 3; ++r) {
-      double s = 0.0;
-      for (int k = 0; a.dtrans && k < a.n_slices; ++k) s += a.dtrans[((size_t)k * a.T + t) * 3 + r];
-      for (int j = 0; dJ && j < nj; ++j) s += dJ[j * 3 + r];
-      a.g_trans[(size_t)t * 3 + r] = (float)s;
-    }
-}
-
-hipError_t launch_mesh_chain_bwd(const MeshChainBwdArgs& a, hipStream_t stream) {
-  hipLaunchKernelGGL(mesh_chain_bwd_kernel, dim3((unsigned)((a.T + MCB_FR - 1) / MCB_FR)), dim3(MCB_FR), 0, stream, a);
-  return hipGetLastError();
-}
-
-// The dense skinning of all V vertices is mesh.hip's mesh_rows_kernel.
-
-// ---------------------------------------------------------------------------------------------------------------
-// Virtual sensors from arbitrary full-mesh vertices (reference virtual_sensors.py:16-38,77-96; utils.py:126-146):
-// one lane per (frame, sensor).
-// ---------------------------------------------------------------------------------------------------------------
-__global__ void virtual_sensors_kernel(VirtualSensorArgs a) {
-  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= a.T * a.M) return;
-  const int t = idx / a.M, m = idx % a.M;
-  const float* V = a.vertices + (size_t)t * a.V * 3;
-  const int deg = a.deg[m];
-  const int* faces = a.faces + (size_t)m * a.max_deg * 3;
-  float n[3] = {0.f, 0.f, 0.f};
-  for (int k = 0; k < deg; ++k) {
-    const float* v0 = V + (size_t)faces[k * 3 + 0] * 3;
-    const float* v1 = V + (size_t)faces[k * 3 + 1] * 3;
-    const float* v2 = V + (size_t)faces[k * 3 + 2] * 3;
-    const float e1[3] = {v1[0] - v0[0], v1[1] - v0[1], v1[2] - v0[2]};
-    const float e2[3] = {v2[0] - v0[0], v2[1] - v0[1], v2[2] - v0[2]};
-    float fn[3];
-    cross3(e1, e2, fn);
-    n[0] += fn[0]; n[1] += fn[1]; n[2] += fn[2];
-  }
-  const float fdeg = (float)deg;
-  n[0] /= fdeg; n[1] /= fdeg; n[2] /= fdeg;
-  const float nn = norm3(n);
-  const float nh[3] = {n[0] / nn, n[1] / nn, n[2] / nn};
-  const float* vc = V + (size_t)a.center[m] * 3;
-  const float* vh = V + (size_t)a.helper[m] * 3;
-  const float e[3] = {vh[0] - vc[0], vh[1] - vc[1], vh[2] - vc[2]};
-  const float ne = norm3(e);
-  const float sv[3] = {e[0] / ne, e[1] / ne, e[2] / ne};
-  float bb[3];
-  cross3(nh, sv, bb);
-  const float nb = norm3(bb);
-  const float tv[3] = {bb[0] / nb, bb[1] / nb, bb[2] / nb};
-  float aa[3];
-  cross3(tv, nh, aa);
-  const float na = norm3(aa);
-  float* po = a.pos + (size_t)idx * 3;
-  float* oo = a.ori + (size_t)idx * 9;
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-    po[r] = vc[r];
-    oo[r * 3 + 0] = aa[r] / na;
-    oo[r * 3 + 1] = tv[r];
-    oo[r * 3 + 2] = nh[r];
-    if (a.normals) a.normals[(size_t)idx * 3 + r] = n[r];
-  }
-}
-
-hipError_t launch_virtual_sensors(const VirtualSensorArgs& a, hipStream_t stream) {
-  const long n = (long)a.T * a.M;
-  hipLaunchKernelGGL(virtual_sensors_kernel, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, stream, a);
-  return hipGetLastError();
 }
 
 }  // namespace empose

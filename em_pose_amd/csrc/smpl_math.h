@@ -1,4 +1,4 @@
-// Small device helpers shared by the SMPL sub-mesh kernels (smpl.hip, smpl_tile.hip). Internal, gfx950 only.
+// Small device helpers shared by the SMPL sub-mesh kernels (smpl_rows.hip, smpl_chain.hip, smpl_tile.hip). Internal, gfx950 only.
 #pragma once
 #include <hip/hip_runtime.h>
 

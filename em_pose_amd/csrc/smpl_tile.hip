@@ -1,6 +1,6 @@
 // SMPL-H on the sensor sub-mesh, one FRAME PER LANE (round 3; replaces chain_sensors_kernel for large launches).
 //
-// chain_sensors_kernel (smpl.hip) maps (frame, item) pairs to lanes: every lane decodes index tables, splits its flat
+// chain_sensors_kernel (smpl_chain.hip) maps (frame, item) pairs to lanes: every lane decodes index tables, splits its flat
 // index into (frame, item) and re-reads bone transforms from LDS for a third of a mat-vec -- 3290 VALU wave-instructions
 // per frame for ~15 k useful multiply-adds (profiles/r02_chain_counters.txt: 14x instruction overhead, issue-bound).
 // Here a wave owns 64 FRAMES (lane = frame) and walks the items itself:

@@ -3,7 +3,7 @@ Exponential / logarithm map of SO(3) under the names and with the clamping seman
 (`so3_exponential_map`, so3.py:87-131: the SQUARED angle is clamped at `eps`, so vectors shorter than sqrt(eps) = 0.01 rad
 do not give the exact small-angle rotation; `so3_log_map`, so3.py:134-170: sin(angle) is clamped away from zero).
 Host-side helpers (any torch device); the HIP kernels carry their own copies of these formulas where they need them
-(`csrc/metrics.hip` for the clamped map, `csrc/smpl.hip` for the body model's Rodrigues formula).
+(`csrc/metrics.hip` for the clamped map, `csrc/smpl_math.h` for the body model's Rodrigues formula).
 """
 import torch
 

@@ -1,6 +1,6 @@
 """
 Loss terms of the reference's `empose/nn/loss.py` (reporting and the autograd training path; the in-loop reconstruction
-residual and the hand-written training step's loss terms live in the HIP kernels: csrc/smpl*.hip, csrc/train.hip
+residual and the hand-written training step's loss terms live in the HIP kernels: csrc/smpl*.hip, csrc/train_loss.hip
 `lgd_losses_kernel`).
 """
 import torch

@@ -770,7 +770,7 @@ int empose_mesh_joints_fwd(const empose_mesh_t* mesh, int T, const float* poses,
  * g_poses [T][66] and g_betas [T][10], and g_trans [T][3] unless NULL (the gradient with respect to trans, which the
  * forward adds to every vertex and joint).  It recomputes the forward's rotations, features, rest joints and transforms
  * from poses and betas; nothing is saved from the forward.  The gradient is that of the exact function, fp32 throughout
- * (csrc/mesh_vjp.hip: the two vertex sweeps on the fp32 MFMA instruction; smpl.hip: the reverse kinematic chain), whatever
+ * (csrc/mesh_vjp.hip: the two vertex sweeps on the fp32 MFMA instruction; mesh_chain.hip: the reverse kinematic chain), whatever
  * arithmetic the forward of the handle uses.  Deterministic: repeated calls give the same bits.
  * Workspace: empose_mesh_vjp_workspace_bytes(mesh, T) -- about 8.2 KB per frame of a slab of min(T, 16384) frames for
  * SMPL-H (the forward's scratch, the sweeps' outputs and the reverse's cotangents); below 8192 frames the vertex sweeps

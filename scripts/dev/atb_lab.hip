@@ -1,4 +1,4 @@
-// Dev lab: where the time of the weight-gradient GEMM C = A^T B (em_pose_amd/csrc/train.hip, gemm_atb_lds_kernel) goes.
+// Dev lab: where the time of the weight-gradient GEMM C = A^T B (em_pose_amd/csrc/gemm_atb.hip, gemm_atb_lds_kernel) goes.
 // A stripped copy of its main loop (no bounds, no segments, no bias) with parts switched off at compile time:
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 scripts/dev/atb_lab.hip -o scripts/dev/bin/atb_lab && scripts/dev/bin/atb_lab
 #include <hip/hip_runtime.h>

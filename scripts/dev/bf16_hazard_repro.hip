@@ -9,13 +9,13 @@
 // MB_NW = waves per workgroup: 8 = two per SIMD (the failing configuration), 4 = one per SIMD (what the tree ships).
 // Variants: -DREPRO_FP32_MFMA is not available here (the fp32 kernel is another function: mesh_rows_kernel, 8 waves,
 // clean); -DMB_RING=n changes the prefetch depth of the coefficient ring (did not matter).
-#include "../../em_pose_amd/csrc/mesh.hip"
+#include "../../em_pose_amd/csrc/mesh_bf16.hip"
+#include "lab_stubs.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 using namespace empose;
-namespace empose { Options& options() { static Options o; return o; } }
 
 __global__ void fill_kernel(float* p, size_t n, unsigned seed, float scale) {
   size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;

@@ -1,5 +1,5 @@
 // EXPERIMENT, not built into the library (round 2): the software-pipelined form of mesh_rows_bf16_kernel.
-// Result (MI355X, T = 16384, scripts/dev/mesh_bf16_lab.hip -DLAB_PIPE with this text pasted into mesh.hip):
+// Result (MI355X, T = 16384, scripts/dev/mesh_bf16_lab.hip -DLAB_PIPE with this text pasted into mesh_bf16.hip):
 // bit-identical output, 828 us per launch against 795 us for the plain kernel (K loop, then skinning).  Per-tile stamps:
 // K loop alone 8.2 k cycles (252 MFMAs x 32 = 8.1 k: ideal), skinning alone 11.7 k, interleaved 23-28 k -- a wave's bf16
 // MFMAs and its vector FMAs do NOT run concurrently on this chip (nor do those of two waves of one SIMD: see the header of

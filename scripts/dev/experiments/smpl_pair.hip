@@ -1,6 +1,6 @@
 // chain_pair_kernel: the per-frame part of one SMPL-H evaluation on the sensor sub-mesh -- kinematic chain, skinning,
 // vertex normals and sensor frames, sensor offsets, reconstruction residual and the hand-derived reverse pass (the same
-// mathematics as chain_sensors_kernel in smpl.hip; reference models.py:471-483,560-579, virtual_sensors.py:16-38,
+// mathematics as chain_sensors_kernel in smpl_chain.hip; reference models.py:471-483,560-579, virtual_sensors.py:16-38,
 // utils.py:126-146, loss.py:23-41; blueprint oracle/analytic_np.py) -- restructured around what the counters said
 // about that kernel (profiles/r02_chain_counters.txt): it was bound by VALU ISSUE, 3290 wave-instructions per frame
 // at 72 % of the issue slots, most of them index arithmetic, table decoding and 4-byte LDS traffic around ~15 k useful

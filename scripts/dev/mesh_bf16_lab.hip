@@ -1,14 +1,14 @@
 // Dev lab: the split-bf16 full-mesh row-block kernel on the bench shape (T frames, V = 6890), timing + per-wave phase stamps.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iem_pose_amd/csrc -Iinclude scripts/dev/mesh_bf16_lab.hip -o /tmp/mesh_bf16_lab && /tmp/mesh_bf16_lab
 #define EMPOSE_MESH_TRACE 1
-#include "../../em_pose_amd/csrc/mesh.hip"
+#include "../../em_pose_amd/csrc/mesh_bf16.hip"
 
 #include <algorithm>
 #include <cstdio>
 #include <vector>
 using namespace empose;
 #include "lab_stubs.h"
-#ifdef LAB_PIPE   // scripts/dev/experiments/mesh_bf16_pipe.hip pasted into mesh.hip
+#ifdef LAB_PIPE   // scripts/dev/experiments/mesh_bf16_pipe.hip pasted into mesh_bf16.hip
 #define LAB_KERNEL mesh_rows_bf16_pipe_kernel
 #else
 #define LAB_KERNEL mesh_rows_bf16_kernel<false>

@@ -1,5 +1,5 @@
 """
-Every output element of the fp32 GEMM family (csrc/gemm_f32.hip, csrc/train.hip: v_mfma_f32_32x32x2_f32) against float64,
+Every output element of the fp32 GEMM family (csrc/gemm_f32.hip, csrc/gemm_atb.hip: v_mfma_f32_32x32x2_f32) against float64,
 each within its own allowance gamma u m (tests/elementwise.py::gemm_reference), on every path `launch_gemm` can take:
 
     a. every kernel of `pick_gemm` through empose_linear_f32_ex -- the 64x64 / 64x128 / 128x64 tiles, the 8-wave 256x128

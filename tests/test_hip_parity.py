@@ -617,7 +617,7 @@ def test_full_mesh_split_bf16_variant(big_model):
         assert torch.equal(j, j32)
     v0, _ = fast(poses_body=torch.zeros(2, 63, device=DEV), betas=torch.zeros(10, device=DEV))
     np.testing.assert_allclose(v0[0].cpu().numpy(), big_model['v_template'], atol=1e-6)   # three pieces: fp32-exact
-    # repeated launches are bit-identical (a two-waves-per-SIMD build of this kernel was not: mesh.hip), both kernels
+    # repeated launches are bit-identical (a two-waves-per-SIMD build of this kernel was not: mesh_bf16.hip), both kernels
     n = 4096
     g = torch.Generator().manual_seed(5)
     kw = dict(poses_body=(torch.randn(n, 63, generator=g) * 0.5).to(DEV), betas=torch.randn(n, 10, generator=g).to(DEV),

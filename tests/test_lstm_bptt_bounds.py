@@ -68,7 +68,7 @@ def forward_planes(inp, dtype=torch.float64):
 
 def over_rows(a, b, block=64):
     """A^T B (column sums of A without B), the rows in blocks of 64 whose partial results are added in order: the
-    reductions over the B F rows are split over rows in the kernels too (csrc/train.hip, atb_splits: a workgroup gets at
+    reductions over the B F rows are split over rows in the kernels too (csrc/gemm_atb.hip, atb_splits: a workgroup gets at
     least 64 rows), and 64 is the shortest range they hand out.  One product over all rows would leave the order, and with
     it the error of the longest chains, to the host BLAS and its thread count: the worst dW element of the 65 x 3 cases
     then moves between 0.44 and 0.51 of its allowance with 1, 8 or 16 threads."""

@@ -1,6 +1,6 @@
 """
 SMPLLayer under autograd: the full-mesh vector-Jacobian product (empose_mesh_vjp, csrc/mesh_vjp.hip and the reverse
-kinematic chain in csrc/smpl.hip) against float64 autograd through the oracle (oracle/torch_ref.py smpl_fk).
+kinematic chain in csrc/mesh_chain.hip) against float64 autograd through the oracle (oracle/torch_ref.py smpl_fk).
 
 The bar, per frame row of g_poses, g_betas and g_trans separately: the largest error of the row is at most 1e-4 x the
 row's largest |g64|, and at most 4 x the error of float32 CPU autograd through the same oracle (the control) plus

@@ -1,5 +1,5 @@
 """
-The loss and bookkeeping kernels of the training step (csrc/train.hip) against their float64 restatements
+The loss and bookkeeping kernels of the training step (csrc/train_glue.hip, csrc/train_loss.hip) against their float64 restatements
 (tests/train_glue_ref.py), at every output element and within allowances derived from the kernels' rounding chains:
 empose_lgd_losses (both kernels), empose_lgd_cotangent_step, empose_lgd_additive_update, empose_window_mean,
 empose_axpby2d, empose_lgd_assemble_inputs, and one training step of the engine whose logged losses are recomputed from

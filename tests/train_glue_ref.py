@@ -1,4 +1,4 @@
-"""Float64 restatements of the loss and bookkeeping kernels of the training step (csrc/train.hip: lgd_losses,
+"""Float64 restatements of the loss and bookkeeping kernels of the training step (csrc/train_loss.hip, csrc/train_glue.hip: lgd_losses,
 lgd_cotangent_step, lgd_additive_update, lgd_assemble_inputs, window_mean, axpby2d), the per-element allowances they are
 held to, input generators and thin callers of the C entry points.  Shared by tests/test_train_glue.py (GPU) and
 tests/test_train_glue_bounds.py (CPU).  Not a test module; imports without a GPU.
