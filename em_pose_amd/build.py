@@ -6,10 +6,13 @@ import glob
 import os
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'csrc')
 LIB = os.path.join(CSRC, 'libempose_hip.so')
 ARCH = 'gfx950'
+# What every .hip source is compiled with (scripts/dev/asm_diff.py compiles with the same list).
+FLAGS = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-Wno-unused-result']
 
 
 def _hipcc():
@@ -23,6 +26,14 @@ def sources():
     return sorted(glob.glob(os.path.join(CSRC, '*.hip')))
 
 
+def jobs():
+    """Compilers at a time: MAX_JOBS where it is set, else 16."""
+    try:
+        return max(1, int(os.environ['MAX_JOBS']))
+    except (KeyError, ValueError):
+        return 16
+
+
 def needs_build():
     if not os.path.exists(LIB):
         return True
@@ -32,24 +43,22 @@ def needs_build():
 
 
 def build(force=False, verbose=True):
-    """Compile every .hip source to an object (parallel), then link the shared library."""
+    """Compile every .hip source to an object (at most jobs() compilers at a time), then link the shared library."""
     if not force and not needs_build():
         return LIB
     hipcc = _hipcc()
-    flags = ['--offload-arch=' + ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics',
-             '-Wno-unused-result']
-    objs, procs = [], []
-    for src in sources():
-        obj = src[:-4] + '.o'
-        objs.append(obj)
-        procs.append((src, subprocess.Popen([hipcc] + flags + ['-c', src, '-o', obj],
-                                            stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))
-    for src, p in procs:
-        out, _ = p.communicate()
+    srcs = sources()
+    objs = [src[:-4] + '.o' for src in srcs]
+
+    def compile_one(src, obj):
+        return subprocess.run([hipcc] + FLAGS + ['-c', src, '-o', obj], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
+    with ThreadPoolExecutor(max_workers=jobs()) as pool:
+        done = list(pool.map(compile_one, srcs, objs))
+    for src, p in zip(srcs, done):
         if p.returncode != 0:
-            raise RuntimeError('hipcc failed on {}:\n{}'.format(src, out.decode()))
-        if verbose and out.strip():
-            print(out.decode())
+            raise RuntimeError('hipcc failed on {}:\n{}'.format(src, p.stdout.decode()))
+        if verbose and p.stdout.strip():
+            print(p.stdout.decode())
     cmd = [hipcc, '--offload-arch=' + ARCH, '-shared', '-fPIC', '-o', LIB] + objs
     out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
     if out.returncode != 0:

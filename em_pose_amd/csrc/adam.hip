@@ -1,5 +1,5 @@
 // The optimiser step of the training engine: Adam over a list of tensors in one launch.
-#include "kernels.h"
+#include "train_kernels.h"
 
 namespace empose {
 

@@ -2,6 +2,10 @@
 // dynamic LDS and co-residency, version.  The entry points of the subsystems live in api_model.hip, api_lstm.hip,
 // api_train.hip and api_mesh.hip.
 #include "api_internal.h"
+#include "gemm_kernels.h"
+#include "launch.h"
+#include "options.h"
+#include "train_kernels.h"
 
 #include <cstdarg>
 #include <cstdio>
@@ -28,7 +32,7 @@ struct Profiler {
 };
 Profiler g_prof;
 
-// The name of every option and where it lives in Options (EMPOSE_OPTIONS, kernels.h); nullptr for an unknown name.
+// The name of every option and where it lives in Options (EMPOSE_OPTIONS, options.h); nullptr for an unknown name.
 int* option_slot(const char* name) {
   static const struct { const char* name; int Options::*field; } table[] = {
 #define EMPOSE_OPTION_ENTRY(name, default_value) {#name, &Options::name},

@@ -2,6 +2,7 @@
 // evaluation of empose_smpl_sensors_fwd_bwd (smpl_sensors_eval, api_internal.h) and one launch of sensor_fit.hip, K times.
 // No host synchronisation, no allocation and no copy inside: the whole call is launches on the caller's stream.
 #include "api_internal.h"
+#include "fit_kernels.h"
 
 #include <cmath>
 

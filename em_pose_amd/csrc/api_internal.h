@@ -2,7 +2,9 @@
 // state, the profiler, workspace carving and upload, the packed model, and the LSTM dispatcher.  Host code only.
 #pragma once
 #include "../../include/empose_hip.h"
-#include "kernels.h"
+#include "gemm_kernels.h"
+#include "mlp_kernels.h"
+#include "smpl_kernels.h"
 
 #include <cstring>
 #include <vector>
@@ -136,7 +138,7 @@ int upload_bf16(std::vector<void*>& allocs, const std::vector<unsigned short>& b
 struct Dense {
   int in_dim = 0, out_dim = 0;
   float* w = nullptr;      // [out][in]
-  float* frag[FUSED_FORMS] = {};   // the same weights in the fragment order of each FusedForm (kernels.h), only for MLP layers
+  float* frag[FUSED_FORMS] = {};   // the same weights in the fragment order of each FusedForm (mlp_kernels.h), only for MLP layers
   float* wexp = nullptr;   // [out] the inverse of the power-of-two scale each output column's pair16 pieces carry
   float* scale = nullptr;  // nullptr => 1
   float* shift = nullptr;  // bias (and folded BN)

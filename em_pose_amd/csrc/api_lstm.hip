@@ -4,7 +4,11 @@
 // lays out; back-propagation through time (Bptt) is two recurrences over one cell builder and one batched tail.
 #include "api_internal.h"
 #include "f16pair.h"
+#include "gemm_kernels.h"
+#include "lstm_kernels.h"
 #include "lstm_wave.h"
+#include "options.h"
+#include "train_kernels.h"
 
 #include <algorithm>
 

@@ -1,6 +1,11 @@
 // C ABI (include/empose_hip.h), full mesh: packing and evaluation of the posed vertices and joints, the metrics rows,
 // the virtual sensors and the root normalisation.
 #include "api_internal.h"
+#include "data_kernels.h"
+#include "gemm_kernels.h"
+#include "mesh_kernels.h"
+#include "options.h"
+#include "smpl_kernels.h"
 
 #include <algorithm>
 

@@ -2,6 +2,10 @@
 // workspaces and the launch sequence of the LGD loop; the stand-alone SMPL and update-net entry points.
 #include "api_internal.h"
 #include "f16pair.h"
+#include "gemm_kernels.h"
+#include "mlp_kernels.h"
+#include "options.h"
+#include "smpl_kernels.h"
 
 #include <cmath>
 
@@ -288,7 +292,7 @@ struct MlpRun {
 
 // Large batches: every layer of both nets in ONE launch (mlp_fused.hip); a workgroup keeps 128 rows through all the
 // layers. Needs enough row panels to fill the chip and layers no wider than the four 128-column waves.
-// form (FusedForm, kernels.h): each piece form rests on the one before it --
+// form (FusedForm, mlp_kernels.h): each piece form rests on the one before it --
 //   x3_32 (option mlp_x3): fp32 products from three bf16 pieces per operand on the bf16 matrix path (mlp_fused_x3.hip;
 //          fp32-equivalent, 2.7 times the fp32 instruction's rate): needs every hidden width to be whole quads of k-steps
 //          of the next layer;

@@ -1,6 +1,7 @@
 // C ABI (include/empose_hip.h), sensor-noise augmentation: the checks of the arguments and of the host copy of the plan,
 // then the one launch of sensor_noise.hip.
 #include "api_internal.h"
+#include "data_kernels.h"
 
 using namespace empose;
 using namespace empose::api;

@@ -1,6 +1,7 @@
 // C ABI (include/empose_hip.h), per-subject sensor offsets from calibration recordings: the checks of the arguments and of
 // the host copy of the group table, then the two launches of offset_stats.hip.
 #include "api_internal.h"
+#include "data_kernels.h"
 
 #include <climits>
 #include <cstddef>

@@ -1,6 +1,7 @@
 // C ABI (include/empose_hip.h), resampling of ragged sequence batches to another frame rate: the checks of the host
 // copy of the sequence table, then the launches of resample.hip.
 #include "api_internal.h"
+#include "data_kernels.h"
 
 #include <cmath>
 #include <cstddef>

@@ -2,6 +2,8 @@
 // forward (sensor_sample.hip), or for the reverse the fold of the cotangents and the two passes of sensors_vjp.hip, slab
 // by slab.
 #include "api_internal.h"
+#include "data_kernels.h"
+#include "mesh_kernels.h"
 
 #include <climits>
 

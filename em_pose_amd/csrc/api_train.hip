@@ -1,6 +1,10 @@
 // C ABI (include/empose_hip.h), training building blocks: plain products, BatchNorm + PReLU, A^T B, transpose,
 // input packing, the LGD update / cotangent / loss kernels, Adam; one MLP (or both update networks) in training mode.
 #include "api_internal.h"
+#include "gemm_kernels.h"
+#include "options.h"
+#include "smpl_kernels.h"
+#include "train_kernels.h"
 
 #include <cmath>
 

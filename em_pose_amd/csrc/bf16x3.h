@@ -5,7 +5,6 @@
 // what is dropped (x_m w_l, x_l w_m, x_l w_l) is below 2^-23 of the product.  Internal, gfx950 only.
 #pragma once
 #include "device_common.h"
-#include "kernels.h"
 
 namespace empose {
 

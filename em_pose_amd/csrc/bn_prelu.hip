@@ -11,7 +11,7 @@
 //   backward: dy = y > 0 ? dz : a * dz;  da += sum_{y <= 0} dz * y;  dbeta = sum dy;  dgamma = sum dy * xhat;
 //             dx = gamma * rstd / M * (M * dy - dbeta - xhat * dgamma)
 // The slope gradient is one partial sum per workgroup; the workgroup that finishes last adds them in index order.
-#include "kernels.h"
+#include "train_kernels.h"
 
 namespace empose {
 

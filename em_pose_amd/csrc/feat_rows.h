@@ -3,7 +3,7 @@
 // carry them as prologue / epilogue (mlp_fused.hip: blend_feat_gemm_kernel, blend_t_gemm_rod_kernel).  One definition,
 // so the stand-alone kernels and the fused ones produce the same bits.  Internal, gfx950 only.
 #pragma once
-#include "kernels.h"
+#include "smpl_kernels.h"
 #include "smpl_math.h"
 
 namespace empose {

@@ -11,7 +11,8 @@
 //                to a workspace and are summed in split order by a second kernel (deterministic).
 #include <algorithm>
 
-#include "kernels.h"
+#include "options.h"
+#include "train_kernels.h"
 
 namespace empose {
 
@@ -142,7 +143,7 @@ __global__ __launch_bounds__(atbl::NT) void gemm_atb_lds_kernel(AtbArgs a) {
   // row segments (the applications of one network): a chunk never straddles two (seg_rows is a multiple of 32), and
   // the segment is looked up again only when the walk leaves it
   const float* A0 = a.A; const float* B0 = a.B;
-  // Operand transform of the fused train-mode layer (kernels.h AtbArgs): a thread stages the same four columns of every
+  // Operand transform of the fused train-mode layer (train_kernels.h AtbArgs): a thread stages the same four columns of every
   // row, so its coefficients are registers, re-read only when the walk enters another segment (= application).
   f4 cbs = {1.f, 1.f, 1.f, 1.f}, cbt = {0.f, 0.f, 0.f, 0.f};
   const float b_slope = a.b_mode ? a.b_slope[0] : 0.f;

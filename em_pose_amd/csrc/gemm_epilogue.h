@@ -1,7 +1,7 @@
 // Shared by the fp32 matrix-core GEMM kernels (gemm_f32.hip, gemm_rec.hip, gemm_train_x3.hip, mlp_fused.hip):
 // accumulator vector types, the tile epilogue and its one-element form. Internal, gfx950 only.
 #pragma once
-#include "kernels.h"
+#include "gemm_kernels.h"
 
 namespace empose {
 

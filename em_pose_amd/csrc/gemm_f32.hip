@@ -14,12 +14,15 @@
 // Besides the tile kernels: the split-K tile for small problems (and its strided form), the matrix-vector kernel for a
 // handful of rows, and the dispatch between them (pick_gemm).  The recurrent products of back-propagation through time
 // are in gemm_rec.hip, the three-piece bf16 training product in gemm_train_x3.hip.
-#include "kernels.h"
 #include <cstdint>
 
 #include "device_common.h"
+#include "gemm_kernels.h"
+#include "launch.h"
 #include "lstm_cell_bwd.h"
+#include "options.h"
 #include "train_epilogue.h"
+#include "train_kernels.h"
 
 namespace empose {
 

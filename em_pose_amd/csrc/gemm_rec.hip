@@ -2,16 +2,18 @@
 // carry), formed and fed straight into the cell of the step below (lstm_cell_bwd.h) instead of being stored.  fp32 on the
 // v_mfma_f32_32x32x2_f32 instruction or plain FMAs; every sum in a fixed order, so results are reproducible.
 //
-// Two kernels by row count, both on a RecBatch (kernels.h): up to two problems per launch, each a sum over up to two K
+// Two kernels by row count, both on a RecBatch (gemm_kernels.h): up to two problems per launch, each a sum over up to two K
 // segments with their own operands, each followed by its own cell.  The wavefront form of the reverse pass launches two
 // problems per step; the layer-after-layer form launches the K-split pair with one problem of one segment (and takes
 // gemm_fewrows_kernel of gemm_f32.hip for a handful of rows).
-#include "kernels.h"
 #include <cstdint>
 
 #include "gemm_epilogue.h"
+#include "gemm_kernels.h"
+#include "launch.h"
 #include "lstm_cell_bwd.h"
 #include "lane_reduce.h"
+#include "train_kernels.h"
 
 namespace empose {
 

@@ -6,10 +6,13 @@
 // optimiser step by pack_x3_kernel, fragment order [k-step][32-column tile][piece] -> 1 KB -- from L2 into a register ring;
 // the accumulators then go through the SAME train_epilogue as the fp32 kernels (train_epilogue.h; same C/D layout).  One
 // workgroup per CU (132 KB of LDS), stores only after the K loop (bf16_hazard_repro.md).
-#include "kernels.h"
 
 #include "bf16x3.h"
+#include "gemm_kernels.h"
+#include "launch.h"
+#include "mlp_kernels.h"
 #include "train_epilogue.h"
+#include "train_kernels.h"
 
 namespace empose {
 

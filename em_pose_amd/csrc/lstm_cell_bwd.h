@@ -9,7 +9,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "train_kernels.h"
 
 namespace empose {
 

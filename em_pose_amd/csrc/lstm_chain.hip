@@ -1,4 +1,6 @@
 // fp32 LSTM step of large batches: lstm_chain_kernel and its launcher (lstm_wave.h: the wavefront, units and segments).
+#include "launch.h"
+#include "lstm_kernels.h"
 #include "lstm_wave.h"
 
 namespace empose {

@@ -23,6 +23,8 @@
 
 #include "f16pair.h"
 #include "gemm_epilogue.h"
+#include "launch.h"
+#include "lstm_kernels.h"
 
 namespace empose {
 

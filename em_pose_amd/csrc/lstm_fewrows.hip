@@ -1,5 +1,6 @@
 // fp32 LSTM steps of up to 16 rows: lstm_small_kernel (a wave per hidden unit), lstm_fewrows_kernel (a workgroup per one or
 // two hidden units, all threads split K) and their launchers (lstm_wave.h: the wavefront, units and segments).
+#include "lstm_kernels.h"
 #include "lstm_wave.h"
 
 namespace empose {

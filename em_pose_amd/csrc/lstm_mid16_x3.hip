@@ -21,6 +21,8 @@
 // One workgroup per CU, one wave per SIMD, stores only in the finish (bf16x3.h).
 #include "bf16x3.h"
 #include "gemm_epilogue.h"
+#include "launch.h"
+#include "lstm_kernels.h"
 
 namespace empose {
 

@@ -18,6 +18,8 @@
 // never write the same accumulator.
 #include "bf16x3.h"
 #include "gemm_epilogue.h"
+#include "launch.h"
+#include "lstm_kernels.h"
 
 namespace empose {
 

@@ -26,9 +26,11 @@
 // Same products, in the same order, with the same two alternating accumulators per row tile as lstm_mid_x3_kernel: the
 // outputs have the same bits (tests/test_hip_round6.py).  One workgroup per CU, one wave per SIMD (bf16x3.h); stores are
 // issued in the finish only, when no MFMA of the workgroup is in flight.  The polls are bounded: a counter that never
-// arrives poisons the outputs with NaN and counts itself in the poll-timeout word (kernels.h) instead of hanging the GPU.
+// arrives poisons the outputs with NaN and counts itself in the poll-timeout word (launch.h) instead of hanging the GPU.
 #include "bf16x3.h"
 #include "gemm_epilogue.h"
+#include "launch.h"
+#include "lstm_kernels.h"
 
 namespace empose {
 

@@ -1,5 +1,7 @@
 // fp32 LSTM, small batches, the whole sequence in one cooperative launch: lstm_persist_kernel and its launcher (lstm_wave.h:
 // the wavefront, units and segments).
+#include "launch.h"
+#include "lstm_kernels.h"
 #include "lstm_wave.h"
 
 namespace empose {

@@ -22,6 +22,8 @@
 // The two units of a launch (layer 0: K = input + H, layer 1: K = 2 H) go to different workgroups (blockIdx.z).
 #include "bf16x3.h"
 #include "gemm_epilogue.h"
+#include "launch.h"
+#include "lstm_kernels.h"
 
 namespace empose {
 

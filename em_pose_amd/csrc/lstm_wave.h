@@ -24,8 +24,8 @@
 #include <type_traits>
 
 #include "device_common.h"
-#include "kernels.h"
 #include "lane_reduce.h"
+#include "lstm_kernels.h"
 
 namespace empose {
 

@@ -20,6 +20,8 @@
 // One wave per SIMD (139 KB of LDS per workgroup), like everything in this tree that issues the bf16 32x32x16 MFMA.
 #include "bf16x3.h"
 #include "gemm_epilogue.h"
+#include "launch.h"
+#include "lstm_kernels.h"
 
 namespace empose {
 

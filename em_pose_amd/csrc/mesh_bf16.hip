@@ -5,8 +5,10 @@
 
 #include "bf16x3.h"
 #include "gemm_epilogue.h"
-#include "kernels.h"
+#include "launch.h"
 #include "mesh_grid.h"
+#include "mesh_kernels.h"
+#include "smpl_kernels.h"
 
 namespace empose {
 

@@ -1,6 +1,7 @@
 // Full mesh (final vertices): the kinematic chain to relative bone transforms and joints, and its reverse.  The dense
 // skinning of all V vertices is mesh_rows.hip's mesh_rows_kernel (mesh_x3.hip by default), its reverse mesh_vjp.hip.
-#include "kernels.h"
+#include "mesh_kernels.h"
+#include "smpl_kernels.h"
 
 namespace empose {
 

@@ -18,8 +18,10 @@
 #include <hip/hip_runtime.h>
 
 #include "gemm_epilogue.h"
-#include "kernels.h"
 #include "lane_reduce.h"
+#include "launch.h"
+#include "mesh_kernels.h"
+#include "smpl_kernels.h"
 
 namespace empose {
 

@@ -19,8 +19,10 @@
 #include <type_traits>
 
 #include "gemm_epilogue.h"
-#include "kernels.h"
+#include "launch.h"
 #include "mesh_grid.h"
+#include "mesh_kernels.h"
+#include "smpl_kernels.h"
 
 namespace empose {
 

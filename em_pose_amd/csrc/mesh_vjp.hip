@@ -22,7 +22,9 @@
 #include <hip/hip_runtime.h>
 
 #include "gemm_epilogue.h"
-#include "kernels.h"
+#include "launch.h"
+#include "mesh_kernels.h"
+#include "smpl_kernels.h"
 
 namespace empose {
 

@@ -19,7 +19,9 @@
 
 #include "bf16x3.h"
 #include "gemm_epilogue.h"
-#include "kernels.h"
+#include "launch.h"
+#include "mesh_kernels.h"
+#include "smpl_kernels.h"
 
 namespace empose {
 

@@ -3,7 +3,7 @@
 // alignment of the prediction onto the ground truth (the reference runs a NumPy SVD per frame in a Python loop), and
 // the geodesic angle between predicted and ground-truth GLOBAL joint orientations.
 // One thread per frame, float64 arithmetic (the accumulated rows feed means / standard deviations on the host).
-#include "kernels.h"
+#include "data_kernels.h"
 #include "svd3.h"
 
 namespace empose {

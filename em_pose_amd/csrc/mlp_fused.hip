@@ -19,6 +19,10 @@
 // Skip connections would need the block input kept besides the activations: such nets take the layer-by-layer path.
 #include "bf16x3.h"
 #include "gemm_epilogue.h"
+#include "gemm_kernels.h"
+#include "launch.h"
+#include "mlp_kernels.h"
+#include "smpl_kernels.h"
 #include "stage_block.h"
 #include "feat_rows.h"
 
@@ -542,7 +546,7 @@ hipError_t launch_gemm_rows(const float* A, int lda, const float* Wp, float* C, 
   return launch_gemm_rows_cfg<64, 1, 4, 2>(a, stream);
 }
 
-// The row-block GEMM with tile-layout operands (kernels.h "tile layout"; the frame-per-lane SMPL kernel, smpl_tile.hip,
+// The row-block GEMM with tile-layout operands (smpl_kernels.h "tile layout"; the frame-per-lane SMPL kernel, smpl_tile.hip,
 // reads and writes columns of 64 frames): 64 rows (= one tile) per workgroup, 2 x 2 waves of 32 x (32 WN).  A comes
 // row-major or in tile layout (A_T: copied to LDS as it lies, K-major); C leaves straight from the accumulators as
 // 16-byte pieces of the tile-layout columns.  No LDS beyond the A block: two workgroups per CU, so that one's staging

@@ -31,6 +31,9 @@
 #include "bf16x3.h"
 #include "f16pair.h"
 #include "gemm_epilogue.h"
+#include "gemm_kernels.h"
+#include "launch.h"
+#include "mlp_kernels.h"
 #include "stage_block.h"
 
 namespace empose {

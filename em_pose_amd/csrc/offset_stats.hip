@@ -7,14 +7,14 @@
 //
 // Pass 1, one workgroup of 256 lanes per (group, chunk of 256 consecutive frames counted from the group's first frame), a
 // lane per frame, a loop over the sensors: o and Q in fp32 (also the optional per-frame outputs; a frame that does not
-// count writes zeros), then the 19 sums of kernels.h in double -- over the wave by the butterfly v += shfl_xor(v, off),
+// count writes zeros), then the 19 sums of data_kernels.h in double -- over the wave by the butterfly v += shfl_xor(v, off),
 // off = 32 .. 1, then over the four waves through LDS in wave order; lane 0 writes them.  Lanes past the group's end add
 // exact zeros.  Pass 2, one lane per (group, sensor): the group's chunks in ascending order, the moments, the SVD.
 // No atomics, and a group's partition into chunks does not depend on the rest of the batch: repeated launches give the same
 // bits, and a group gives the same bits alone as in a batch.
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "data_kernels.h"
 #include "sensor_frame.h"
 #include "svd3.h"
 

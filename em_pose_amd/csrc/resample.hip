@@ -31,7 +31,7 @@
 // One fixed order, no atomics: repeated launches give the same bits.
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "data_kernels.h"
 
 namespace empose {
 

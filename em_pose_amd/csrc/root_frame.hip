@@ -30,7 +30,7 @@
 // and writes the first frame's rows.  No atomics: repeated launches give the same bits.
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "data_kernels.h"
 #include "lane_reduce.h"
 #include "smpl_math.h"
 

@@ -17,7 +17,7 @@
 // order.  No atomics: a second launch gives the same bits, and a window gives the same bits alone as in a batch.
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "fit_kernels.h"
 #include "lane_reduce.h"
 
 namespace empose {

@@ -16,7 +16,7 @@
 //                plan names a sensor twice, the last entry counts.  Orientation and normal are not touched.
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "data_kernels.h"
 
 namespace empose {
 

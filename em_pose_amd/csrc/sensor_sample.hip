@@ -14,7 +14,7 @@
 // passes of sensors_vjp.hip take it from there (api_sample.hip).  No atomics: repeated calls give the same bits.
 #include <hip/hip_runtime.h>
 
-#include "kernels.h"
+#include "data_kernels.h"
 #include "sensor_frame.h"
 
 namespace empose {

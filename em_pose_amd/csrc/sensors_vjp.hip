@@ -18,7 +18,7 @@
 
 #include <cstdint>
 
-#include "kernels.h"
+#include "mesh_kernels.h"
 #include "smpl_math.h"
 
 namespace empose {

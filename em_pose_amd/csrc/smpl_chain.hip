@@ -10,7 +10,8 @@
 // flat parallel-for over (frame, item) so that no lane idles on the serial structure of the skeleton: the forward
 // chain is a per-(joint,row) walk down the root path, the reverse chain uses the world-space form
 // dR_j = G_p^T (sum_subtree M_b - F_b (x) t_j) G_j, which needs subtree sums instead of a level-by-level sweep.
-#include "kernels.h"
+#include "launch.h"
+#include "smpl_kernels.h"
 #include "smpl_math.h"
 
 namespace empose {

@@ -10,7 +10,7 @@
 #include <cstdint>
 
 #include "feat_rows.h"
-#include "kernels.h"
+#include "smpl_kernels.h"
 #include "smpl_math.h"
 
 namespace empose {

@@ -21,7 +21,8 @@
 // Phases of a workgroup (4 waves with the reverse pass, 8 without; 64 frames): Rodrigues + chain, a wave per limb path |
 // sensors, wave w takes w, w + NW, ... | reverse chain, a wave per limb, then the spine.  Maths: reference models.py:471-483, 560-579, virtual_sensors.py:16-38, utils.py:126-146,
 // loss.py:23-41; reverse pass as in oracle/analytic_np.py (same formulas as chain_sensors_kernel).
-#include "kernels.h"
+#include "launch.h"
+#include "smpl_kernels.h"
 #include "smpl_math.h"
 #include "feat_rows.h"
 

@@ -23,7 +23,9 @@
 // What it writes is what the layer-by-layer path writes (save layout 1: z | a | mean | rstd), so forward and backward
 // choose their path independently.
 #include "gemm_epilogue.h"
-#include "kernels.h"
+#include "launch.h"
+#include "options.h"
+#include "train_kernels.h"
 
 namespace empose {
 

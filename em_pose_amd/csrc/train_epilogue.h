@@ -2,6 +2,7 @@
 // and the three-piece bf16 kernel (gemm_train_x3.hip), whose accumulators have the same layout. Internal, gfx950 only.
 #pragma once
 #include "gemm_epilogue.h"
+#include "gemm_kernels.h"
 
 namespace empose {
 

@@ -22,9 +22,9 @@
 // The GEMM side lives in gemm_f32.hip (gemm_tn_f32_kernel<CfgS12, 2>: the training step's tuned 64 x 128 tile with an
 // optional A-operand transform and the two train epilogues; a separate, simpler tile kernel was 27 % slower than the
 // tuned one and ate the gain).  This file: the small kernels between the GEMMs.
-#include "kernels.h"
 
 #include "gemm_epilogue.h"
+#include "train_kernels.h"
 
 #include <algorithm>
 

@@ -7,8 +7,8 @@
 //                activations saved by the forward kernels (LstmUnitArgs::sv_*); the recurrent product dh_{t-1} = dG_t W_hh
 //                is a GEMM launch per step (gemm_rec.hip runs the same cell inside that product).
 //   lgd_assemble / lgd_update / lgd_cotangent   the bookkeeping of the LGD loop around the update networks
-#include "kernels.h"
 #include "lstm_cell_bwd.h"
+#include "train_kernels.h"
 
 namespace empose {
 

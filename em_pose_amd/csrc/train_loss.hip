@@ -1,6 +1,6 @@
 // lgd_losses: the loss terms of IterativeErrorFeedback.backward (reference models.py:634-688, loss.py:13-41) and their
 // cotangents in one pass, and the fixed-order reduction to the five loss values.
-#include "kernels.h"
+#include "train_kernels.h"
 
 namespace empose {
 

@@ -1,6 +1,6 @@
 // Virtual sensors from arbitrary full-mesh vertices (reference virtual_sensors.py:16-38,77-96; utils.py:126-146):
 // one lane per (frame, sensor).  The vector-Jacobian product is sensors_vjp.hip.
-#include "kernels.h"
+#include "mesh_kernels.h"
 #include "smpl_math.h"
 
 namespace empose {

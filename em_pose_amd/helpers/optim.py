@@ -16,7 +16,7 @@ import torch
 
 from em_pose_amd import _lib
 
-_CHUNK = 4096   # ADAM_CHUNK in csrc/kernels.h
+_CHUNK = 4096   # ADAM_CHUNK in csrc/train_kernels.h
 
 
 class HipAdam(object):

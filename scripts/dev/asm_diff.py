@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """
-Same machine code?  Compiles every em_pose_amd/csrc/*.hip of two git revisions to gfx950 assembly with the flags of
+Same machine code?  Compiles every em_pose_amd/csrc/*.hip of two git revisions to gfx950 assembly with FLAGS of
 em_pose_amd/build.py (plus --cuda-device-only -S) and diffs the two outputs per file.  CPU only: hipcc cross-compiles.
 
     python scripts/dev/asm_diff.py HEAD~1 HEAD         # two revisions
@@ -34,7 +34,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)
 sys.path.insert(0, ROOT)
 from em_pose_amd import build as B   # noqa: E402  (the flags and the compiler come from the build itself)
 
-FLAGS = ['--offload-arch=' + B.ARCH, '-O3', '-std=c++17', '-fPIC', '-munsafe-fp-atomics', '-Wno-unused-result']
+FLAGS = B.FLAGS
 DEBUG_DIRECTIVES = ('.file', '.ident', '.loc', '.cfi_', '.section\t.debug', '.section .debug')
 
 

@@ -18,7 +18,7 @@
 //     tiles of NPAIR frame pairs.
 // Every accumulation runs in a fixed order over fixed operands: results are bitwise reproducible and do not depend on
 // the batch, the tile or the frame a frame is paired with.
-#include "kernels.h"
+#include "smpl_kernels.h"
 
 #include <algorithm>
 

@@ -1,6 +1,8 @@
 // What the stand-alone labs need from api.hip (options, dynamic LDS, co-residency, the poll-timeout word) when they
 // #include a production kernel file directly.
 #pragma once
+#include "../../em_pose_amd/csrc/launch.h"
+#include "../../em_pose_amd/csrc/options.h"
 namespace empose {
 #ifndef EMPOSE_LAB_HAS_OPTIONS
 Options& options() { static Options o; return o; }

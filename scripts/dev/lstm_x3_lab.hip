@@ -1,7 +1,6 @@
 // Dev lab: one wavefront step of the bench LSTM (2 layers, 296 -> 512 -> 512, B rows) on lstm_chain_x3_kernel, timed per
 // launch; built with -DLX_LAB_TIMES it prints the phase stamps of every workgroup.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -Iem_pose_amd/csrc scripts/dev/lstm_x3_lab.hip -o /tmp/lstm_x3_lab
-#include "../../em_pose_amd/csrc/kernels.h"
 #include "../../em_pose_amd/csrc/lstm_x3.hip"
 #include "lab_stubs.h"
 

@@ -2,7 +2,6 @@
 // cols_kernel (train_cols.hip): time per launch back to back, and -- built with -DTC_LAB_TIMES -- where a workgroup's
 // time goes (shader-clock stamps: start, loads issued, products done, after the barrier, statistics ready, exchange done, end).
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -DTC_LAB_TIMES -Iem_pose_amd/csrc scripts/dev/train_cols_lab.hip -o /tmp/train_cols_lab
-#include "../../em_pose_amd/csrc/kernels.h"
 #include "../../em_pose_amd/csrc/train_cols.hip"
 #include "lab_stubs.h"
 

@@ -157,7 +157,7 @@ def test_cpu_tensors_raise_instead_of_falling_back():
 
 EMPOSE_EINVAL = -1   # include/empose_hip.h
 
-# The 27 kernel-variant options and their defaults (EMPOSE_OPTIONS, csrc/kernels.h).
+# Kernel-variant options and their defaults (EMPOSE_OPTIONS, csrc/options.h).
 OPTION_DEFAULTS = {
     'mlp_fused': 1, 'lstm_persist': 1, 'gemm_splitk': 1, 'heads_rows': 1, 'lstm_seq': 0, 'bptt_wave': 1, 'gemm_wide': 1,
     'smpl_tile': 1, 'smpl_fuse': 1, 'train_fused': 0, 'atb_target': 0, 'atb_fast': 1, 'atb_chunk': 0,
