@@ -283,6 +283,10 @@ SIGNATURES = {
     # (mesh, T; poses, betas, trans of body A and of body B; sums; workspace, its bytes; stream)
     'empose_mesh_vertex_error': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p, C.c_void_p, C.c_size_t,
                                                                                       C.c_void_p]),
+    'empose_mesh_vertex_error_pa_workspace_bytes': (C.c_size_t, [C.c_void_p, C.c_int]),
+    # (the same arguments; sums [T][4])
+    'empose_mesh_vertex_error_pa': (C.c_int, [C.c_void_p, C.c_int] + [C.c_void_p] * 6 +
+                                             [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'empose_root_frame_fwd': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                         C.c_int, C.c_void_p]),
     'empose_root_frame_vjp_workspace_bytes': (C.c_size_t, [C.c_int, C.c_int]),

@@ -267,14 +267,18 @@ class SMPLLayer(nn.Module):
         return joints[:, :C.N_JOINTS + 1].contiguous()
 
     def vertex_error(self, poses_body, betas, poses_body_hat, betas_hat, poses_root=None, poses_root_hat=None,
-                     trans=None, trans_hat=None):
+                     trans=None, trans_hat=None, procrustes=False):
         """Per-vertex error between the body (poses_body, betas, poses_root, trans) and the body (`*_hat`), N frames
         each, without writing either mesh (empose_mesh_vertex_error, csrc/mesh_err.hip): `sums` (N, 2) float64 on the
         device, per frame the sum over this layer's vertices of |v - v_hat| (metres) and of |v - v_hat|^2; a frame's
         mean per-vertex error is `sums[:, 0] / n_vertices`.  The inputs are packed as `forward` packs them (betas
         broadcast, the first 63 body columns, `num_betas` shape coefficients).  No autograd: the inputs are detached and
         the result never carries a `grad_fn`.  fp32 on the fp32 matrix cores whatever `arithmetic` the layer has;
-        deterministic, and a frame's row depends on that frame alone."""
+        deterministic, and a frame's row depends on that frame alone.
+        `procrustes=True`: `sums` (N, 4), the same two columns and then the same two sums after the similarity transform
+        (rotation, scale, translation; the convention of PA-MPJPE) that best maps the `*_hat` vertices onto the others,
+        PA-PVE -- two sweeps over both bodies around a per-frame 3 x 3 SVD in float64, still without a mesh
+        (empose_mesh_vertex_error_pa)."""
         if not (poses_body.is_cuda and poses_body_hat.is_cuda):
             raise _lib.EmposeError('SMPLLayer needs GPU tensors; there is no CPU fallback')
         if poses_body_hat.shape[0] != poses_body.shape[0]:
@@ -286,12 +290,14 @@ class SMPLLayer(nn.Module):
         lib = _lib.lib()
         with torch.cuda.device(dev):
             handle = self._mesh_handle(dev)
-            sums = torch.empty(n, 2, dtype=torch.float64, device=dev)
-            ws_bytes = lib.empose_mesh_vertex_error_workspace_bytes(handle, n)
+            sums = torch.empty(n, 4 if procrustes else 2, dtype=torch.float64, device=dev)
+            ws_query = lib.empose_mesh_vertex_error_pa_workspace_bytes if procrustes else \
+                lib.empose_mesh_vertex_error_workspace_bytes
+            entry = lib.empose_mesh_vertex_error_pa if procrustes else lib.empose_mesh_vertex_error
+            ws_bytes = ws_query(handle, n)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            _lib.check(lib.empose_mesh_vertex_error(handle, n, _lib.dptr(pa), _lib.dptr(ba), _lib.dptr(ta), _lib.dptr(pb),
-                                                    _lib.dptr(bb), _lib.dptr(tb), _lib.dptr(sums), _lib.dptr(ws),
-                                                    ws_bytes, _lib.current_stream()))
+            _lib.check(entry(handle, n, _lib.dptr(pa), _lib.dptr(ba), _lib.dptr(ta), _lib.dptr(pb), _lib.dptr(bb),
+                             _lib.dptr(tb), _lib.dptr(sums), _lib.dptr(ws), ws_bytes, _lib.current_stream()))
         return sums
 
     def fk(self, poses_body, betas, poses_root=None, trans=None, normalize_root=False, window_size=None):

@@ -537,6 +537,82 @@ int empose_mesh_vertex_error(const empose_mesh_t* mesh, int T, const float* pose
   return EMPOSE_OK;
 }
 
+// ---- ... and after a Procrustes alignment of B onto A --------------------------------------------------------------
+// Scratch for a slab of S frames: as above with the posed joints of each body kept apart (their roots are the pivots of
+// the moments), the 17 moment partials per frame and tile and the 16 floats per frame from the solve to the second sweep.
+struct MeshErrPaWs { MeshWs a, b; float *joints_a, *joints_b, *part, *part_m, *align; double *rot64, *jrest64; };
+static MeshErrPaWs carve_mesh_err_pa(Carver& c, const empose_mesh* mesh, size_t S) {
+  const size_t n_tiles = (size_t)((mesh->V + 31) / 32);
+  MeshErrPaWs w;
+  w.a = carve_mesh(c, mesh, S);
+  w.b = carve_mesh(c, mesh, S);
+  w.joints_a = c.f(S * (size_t)mesh->n_joints * 3);
+  w.joints_b = c.f(S * (size_t)mesh->n_joints * 3);
+  w.part = c.f(S * n_tiles * 2);
+  w.part_m = c.f(S * n_tiles * MESH_PA_MOMENTS);
+  w.align = c.f(S * MESH_PA_ALIGN);
+  w.rot64 = reinterpret_cast<double*>(c.f(S * NB * 9 * 2));
+  w.jrest64 = reinterpret_cast<double*>(c.f(S * NB * 3 * 2));
+  return w;
+}
+
+size_t empose_mesh_vertex_error_pa_workspace_bytes(const empose_mesh_t* mesh, int T) {
+  if (!mesh || T <= 0) return 0;
+  return Carver::measure([&](Carver& c) { carve_mesh_err_pa(c, mesh, T < MESH_SLAB ? T : MESH_SLAB); });
+}
+
+int empose_mesh_vertex_error_pa(const empose_mesh_t* mesh, int T, const float* poses_a, const float* betas_a,
+                                const float* trans_a, const float* poses_b, const float* betas_b, const float* trans_b,
+                                double* sums, void* workspace, size_t workspace_bytes, empose_stream_t stream_) {
+  if (!mesh) return fail(EMPOSE_EINVAL, "mesh is NULL");
+  if (!poses_a) return fail(EMPOSE_EINVAL, "poses_a is NULL");
+  if (!betas_a) return fail(EMPOSE_EINVAL, "betas_a is NULL");
+  if (!poses_b) return fail(EMPOSE_EINVAL, "poses_b is NULL");
+  if (!betas_b) return fail(EMPOSE_EINVAL, "betas_b is NULL");
+  if (!sums) return fail(EMPOSE_EINVAL, "sums is NULL");
+  if (!workspace) return fail(EMPOSE_EINVAL, "workspace is NULL");
+  if (T <= 0) return fail(EMPOSE_EINVAL, "T must be positive");
+  if (workspace_bytes < empose_mesh_vertex_error_pa_workspace_bytes(mesh, T))
+    return fail(EMPOSE_ENOMEM, "workspace too small (empose_mesh_vertex_error_pa_workspace_bytes)");
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const int S = T < MESH_SLAB ? T : MESH_SLAB;
+  const int n_tiles = (mesh->V + 31) / 32, ld_j = mesh->n_joints * 3;
+  Carver c(workspace);
+  const MeshErrPaWs w = carve_mesh_err_pa(c, mesh, (size_t)S);
+  for (int t0 = 0; t0 < T; t0 += S) {
+    const int n = (T - t0) < S ? (T - t0) : S;
+    const float* tra = trans_a ? trans_a + (size_t)t0 * 3 : nullptr;
+    const float* trb = trans_b ? trans_b + (size_t)t0 * 3 : nullptr;
+    TRY(mesh_slab_prologue(mesh, w.a, poses_a, betas_a, t0, n, tra, w.joints_a, stream));
+    TRY(mesh_slab_prologue(mesh, w.b, poses_b, betas_b, t0, n, trb, w.joints_b, stream));
+    MeshPairErrorArgs pa;
+    pa.feat_a = w.a.feat; pa.xf_a = w.a.xf; pa.trans_a = tra;
+    pa.feat_b = w.b.feat; pa.xf_b = w.b.xf; pa.trans_b = trb;
+    pa.skin_idx = mesh->skin_idx; pa.skin_w = mesh->skin_w; pa.kb = mesh->kb; pa.T = n; pa.V = mesh->V;
+    pa.wc_frag = mesh->wc_frag; pa.skin_idx4 = mesh->skin_idx4; pa.skin_w4 = mesh->skin_w4; pa.part = w.part;
+    // the posed root joints (translation included), the first of each frame's joints, are the pivots
+    pa.mode = MESH_PAIR_MOMENTS; pa.pivot_a = w.joints_a; pa.pivot_b = w.joints_b; pa.ld_pivot = ld_j; pa.part_m = w.part_m;
+    HIP_CHECK(launch_mesh_pair_error(pa, stream), "mesh pair moments kernel");
+    MeshPaSolveArgs so;
+    so.part = w.part; so.part_m = w.part_m; so.pivot_a = w.joints_a; so.pivot_b = w.joints_b; so.ld_pivot = ld_j;
+    so.align = w.align; so.sums = sums + (size_t)t0 * 4; so.T = n; so.V = mesh->V;
+    HIP_CHECK(launch_mesh_pa_solve(so, stream), "mesh alignment solve kernel");
+    // the aligned sweep on transforms from a float64 prologue (the moments sweep is done with the float32 ones, which it
+    // needs for the plain columns): the sums of squares are stationary in the alignment, so the two go together
+    MeshChainF64Args cf;
+    cf.wj = mesh->wc + (size_t)mesh->j_off * 200; cf.parents = mesh->parents; cf.rot = w.rot64; cf.jrest = w.jrest64;
+    cf.T = n; cf.rod_conv = mesh->rod_conv;
+    cf.poses = poses_a + (size_t)t0 * 66; cf.betas = betas_a + (size_t)t0 * 10; cf.xf = w.a.xf;
+    HIP_CHECK(launch_mesh_chain_f64(cf, stream), "mesh chain in float64, body A");
+    cf.poses = poses_b + (size_t)t0 * 66; cf.betas = betas_b + (size_t)t0 * 10; cf.xf = w.b.xf;
+    HIP_CHECK(launch_mesh_chain_f64(cf, stream), "mesh chain in float64, body B");
+    pa.mode = MESH_PAIR_ALIGNED; pa.align = w.align;
+    HIP_CHECK(launch_mesh_pair_error(pa, stream), "mesh pair aligned kernel");
+    HIP_CHECK(launch_mesh_err_sum(w.part, n_tiles, n, sums + (size_t)t0 * 4 + 2, stream, 4), "mesh error sum kernel");
+  }
+  return EMPOSE_OK;
+}
+
 // ---- root normalisation -----------------------------------------------------------------------------------------
 static int root_frame_args_ok(int T, int seg_len, int rodrigues, int ld_root, int flags) {
   if (T <= 0 || seg_len <= 0) return fail(EMPOSE_EINVAL, "T and seg_len must be positive");

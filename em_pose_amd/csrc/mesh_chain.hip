@@ -75,6 +75,88 @@ hipError_t launch_mesh_chain(const MeshChainArgs& a, hipStream_t stream) {
   return hipGetLastError();
 }
 
+// ---- the transforms in float64 (mesh_kernels.h MeshChainF64Args) -----------------------------------------------------
+// One thread per (frame, body joint): Rodrigues in double, both conventions as smpl_math.h states them.
+__global__ void mesh_rot_f64_kernel(MeshChainF64Args a) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= a.T * NB) return;
+  const float* th = a.poses + (size_t)(idx / NB) * 66 + (idx % NB) * 3;
+  const double rx = th[0], ry = th[1], rz = th[2];
+  double ang;
+  if (a.rod_conv == 0) {
+    const double ux = rx + 1e-8, uy = ry + 1e-8, uz = rz + 1e-8;
+    ang = sqrt(ux * ux + uy * uy + uz * uz);
+  } else {
+    ang = sqrt(fmax(rx * rx + ry * ry + rz * rz, 1e-4));
+  }
+  const double dx = rx / ang, dy = ry / ang, dz = rz / ang, s = sin(ang), oc = 1.0 - cos(ang);
+  double* R = a.rot + (size_t)idx * 9;
+  R[0] = 1.0 + oc * (-dz * dz - dy * dy); R[1] = -s * dz + oc * (dx * dy);        R[2] = s * dy + oc * (dx * dz);
+  R[3] = s * dz + oc * (dx * dy);         R[4] = 1.0 + oc * (-dz * dz - dx * dx); R[5] = -s * dx + oc * (dy * dz);
+  R[6] = -s * dy + oc * (dx * dz);        R[7] = s * dx + oc * (dy * dz);         R[8] = 1.0 + oc * (-dy * dy - dx * dx);
+}
+
+// One thread per (frame, rest-joint coordinate): the row of wc times the feature row [vec(R_j - I), j = 1..21 | beta | 1].
+__global__ void mesh_jrest_f64_kernel(MeshChainF64Args a) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= a.T * NB * 3) return;
+  const int t = idx / (NB * 3), c = idx % (NB * 3);
+  const float* __restrict__ w = a.wj + (size_t)c * 200;
+  const double* __restrict__ R = a.rot + (size_t)t * NB * 9 + 9;
+  double s = w[199];
+  for (int k = 0; k < 189; ++k) s += (double)w[k] * (R[k] - ((k % 9) % 4 == 0 ? 1.0 : 0.0));
+  for (int k = 0; k < 10; ++k) s += (double)w[189 + k] * (double)a.betas[(size_t)t * 10 + k];
+  a.jrest[idx] = s;
+}
+
+// mesh_chain_kernel in double for the body joints, transforms only.
+__global__ void mesh_chain_f64_kernel(MeshChainF64Args a) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  __shared__ int parents_s[NB];
+  for (int i = threadIdx.x; i < NB; i += blockDim.x) parents_s[i] = a.parents[i];
+  __syncthreads();
+  if (idx >= a.T * NB) return;
+  const int t = idx / NB, j = idx % NB;
+  const double* R = a.rot + (size_t)t * NB * 9;
+  const double* J = a.jrest + (size_t)t * NB * 3;
+  int n = 0;
+  for (int q = j; q >= 0; q = parents_s[q]) ++n;
+  double G[3][3], tr[3];
+  for (int r = 0; r < 3; ++r) {
+    G[r][0] = R[r * 3 + 0]; G[r][1] = R[r * 3 + 1]; G[r][2] = R[r * 3 + 2];
+    tr[r] = J[r];
+  }
+  int prev = 0;
+  for (int k = n - 2; k >= 0; --k) {
+    int q = j;
+    for (int up = 0; up < k; ++up) q = parents_s[q];
+    const double dx = J[q * 3] - J[prev * 3], dy = J[q * 3 + 1] - J[prev * 3 + 1], dz = J[q * 3 + 2] - J[prev * 3 + 2];
+    for (int r = 0; r < 3; ++r) tr[r] = G[r][0] * dx + G[r][1] * dy + G[r][2] * dz + tr[r];
+    const double* Rv = R + q * 9;
+    for (int r = 0; r < 3; ++r) {
+      const double n0 = G[r][0] * Rv[0] + G[r][1] * Rv[3] + G[r][2] * Rv[6];
+      const double n1 = G[r][0] * Rv[1] + G[r][1] * Rv[4] + G[r][2] * Rv[7];
+      const double n2 = G[r][0] * Rv[2] + G[r][1] * Rv[5] + G[r][2] * Rv[8];
+      G[r][0] = n0; G[r][1] = n1; G[r][2] = n2;
+    }
+    prev = q;
+  }
+  const double* Jj = J + j * 3;
+  for (int r = 0; r < 3; ++r)
+    *reinterpret_cast<float4*>(a.xf + (((size_t)t * NB + j) * 3 + r) * 4) =
+        make_float4((float)G[r][0], (float)G[r][1], (float)G[r][2],
+                    (float)(tr[r] - (G[r][0] * Jj[0] + G[r][1] * Jj[1] + G[r][2] * Jj[2])));
+}
+
+hipError_t launch_mesh_chain_f64(const MeshChainF64Args& a, hipStream_t stream) {
+  if (a.T <= 0) return hipErrorInvalidValue;
+  const long n = (long)a.T * NB;
+  hipLaunchKernelGGL(mesh_rot_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(mesh_jrest_f64_kernel, dim3((unsigned)((n * 3 + 255) / 256)), dim3(256), 0, stream, a);
+  hipLaunchKernelGGL(mesh_chain_f64_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  return hipGetLastError();
+}
+
 // Reverse of mesh_chain_kernel (+ the skinning transforms): one thread per frame.  Forward, per joint j with parent p:
 // G_j = G_p R_j (R_j = I for the hand joints), t_j = G_p (J_j - J_p) + t_p, joints_j = t_j + trans, and per body bone
 // A_b = [G_b | t_b - G_b J_b].  The joints are visited from the last to the root, so that dt_j and dG_j are complete when

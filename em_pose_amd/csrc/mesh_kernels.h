@@ -19,6 +19,19 @@ struct MeshChainArgs {
   int n_joints = NB;       // 22 (body) or up to MESH_MAX_JOINTS (hand joints ride on their parents, zero hand pose)
 };
 hipError_t launch_mesh_chain(const MeshChainArgs& a, hipStream_t stream);
+// The 22 skinning transforms once more with everything ahead of them in float64 -- Rodrigues, the rest joints (the joint
+// rows of wc times the feature row) and the chain -- and one rounding to float32 at the end: the transforms of the aligned
+// sweep of the Procrustes-aligned vertex error (mesh_err.hip), whose error is otherwise that of the float32 rotations and
+// rest joints.  Three small launches through the scratch rot [T][22][9] and jrest [T][66] (doubles).
+struct MeshChainF64Args {
+  const float* poses; const float* betas;   // [T][66] (root first), [T][10]
+  const float* wj;                          // the rest-joint rows of wc, [>= 66][200]
+  const int* parents;                       // the first NB entries are used
+  double* rot; double* jrest;
+  float* xf;                                // [T][22][3][4], as MeshChainArgs::xf
+  int T, rod_conv;
+};
+hipError_t launch_mesh_chain_f64(const MeshChainF64Args& a, hipStream_t stream);
 struct MeshSkinArgs {
   const float* feat;           // [T][200]
   const float* wc;             // [V*3 (+66)][200]: row 3s+c = coefficients of coordinate c of vertex s
@@ -62,9 +75,32 @@ struct MeshPairErrorArgs {
   const float* wc_frag;                   // as MeshSkinArgs
   const int* skin_idx4; const float* skin_w4;
   float* part;
+  // The Procrustes-aligned error (PA-PVE) takes two sweeps of the same kernel around mesh_pa_solve_kernel:
+  //   MESH_PAIR_MOMENTS  part as the plain form, bit for bit, and part_m [T][tiles][MESH_PA_MOMENTS]: with a = v_A - pivot_a
+  //                      and b = v_B - pivot_b the tile's sums of a (3), b (3), a b^T (9, row-major), |a|^2 and |b|^2;
+  //   MESH_PAIR_ALIGNED  part holds the sums of d = |(v_A - c_A) - sR (v_B - c_B)| and d^2, sR and the centroids from
+  //                      align [T][MESH_PA_ALIGN]: M (9, the aligned b is b M), c_A (3), c_B (3), one unused.
+  int mode = 0;
+  const float *pivot_a = nullptr, *pivot_b = nullptr; int ld_pivot = 0;   // MOMENTS: [T][ld_pivot], three used
+  float* part_m = nullptr;
+  const float* align = nullptr;
 };
+constexpr int MESH_PAIR_PLAIN = 0, MESH_PAIR_MOMENTS = 1, MESH_PAIR_ALIGNED = 2;
+constexpr int MESH_PA_MOMENTS = 17, MESH_PA_ALIGN = 16;
 hipError_t launch_mesh_pair_error(const MeshPairErrorArgs& a, hipStream_t stream);
-hipError_t launch_mesh_err_sum(const float* part, int n_tiles, int T, double* out, hipStream_t stream);
+// out[t * ld_out + 0 .. 1]
+hipError_t launch_mesh_err_sum(const float* part, int n_tiles, int T, double* out, hipStream_t stream, int ld_out = 2);
+// One lane per frame, float64: the tile partials of a MOMENTS sweep in ascending tile order, centred, normalised, the
+// 3 x 3 SVD and the conventions of the joints' alignment (svd3.h procrustes_rotation).  Writes align [T][MESH_PA_ALIGN]
+// for the ALIGNED sweep and the frame's plain sums to sums[t * 4 + 0 .. 1].  A NaN moment gives NaNs.
+struct MeshPaSolveArgs {
+  const float *part, *part_m;
+  const float *pivot_a, *pivot_b; int ld_pivot;
+  float* align;
+  double* sums;
+  int T, V;
+};
+hipError_t launch_mesh_pa_solve(const MeshPaSolveArgs& a, hipStream_t stream);
 
 // Full-mesh vector-Jacobian product (mesh_vjp.hip): the two vertex sweeps of the reverse for a cotangent dV [T][V][3].
 //   feat sweep: d_feat[t][k] = sum_v,c dvp[t][v][c] wc[3v+c][k], dvp_v = sum_b w_vb (A_b^R)^T dV_v   -> out [T][200]

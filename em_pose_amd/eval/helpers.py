@@ -149,9 +149,10 @@ def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, 
 
 
 def compute_loss_and_metrics(data_loader, net, preprocess_fn, model_id, smpl_model=None, device=None,
-                             vertex_error=False):
+                             vertex_error=False, vertex_error_procrustes=False):
     """reference eval/helpers.py:114-128.  `vertex_error` (not in the reference): also accumulate the per-vertex error
-    (eval/mesh_metrics.py) and print it as a second table line; the returned values are the same either way."""
+    (eval/mesh_metrics.py) and print it as a second table line, with `vertex_error_procrustes` the Procrustes-aligned
+    error in the same line; the returned values are the same either way."""
     if smpl_model is None:
         from em_pose_amd.bodymodels.smpl import create_default_smpl_model
         smpl_model = create_default_smpl_model(device)
@@ -159,7 +160,7 @@ def compute_loss_and_metrics(data_loader, net, preprocess_fn, model_id, smpl_mod
     ve = None
     if vertex_error:
         from em_pose_amd.eval.mesh_metrics import VertexErrorEngine
-        ve = VertexErrorEngine(smpl_model)
+        ve = VertexErrorEngine(smpl_model, procrustes=vertex_error_procrustes)
     losses = evaluate(data_loader, net, preprocess_fn, me, device=device, vertex_engine=ve)
     print('[LOSS] loss: {:.6f}'.format(losses['total_loss']))
     metrics = me.get_metrics()

@@ -14,6 +14,12 @@ written).  These (frames, 2) float64 rows are the accumulator -- a mergeable val
   'PVE [mm]'  sum of all distances / (frames * V)
   'PVE STD'   the standard deviation over all (frame, vertex) distances, as the reference's STD columns are `np.std` over
               all entries -- here from the two moments, in float64: sqrt(sum d^2 / n - mean^2)
+`VertexErrorEngine(smpl_model, procrustes=True)` adds the Procrustes-aligned error, PA-PVE (PA-MPVPE), as PA-MPJPE
+stands beside MPJPE: the same distances after the similarity transform that best maps the estimate's vertices onto the
+ground truth's (the convention of `eval/metrics.py procrustes_align`).  A globally rotated but correctly posed and shaped
+body has a large PVE and a PA-PVE near zero.  Still one call to the layer per `compute` (`vertex_error(...,
+procrustes=True)`, four numbers per frame); the second pair of columns is kept as 'sums_pa' beside an unchanged 'sums',
+and `get_metrics` appends 'PA-PVE [mm]' and 'PA-PVE STD' with the conventions above.  Also this project's addition.
 There is no CPU path: the layer refuses CPU tensors.
 """
 import numpy as np
@@ -23,9 +29,10 @@ from em_pose_amd.eval.metrics import MetricsEngine
 
 
 class VertexErrorEngine(object):
-    def __init__(self, smpl_model):
+    def __init__(self, smpl_model, procrustes=False):
         """`smpl_model`: an `SMPLLayer`, or a `SubMeshLayer` for the error over its vertex subset."""
         self.smpl_model = smpl_model
+        self.procrustes = bool(procrustes)
         self.reset()
 
     @property
@@ -33,7 +40,7 @@ class VertexErrorEngine(object):
         return int(self.smpl_model.n_vertices)
 
     def reset(self):
-        self._sums = []       # host rows, (m, 2) float64 each
+        self._sums = []       # host rows, (m, 2) float64 each -- (m, 4) with `procrustes`: sums | sums_pa
         self._pending = []    # (device rows (n * f, 2), valid (n * f,) bool) of `compute` calls not read yet
 
     @property
@@ -54,8 +61,9 @@ class VertexErrorEngine(object):
         per_frame = lambda s_: flat(s_) if s_.dim() == 3 else flat(s_.unsqueeze(1).expand(n, f, s_.shape[-1]))
         root_f = None if pose_root is None else flat(pose_root)
         root_hat_f = None if pose_root is None else flat(pose_root_hat)
+        kw = {'procrustes': True} if self.procrustes else {}
         rows = self.smpl_model.vertex_error(flat(pose), per_frame(shape), flat(pose_hat), per_frame(shape_hat),
-                                            poses_root=root_f, poses_root_hat=root_hat_f)
+                                            poses_root=root_f, poses_root_hat=root_hat_f, **kw)
         self._pending.append((rows, mask.reshape(n * f)))
 
     def _flush(self):
@@ -69,11 +77,25 @@ class VertexErrorEngine(object):
             self._sums.append(rows.cpu().numpy())
 
     # ---- mergeable state ------------------------------------------------------------------------------------------
+    @property
+    def _width(self):
+        return 4 if self.procrustes else 2
+
     def state(self):
-        return {'sums': np.concatenate(self.sums, axis=0) if self.sums else np.zeros((0, 2))}
+        rows = np.concatenate(self.sums, axis=0) if self.sums else np.zeros((0, self._width))
+        if not self.procrustes:
+            return {'sums': rows}
+        return {'sums': np.ascontiguousarray(rows[:, :2]), 'sums_pa': np.ascontiguousarray(rows[:, 2:])}
 
     def merge(self, state):
         rows = np.asarray(state['sums'], dtype=np.float64).reshape(-1, 2)
+        if self.procrustes:
+            if 'sums_pa' not in state:
+                raise ValueError("a state without 'sums_pa' cannot be merged into a Procrustes engine")
+            rows_pa = np.asarray(state['sums_pa'], dtype=np.float64).reshape(-1, 2)
+            if rows_pa.shape[0] != rows.shape[0]:
+                raise ValueError("'sums' and 'sums_pa' count different frames")
+            rows = np.concatenate([rows, rows_pa], axis=1)
         if rows.shape[0]:
             self.sums.append(rows)
 
@@ -85,31 +107,36 @@ class VertexErrorEngine(object):
             return self
         world = dist.get_world_size(group)
         dev = torch.device('cpu') if device is None else device
-        mine = torch.from_numpy(self.state()['sums']).to(dev)
+        w = self._width
+        mine = torch.from_numpy(np.concatenate(list(self.state().values()), axis=1)).to(dev)
         count = torch.tensor([mine.shape[0]], dtype=torch.int64, device=dev)
         counts = [torch.zeros_like(count) for _ in range(world)]
         dist.all_gather(counts, count, group=group)
         counts = [int(c.item()) for c in counts]
-        padded = torch.zeros(max(max(counts), 1), 2, dtype=torch.float64, device=dev)
+        padded = torch.zeros(max(max(counts), 1), w, dtype=torch.float64, device=dev)
         padded[:mine.shape[0]] = mine
         parts = [torch.zeros_like(padded) for _ in range(world)]
         dist.all_gather(parts, padded, group=group)
         merged = np.concatenate([p[:c].cpu().numpy() for p, c in zip(parts, counts)], axis=0)
         self.reset()
-        self.merge({'sums': merged})
+        self.merge({'sums': merged[:, :2], 'sums_pa': merged[:, 2:]} if self.procrustes else {'sums': merged})
         return self
 
     # ---- reduction ------------------------------------------------------------------------------------------------
     def get_metrics(self):
         # NaN, not 0, without a single accumulated row (as MetricsEngine: "0 mm" reads as a perfect score)
-        out = {'PVE [mm]': float('nan'), 'PVE STD': float('nan')}
+        names = ['PVE'] + (['PA-PVE'] if self.procrustes else [])
+        out = {}
+        for name in names:
+            out[name + ' [mm]'] = out[name + ' STD'] = float('nan')
         if self.sums:
             rows = np.concatenate(self.sums, axis=0)
             count = float(rows.shape[0]) * self.n_vertices
-            mean = rows[:, 0].sum() / count
-            var = max(rows[:, 1].sum() / count - mean * mean, 0.0)
-            out['PVE [mm]'] = float(mean * 1000.0)
-            out['PVE STD'] = float(np.sqrt(var) * 1000.0)
+            for i, name in enumerate(names):
+                mean = rows[:, 2 * i].sum() / count
+                var = max(rows[:, 2 * i + 1].sum() / count - mean * mean, 0.0)
+                out[name + ' [mm]'] = float(mean * 1000.0)
+                out[name + ' STD'] = float(np.sqrt(var) * 1000.0)
         return out
 
     @staticmethod

@@ -801,6 +801,28 @@ int empose_mesh_vertex_error(const empose_mesh_t* mesh, int T, const float* pose
                              const float* trans_a, const float* poses_b, const float* betas_b, const float* trans_b,
                              double* sums, void* workspace, size_t workspace_bytes, empose_stream_t stream);
 
+/* The same with the Procrustes-aligned error beside it (PA-PVE / PA-MPVPE; this project's addition like PVE): sums [T][4]
+ * (double) receives per frame the two sums of empose_mesh_vertex_error, bit for bit, and then the sums of d_pa and d_pa^2
+ * over the V vertices, d_pa = |v_A - (s R v_B + t)| with the similarity transform (optimal rotation, scale and
+ * translation, a reflection turned into a rotation by flipping the last singular vector and value) that best maps the
+ * vertices of B onto those of A -- the convention of the PA-MPJPE rows of empose_metrics_rows, over the vertices instead
+ * of the joints.  No mesh is written: the bodies are evaluated twice in registers (csrc/mesh_err.hip), once for the 17
+ * moments of the alignment, taken about each body's posed root joint, and once for the aligned distances; a 3 x 3 SVD per
+ * frame in float64 lies between; the bone transforms of the second sweep are recomputed in float64 (Rodrigues, rest
+ * joints, chain) and rounded once.  Deterministic, a frame's four numbers depend on that frame alone.  The transform itself
+ * is not returned.
+ * Workspace: empose_mesh_vertex_error_pa_workspace_bytes(mesh, T), for a slab of min(T, 16384) frames the scratch of
+ * empose_mesh_vertex_error, a second set of posed joints, 68 bytes per frame and 32 vertices for the moments, 64 bytes
+ * per frame for the transform and 2.1 KB per frame for the float64 rotations and rest joints (about 26 KB per frame for
+ * SMPL-H); 0 for a NULL handle or T <= 0.  Asynchronous on
+ * `stream`; allocates, copies and synchronises nothing.
+ * Before any GPU work: EMPOSE_EINVAL for a NULL mesh, poses_a, betas_a, poses_b, betas_b, sums or workspace and for
+ * T <= 0, EMPOSE_ENOMEM for a workspace that is too small; empose_last_error() names the argument. */
+size_t empose_mesh_vertex_error_pa_workspace_bytes(const empose_mesh_t* mesh, int T);
+int empose_mesh_vertex_error_pa(const empose_mesh_t* mesh, int T, const float* poses_a, const float* betas_a,
+                                const float* trans_a, const float* poses_b, const float* betas_b, const float* trans_b,
+                                double* sums, void* workspace, size_t workspace_bytes, empose_stream_t stream);
+
 /* ---- root normalisation (reference bodymodels/smpl.py:112-119, data/transforms.py:247-254) ----------------------- */
 /* T frames in segments of seg_len consecutive rows (T % seg_len == 0): a sequence is re-expressed in the frame of the
  * first root orientation of its segment, R_0 = exp(root[first]):

@@ -171,9 +171,9 @@ def train_on_amass(args, dev, rank, world):
         print('Saving checkpoints to {}'.format(checkpoint))
     me = MetricsEngine(smpl)
     ve = None
-    if args.valid_vertex_error:
+    if args.valid_vertex_error or args.valid_vertex_error_pa:
         from em_pose_amd.eval.mesh_metrics import VertexErrorEngine
-        ve = VertexErrorEngine(smpl)
+        ve = VertexErrorEngine(smpl, procrustes=args.valid_vertex_error_pa)
     step, best, done, skipped = 0, float('inf'), False, 0
     for epoch in range(args.n_epochs):
         for i, abatch in enumerate(train_loader):
@@ -289,6 +289,9 @@ def main():
     p.add_argument('--valid_vertex_error', action='store_true',
                    help='the periodic validation also reports the mean per-vertex error (PVE) of the body surface, a second '
                         'table line (eval/mesh_metrics.py); default off')
+    p.add_argument('--valid_vertex_error_pa', action='store_true',
+                   help='as --valid_vertex_error (which it implies), with the Procrustes-aligned per-vertex error (PA-PVE) '
+                        'in the same line; default off')
     p.add_argument('--offset_noise_level', type=int, default=0)
     # sensor-noise augmentation (reference configuration.py: the same five flags; data/noise_functions.py)
     p.add_argument('--noise_num_markers', type=int, default=1, help='how many sensors the sensor noise affects')
