@@ -129,6 +129,21 @@ class FitIO(C.Structure):        # empose_fit_io
                 ('ori', C.c_void_p), ('objective', C.c_void_p), ('energy', C.c_void_p)]
 
 
+RENDER_MAX_IMAGE = 2048   # EMPOSE_RENDER_MAX_IMAGE
+RENDER_COLOR_UNIFORM, RENDER_COLOR_VERTEX, RENDER_COLOR_FRAME = 0, 1, 2   # EMPOSE_RENDER_COLOR_*
+
+
+class RenderDesc(C.Structure):   # empose_render_desc
+    _fields_ = [('T', C.c_int), ('V', C.c_int), ('n_faces', C.c_int), ('H', C.c_int), ('W', C.c_int),
+                ('vertices', C.c_void_p), ('faces', C.c_void_p), ('faces_host', c_int_p),
+                ('normals', C.c_void_p), ('colors', C.c_void_p), ('color_mode', C.c_int),
+                ('cam_R', C.c_void_p), ('cam_t', C.c_void_p), ('camera_per_frame', C.c_int),
+                ('fx', C.c_float), ('fy', C.c_float), ('cx', C.c_float), ('cy', C.c_float), ('near', C.c_float),
+                ('light', C.c_float * 3), ('ambient', C.c_float), ('background', C.c_float * 3),
+                ('slab_frames', C.c_int),
+                ('rgb', C.c_void_p), ('face_id', C.c_void_p), ('depth', C.c_void_p)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests check against the header.
 SIGNATURES = {
     'empose_last_error': (C.c_char_p, []),
@@ -307,6 +322,8 @@ SIGNATURES = {
     # (model, io, k; theta, beta, g_theta, g_beta, pos, ori, s; the four moments; theta_next, beta_next; energy, J; best_J,
     # best_theta, best_beta; stream)
     'empose_sensor_fit_step': (C.c_int, [C.c_void_p, C.POINTER(FitIO), C.c_int] + [C.c_void_p] * 18 + [C.c_void_p]),
+    'empose_render_workspace_bytes': (C.c_size_t, [C.c_int] * 4),
+    'empose_render_meshes': (C.c_int, [C.POINTER(RenderDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

@@ -995,6 +995,56 @@ int empose_sensor_fit_step(const empose_model_t* model, const empose_fit_io* io,
                            float* v_beta, float* theta_next, float* beta_next, float* energy, float* J, float* best_J,
                            float* best_theta, float* best_beta, empose_stream_t stream);
 
+/* ---- headless mesh rendering (new in this library) -------------------------------------------- */
+/* A z-buffer rasteriser for posed meshes: T frames of V vertices and one table of n_faces triangles to T images of
+ * H x W pixels, in three launches per slab of frames (csrc/raster.hip).  The definition is this library's own:
+ *   camera    p_c = R p + t with a row-major 3 x 3 R and a 3-vector t, one for all frames or, camera_per_frame != 0, one
+ *             per frame ([T][3][3], [T][3]); the camera looks along +z; x = fx X / Z + cx, y = fy Y / Z + cy, image y
+ *             points down, and the pixel of row i, column j has its centre at (j + 0.5, i + 0.5).
+ *   coverage  a face with a vertex at Z <= near is dropped whole (no clipping against the near plane), a face whose
+ *             bounding box holds no pixel centre or whose screen area is exactly 0 is skipped, and there is no back-face
+ *             culling.  A pixel centre is covered where the three edge functions, oriented by the sign of the area, are
+ *             all >= 0: edges are inclusive.
+ *   depth     perspective-correct, Z = 1 / sum_k lambda_k / Z_k.  The nearest face wins; on an exact tie of the depth the
+ *             lower face id does.  The z-buffer is a 64-bit integer key per pixel, (bits of Z) << 32 | face id, updated
+ *             with integer atomicMin: no floating-point atomics, the result does not depend on the order of arrival.
+ *   shading   intensity = ambient + (1 - ambient) |n . l| / (|n| |l|), two-sided; `light` is a direction in camera
+ *             space (normalised here); n is interpolated from `normals` ([T][V][3], un-normalised, world space, rotated
+ *             by R) or, normals == NULL, the face normal (flat shading).  The base colour is `colors`: [3] for
+ *             EMPOSE_RENDER_COLOR_UNIFORM, [V][3] for _VERTEX, [T][V][3] for _FRAME, the latter two interpolated like
+ *             the normals; a byte is floor(255 c + 0.5) clamped to 0 .. 255.
+ *   outputs   rgb uint8 [T][H][W][3]; face_id int32 [T][H][W] (or NULL); depth float32 [T][H][W] (or NULL).  Pixels no
+ *             face covers: face_id -1, depth +inf, `background`.
+ * Every pixel depends on its own frame alone and nothing is summed: a second call gives the same bits, and a frame gives
+ * the same bits alone, inside a batch and on either side of a slab edge.  H and W are at most EMPOSE_RENDER_MAX_IMAGE,
+ * which bounds the pixels one face can cover; a face whose bounding box holds more than 256 pixel centres is walked by its
+ * whole wave, not by one lane.  Frames are rendered in slabs (slab_frames of them, 0: what fits 64 MB of workspace, at
+ * least one; a larger value than that is lowered to it), so empose_render_workspace_bytes(T, V, H, W) -- the projected
+ * vertices and the keys of one slab; 0 for sizes the call refuses -- is bounded whatever T is.
+ * Face indices: `faces_host`, when given, is a host copy of the device table `faces` and is checked against [0, V) on
+ * every call; the kernels clamp an index into [0, V) in any case, so a table that was not checked reads inside `vertices`.
+ * All other pointers are device memory.  The call is asynchronous on `stream`: it never synchronises, allocates or copies.
+ * Returns EMPOSE_EINVAL, before any GPU work, for a NULL descriptor, vertices, faces, colors, cam_R, cam_t, rgb or
+ * workspace, T, V, n_faces, H or W <= 0 (V above 2^24, n_faces above 2^26), H or W above the cap, an unknown color_mode,
+ * near <= 0 or not finite, fx, fy, cx, cy not finite or fx, fy zero, ambient outside [0, 1], a zero or non-finite light,
+ * a non-finite background, slab_frames < 0, a face index of faces_host outside [0, V) and a workspace that is too small. */
+#define EMPOSE_RENDER_MAX_IMAGE 2048
+#define EMPOSE_RENDER_COLOR_UNIFORM 0
+#define EMPOSE_RENDER_COLOR_VERTEX 1
+#define EMPOSE_RENDER_COLOR_FRAME 2
+typedef struct {
+  int T, V, n_faces, H, W;
+  const float* vertices; const int* faces; const int* faces_host;
+  const float* normals; const float* colors; int color_mode;
+  const float* cam_R; const float* cam_t; int camera_per_frame;
+  float fx, fy, cx, cy, near;
+  float light[3]; float ambient; float background[3];
+  int slab_frames;
+  unsigned char* rgb; int* face_id; float* depth;
+} empose_render_desc;
+size_t empose_render_workspace_bytes(int T, int V, int H, int W);
+int empose_render_meshes(const empose_render_desc* desc, void* workspace, size_t workspace_bytes, empose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -125,10 +125,53 @@ def real_setup(args, device):
     return net, smpl, lengths, (lambda i: sample_to_batch(RealSample.from_npz_clean(files[i]))), str(args.model_id)
 
 
+def visualize(net, smpl, batch, device, args):
+    """`--visualize i`: the recording goes through the model once more, in chunks of 256 frames with the LSTM state
+    carried and the first chunk's shape for the whole recording, as the evaluation ran it; every `--visualize_stride`-th
+    frame is rendered on the device (em_pose_amd/vis) and written as an image."""
+    from em_pose_amd.eval.helpers import window_generator
+    from em_pose_amd.nn.models import IterativeErrorFeedback
+    from em_pose_amd.vis import MeshRenderer, save_frames
+    from em_pose_amd.vis.compare import render_comparison
+    say = lambda m: print(m, file=sys.stderr, flush=True)
+    if device.type != 'cuda' or smpl is None:
+        say('--visualize needs a GPU: the renderer is a HIP kernel and has no CPU path; nothing written')
+        return
+    stride = max(args.visualize_stride, 1)
+    rows = {k: [] for k in ('pose', 'root', 'pose_hat', 'root_hat')}
+    shape_hat = None
+    with torch.no_grad():
+        chunks = window_generator(batch, 256 if isinstance(net, IterativeErrorFeedback) else None)
+        for c, chunk in enumerate(chunks):
+            chunk = chunk.to_gpu(device)
+            out = net(chunk, is_new_sequence=(c == 0))
+            if c == 0:
+                shape_hat = out['shape_hat'][:, 0] if out['shape_hat'] is not None else chunk.shapes
+            rows['pose'].append(chunk.poses_body[0])
+            rows['root'].append(chunk.poses_root[0])
+            rows['pose_hat'].append(out['pose_hat'][0] if out['pose_hat'] is not None else chunk.poses_body[0])
+            rows['root_hat'].append(out['root_ori_hat'][0] if out['root_ori_hat'] is not None else chunk.poses_root[0])
+            shapes = chunk.shapes
+        every = {k: torch.cat(v)[::stride].contiguous().float() for k, v in rows.items()}
+        gt = {'poses_body': every['pose'], 'betas': shapes.reshape(1, -1).float(), 'poses_root': every['root']}
+        hat = {'poses_body': every['pose_hat'], 'betas': shape_hat.reshape(1, -1).float(), 'poses_root': every['root_hat']}
+        renderer = MeshRenderer(smpl, args.visualize_size, args.visualize_size)
+        rgb = render_comparison(renderer, gt, hat)
+    out_dir = args.visualize_dir or os.path.join('vis', str(batch.ids[0]))
+    paths = save_frames(out_dir, rgb, step=stride)
+    say('--visualize {}: {} frames of {} ({} in all) written to {}'.format(args.visualize, len(paths), batch.ids[0],
+                                                                        int(batch.seq_lengths[0]), out_dir))
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--model_id', type=int, default=1615631737, help='Which end-to-end model to evaluate.')
-    p.add_argument('--visualize', type=int, default=-1, help='(accepted for compatibility; not implemented)')
+    p.add_argument('--visualize', type=int, default=-1,
+                   help='Render recording i after the tables (needs a GPU): ground truth in grey beside the estimate coloured '
+                        'by its per-vertex error, one image per --visualize_stride frames. -1: nothing.')
+    p.add_argument('--visualize_stride', type=int, default=10, help='--visualize: every how many frames an image is written.')
+    p.add_argument('--visualize_dir', default=None, help='--visualize: where the images go (default ./vis/<recording id>).')
+    p.add_argument('--visualize_size', type=int, default=256, help='--visualize: height and width of each half, pixels.')
     p.add_argument('--cross_subject', action='store_true', help='Evaluate on hold-out subject 0715.')
     p.add_argument('--synthetic', action='store_true', help='Synthetic recordings / body model / weights.')
     p.add_argument('--n_markers', type=int, default=6)
@@ -246,6 +289,10 @@ def main():
                               'seconds_per_pass': passes, 'host_seconds_per_section_per_pass': host_times,
                               'metrics': metrics, 'headers': list(metrics.keys()),
                               'rows': [[r[0], str(r[1])] + [float(v) for v in r[2:]] for r in table]}))
+    if args.visualize in mine:    # the rank that owns the recording; everything it prints goes to stderr
+        visualize(net, smpl, batches[mine.index(args.visualize)], device, args)
+    elif args.visualize >= len(lengths) and rank == 0:
+        print('--visualize {}: there are only {} recordings'.format(args.visualize, len(lengths)), file=sys.stderr)
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
