@@ -273,6 +273,14 @@ SIGNATURES = {
     'empose_offset_stats': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4 +
                                      [C.c_void_p] * 3 + [C.c_int, C.c_void_p, C.c_void_p] + [C.c_void_p] * 5 +
                                      [C.c_void_p] * 2 + [C.c_void_p, C.c_size_t, C.c_void_p]),
+    'empose_placement_workspace_bytes': (C.c_size_t, [C.c_int] * 3),
+    # (T, V, vertices, M, p, masks; C and the candidate ids on the host and on the device; sums, counts; workspace, its
+    # bytes; stream)
+    'empose_placement_accumulate': (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p] +
+                                             [C.c_int, C.c_void_p, C.c_void_p] + [C.c_void_p] * 2 +
+                                             [C.c_void_p, C.c_size_t, C.c_void_p]),
+    # (M, C, sums, counts, the candidate ids on the device; score, best, best_score; stream)
+    'empose_placement_finish': (C.c_int, [C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_void_p]),
     'empose_profile_enable': (C.c_int, [C.c_int]),
     'empose_profile_enable_only': (C.c_int, [C.c_char_p]),
     'empose_profile_ntags': (C.c_int, []),

@@ -1,5 +1,6 @@
 // Launch interfaces of the kernels around the model: synthetic sensors, root frame, resampling, sensor noise, offset
-// statistics, metrics (sensor_sample.hip, root_frame.hip, resample.hip, sensor_noise.hip, offset_stats.hip, metrics.hip).
+// statistics, placement search, metrics (sensor_sample.hip, root_frame.hip, resample.hip, sensor_noise.hip,
+// offset_stats.hip, placement.hip, metrics.hip).
 // Internal, not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -108,6 +109,28 @@ struct OffsetStatsArgs {
   int n_chunks;                     // sum over the groups of ceil(n_frames / OFFSET_STATS_CHUNK)
 };
 hipError_t launch_offset_stats(const OffsetStatsArgs& a, hipStream_t stream);
+
+// Sensor placement search (placement.hip): which vertex does a sensor sit over?  Per sensor m and candidate vertex c, over
+// the frames of a group with mask == 1,
+//   score[m][c] = sum_f |p_f(m) - x_f(c)|^2 / n,   best[m] = the candidate with the lowest score (the lowest id on a tie).
+// A call accumulates one slab of T frames into running sums; groups and slabs are the caller's loop.
+constexpr int PLACEMENT_CHUNK = 64;     // frames per workgroup of the accumulation, counted from the slab's first frame
+constexpr int PLACEMENT_SENSORS = 12;   // sensors a lane carries at a time; more take another grid row
+struct PlacementArgs {
+  const float* vertices;   // [T][V][3]
+  const float* p;          // [T][M][3]
+  const float* masks;      // [T][M] or nullptr (every frame counts)
+  const int* cand;         // [C] ascending vertex ids, or nullptr (C == V, candidate c is vertex c)
+  double* part;            // [ceil(T / PLACEMENT_CHUNK)][M][C] the chunks' sums (accumulate only)
+  double* sums;            // [M][C] running sums of squared distances
+  int* counts;             // [M] running numbers of counting frames
+  float* score;            // finish: [M][C]
+  int* best;               // finish: [M] vertex id, -1 when no frame counts
+  float* best_score;       // finish: [M]
+  int T, V, M, C;
+};
+hipError_t launch_placement_accumulate(const PlacementArgs& a, hipStream_t stream);
+hipError_t launch_placement_finish(const PlacementArgs& a, hipStream_t stream);
 
 struct MetricsArgs {
   const float* joints_gt; const float* joints_hat;   // [T][22][3]

@@ -88,6 +88,62 @@ def r_spread_deg(r_trace):
     return np.degrees(np.arccos(np.clip((np.asarray(r_trace, dtype=np.float64) - 1.0) * 0.5, -1.0, 1.0)))
 
 
+def pooled_recordings(smpl_model, samples, subjects, m, normalized, device, who):
+    """What `estimate_offsets` and `search_placement` (data/placement.py) read of their recordings, a list of `RealSample`
+    in numpy form with `m` sensors each: the samples pooled by subject key -- in the order of the keys' first appearance,
+    in the given order within a key -- and concatenated along the frames.  Unless `normalized`, a copy of every sample
+    goes through `NormalizeRealMarkers`; the caller's arrays are not modified.  Returns a dict: device, keys, firsts and
+    per_subject (each key's first pooled frame and number of frames), lengths (frames per pooled sample) and the float32
+    arrays poses (T, 66), betas (T, 10: the sample's shape in every frame), pos (T, m, 3), ori (T, m, 3, 3), masks (T, m).
+    `who` names the caller in the errors."""
+    from em_pose_amd.data.transforms import NormalizeRealMarkers
+    from em_pose_amd.helpers.configuration import CONSTANTS as C
+    samples = list(samples)
+    if not samples:
+        raise ValueError('{} needs at least one recording'.format(who))
+    subjects = ['all'] * len(samples) if subjects is None else list(subjects)
+    if len(subjects) != len(samples):
+        raise ValueError('{} subject keys for {} samples'.format(len(subjects), len(samples)))
+    device = torch.device(smpl_model.bm.f.device if device is None else device)
+    if device.type != 'cuda':
+        raise _lib.EmposeError('{} needs a GPU (got device {}); there is no CPU fallback'.format(who, device))
+
+    keys = list(dict.fromkeys(subjects))
+    order = [i for k in keys for i in range(len(samples)) if subjects[i] == k]   # pooled by subject, given order within
+    if not normalized:
+        samples = [NormalizeRealMarkers()(copy.copy(s)) for s in samples]
+    for s in samples:
+        if np.asarray(s.marker_pos_real).shape[-1] != m * 3:
+            raise ValueError('recording {} has {} sensors, vertex_ids {}'.format(
+                s.id, np.asarray(s.marker_pos_real).shape[-1] // 3, m))
+    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
+    per_subject = [sum(samples[i].n_frames for i in order if subjects[i] == k) for k in keys]
+    return {
+        'device': device, 'keys': keys, 'per_subject': per_subject,
+        'firsts': np.concatenate([[0], np.cumsum(per_subject)[:-1]]),
+        'lengths': [samples[i].n_frames for i in order],
+        'poses': np.concatenate([f32(samples[i].smpl_poses)[:, :C.MAX_INDEX_ROOT_AND_BODY] for i in order]),
+        'betas': np.concatenate([np.repeat(f32(samples[i].smpl_shape).reshape(1, -1), samples[i].n_frames, axis=0)
+                                 for i in order]),
+        'pos': np.concatenate([f32(samples[i].marker_pos_real).reshape(-1, m, 3) for i in order]),
+        'ori': np.concatenate([f32(samples[i].marker_ori_real).reshape(-1, m, 3, 3) for i in order]),
+        'masks': np.concatenate([f32(samples[i].marker_masks).reshape(-1, m) for i in order])}
+
+
+def root_normalized_poses(smpl_model, rec, device):
+    """The pooled poses of `pooled_recordings` on the device, the root orientations of every sample relative to its first
+    (the root-frame kernel, one segment per sample): the frame `NormalizeRealMarkers` puts the readings in."""
+    from em_pose_amd.bodymodels.smpl import root_frame_fwd
+    poses_d = torch.from_numpy(rec['poses']).to(device)
+    at = 0
+    for n in rec['lengths']:
+        if n > 0:
+            seg = poses_d[at:at + n]
+            seg[:, :3] = root_frame_fwd(seg, None, n, _lib.RODRIGUES[smpl_model.rodrigues_convention])[0]
+        at += n
+    return poses_d
+
+
 def estimate_offsets(smpl_model, samples, subjects=None, vertex_ids=None, normalized=False, device=None,
                      per_frame=False):
     """
@@ -105,56 +161,21 @@ def estimate_offsets(smpl_model, samples, subjects=None, vertex_ids=None, normal
     the subject's n pooled frames.  Warns, and does not fail, about a sensor with fewer than two counting frames or a
     spread above 45 degrees.  `vertex_ids` defaults to CONSTANTS.VERTEX_IDS.
     """
-    from em_pose_amd.bodymodels.smpl import root_frame_fwd
-    from em_pose_amd.data.transforms import NormalizeRealMarkers
     from em_pose_amd.data.virtual_sensors import VirtualMarkerHelper
     from em_pose_amd.helpers.configuration import CONSTANTS as C
-    samples = list(samples)
-    if not samples:
-        raise ValueError('estimate_offsets needs at least one recording')
-    subjects = ['all'] * len(samples) if subjects is None else list(subjects)
-    if len(subjects) != len(samples):
-        raise ValueError('{} subject keys for {} samples'.format(len(subjects), len(samples)))
     vertex_ids = [int(v) for v in (C.VERTEX_IDS if vertex_ids is None else vertex_ids)]
     m = len(vertex_ids)
-    device = torch.device(smpl_model.bm.f.device if device is None else device)
-    if device.type != 'cuda':
-        raise _lib.EmposeError('estimate_offsets needs a GPU (got device {}); there is no CPU fallback'.format(device))
-
-    keys = list(dict.fromkeys(subjects))
-    order = [i for k in keys for i in range(len(samples)) if subjects[i] == k]   # pooled by subject, given order within
-    if not normalized:
-        samples = [NormalizeRealMarkers()(copy.copy(s)) for s in samples]
-    for s in samples:
-        if np.asarray(s.marker_pos_real).shape[-1] != m * 3:
-            raise ValueError('recording {} has {} sensors, vertex_ids {}'.format(
-                s.id, np.asarray(s.marker_pos_real).shape[-1] // 3, m))
-    lengths = [samples[i].n_frames for i in order]
-    t = int(sum(lengths))
-    f32 = lambda a: np.ascontiguousarray(a, dtype=np.float32)
-    poses = np.concatenate([f32(samples[i].smpl_poses)[:, :C.MAX_INDEX_ROOT_AND_BODY] for i in order])
-    betas = np.concatenate([np.repeat(f32(samples[i].smpl_shape).reshape(1, -1), samples[i].n_frames, axis=0)
-                            for i in order])
-    pos = np.concatenate([f32(samples[i].marker_pos_real).reshape(-1, m, 3) for i in order])
-    ori = np.concatenate([f32(samples[i].marker_ori_real).reshape(-1, m, 3, 3) for i in order])
-    masks = np.concatenate([f32(samples[i].marker_masks).reshape(-1, m) for i in order])
-    per_subject = [sum(samples[i].n_frames for i in order if subjects[i] == k) for k in keys]
-    firsts = np.concatenate([[0], np.cumsum(per_subject)[:-1]])
+    rec = pooled_recordings(smpl_model, samples, subjects, m, normalized, device, 'estimate_offsets')
+    device, keys, firsts, per_subject = rec['device'], rec['keys'], rec['firsts'], rec['per_subject']
     groups = np.stack([firsts, per_subject], axis=1)
 
     up = lambda a: torch.from_numpy(a).to(device)
     with torch.no_grad(), torch.cuda.device(device):
-        poses_d = up(poses)
-        at = 0
-        for n in lengths:   # the root orientations in the frame of the sample's first
-            if n > 0:
-                seg = poses_d[at:at + n]
-                seg[:, :3] = root_frame_fwd(seg, None, n, _lib.RODRIGUES[smpl_model.rodrigues_convention])[0]
-            at += n
+        poses_d = root_normalized_poses(smpl_model, rec, device)
         sub = smpl_model.sub_mesh(vertex_ids)
-        vertices, _ = sub(poses_body=poses_d[:, 3:], betas=up(betas), poses_root=poses_d[:, :3])
-        stats = offset_stats(VirtualMarkerHelper(sub), vertices, sub.local_ids(vertex_ids), up(pos), up(ori), up(masks),
-                             groups, per_frame=per_frame)
+        vertices, _ = sub(poses_body=poses_d[:, 3:], betas=up(rec['betas']), poses_root=poses_d[:, :3])
+        stats = offset_stats(VirtualMarkerHelper(sub), vertices, sub.local_ids(vertex_ids), up(rec['pos']), up(rec['ori']),
+                             up(rec['masks']), groups, per_frame=per_frame)
         host = {k: v.cpu().numpy() for k, v in stats.items()}
 
     out = {}

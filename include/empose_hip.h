@@ -703,6 +703,41 @@ int empose_offset_stats(int T, int V, const float* vertices, int M, int max_deg,
                         float* covs, float* r, float* r_trace, int* counts, float* local_f, float* q_f,
                         void* workspace, size_t workspace_bytes, empose_stream_t stream);
 
+/* ---- sensor placement search (the step before empose_offset_stats) -------------------------------------------------- */
+/* Which vertex does each sensor sit over?  The same recordings as empose_offset_stats, searched over the whole mesh
+ * (csrc/placement.hip).  The definition is this library's own; the reference has no such tool.  Per sensor m and candidate
+ * vertex c, over the n frames of a group in which the sensor was read, with p [T][M][3] the real reading and
+ * vertices [T][V][3] the ground-truth mesh in the same frame:
+ *   score[m][c] = sum_f |p_f(m) - x_f(c)|^2 / n   (m^2)        site[m] = argmin_c score[m][c], the lowest c on an exact tie
+ * which is what the offsets pay for a site: |means|^2 + (n - 1) / n trace(covs) of empose_offset_stats there.
+ *
+ * empose_placement_accumulate adds one slab of T frames of one group to the running sums [M][C] (float64, device) and
+ * counts [M] (int32, device), which the caller zeroes before a group's first slab; groups and slabs are the caller's loop.
+ * A frame counts for a sensor iff masks [T][M] reads 1 there (masks NULL: every frame counts); what p holds where it does not
+ * count is never used.  Candidates: cand NULL and C == V (candidate c is vertex c), or C strictly ascending vertex ids,
+ * given twice like the group table of empose_offset_stats: cand_host is checked here, cand_dev (the same C ids in device
+ * memory) is what the kernels read.  The difference and the square are fp32, every sum over frames float64, added in a
+ * fixed order without atomics: the slab in chunks of 64 frames counted from its first frame, the chunks in ascending
+ * order onto the running sum.  The same inputs in slabs of the same size give the same bits; other slab sizes agree to
+ * float64 rounding.
+ * Workspace: empose_placement_workspace_bytes(T, M, C) -- one double per sensor, candidate and chunk (0 for T, M or
+ * C <= 0).
+ * Returns EMPOSE_EINVAL, before any GPU work, for a NULL vertices, p, sums or counts, T, V, M or C <= 0, T * M or M * C above
+ * 2^31 - 1, T above 64 * 65535 (use slabs), only one of cand_host and cand_dev, C != V without a list, a list that is not
+ * strictly ascending within [0, V), or a workspace that is too small.
+ *
+ * empose_placement_finish turns the sums into score [M][C] (fp32; +inf where counts[m] == 0), best [M] (int32: the vertex
+ * id of the winning candidate, cand_dev[c] or c; -1 where counts[m] == 0) and best_score [M].  The argmin runs over the
+ * fp32 scores it writes, in a fixed order, and takes the lower id on equal scores.  cand_dev: the device list of the
+ * accumulation, or NULL.  Returns EMPOSE_EINVAL for a NULL sums, counts or output pointer, M or C <= 0, or M * C above
+ * 2^31 - 1. */
+size_t empose_placement_workspace_bytes(int T, int M, int C);
+int empose_placement_accumulate(int T, int V, const float* vertices, int M, const float* p, const float* masks, int C,
+                                const int* cand_host, const int* cand_dev, double* sums, int* counts, void* workspace,
+                                size_t workspace_bytes, empose_stream_t stream);
+int empose_placement_finish(int M, int C, const double* sums, const int* counts, const int* cand_dev, float* score,
+                            int* best, float* best_score, empose_stream_t stream);
+
 /* ---- optional per-launch timing ------------------------------------------------------------------------------- */
 /* While enabled, every kernel launch issued by the entry points above is bracketed by HIP events on the launch stream
  * and attributed to one of empose_profile_ntags() categories (GEMMs by role, LSTM step, chain kernel, ...).

@@ -6,12 +6,19 @@ HIP, csrc/offset_stats.hip) and writes one `<subject>_offsets.npz` per subject -
 
     python scripts/estimate_offsets.py --recordings DIR --out DIR [--smpl_model model.npz] [--subject_from_id REGEX]
     python scripts/estimate_offsets.py --synthetic --out DIR
+    python scripts/estimate_offsets.py --recordings DIR --out DIR --search_placement [--exclude_hands]
 
 `--recordings`: a directory of `*_clean.npz` recordings (real sensor readings with ground-truth SMPL parameters).  The
 recordings are grouped by subject: the part of the recording id before the first `_`, or the first group (or the whole
 match) of `--subject_from_id`.  `--synthetic` needs no data: a few `synthetic.make_sequence` recordings of two subjects on
 the stand-in body model.  Per sensor the script prints the number of frames, |means| in mm, sqrt(trace covs) in mm and
 the spread of the rotational offsets in degrees.
+
+`--search_placement` first searches the mesh for the sites of the sensors (em_pose_amd/data/placement.py; the search runs in
+HIP, csrc/placement.hip), all recordings pooled: per sensor it prints the vertex the readings are closest to, its rms
+distance in mm, the runner-up with its rms, and whether the site is CONSTANTS.VERTEX_IDS[m].  The offsets are then
+estimated at the found sites and the files carry them as `vertex_ids`.  `--exclude_hands` leaves the vertices skinned to
+the finger joints out of the search.
 """
 import argparse
 import glob
@@ -66,7 +73,30 @@ def synthetic_recordings(smpl, device):
     return samples, subjects
 
 
-def main():
+def search_sites(smpl, samples, exclude_hands, device):
+    """The sites of the sensors, all recordings pooled, printed per sensor; a sensor without a site ends the script."""
+    from em_pose_amd.data.placement import candidates_excluding_bones, search_placement
+    from em_pose_amd.helpers.configuration import CONSTANTS
+    candidates = None
+    if exclude_hands:
+        candidates = candidates_excluding_bones(smpl, range(CONSTANTS.N_JOINTS + 1, smpl.n_joints))
+        print('searching {} of {} vertices (hands excluded)'.format(len(candidates), smpl.n_vertices))
+    found = search_placement(smpl, samples, candidates=candidates, device=device)['all']
+    print('placement of {} sensors from {} recording(s)'.format(len(found['vertex_ids']), len(samples)))
+    print('  {:>6} {:>8} {:>8} {:>10} {:>10} {:>14} {:>10}'.format('sensor', 'n', 'site', 'rms mm', 'runner-up', 'runner-up mm',
+                                                                  'default'))
+    for m, site in enumerate(found['vertex_ids']):
+        default = CONSTANTS.VERTEX_IDS[m] if m < len(CONSTANTS.VERTEX_IDS) else None
+        print('  {:>6} {:>8} {:>8} {:>10.2f} {:>10} {:>14.2f} {:>10}'.format(
+            m, int(found['counts'][m]), int(site), float(found['rms_mm'][m]), int(found['runner_up_ids'][m]),
+            float(found['runner_up_rms_mm'][m]), 'same' if default == int(site) else 'was {}'.format(default)))
+    if (found['vertex_ids'] < 0).any():
+        raise SystemExit('sensors {} were read in no frame: no site, no offsets'.format(
+            np.nonzero(found['vertex_ids'] < 0)[0].tolist()))
+    return [int(v) for v in found['vertex_ids']]
+
+
+def arg_parser():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument('--recordings', default=None, help='directory of *_clean.npz recordings')
     p.add_argument('--out', required=True, help='directory for the <subject>_offsets.npz files')
@@ -75,8 +105,18 @@ def main():
                    help='the subject of a recording: first group (or the match) of REGEX in its id; default: the id up to '
                         'the first "_"')
     p.add_argument('--synthetic', action='store_true', help='synthetic recordings on the stand-in body model')
+    p.add_argument('--search_placement', action='store_true',
+                   help='search the mesh for the sites of the sensors first and estimate the offsets there')
+    p.add_argument('--exclude_hands', action='store_true',
+                   help='with --search_placement: leave out the vertices skinned to the finger joints')
     p.add_argument('--device', default='cuda:0')
-    args = p.parse_args()
+    return p
+
+
+def main():
+    args = arg_parser().parse_args()
+    if args.exclude_hands and not args.search_placement:
+        raise SystemExit('--exclude_hands goes with --search_placement')
     if not args.synthetic and not args.recordings:
         raise SystemExit('pass --recordings DIR or --synthetic')
     if not torch.cuda.is_available():
@@ -91,7 +131,8 @@ def main():
             raise SystemExit('no *_clean.npz files in {}'.format(args.recordings))
         samples = [RealSample.from_npz_clean(f) for f in files]
         subjects = [subject_of(s.id, args.subject_from_id) for s in samples]
-    estimates = estimate_offsets(smpl, samples, subjects=subjects, device=device)
+    vertex_ids = search_sites(smpl, samples, args.exclude_hands, device) if args.search_placement else None
+    estimates = estimate_offsets(smpl, samples, subjects=subjects, vertex_ids=vertex_ids, device=device)
     os.makedirs(args.out, exist_ok=True)
     for subject, est in estimates.items():
         path = os.path.join(args.out, '{}_offsets.npz'.format(subject))
