@@ -144,6 +144,21 @@ class RenderDesc(C.Structure):   # empose_render_desc
                 ('rgb', C.c_void_p), ('face_id', C.c_void_p), ('depth', C.c_void_p)]
 
 
+OVERLAY_MAX_PRIMS = 4096   # EMPOSE_OVERLAY_MAX_PRIMS
+
+
+class OverlayDesc(C.Structure):   # empose_overlay_desc
+    _fields_ = [('T', C.c_int), ('P', C.c_int), ('H', C.c_int), ('W', C.c_int),
+                ('seg_a', C.c_void_p), ('seg_b', C.c_void_p), ('radius', C.c_void_p), ('radius_per_frame', C.c_int),
+                ('colors', C.c_void_p),
+                ('cam_R', C.c_void_p), ('cam_t', C.c_void_p), ('camera_per_frame', C.c_int),
+                ('fx', C.c_float), ('fy', C.c_float), ('cx', C.c_float), ('cy', C.c_float), ('near', C.c_float),
+                ('light', C.c_float * 3), ('ambient', C.c_float), ('hidden_alpha', C.c_float),
+                ('mesh_depth', C.c_void_p),
+                ('slab_frames', C.c_int),
+                ('rgb', C.c_void_p), ('prim_id', C.c_void_p), ('prim_depth', C.c_void_p)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests check against the header.
 SIGNATURES = {
     'empose_last_error': (C.c_char_p, []),
@@ -332,6 +347,8 @@ SIGNATURES = {
     'empose_sensor_fit_step': (C.c_int, [C.c_void_p, C.POINTER(FitIO), C.c_int] + [C.c_void_p] * 18 + [C.c_void_p]),
     'empose_render_workspace_bytes': (C.c_size_t, [C.c_int] * 4),
     'empose_render_meshes': (C.c_int, [C.POINTER(RenderDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'empose_render_overlay_workspace_bytes': (C.c_size_t, [C.c_int] * 4),
+    'empose_render_overlay': (C.c_int, [C.POINTER(OverlayDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

@@ -39,7 +39,8 @@ class MeshRenderer(object):
             self._faces_dev = torch.from_numpy(self._faces_host).to(device)
         return self._faces_host, self._faces_dev
 
-    def render(self, vertices, normals='smooth', colors=None, return_buffers=False, camera=None):
+    def render(self, vertices, normals='smooth', colors=None, return_buffers=False, camera=None, overlays=None,
+               hidden_alpha=0.0):
         """
         :param vertices: (T, V, 3) float32 on the device.
         :param normals: 'smooth' (`layer.vertex_normals(vertices)`), 'flat' (face normals) or a (T, V, 3) tensor of
@@ -47,7 +48,18 @@ class MeshRenderer(object):
         :param colors: None (the renderer's colour), an RGB triple, (V, 3) or (T, V, 3), values in [0, 1].
         :return: rgb uint8 (T, H, W, 3) on the device; with `return_buffers` also face_id int32 (T, H, W), -1 where no
           face covers the pixel, and depth float32 (T, H, W), +inf there.
+        :param overlays: None, or `vis.overlay.Primitives` (or a list of them) of the same T frames, drawn into the
+          images with `vis.overlay.draw_primitives` and depth-tested against the mesh; face_id and depth stay the mesh's.
+        :param hidden_alpha: how much of an overlay shows through the mesh that hides it (0: not at all).
         """
+        if overlays is not None:
+            from em_pose_amd.vis.overlay import Primitives, draw_primitives
+            rgb, face_id, depth = self.render(vertices, normals=normals, colors=colors, return_buffers=True, camera=camera)
+            if rgb.shape[0]:
+                draw_primitives(rgb, Primitives.cat(overlays), camera if camera is not None else self.camera, depth=depth,
+                                hidden_alpha=hidden_alpha, light=self.light, ambient=self.ambient,
+                                slab_frames=self.slab_frames)
+            return (rgb, face_id, depth) if return_buffers else rgb
         if not torch.is_tensor(vertices) or not vertices.is_cuda:
             raise _lib.EmposeError('MeshRenderer needs GPU tensors; there is no CPU fallback')
         if vertices.dim() != 3 or vertices.shape[2] != 3:
@@ -113,16 +125,20 @@ class MeshRenderer(object):
         return colors, modes[tuple(colors.shape)]
 
     def render_bodies(self, poses_body, betas, poses_root=None, trans=None, normals='smooth', colors=None,
-                      return_buffers=False, camera=None):
+                      return_buffers=False, camera=None, overlays=None, hidden_alpha=0.0):
         """`layer.forward` and, for smooth shading, `layer.vertex_normals`, then `render`.  Without a camera anywhere,
-        the first call fits one to its joints and keeps it."""
+        the first call fits one to its joints and keeps it.  `overlays`: as `render`, or a function of (vertices, joints)
+        that returns them."""
         if not poses_body.is_cuda:
             raise _lib.EmposeError('MeshRenderer needs GPU tensors; there is no CPU fallback')
         with torch.no_grad():
             vertices, joints = self.layer(poses_body=poses_body, betas=betas, poses_root=poses_root, trans=trans)
         if camera is None and self.camera is None:
             self.camera = fit_camera(joints, self.width, self.height)
-        return self.render(vertices, normals=normals, colors=colors, return_buffers=return_buffers, camera=camera)
+        if callable(overlays):
+            overlays = overlays(vertices, joints)
+        return self.render(vertices, normals=normals, colors=colors, return_buffers=return_buffers, camera=camera,
+                           overlays=overlays, hidden_alpha=hidden_alpha)
 
 
 def error_colors(vertices, vertices_hat, max_mm=100.0):

@@ -1080,6 +1080,56 @@ typedef struct {
 size_t empose_render_workspace_bytes(int T, int V, int H, int W);
 int empose_render_meshes(const empose_render_desc* desc, void* workspace, size_t workspace_bytes, empose_stream_t stream);
 
+/* ---- overlay primitives in rendered frames (new in this library) -------------------------------- */
+/* A per-pixel analytic ray caster that draws thin solid primitives -- a skeleton, sensor tripods, residuals -- into the
+ * frames empose_render_meshes produced, depth-tested against the mesh (csrc/overlay.hip: two launches per slab of frames,
+ * no atomics).  The definition is this library's own:
+ *   primitive one type, the CAPSULE: all points within `radius` of the segment a - b, world coordinates.  a == b in all
+ *             three components is a sphere.  A frame has P of them: seg_a, seg_b [T][P][3], radius [P] or, radius_per_frame
+ *             != 0, [T][P], colors [P][3] in [0, 1].  A primitive is SKIPPED in a frame when its radius there is not > 0 or
+ *             a component of a, b or the radius is not finite (how a missing sensor is left out: radius 0).
+ *   camera    that of empose_render_meshes: p_c = R p + t, one camera or one per frame; the ray of the pixel of row i,
+ *             column j is s d with d = ((j + 0.5 - cx) / fx, (i + 0.5 - cy) / fy, 1), so the ray parameter s IS camera-space
+ *             Z, the quantity empose_render_meshes writes to `depth`.
+ *   hit       of one primitive at one pixel: where the ray enters the union of the sphere about a_c, the sphere about b_c
+ *             and the open side surface of the cylinder between them -- the smaller root of each quadratic where its
+ *             discriminant is >= 0; the side root only where the leading coefficient is > 0 and the axial coordinate of
+ *             the hit lies strictly inside (0, |b - a|^2); s is the smallest of those that exist (a sphere has the one).
+ *             s <= near: the primitive does not cover the pixel (no clipping, no view from inside).  The quadratics are
+ *             formed about the point of the ray at the depth of the segment's midpoint, not about the eye.
+ *   pixel     (s*, id*) is the lexicographic minimum of (s, primitive index) over the frame's primitives: the nearest wins,
+ *             the lower index an exact tie.  prim_id = id* or -1, prim_depth = s* or +inf (both optional, both independent
+ *             of the mesh).  Without a hit rgb keeps its bytes.  Else n = (hit point - nearest point of the segment) /
+ *             radius in camera space and c = colour (ambient + (1 - ambient) |n . l|), `light` as for the mesh.  The hit
+ *             is VISIBLE when mesh_depth is NULL or s* < mesh_depth there, strictly (a tie goes to the mesh; +inf never
+ *             hides): rgb = clamp(floor(255 c + 0.5)).  Hidden: rgb = clamp(floor((1 - alpha) rgb + alpha 255 c + 0.5))
+ *             with alpha = hidden_alpha; 0 leaves the bytes as they are (the plain depth test), 1 gives what no
+ *             mesh_depth gives (x-ray).  Only the nearest primitive is considered: there are no layers.
+ * Every pixel depends on its own frame alone, nothing is summed: a second call gives the same bits, and a frame gives the
+ * same bits alone, inside a batch and on either side of a slab edge.  P is at most EMPOSE_OVERLAY_MAX_PRIMS, H and W at
+ * most EMPOSE_RENDER_MAX_IMAGE.  Frames go in slabs (slab_frames of them, 0: what fits 16 MB of workspace, at most 4096; a
+ * larger value is lowered to that), so empose_render_overlay_workspace_bytes(T, P, H, W) -- the camera-space primitives
+ * and their screen boxes of one slab; 0 for sizes the call refuses -- is bounded whatever T is.  The screen boxes only
+ * bound the work (they are conservative) and are no part of the definition.
+ * All pointers are device memory.  The call is asynchronous on `stream`: it never synchronises, allocates or copies.
+ * Returns EMPOSE_EINVAL, before any GPU work, for a NULL descriptor, seg_a, seg_b, radius, colors, cam_R, cam_t, rgb or
+ * workspace, T, P, H or W <= 0, P or the image above its cap, hidden_alpha or ambient outside [0, 1], fx, fy, cx, cy not
+ * finite or fx, fy zero, near <= 0 or not finite, a zero or non-finite light, slab_frames < 0 and a workspace that is too
+ * small. */
+#define EMPOSE_OVERLAY_MAX_PRIMS 4096
+typedef struct {
+  int T, P, H, W;
+  const float* seg_a; const float* seg_b; const float* radius; int radius_per_frame; const float* colors;
+  const float* cam_R; const float* cam_t; int camera_per_frame;
+  float fx, fy, cx, cy, near;
+  float light[3]; float ambient; float hidden_alpha;
+  const float* mesh_depth;
+  int slab_frames;
+  unsigned char* rgb; int* prim_id; float* prim_depth;
+} empose_overlay_desc;
+size_t empose_render_overlay_workspace_bytes(int T, int P, int H, int W);
+int empose_render_overlay(const empose_overlay_desc* desc, void* workspace, size_t workspace_bytes, empose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,7 +10,10 @@ no OpenGL).
 An AMASS-style file holds `poses` (T, >= 66: root, then 21 body joints, axis-angle), `betas` (>= 10) and optionally
 `trans` (T, 3); `smpl_poses` / `smpl_shape` / `smpl_trans` of a `*_clean.npz` recording are read as well.  With
 `--side_by_side` the first body is drawn in grey on the left and the second on the right, coloured by its per-vertex
-distance to the first.  Images are PNG where PIL is installed, binary PPM otherwise.
+distance to the first.  `--skeleton` draws the joints and bones into every body and `--sensors` the virtual sensors of
+the rendered body (VirtualMarkerHelper at the 12 sensor vertices) as tripods, both by the overlay ray caster
+(em_pose_amd/vis/overlay.py); `--xray ALPHA` is how much of them shows through the surface that hides them (default 0.6
+with --skeleton, which lies inside the body, else 0).  Images are PNG where PIL is installed, binary PPM otherwise.
 """
 import argparse
 import os
@@ -62,6 +65,10 @@ def main():
     p.add_argument('--width', type=int, default=256)
     p.add_argument('--height', type=int, default=256)
     p.add_argument('--shading', default='smooth', choices=['smooth', 'flat'])
+    p.add_argument('--skeleton', action='store_true', help='Draw the skeleton: a capsule per bone, a sphere per joint.')
+    p.add_argument('--sensors', action='store_true', help='Draw the virtual sensors of the rendered body as tripods.')
+    p.add_argument('--xray', type=float, default=None, metavar='ALPHA',
+                   help='How much of an overlay shows through the surface that hides it, 0 .. 1 (default 0.6 with --skeleton, else 0).')
     p.add_argument('--sheet', type=int, default=0, metavar='COLUMNS', help='Also write one contact sheet with this many columns.')
     args = p.parse_args()
     if args.synthetic == (args.npz is not None):
@@ -74,6 +81,9 @@ def main():
     from em_pose_amd.bodymodels.smpl import SMPLLayer, create_default_smpl_model
     from em_pose_amd.vis import MeshRenderer, contact_sheet, fit_camera, save_frames, save_image
     from em_pose_amd.vis.compare import render_comparison
+    xray = args.xray if args.xray is not None else (0.6 if args.skeleton else 0.0)
+    if not 0.0 <= xray <= 1.0:
+        raise SystemExit('--xray must lie inside [0, 1]')
     if args.synthetic:
         from em_pose_amd import synthetic
         layer = SMPLLayer(synthetic.make_model()).to(device)
@@ -88,8 +98,39 @@ def main():
     stride = max(args.stride, 1)
     cut = lambda d: {k: (v[::stride].contiguous() if k != 'betas' else v) for k, v in d.items()}
     renderer = MeshRenderer(layer, args.width, args.height)
+
+    def overlays_of(vertices, joints):
+        """The overlays of posed bodies: the skeleton from the joints, the virtual sensors from the mesh."""
+        from em_pose_amd.bodymodels.tables import model_parents
+        from em_pose_amd.data.virtual_sensors import VirtualMarkerHelper
+        from em_pose_amd.helpers.configuration import CONSTANTS as C
+        from em_pose_amd.vis import sensor_primitives, skeleton_primitives
+        out = []
+        if args.skeleton:
+            out.append(skeleton_primitives(joints, model_parents(layer.model)))
+        if args.sensors:
+            pos, ori, _ = VirtualMarkerHelper(layer).get_virtual_pos_and_rot(vertices, C.VERTEX_IDS)
+            out.append(sensor_primitives(pos, ori))
+        return out or None
+
+    def overlays_all(d):
+        if not (args.skeleton or args.sensors):
+            return None
+        T = d['poses_body'].shape[0]
+        parts = []
+        with torch.no_grad():
+            for t0 in range(0, T, 64):
+                parts.append(overlays_of(*layer(**{k: (v[t0:t0 + 64] if v.shape[0] == T else v) for k, v in d.items()})))
+        from em_pose_amd.vis import Primitives
+        whole = [Primitives.cat(p) for p in parts]
+        return Primitives(torch.cat([p.a for p in whole]), torch.cat([p.b for p in whole]),
+                          torch.cat([p.radius if p.radius.dim() == 2 else p.radius.expand(p.n_frames, -1) for p in whole]),
+                          whole[0].colors)
+
     if other is not None:
-        rgb = render_comparison(renderer, cut(body), cut(other))
+        body, other = cut(body), cut(other)
+        rgb = render_comparison(renderer, body, other, overlays=overlays_all(body), overlays_hat=overlays_all(other),
+                                hidden_alpha=xray)
     else:
         body = cut(body)
         T = body['poses_body'].shape[0]
@@ -98,7 +139,8 @@ def main():
             renderer.camera = fit_camera(layer.fk_joints(**body), args.width, args.height)
         for t0 in range(0, T, 64):
             part = {k: (v[t0:t0 + 64] if k != 'betas' else v) for k, v in body.items()}
-            parts.append(renderer.render_bodies(normals=args.shading, **part))
+            parts.append(renderer.render_bodies(normals=args.shading, hidden_alpha=xray,
+                                                overlays=overlays_of if args.skeleton or args.sensors else None, **part))
         rgb = torch.cat(parts)
     paths = save_frames(args.out, rgb, step=stride)
     if args.sheet > 0 and len(paths):
