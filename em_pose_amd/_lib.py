@@ -145,6 +145,8 @@ class RenderDesc(C.Structure):   # empose_render_desc
 
 
 OVERLAY_MAX_PRIMS = 4096   # EMPOSE_OVERLAY_MAX_PRIMS
+TEMPORAL_SEGMENT = 32      # EMPOSE_TEMPORAL_SEGMENT: frames per segment of csrc/temporal.hip
+TEMPORAL_ACC, TEMPORAL_JERK = 1, 2   # EMPOSE_TEMPORAL_*: bits of `defined`
 
 
 class OverlayDesc(C.Structure):   # empose_overlay_desc
@@ -310,6 +312,8 @@ SIGNATURES = {
                                           C.c_size_t, C.c_void_p]),
     'empose_metrics_rows': (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                        C.c_void_p, C.c_void_p]),
+    # (N, F, P, x_gt, x_hat, valid, fps, reduce, rows, defined, stream)
+    'empose_temporal_rows': (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_double, C.c_int] + [C.c_void_p] * 3),
     'empose_mesh_vertices_fwd': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'empose_mesh_vertices_fwd_bf16x3': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

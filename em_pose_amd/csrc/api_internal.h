@@ -1,4 +1,4 @@
-// What the pieces of the C ABI (api.hip, api_model.hip, api_lstm.hip, api_train.hip, api_mesh.hip, api_fit.hip) share: the error
+// What the pieces of the C ABI (api.hip, api_model.hip, api_lstm.hip, api_train.hip, api_mesh.hip, api_fit.hip, ...) share: the error
 // state, the profiler, workspace carving and upload, the packed model, and the LSTM dispatcher.  Host code only.
 #pragma once
 #include "../../include/empose_hip.h"

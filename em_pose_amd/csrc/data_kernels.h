@@ -1,6 +1,6 @@
 // Launch interfaces of the kernels around the model: synthetic sensors, root frame, resampling, sensor noise, offset
-// statistics, placement search, metrics (sensor_sample.hip, root_frame.hip, resample.hip, sensor_noise.hip,
-// offset_stats.hip, placement.hip, metrics.hip).
+// statistics, placement search, metrics, temporal metrics (sensor_sample.hip, root_frame.hip, resample.hip,
+// sensor_noise.hip, offset_stats.hip, placement.hip, metrics.hip, temporal.hip).
 // Internal, not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -140,5 +140,22 @@ struct MetricsArgs {
   int T;
 };
 hipError_t launch_metrics_rows(const MetricsArgs& a, hipStream_t stream);
+
+// Temporal metrics (temporal.hip): backward second and third differences of two point trajectories over ragged sequences,
+//   acc[t] = (x[t] - 2 x[t-1] + x[t-2]) fps^2,   jerk[t] = (x[t] - 3 x[t-1] + 3 x[t-2] - x[t-3]) fps^3,
+// each defined where all of its frames count (valid != 0) -- never across a frame that does not, never across two rows.
+// Per (frame, point): |acc_gt - acc_hat|, |jerk_hat|, |jerk_gt|, float64 from float32 inputs.
+constexpr int TEMPORAL_SEGMENT = 32;   // EMPOSE_TEMPORAL_SEGMENT (include/empose_hip.h): frames a lane walks after its lead-in
+constexpr int TEMPORAL_DEFINED_ACC = 1, TEMPORAL_DEFINED_JERK = 2;   // bits of `defined`
+struct TemporalArgs {
+  const float* x_gt; const float* x_hat;   // [N][F][P][3]
+  const unsigned char* valid;              // [N][F]
+  double* rows;                            // reduce == 0: [N * F][3 P]; reduce == 1: [N * F][6] sums and sums of squares
+  unsigned char* defined;                  // [N][F]
+  double fps2, fps3;                       // fps^2, fps^3
+  int N, F, P, reduce;
+};
+long temporal_rows_blocks(int N, int F, int P, int reduce);   // workgroups of the launch
+hipError_t launch_temporal_rows(const TemporalArgs& a, hipStream_t stream);
 
 }  // namespace empose

@@ -7,25 +7,25 @@
 
 namespace empose {
 
-template <int N, int OFF, int CAP>
+template <int N, int OFF, int CAP, typename T = float>   // T: float or double
 struct LaneReduceScatter {   // v[0 .. N) summed over lanes; on return the lane holds sums base .. base + count - 1 of the original N
-  static __device__ __forceinline__ void run(float (&v)[CAP], int lane, int& base, int& count) {
+  static __device__ __forceinline__ void run(T (&v)[CAP], int lane, int& base, int& count) {
     if constexpr (OFF == 0) {
       count = N;
     } else if constexpr (N % 2 == 0) {
       const bool up = (lane & OFF) != 0;
 #pragma unroll
       for (int i = 0; i < N / 2; ++i) {
-        const float send = up ? v[i] : v[i + N / 2];
-        const float keep = up ? v[i + N / 2] : v[i];
+        const T send = up ? v[i] : v[i + N / 2];
+        const T keep = up ? v[i + N / 2] : v[i];
         v[i] = keep + __shfl_xor(send, OFF, 64);
       }
       base += up ? N / 2 : 0;
-      LaneReduceScatter<N / 2, OFF / 2, CAP>::run(v, lane, base, count);
+      LaneReduceScatter<N / 2, OFF / 2, CAP, T>::run(v, lane, base, count);
     } else {
 #pragma unroll
       for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], OFF, 64);
-      LaneReduceScatter<N, OFF / 2, CAP>::run(v, lane, base, count);
+      LaneReduceScatter<N, OFF / 2, CAP, T>::run(v, lane, base, count);
     }
   }
 };

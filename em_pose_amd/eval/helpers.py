@@ -102,13 +102,16 @@ def get_model_config(model_id):
     return Configuration.from_json(os.path.join(model_dir, 'config.json')), model_dir
 
 
-def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, device=None, vertex_engine=None):
+def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, device=None, vertex_engine=None,
+             temporal_engine=None):
     """
     Losses and metrics over a hold-out set (reference eval/helpers.py:51-111): every batch is normalised as a whole,
     cut into temporal chunks (`window_size`, single-recording `RealBatch`es only, as in the reference), preprocessed,
     run through the model with the LSTM state carried over the chunks, and fed to the metrics engine with the shape of
     the first chunk.  `vertex_engine` (optional, eval/mesh_metrics.py `VertexErrorEngine`) is reset and fed beside the
     metrics engine, with the same tensors and the first chunk's shape: the per-vertex error of the same frames.
+    `temporal_engine` (optional, eval/temporal_metrics.py `TemporalMetricsEngine`) likewise, with `is_new_sequence` as the
+    model gets it: the acceleration error and the jitter over the same frames, the stencils carried across the chunks.
     :return: dict of loss values averaged over the samples of the set.
     """
     device = C.DEVICE if device is None else device
@@ -119,6 +122,8 @@ def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, 
     metrics_engine.reset()
     if vertex_engine is not None:
         vertex_engine.reset()
+    if temporal_engine is not None:
+        temporal_engine.reset()
     try:
         with torch.no_grad():
             for b, abatch in enumerate(data_loader):
@@ -139,6 +144,10 @@ def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, 
                         vertex_engine.compute(chunk.poses_body, chunk.shapes, pose_hat, first_shape_hat,
                                               chunk.seq_lengths, chunk.poses_root, out['root_ori_hat'],
                                               frame_mask=chunk.marker_masks)
+                    if temporal_engine is not None:
+                        temporal_engine.compute(chunk.poses_body, chunk.shapes, pose_hat, first_shape_hat,
+                                                chunk.seq_lengths, chunk.poses_root, out['root_ori_hat'],
+                                                frame_mask=chunk.marker_masks, is_new_sequence=(i == 0))
                     n_chunks, bs = i + 1, chunk.batch_size
                 for k, v in seq_vals.items():
                     agg[k] += v / n_chunks * bs
@@ -149,10 +158,13 @@ def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, 
 
 
 def compute_loss_and_metrics(data_loader, net, preprocess_fn, model_id, smpl_model=None, device=None,
-                             vertex_error=False, vertex_error_procrustes=False):
+                             vertex_error=False, vertex_error_procrustes=False, temporal=False,
+                             temporal_surface=False):
     """reference eval/helpers.py:114-128.  `vertex_error` (not in the reference): also accumulate the per-vertex error
     (eval/mesh_metrics.py) and print it as a second table line, with `vertex_error_procrustes` the Procrustes-aligned
-    error in the same line; the returned values are the same either way."""
+    error in the same line.  `temporal` (not in the reference): also accumulate the acceleration error and the jitter
+    (eval/temporal_metrics.py) and print them as a further table line, with `temporal_surface` the surface columns in the
+    same line.  The returned values are the same either way."""
     if smpl_model is None:
         from em_pose_amd.bodymodels.smpl import create_default_smpl_model
         smpl_model = create_default_smpl_model(device)
@@ -161,12 +173,18 @@ def compute_loss_and_metrics(data_loader, net, preprocess_fn, model_id, smpl_mod
     if vertex_error:
         from em_pose_amd.eval.mesh_metrics import VertexErrorEngine
         ve = VertexErrorEngine(smpl_model, procrustes=vertex_error_procrustes)
-    losses = evaluate(data_loader, net, preprocess_fn, me, device=device, vertex_engine=ve)
+    te = None
+    if temporal or temporal_surface:
+        from em_pose_amd.eval.temporal_metrics import TemporalMetricsEngine
+        te = TemporalMetricsEngine(smpl_model, surface=temporal_surface)
+    losses = evaluate(data_loader, net, preprocess_fn, me, device=device, vertex_engine=ve, temporal_engine=te)
     print('[LOSS] loss: {:.6f}'.format(losses['total_loss']))
     metrics = me.get_metrics()
     print(me.to_pretty_string(metrics, model_id))
     if ve is not None:
         print(ve.to_pretty_string(ve.get_metrics(), model_id))
+    if te is not None:
+        print(te.to_pretty_string(te.get_metrics(), model_id))
     return losses, metrics
 
 

@@ -968,6 +968,31 @@ int empose_sensor_noise(int mode, int N, int F, int M, int K, int window_len, co
 int empose_metrics_rows(int T, const float* joints_gt, const float* joints_hat, const float* pose_gt,
                         const float* pose_hat, const int* parents_host, double* rows, empose_stream_t stream);
 
+/* ---- temporal metrics (new in this library) ---------------------------------------------------- */
+/* Acceleration error and jitter of two point trajectories over a ragged batch of sequences (csrc/temporal.hip).  The
+ * definitions are this library's own; the reference has no temporal metric.  x_gt, x_hat [N][F][P][3] (fp32, metres,
+ * contiguous), valid [N][F] (non-zero where the frame counts), fps frames per second.  Backward stencils, per row:
+ *   acc[t]  = (x[t] - 2 x[t-1] + x[t-2]) fps^2               defined where frames t-2 .. t all count
+ *   jerk[t] = (x[t] - 3 x[t-1] + 3 x[t-2] - x[t-3]) fps^3    defined where frames t-3 .. t all count
+ * A stencil never reaches across a frame that does not count and never across two rows; what the inputs hold at a frame
+ * that does not count is never used.  defined [N][F]: bit 0 (EMPOSE_TEMPORAL_ACC) acc is defined at the frame, bit 1
+ * (EMPOSE_TEMPORAL_JERK) jerk is.
+ *   reduce = 0: rows [N * F][3 P] float64 -- |acc_gt - acc_hat| per point (m/s^2), then |jerk_hat| per point, then
+ *               |jerk_gt| per point (m/s^3)
+ *   reduce = 1: rows [N * F][6] float64 -- for each of the three quantities the sum over the P points and the sum of
+ *               squares, added in an order fixed by P alone, without atomics
+ * Undefined entries are written as 0; every element of rows and defined is written by every call.  Every difference,
+ * product and norm is float64 on the fp32 inputs, without fused multiply-adds.  A frame's row depends only on its own four
+ * frames: two calls, or a call on a slab that holds those frames, give the same bits.  The time axis is walked in segments
+ * of EMPOSE_TEMPORAL_SEGMENT frames, each after three frames of lead-in.  F < 3 is legal and yields nothing defined.
+ * Returns EMPOSE_EINVAL, before any GPU work, for N, F or P <= 0, a NULL pointer, fps <= 0 or not finite, reduce other
+ * than 0 or 1, or N * F (or the launch's workgroups) above 2^31 - 1. */
+#define EMPOSE_TEMPORAL_SEGMENT 32
+#define EMPOSE_TEMPORAL_ACC 1
+#define EMPOSE_TEMPORAL_JERK 2
+int empose_temporal_rows(int N, int F, int P, const float* x_gt, const float* x_hat, const unsigned char* valid, double fps,
+                         int reduce, double* rows, unsigned char* defined, empose_stream_t stream);
+
 /* ---- model-free sensor fitting (new in this library) ------------------------------------------- */
 /* A pose per frame and a shape per window (or per frame) from sensor readings alone: K steps of Adam on, per window w
  * of F frames with live_t = [t < seq_length],

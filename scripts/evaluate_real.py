@@ -21,6 +21,10 @@ the reference's `C.DEVICE` fallback (reference configuration.py:23, scripts/eval
 Only that model has a CPU path (the LGD models are the HIP path and refuse CPU tensors); without a device the joint
 position metrics, which need an SMPL-H evaluation, are skipped and the joint-angle metric is reported.
 
+`--temporal [--temporal_surface]`: after the tables the recordings go through the model once more and the acceleration
+error and the jitter of the joints (and of the surface) per recording are printed to stderr (eval/temporal_metrics.py);
+stdout is what it is without the flag.
+
 Multi-GPU: `--gpus N` (spawns one rank per GPU; `python -m torch.distributed.run --nproc-per-node N
 scripts/evaluate_real.py ...` works too); whole recordings are assigned to ranks longest-first (chunks of one
 recording are serially dependent), and the per-rank metric accumulators are combined with one all_gather over RCCL.
@@ -176,6 +180,35 @@ def visualize(net, smpl, batch, device, args):
                                                                         int(batch.seq_lengths[0]), out_dir))
 
 
+def temporal_tables(net, smpl, batches, device, args):
+    """`--temporal`: the rank's recordings go through the model once more, in chunks of 256 frames with the LSTM state
+    carried and the first chunk's shape for the whole recording, as the evaluation ran them, and feed a
+    `TemporalMetricsEngine` (eval/temporal_metrics.py) whose stencils are carried across the chunks.
+    :return: (engine over all of the rank's recordings, [(recording id, metrics dict)])"""
+    from em_pose_amd.eval.helpers import window_generator
+    from em_pose_amd.eval.temporal_metrics import TemporalMetricsEngine
+    from em_pose_amd.nn.models import IterativeErrorFeedback
+    te_all = TemporalMetricsEngine(smpl, surface=args.temporal_surface)
+    per_seq = []
+    with torch.no_grad():
+        for batch in batches:
+            te = TemporalMetricsEngine(smpl, surface=args.temporal_surface)
+            shape_hat = None
+            for c, chunk in enumerate(window_generator(batch, 256 if isinstance(net, IterativeErrorFeedback) else None)):
+                chunk = chunk.to_gpu(device)
+                out = net(chunk, is_new_sequence=(c == 0))
+                if c == 0:
+                    shape_hat = out['shape_hat'][:, 0] if out['shape_hat'] is not None else None
+                te.compute(chunk.poses_body, chunk.shapes,
+                           out['pose_hat'] if out['pose_hat'] is not None else chunk.poses_body, shape_hat,
+                           chunk.seq_lengths, chunk.poses_root,
+                           out['root_ori_hat'] if out['root_ori_hat'] is not None else chunk.poses_root,
+                           frame_mask=chunk.marker_masks, is_new_sequence=(c == 0))
+            per_seq.append((batch.ids[0], te.get_metrics()))
+            te_all.merge(te.state())
+    return te_all, per_seq
+
+
 def main():
     p = argparse.ArgumentParser()
     p.add_argument('--model_id', type=int, default=1615631737, help='Which end-to-end model to evaluate.')
@@ -188,6 +221,11 @@ def main():
     p.add_argument('--visualize_sensors', action='store_true',
                    help='--visualize: also draw the readings as tripods in both halves and, in the right half, the '
                         "estimate's virtual sensors and a capsule from each reading to its virtual sensor.")
+    p.add_argument('--temporal', action='store_true',
+                   help='After the tables, run the recordings through the model once more and print the acceleration error '
+                        'and the jitter of the joints per recording to stderr (needs a GPU); stdout is unchanged.')
+    p.add_argument('--temporal_surface', action='store_true',
+                   help='--temporal (which it implies) with the same figures over the vertices of the body surface.')
     p.add_argument('--cross_subject', action='store_true', help='Evaluate on hold-out subject 0715.')
     p.add_argument('--synthetic', action='store_true', help='Synthetic recordings / body model / weights.')
     p.add_argument('--n_markers', type=int, default=6)
@@ -305,6 +343,24 @@ def main():
                               'seconds_per_pass': passes, 'host_seconds_per_section_per_pass': host_times,
                               'metrics': metrics, 'headers': list(metrics.keys()),
                               'rows': [[r[0], str(r[1])] + [float(v) for v in r[2:]] for r in table]}))
+    if args.temporal or args.temporal_surface:     # every rank; everything it prints goes to stderr
+        if device.type != 'cuda' or smpl is None:
+            if rank == 0:
+                print('--temporal needs a GPU: the joints come from the HIP layer; nothing printed', file=sys.stderr)
+        else:
+            te_all, te_seq = temporal_tables(net, smpl, batches, device, args)
+            te_rows = [(i, sid, m) for i, (sid, m) in zip(mine, te_seq)]
+            if dist is not None:
+                te_all.gather(device=D.collective_device(device), force=args.force_dist)
+                gathered = [None] * world
+                dist.all_gather_object(gathered, te_rows)
+                te_rows = sorted(r for g in gathered for r in g)
+            if rank == 0:
+                te_metrics = te_all.get_metrics()
+                table = [[i, sid] + list(m.values()) for i, sid, m in te_rows]
+                table.append([len(table), 'Overall average'] + list(te_metrics.values()))
+                print(tabulate(table, headers=['Nr', 'E2E {}'.format(name)] + list(te_metrics.keys())), file=sys.stderr,
+                      flush=True)
     if args.visualize in mine:    # the rank that owns the recording; everything it prints goes to stderr
         visualize(net, smpl, batches[mine.index(args.visualize)], device, args)
     elif args.visualize >= len(lengths) and rank == 0:

@@ -5,6 +5,8 @@ csrc/sensor_fit.hip) and prints the metric table of the zero pose, of the fitter
 random-weight LGD model before and after a few descent steps from its estimate.  Beside the joint metrics stand the
 per-vertex error of the surface and its Procrustes-aligned form (PVE, PA-PVE; eval/mesh_metrics.py): with few sensors
 the fit drifts globally, and only the aligned figures tell a rotated but well-posed body from a wrongly posed one.
+A second table holds the temporal columns of the joints (eval/temporal_metrics.py) for the same rows: the acceleration
+error and the jitter of the estimate beside the jitter of the ground truth, each window a sequence of its own.
 
     python scripts/fit_sensors.py --synthetic [--n_markers 6|12] [--steps K] [--refine] [--windows B] [--frames F]
 
@@ -26,6 +28,7 @@ from em_pose_amd.bodymodels.smpl import SMPLLayer  # noqa: E402
 from em_pose_amd.data.data import SyntheticBatch  # noqa: E402
 from em_pose_amd.eval.mesh_metrics import VertexErrorEngine  # noqa: E402
 from em_pose_amd.eval.metrics import MetricsEngine  # noqa: E402
+from em_pose_amd.eval.temporal_metrics import TemporalMetricsEngine  # noqa: E402
 from em_pose_amd.helpers.configuration import lgd_config  # noqa: E402
 from em_pose_amd.nn.fitting import SensorFitter  # noqa: E402
 from em_pose_amd.nn.models import create_model  # noqa: E402
@@ -41,6 +44,8 @@ def synthetic_batch(net, n_windows, n_frames, device):
 
 COLUMNS = ('MPJPE [mm]', 'PA-MPJPE [mm]', 'MPJAE [deg]', 'PVE [mm]', 'PA-PVE [mm]')
 HEAD = '{:<22s} {:>12s} {:>15s} {:>13s} {:>10s} {:>13s}'
+TEMPORAL_COLUMNS = ('Accel [m/s^2]', 'Jitter [m/s^3]', 'Jitter GT [m/s^3]')
+TEMPORAL_HEAD = '{:<22s} {:>15s} {:>16s} {:>19s}'
 
 
 def row(smpl, batch, name, out):
@@ -50,6 +55,14 @@ def row(smpl, batch, name, out):
                     batch.poses_root, out['root_ori_hat'])
         m.update(eng.get_metrics())
     return HEAD.format(name, *['{:.2f}'.format(m[k]) if 'deg' in k else '{:.1f}'.format(m[k]) for k in COLUMNS])
+
+
+def temporal_row(smpl, batch, name, out):
+    eng = TemporalMetricsEngine(smpl)
+    eng.compute(batch.poses_body, batch.shapes, out['pose_hat'], out['shape_hat'], batch.seq_lengths, batch.poses_root,
+                out['root_ori_hat'])
+    m = eng.get_metrics()
+    return TEMPORAL_HEAD.format(name, *['{:.1f}'.format(m[k]) for k in TEMPORAL_COLUMNS])
 
 
 def main():
@@ -77,6 +90,7 @@ def main():
     print(row(smpl, batch, 'zero init', zero))
     print(row(smpl, batch, 'fitter, {} steps'.format(args.steps), fit))
     checks = [('fitter', fit['objective'])]
+    shown = [('zero init', zero), ('fitter, {} steps'.format(args.steps), fit)]
     if args.refine:
         with torch.no_grad():
             est = net(batch)
@@ -84,6 +98,10 @@ def main():
         print(row(smpl, batch, 'LGD (random weights)', est))
         print(row(smpl, batch, 'LGD + {} steps'.format(args.steps), polished))
         checks.append(('polish', polished['objective']))
+        shown += [('LGD (random weights)', est), ('LGD + {} steps'.format(args.steps), polished)]
+    print(TEMPORAL_HEAD.format('', *TEMPORAL_COLUMNS))
+    for name, out in shown:
+        print(temporal_row(smpl, batch, name, out))
     worse = 0
     for name, rows in checks:
         rows = rows.cpu()

@@ -174,6 +174,10 @@ def train_on_amass(args, dev, rank, world):
     if args.valid_vertex_error or args.valid_vertex_error_pa:
         from em_pose_amd.eval.mesh_metrics import VertexErrorEngine
         ve = VertexErrorEngine(smpl, procrustes=args.valid_vertex_error_pa)
+    te = None
+    if args.valid_temporal:
+        from em_pose_amd.eval.temporal_metrics import TemporalMetricsEngine
+        te = TemporalMetricsEngine(smpl)
     step, best, done, skipped = 0, float('inf'), False, 0
     for epoch in range(args.n_epochs):
         for i, abatch in enumerate(train_loader):
@@ -216,7 +220,7 @@ def train_on_amass(args, dev, rank, world):
             step += 1
             if step % args.eval_every == 0 or step == args.steps:
                 losses = evaluate(valid_loader, net, fn_valid, me, device=dev,     # every rank: same held-out set
-                                  vertex_engine=ve)
+                                  vertex_engine=ve, temporal_engine=te)
                 if rank == 0:
                     better = losses['total_loss'] < best
                     print('[VALID {:0>5d} | {:0>3d}] '.format(i + 1, epoch + 1) +
@@ -224,6 +228,8 @@ def train_on_amass(args, dev, rank, world):
                     print(me.to_pretty_string(me.get_metrics(), 'VALID'))
                     if ve is not None:
                         print(ve.to_pretty_string(ve.get_metrics(), 'VALID'))
+                    if te is not None:
+                        print(te.to_pretty_string(te.get_metrics(), 'VALID'))
                     if better:
                         best = losses['total_loss']
                         torch.save({'iteration': i, 'epoch': epoch, 'global_step': step,
@@ -292,6 +298,9 @@ def main():
     p.add_argument('--valid_vertex_error_pa', action='store_true',
                    help='as --valid_vertex_error (which it implies), with the Procrustes-aligned per-vertex error (PA-PVE) '
                         'in the same line; default off')
+    p.add_argument('--valid_temporal', action='store_true',
+                   help='the periodic validation also reports the acceleration error and the jitter of the joints over the '
+                        'held-out sequences, a further table line (eval/temporal_metrics.py); default off')
     p.add_argument('--offset_noise_level', type=int, default=0)
     # sensor-noise augmentation (reference configuration.py: the same five flags; data/noise_functions.py)
     p.add_argument('--noise_num_markers', type=int, default=1, help='how many sensors the sensor noise affects')
