@@ -147,6 +147,9 @@ class RenderDesc(C.Structure):   # empose_render_desc
 OVERLAY_MAX_PRIMS = 4096   # EMPOSE_OVERLAY_MAX_PRIMS
 TEMPORAL_SEGMENT = 32      # EMPOSE_TEMPORAL_SEGMENT: frames per segment of csrc/temporal.hip
 TEMPORAL_ACC, TEMPORAL_JERK = 1, 2   # EMPOSE_TEMPORAL_*: bits of `defined`
+SMOOTH_SEGMENT = 64        # EMPOSE_SMOOTH_SEGMENT: frames per workgroup of the window of csrc/smooth.hip
+SMOOTH_MAX_RADIUS = 32     # EMPOSE_SMOOTH_MAX_RADIUS
+SMOOTH_STATE = 6           # EMPOSE_SMOOTH_STATE: doubles of one-euro state per joint or channel
 
 
 class OverlayDesc(C.Structure):   # empose_overlay_desc
@@ -314,6 +317,12 @@ SIGNATURES = {
                                        C.c_void_p, C.c_void_p]),
     # (N, F, P, x_gt, x_hat, valid, fps, reduce, rows, defined, stream)
     'empose_temporal_rows': (C.c_int, [C.c_int] * 3 + [C.c_void_p] * 3 + [C.c_double, C.c_int] + [C.c_void_p] * 3),
+    # (N, F, J, C, in, ld_in, valid, R, taps_host, out, ld_out, stream)
+    'empose_smooth_window': (C.c_int, [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.POINTER(C.c_double),
+                                                       C.c_void_p, C.c_int, C.c_void_p]),
+    # (N, F, J, C, in, ld_in, valid, fps, min_cutoff, beta, d_cutoff, state_in, state_out, out, ld_out, stream)
+    'empose_smooth_one_euro': (C.c_int, [C.c_int] * 4 + [C.c_void_p, C.c_int, C.c_void_p] + [C.c_double] * 4 +
+                                        [C.c_void_p] * 3 + [C.c_int, C.c_void_p]),
     'empose_mesh_vertices_fwd': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     'empose_mesh_vertices_fwd_bf16x3': (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -1,6 +1,6 @@
 // Launch interfaces of the kernels around the model: synthetic sensors, root frame, resampling, sensor noise, offset
-// statistics, placement search, metrics, temporal metrics (sensor_sample.hip, root_frame.hip, resample.hip,
-// sensor_noise.hip, offset_stats.hip, placement.hip, metrics.hip, temporal.hip).
+// statistics, placement search, metrics, temporal metrics, pose smoothing (sensor_sample.hip, root_frame.hip, resample.hip,
+// sensor_noise.hip, offset_stats.hip, placement.hip, metrics.hip, temporal.hip, smooth.hip).
 // Internal, not part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -157,5 +157,26 @@ struct TemporalArgs {
 };
 long temporal_rows_blocks(int N, int F, int P, int reduce);   // workgroups of the launch
 hipError_t launch_temporal_rows(const TemporalArgs& a, hipStream_t stream);
+
+// Smoothing of pose sequences (smooth.hip).  A row is [3 J rotation-vector columns | C linear columns | padding]; an *item*
+// is one joint or one channel.  Rotations are filtered on SO(3) through unit quaternions, never across a frame that does
+// not count (valid == 0; valid == nullptr: every frame counts) and never across two rows.
+constexpr int SMOOTH_SEGMENT = 64;      // EMPOSE_SMOOTH_SEGMENT (include/empose_hip.h): frames a workgroup of the window owns
+constexpr int SMOOTH_MAX_RADIUS = 32;   // EMPOSE_SMOOTH_MAX_RADIUS
+constexpr int SMOOTH_STATE = 6;         // doubles of one-euro state per item: x^ (4; a channel uses the first) | s^ | live
+struct SmoothArgs {
+  const float* in; float* out;   // [N * F][ld_in], [N * F][ld_out]
+  const unsigned char* valid;    // [N][F] or nullptr
+  int N, F, J, C, ld_in, ld_out;
+  // window: one side of the symmetric kernel, w[0 .. R]
+  int R;
+  double taps[SMOOTH_MAX_RADIUS + 1];
+  // one-euro
+  double fps, min_cutoff, beta, d_cutoff;
+  const double* state_in; double* state_out;   // [N][J + C][SMOOTH_STATE], each or nullptr
+};
+long smooth_window_blocks(int N, int F, int J, int C);   // workgroups of the launch
+hipError_t launch_smooth_window(const SmoothArgs& a, hipStream_t stream);
+hipError_t launch_smooth_one_euro(const SmoothArgs& a, hipStream_t stream);
 
 }  // namespace empose

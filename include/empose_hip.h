@@ -993,6 +993,50 @@ int empose_metrics_rows(int T, const float* joints_gt, const float* joints_hat, 
 int empose_temporal_rows(int N, int F, int P, const float* x_gt, const float* x_hat, const unsigned char* valid, double fps,
                          int reduce, double* rows, unsigned char* defined, empose_stream_t stream);
 
+/* ---- smoothing of pose sequences (new in this library) ----------------------------------------- */
+/* Two filters for estimated pose sequences (csrc/smooth.hip); the reference has none, and the definitions below are this
+ * library's own.  A row of `in` [N * F][ld_in] (fp32, device) is [3 J rotation-vector columns | C linear columns |
+ * padding]; `out` [N * F][ld_out] likewise, and its columns at or beyond 3 J + C are never written.  valid [N][F]: non-zero
+ * where the frame counts; NULL: every frame counts.  A run is a maximal stretch of consecutive counting frames of one
+ * row.  Neither filter reaches across a frame that does not count or across two rows; such a frame gets its input columns
+ * copied bit for bit, and what it holds (NaN included) never reaches another frame.  Rotations are filtered on SO(3)
+ * through unit quaternions q(.), not as rotation-vector components; every rotation written has |r| <= pi.  Arithmetic
+ * inside a thread is float64 on the fp32 inputs without fused multiply-adds; there are no atomics; a row's result does not
+ * depend on the rest of the batch, and repeated calls give the same bits.
+ *
+ * empose_smooth_window: a zero-phase FIR filter.  taps_host: R + 1 host doubles w[0 .. R], one side of a symmetric
+ * kernel, 0 <= R <= EMPOSE_SMOOTH_MAX_RADIUS.  For a counting frame t of the run [a, b] the half-width shrinks
+ * symmetrically, r = min(R, t - a, b - t): the window never leaves the run and stays symmetric, so constant-velocity
+ * motion is reproduced, and the end frames of a run pass through.
+ *   channel:   acc = w0 x[t], then for k = 1 .. r ascending acc += w_k (x[t-k] + x[t+k]); wsum = w0, wsum += 2 w_k;
+ *              out = acc / wsum
+ *   rotation:  c = q(r[t]); acc = w0 c; acc += w_k (s- q(r[t-k]) + s+ q(r[t+k])) with s = -1 where the dot product with
+ *              c is negative, else +1; out = the rotation vector of acc / |acc| with w >= 0.  |acc| >= w0 > 0.
+ * This sign-aligned chordal mean is this library's definition of the windowed mean of rotations (not the Karcher mean).
+ * The time axis is cut into segments of EMPOSE_SMOOTH_SEGMENT frames, which does not change the result.
+ *
+ * empose_smooth_one_euro: the causal One-Euro filter (Casiez, Roussel, Vogel 2012), alpha(fc) = 1 / (1 + fps / (2 pi fc)).
+ * At the first counting frame of a run x^ = x, s^ = 0.  Afterwards
+ *   channel:   d = (x - x^) fps; s^ += alpha(d_cutoff) (d - s^); fc = min_cutoff + beta |s^|; x^ += alpha(fc) (x - x^)
+ *   rotation:  q = q(r) in the hemisphere of x^; delta = log(x^-1 q); theta = 2 |delta| in [0, pi]; d = theta fps; s^ and
+ *              fc as above; x^ <- x^ exp(alpha(fc) delta), renormalised; out = its rotation vector.
+ * A frame that does not count ends the run and clears the state.  state_in / state_out: [N][J + C][EMPOSE_SMOOTH_STATE]
+ * device doubles (x^ as 4 -- a channel uses the first --, s^, live flag), each may be NULL; state_in NULL: every row starts
+ * fresh; state_out receives the state after frame F - 1.  Feeding a sequence in chunks through the state gives the bits
+ * of feeding it whole.
+ *
+ * Both return EMPOSE_EINVAL, before any GPU work, for N or F <= 0, J or C < 0 or J + C = 0, a leading dimension below
+ * 3 J + C, NULL in, out or taps_host, out == in, R outside [0, 32], a tap that is negative or not finite or w0 <= 0, fps,
+ * min_cutoff or d_cutoff not positive and finite, beta negative or not finite, or N * F above 2^31 - 1. */
+#define EMPOSE_SMOOTH_SEGMENT 64
+#define EMPOSE_SMOOTH_MAX_RADIUS 32
+#define EMPOSE_SMOOTH_STATE 6
+int empose_smooth_window(int N, int F, int J, int C, const float* in, int ld_in, const unsigned char* valid, int R,
+                         const double* taps_host, float* out, int ld_out, empose_stream_t stream);
+int empose_smooth_one_euro(int N, int F, int J, int C, const float* in, int ld_in, const unsigned char* valid, double fps,
+                           double min_cutoff, double beta, double d_cutoff, const double* state_in, double* state_out,
+                           float* out, int ld_out, empose_stream_t stream);
+
 /* ---- model-free sensor fitting (new in this library) ------------------------------------------- */
 /* A pose per frame and a shape per window (or per frame) from sensor readings alone: K steps of Adam on, per window w
  * of F frames with live_t = [t < seq_length],

@@ -23,7 +23,9 @@ position metrics, which need an SMPL-H evaluation, are skipped and the joint-ang
 
 `--temporal [--temporal_surface]`: after the tables the recordings go through the model once more and the acceleration
 error and the jitter of the joints (and of the surface) per recording are printed to stderr (eval/temporal_metrics.py);
-stdout is what it is without the flag.
+stdout is what it is without the flag.  With `--smooth {window,one_euro} [--smooth_sigma S] [--smooth_min_cutoff F
+--smooth_beta B]` the estimate is also filtered (eval/smoothing.py) and a second table on stderr holds the same columns
+plus MPJPE and MPJAE of the smoothed estimate.
 
 Multi-GPU: `--gpus N` (spawns one rank per GPU; `python -m torch.distributed.run --nproc-per-node N
 scripts/evaluate_real.py ...` works too); whole recordings are assigned to ranks longest-first (chunks of one
@@ -190,6 +192,7 @@ def temporal_tables(net, smpl, batches, device, args):
     from em_pose_amd.nn.models import IterativeErrorFeedback
     te_all = TemporalMetricsEngine(smpl, surface=args.temporal_surface)
     per_seq = []
+    smoother = SmoothedTables(smpl, args) if args.smooth else None
     with torch.no_grad():
         for batch in batches:
             te = TemporalMetricsEngine(smpl, surface=args.temporal_surface)
@@ -199,14 +202,94 @@ def temporal_tables(net, smpl, batches, device, args):
                 out = net(chunk, is_new_sequence=(c == 0))
                 if c == 0:
                     shape_hat = out['shape_hat'][:, 0] if out['shape_hat'] is not None else None
-                te.compute(chunk.poses_body, chunk.shapes,
-                           out['pose_hat'] if out['pose_hat'] is not None else chunk.poses_body, shape_hat,
-                           chunk.seq_lengths, chunk.poses_root,
-                           out['root_ori_hat'] if out['root_ori_hat'] is not None else chunk.poses_root,
-                           frame_mask=chunk.marker_masks, is_new_sequence=(c == 0))
+                pose_hat = out['pose_hat'] if out['pose_hat'] is not None else chunk.poses_body
+                root_hat = out['root_ori_hat'] if out['root_ori_hat'] is not None else chunk.poses_root
+                te.compute(chunk.poses_body, chunk.shapes, pose_hat, shape_hat, chunk.seq_lengths, chunk.poses_root,
+                           root_hat, frame_mask=chunk.marker_masks, is_new_sequence=(c == 0))
+                if smoother is not None:
+                    smoother.chunk(chunk, pose_hat, root_hat, shape_hat if shape_hat is not None else chunk.shapes, c == 0)
             per_seq.append((batch.ids[0], te.get_metrics()))
             te_all.merge(te.state())
-    return te_all, per_seq
+            if smoother is not None:
+                smoother.end_of_recording(batch.ids[0])
+    return te_all, per_seq, smoother
+
+
+def smooth_label(args):
+    if args.smooth == 'window':
+        return 'window (sigma {:g} frames)'.format(args.smooth_sigma)
+    return 'one-euro (min_cutoff {:g} Hz, beta {:g})'.format(args.smooth_min_cutoff, args.smooth_beta)
+
+
+SMOOTH_COLUMNS = ('MPJPE [mm]', 'MPJAE [deg]')   # of MetricsEngine, beside the temporal columns of the smoothed estimate
+
+
+class SmoothedTables(object):
+    """`--temporal --smooth`: the estimate of every recording goes through a filter of eval/smoothing.py and then through
+    a `TemporalMetricsEngine` and a `MetricsEngine` of its own.  `window` filters the whole recording once its chunks are
+    gathered (the filter is zero-phase: it needs the frames to come); `one_euro` filters chunk by chunk with the state
+    carried, as a streaming user would."""
+
+    def __init__(self, smpl, args):
+        from em_pose_amd.eval.metrics import MetricsEngine
+        from em_pose_amd.eval.temporal_metrics import TemporalMetricsEngine
+        self.smpl, self.mode = smpl, args.smooth
+        self.sigma, self.min_cutoff, self.beta = args.smooth_sigma, args.smooth_min_cutoff, args.smooth_beta
+        self.engines = lambda: (TemporalMetricsEngine(smpl), MetricsEngine(smpl))
+        self.all = self.engines()
+        self.per_seq = []
+        self._begin()
+
+    def _begin(self):
+        self.seq = self.engines()
+        self.parts = []       # window: the chunks of the recording
+        self.filter = None    # one_euro: made at the first chunk, when the number of betas is known
+
+    def _feed(self, gt, est, valid, is_new_sequence):
+        pose, shape, root = gt
+        self.seq[0].compute(pose, shape, est['pose_hat'], est['shape_hat'], pose_root=root,
+                            pose_root_hat=est['root_ori_hat'], valid=valid, is_new_sequence=is_new_sequence)
+        self.seq[1].compute(pose, shape, est['pose_hat'], est['shape_hat'], pose_root=root,
+                            pose_root_hat=est['root_ori_hat'], valid=valid)
+
+    def chunk(self, chunk, pose_hat, root_hat, shape_hat, first):
+        from em_pose_amd.eval.metrics import MetricsEngine
+        from em_pose_amd.eval.smoothing import OneEuroFilter, smooth_model_output
+        n, f = pose_hat.shape[0], pose_hat.shape[1]
+        per_frame = lambda s_: s_ if s_.dim() == 3 else s_.unsqueeze(1).expand(n, f, s_.shape[-1])
+        valid = MetricsEngine._mask(chunk.seq_lengths, n, f, chunk.marker_masks, pose_hat.device)
+        gt = (chunk.poses_body, per_frame(chunk.shapes), chunk.poses_root)
+        est = {'pose_hat': pose_hat, 'root_ori_hat': root_hat, 'shape_hat': per_frame(shape_hat)}
+        if self.mode == 'window':
+            self.parts.append((gt, est, valid))
+            return
+        if self.filter is None:
+            self.filter = OneEuroFilter(22, est['shape_hat'].shape[-1], min_cutoff=self.min_cutoff, beta=self.beta)
+        est = smooth_model_output(est, valid, self.smpl, self.filter, is_new_sequence=first)
+        self._feed(gt, est, valid, first)
+
+    def end_of_recording(self, name):
+        from em_pose_amd.eval.smoothing import gaussian_taps, smooth_model_output, window_filter
+        if self.mode == 'window' and self.parts:
+            cat = lambda ts: torch.cat(list(ts), dim=1)
+            gt = tuple(cat(p[0][k] for p in self.parts) for k in range(3))
+            est = {k: cat(p[1][k] for p in self.parts) for k in ('pose_hat', 'root_ori_hat', 'shape_hat')}
+            valid = cat(p[2] for p in self.parts)
+            est = smooth_model_output(est, valid, self.smpl, window_filter(gaussian_taps(self.sigma)))
+            self._feed(gt, est, valid, True)
+        m = dict(self.seq[0].get_metrics())
+        mm = self.seq[1].get_metrics()
+        m.update({k: mm[k] for k in SMOOTH_COLUMNS})
+        self.per_seq.append((name, m))
+        for mine, total in zip(self.seq, self.all):
+            total.merge(mine.state())
+        self._begin()
+
+    def overall(self):
+        m = dict(self.all[0].get_metrics())
+        mm = self.all[1].get_metrics()
+        m.update({k: mm[k] for k in SMOOTH_COLUMNS})
+        return m
 
 
 def main():
@@ -226,6 +309,13 @@ def main():
                         'and the jitter of the joints per recording to stderr (needs a GPU); stdout is unchanged.')
     p.add_argument('--temporal_surface', action='store_true',
                    help='--temporal (which it implies) with the same figures over the vertices of the body surface.')
+    p.add_argument('--smooth', default=None, choices=['window', 'one_euro'],
+                   help='--temporal: also filter the estimate (eval/smoothing.py) and print, in a second table on stderr, the '
+                        'same columns plus MPJPE and MPJAE of the smoothed estimate.  window: a zero-phase Gaussian window over '
+                        'the whole recording; one_euro: the causal One-Euro filter, chunk by chunk with its state carried.')
+    p.add_argument('--smooth_sigma', type=float, default=2.0, help='--smooth window: sigma of the Gaussian, frames.')
+    p.add_argument('--smooth_min_cutoff', type=float, default=1.0, help='--smooth one_euro: cut-off at rest, Hz.')
+    p.add_argument('--smooth_beta', type=float, default=0.0, help='--smooth one_euro: rise of the cut-off with the speed.')
     p.add_argument('--cross_subject', action='store_true', help='Evaluate on hold-out subject 0715.')
     p.add_argument('--synthetic', action='store_true', help='Synthetic recordings / body model / weights.')
     p.add_argument('--n_markers', type=int, default=6)
@@ -348,19 +438,31 @@ def main():
             if rank == 0:
                 print('--temporal needs a GPU: the joints come from the HIP layer; nothing printed', file=sys.stderr)
         else:
-            te_all, te_seq = temporal_tables(net, smpl, batches, device, args)
+            te_all, te_seq, smoother = temporal_tables(net, smpl, batches, device, args)
             te_rows = [(i, sid, m) for i, (sid, m) in zip(mine, te_seq)]
+            sm_rows = [(i, sid, m) for i, (sid, m) in zip(mine, smoother.per_seq)] if smoother is not None else []
             if dist is not None:
                 te_all.gather(device=D.collective_device(device), force=args.force_dist)
                 gathered = [None] * world
                 dist.all_gather_object(gathered, te_rows)
                 te_rows = sorted(r for g in gathered for r in g)
+                if smoother is not None:
+                    for eng in smoother.all:
+                        eng.gather(device=D.collective_device(device), force=args.force_dist)
+                    dist.all_gather_object(gathered, sm_rows)
+                    sm_rows = sorted(r for g in gathered for r in g)
             if rank == 0:
                 te_metrics = te_all.get_metrics()
                 table = [[i, sid] + list(m.values()) for i, sid, m in te_rows]
                 table.append([len(table), 'Overall average'] + list(te_metrics.values()))
                 print(tabulate(table, headers=['Nr', 'E2E {}'.format(name)] + list(te_metrics.keys())), file=sys.stderr,
                       flush=True)
+                if smoother is not None:
+                    sm_metrics = smoother.overall()
+                    table = [[i, sid] + list(m.values()) for i, sid, m in sm_rows]
+                    table.append([len(table), 'Overall average'] + list(sm_metrics.values()))
+                    print(tabulate(table, headers=['Nr', 'E2E {} + {}'.format(name, smooth_label(args))] +
+                                   list(sm_metrics.keys())), file=sys.stderr, flush=True)
     if args.visualize in mine:    # the rank that owns the recording; everything it prints goes to stderr
         visualize(net, smpl, batches[mine.index(args.visualize)], device, args)
     elif args.visualize >= len(lengths) and rank == 0:

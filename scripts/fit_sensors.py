@@ -9,6 +9,10 @@ A second table holds the temporal columns of the joints (eval/temporal_metrics.p
 error and the jitter of the estimate beside the jitter of the ground truth, each window a sequence of its own.
 
     python scripts/fit_sensors.py --synthetic [--n_markers 6|12] [--steps K] [--refine] [--windows B] [--frames F]
+                                  [--smooth {window,one_euro} [--smooth_sigma S] [--smooth_min_cutoff F --smooth_beta B]]
+
+`--smooth` adds a third table: the temporal columns, MPJPE and MPJAE of every row, raw and after the filter
+(eval/smoothing.py); the first two tables are what they are without it.
 
 `--synthetic` needs no data: `synthetic.make_windows` on the stand-in body model.  The script exits non-zero if the
 objective of what the fitter returns exceeds, for any window, the objective at its init.
@@ -28,6 +32,7 @@ from em_pose_amd.bodymodels.smpl import SMPLLayer  # noqa: E402
 from em_pose_amd.data.data import SyntheticBatch  # noqa: E402
 from em_pose_amd.eval.mesh_metrics import VertexErrorEngine  # noqa: E402
 from em_pose_amd.eval.metrics import MetricsEngine  # noqa: E402
+from em_pose_amd.eval.smoothing import OneEuroFilter, gaussian_taps, smooth_model_output, window_filter  # noqa: E402
 from em_pose_amd.eval.temporal_metrics import TemporalMetricsEngine  # noqa: E402
 from em_pose_amd.helpers.configuration import lgd_config  # noqa: E402
 from em_pose_amd.nn.fitting import SensorFitter  # noqa: E402
@@ -65,8 +70,38 @@ def temporal_row(smpl, batch, name, out):
     return TEMPORAL_HEAD.format(name, *['{:.1f}'.format(m[k]) for k in TEMPORAL_COLUMNS])
 
 
+SMOOTH_COLUMNS = TEMPORAL_COLUMNS + ('MPJPE [mm]', 'MPJAE [deg]')
+SMOOTH_HEAD = '{:<34s} {:>15s} {:>16s} {:>19s} {:>12s} {:>13s}'
+
+
+def smooth_row(smpl, batch, name, out):
+    """`--smooth`: the temporal columns, MPJPE and MPJAE of an estimate, raw or filtered."""
+    m = {}
+    for eng in (TemporalMetricsEngine(smpl), MetricsEngine(smpl)):
+        eng.compute(batch.poses_body, batch.shapes, out['pose_hat'], out['shape_hat'], batch.seq_lengths, batch.poses_root,
+                    out['root_ori_hat'])
+        m.update(eng.get_metrics())
+    return SMOOTH_HEAD.format(name, *['{:.2f}'.format(m[k]) if 'deg' in k else '{:.1f}'.format(m[k])
+                                      for k in SMOOTH_COLUMNS])
+
+
+def smoothing_filter(args):
+    """(a `filt` of `smooth_model_output`, its label).  Every window is a sequence of its own, so the One-Euro filter
+    starts fresh on every call."""
+    if args.smooth == 'window':
+        return window_filter(gaussian_taps(args.smooth_sigma)), 'window, sigma {:g}'.format(args.smooth_sigma)
+    return (OneEuroFilter(22, 10, min_cutoff=args.smooth_min_cutoff, beta=args.smooth_beta),
+            'one-euro, {:g} Hz, beta {:g}'.format(args.smooth_min_cutoff, args.smooth_beta))
+
+
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument('--smooth', default=None, choices=['window', 'one_euro'],
+                   help='a third table: the temporal columns, MPJPE and MPJAE of every row raw and after a filter of '
+                        'eval/smoothing.py (window: zero-phase Gaussian; one_euro: the causal One-Euro filter)')
+    p.add_argument('--smooth_sigma', type=float, default=2.0, help='--smooth window: sigma of the Gaussian, frames')
+    p.add_argument('--smooth_min_cutoff', type=float, default=1.0, help='--smooth one_euro: cut-off at rest, Hz')
+    p.add_argument('--smooth_beta', type=float, default=0.0, help='--smooth one_euro: rise of the cut-off with the speed')
     p.add_argument('--synthetic', action='store_true', help='synthetic windows on the stand-in body model')
     p.add_argument('--n_markers', type=int, default=12, choices=(6, 12))
     p.add_argument('--steps', type=int, default=30)
@@ -102,6 +137,13 @@ def main():
     print(TEMPORAL_HEAD.format('', *TEMPORAL_COLUMNS))
     for name, out in shown:
         print(temporal_row(smpl, batch, name, out))
+    if args.smooth:
+        filt, label = smoothing_filter(args)
+        valid = MetricsEngine.valid_frames(batch.seq_lengths, batch.poses_body.shape[0], batch.poses_body.shape[1])
+        print(SMOOTH_HEAD.format('', *SMOOTH_COLUMNS))
+        for name, out in shown:
+            print(smooth_row(smpl, batch, name, out))
+            print(smooth_row(smpl, batch, '  + ' + label, smooth_model_output(out, valid.to(device), smpl, filt)))
     worse = 0
     for name, rows in checks:
         rows = rows.cpu()
