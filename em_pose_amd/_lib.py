@@ -164,6 +164,18 @@ class OverlayDesc(C.Structure):   # empose_overlay_desc
                 ('rgb', C.c_void_p), ('prim_id', C.c_void_p), ('prim_depth', C.c_void_p)]
 
 
+SURFACE_MAX_FRAMES = 1 << 22   # EMPOSE_SURFACE_MAX_FRAMES: per call
+SURFACE_MAX_VERTICES, SURFACE_MAX_FACES, SURFACE_MAX_QUERIES = 1 << 24, 1 << 26, 4096   # EMPOSE_SURFACE_MAX_*
+
+
+class SurfaceDesc(C.Structure):   # empose_surface_desc
+    _fields_ = [('T', C.c_int), ('V', C.c_int), ('F', C.c_int), ('Q', C.c_int),
+                ('vertices', C.c_void_p), ('faces_host', c_int_p), ('faces_dev', C.c_void_p),
+                ('points', C.c_void_p), ('mask', C.c_void_p), ('want_inside', C.c_int),
+                ('dist', C.c_void_p), ('face', C.c_void_p), ('bary', C.c_void_p), ('closest', C.c_void_p),
+                ('inside', C.c_void_p)]
+
+
 # symbol -> (restype, argtypes); this table is also what tests check against the header.
 SIGNATURES = {
     'empose_last_error': (C.c_char_p, []),
@@ -362,6 +374,8 @@ SIGNATURES = {
     'empose_render_meshes': (C.c_int, [C.POINTER(RenderDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
     'empose_render_overlay_workspace_bytes': (C.c_size_t, [C.c_int] * 4),
     'empose_render_overlay': (C.c_int, [C.POINTER(OverlayDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
+    'empose_surface_query_workspace_bytes': (C.c_size_t, [C.c_int] * 4),
+    'empose_surface_query': (C.c_int, [C.POINTER(SurfaceDesc), C.c_void_p, C.c_size_t, C.c_void_p]),
 }
 
 _lib = None

@@ -300,6 +300,28 @@ class SMPLLayer(nn.Module):
                              _lib.dptr(tb), _lib.dptr(sums), _lib.dptr(ws), ws_bytes, _lib.current_stream()))
         return sums
 
+    def surface_faces(self, device):
+        """The face table as `eval.surface_metrics.Faces` (host and device copy), cached per device and table version."""
+        from em_pose_amd.eval.surface_metrics import Faces
+        key = (self.tables_version, str(device))
+        cache = self.__dict__.setdefault('_surface_faces', {})
+        if key not in cache:
+            for stale in [k for k in cache if k[0] != self.tables_version]:
+                del cache[stale]
+            cache[key] = Faces(np.asarray(self.model['f']), device)
+        return cache[key]
+
+    def surface_distance(self, points, poses_body, betas, poses_root=None, trans=None, mask=None, inside=True, slab=1024):
+        """The distance of `points` (N, Q, 3) or (N, Q * 3), given in the frame of the posed body, to the body's surface,
+        and whether they lie inside it (eval/surface_metrics.py, csrc/surface_query.hip): `SurfaceResult(dist (N, Q), face,
+        bary, closest, inside)` on the device, `mask` (N, Q) as in `closest_point_on_mesh`.  The mesh is evaluated with
+        `forward` in slabs of at most `slab` frames and each slab is queried at once, so the memory beyond the inputs and
+        the outputs does not grow with N; the results equal the one-shot query of the whole mesh bit for bit.  The body
+        inputs are packed as `forward` packs them.  No autograd."""
+        from em_pose_amd.eval.surface_metrics import surface_distance
+        return surface_distance(self, points, poses_body, betas, poses_root=poses_root, trans=trans, mask=mask,
+                                inside=inside, slab=slab)
+
     def fk(self, poses_body, betas, poses_root=None, trans=None, normalize_root=False, window_size=None):
         # The reference slices long inputs into windows to bound memory (smpl.py:124-144); the HIP entry point already
         # processes slabs of 2048 frames internally, so `window_size` only has to be accepted.

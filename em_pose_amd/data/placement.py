@@ -22,6 +22,7 @@ import torch
 
 from em_pose_amd import _lib
 from em_pose_amd.data.offsets import pooled_recordings, root_normalized_poses
+from em_pose_amd.eval.surface_metrics import closest_point_on_mesh
 
 
 class Candidates(object):
@@ -134,9 +135,12 @@ def search_placement(smpl_model, samples, subjects=None, per_subject=False, cand
     group, so the memory beyond the inputs and the (M, C) tables does not grow with the number of frames.
 
     Returns {key: {'vertex_ids' (M,) int64, 'rms_mm' (M,), 'runner_up_ids' (M,) int64, 'runner_up_rms_mm' (M,),
-    'counts' (M,) int32, 'score' (M, C) float32}} as numpy arrays: the site, the root of its score in millimetres, the
-    second-best candidate and its rms (-1 and inf where there is none), the counting frames and the whole table.  Warns,
-    and does not fail, about a sensor with no counting frame (site -1) and about two sensors on the same vertex.
+    'counts' (M,) int32, 'score' (M, C) float32, 'skin_mm' (M,)}} as numpy arrays: the site, the root of its score in
+    millimetres, the second-best candidate and its rms (-1 and inf where there is none), the counting frames, the whole
+    table, and per sensor the mean distance of its counting readings to the ground-truth SURFACE in millimetres (inf
+    without one; eval/surface_metrics.py, one more query on each slab's mesh, the whole mesh whatever `candidates` is).
+    A site whose `rms_mm` is far above `skin_mm` is a vertex that is not under the strap.  Warns, and does not fail, about
+    a sensor with no counting frame (site -1) and about two sensors on the same vertex.
     """
     samples = list(samples)
     if not samples:
@@ -152,20 +156,28 @@ def search_placement(smpl_model, samples, subjects=None, per_subject=False, cand
     up = lambda a: torch.from_numpy(a).to(device)
     with torch.no_grad(), torch.cuda.device(device):
         cand = Candidates.of(candidates, device)
+        faces = smpl_model.surface_faces(device)
         poses_d = root_normalized_poses(smpl_model, rec, device)
         betas_d, pos_d, masks_d = up(rec['betas']), up(rec['pos']), up(rec['masks'])
         c = smpl_model.n_vertices if cand is None else len(cand)
         for key, first, n in zip(rec['keys'], rec['firsts'], rec['per_subject']):
             sums = torch.zeros(m, c, dtype=torch.float64, device=device)
             counts = torch.zeros(m, dtype=torch.int32, device=device)
+            skin = torch.zeros(m, dtype=torch.float64, device=device)
             for at in range(int(first), int(first) + int(n), int(slab)):
                 sl = slice(at, min(at + int(slab), int(first) + int(n)))
                 vertices, _ = smpl_model(poses_body=poses_d[sl, 3:], betas=betas_d[sl], poses_root=poses_d[sl, :3])
                 placement_scores(vertices, pos_d[sl], masks_d[sl], sums, counts, cand)
+                read = masks_d[sl] == 1.0
+                dist = closest_point_on_mesh(vertices, faces, pos_d[sl], read).dist
+                skin += torch.where(read, dist.double(), torch.zeros_like(skin)).sum(dim=0)
                 del vertices
             score, best, _ = placement_finish(sums, counts, cand)
             out[key] = _placement(key, score.cpu().numpy(), best.cpu().numpy(), counts.cpu().numpy(),
                                   None if cand is None else cand.host)
+            n_read = out[key]['counts'].astype(np.float64)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                out[key]['skin_mm'] = np.where(n_read > 0, 1e3 * skin.cpu().numpy() / n_read, np.inf).astype(np.float32)
     return out
 
 

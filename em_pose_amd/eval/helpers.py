@@ -103,7 +103,7 @@ def get_model_config(model_id):
 
 
 def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, device=None, vertex_engine=None,
-             temporal_engine=None):
+             temporal_engine=None, skin_engine=None):
     """
     Losses and metrics over a hold-out set (reference eval/helpers.py:51-111): every batch is normalised as a whole,
     cut into temporal chunks (`window_size`, single-recording `RealBatch`es only, as in the reference), preprocessed,
@@ -112,6 +112,8 @@ def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, 
     metrics engine, with the same tensors and the first chunk's shape: the per-vertex error of the same frames.
     `temporal_engine` (optional, eval/temporal_metrics.py `TemporalMetricsEngine`) likewise, with `is_new_sequence` as the
     model gets it: the acceleration error and the jitter over the same frames, the stencils carried across the chunks.
+    `skin_engine` (optional, eval/surface_metrics.py `SkinDistanceEngine`) likewise, with the chunk's readings
+    (`batch_readings`): how far the readings are from the skin of the estimate and of the ground truth.
     :return: dict of loss values averaged over the samples of the set.
     """
     device = C.DEVICE if device is None else device
@@ -124,6 +126,9 @@ def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, 
         vertex_engine.reset()
     if temporal_engine is not None:
         temporal_engine.reset()
+    if skin_engine is not None:
+        from em_pose_amd.eval.surface_metrics import batch_readings
+        skin_engine.reset()
     try:
         with torch.no_grad():
             for b, abatch in enumerate(data_loader):
@@ -148,6 +153,12 @@ def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, 
                         temporal_engine.compute(chunk.poses_body, chunk.shapes, pose_hat, first_shape_hat,
                                                 chunk.seq_lengths, chunk.poses_root, out['root_ori_hat'],
                                                 frame_mask=chunk.marker_masks, is_new_sequence=(i == 0))
+                    if skin_engine is not None:
+                        readings, reading_masks = batch_readings(chunk)
+                        skin_engine.compute(chunk.poses_body, chunk.shapes, pose_hat, first_shape_hat,
+                                            chunk.seq_lengths, chunk.poses_root, out['root_ori_hat'],
+                                            frame_mask=chunk.marker_masks, marker_pos=readings,
+                                            marker_masks=reading_masks)
                     n_chunks, bs = i + 1, chunk.batch_size
                 for k, v in seq_vals.items():
                     agg[k] += v / n_chunks * bs
@@ -159,12 +170,14 @@ def evaluate(data_loader, net, preprocess_fn, metrics_engine, window_size=None, 
 
 def compute_loss_and_metrics(data_loader, net, preprocess_fn, model_id, smpl_model=None, device=None,
                              vertex_error=False, vertex_error_procrustes=False, temporal=False,
-                             temporal_surface=False):
+                             temporal_surface=False, skin_distance=False):
     """reference eval/helpers.py:114-128.  `vertex_error` (not in the reference): also accumulate the per-vertex error
     (eval/mesh_metrics.py) and print it as a second table line, with `vertex_error_procrustes` the Procrustes-aligned
     error in the same line.  `temporal` (not in the reference): also accumulate the acceleration error and the jitter
     (eval/temporal_metrics.py) and print them as a further table line, with `temporal_surface` the surface columns in the
-    same line.  The returned values are the same either way."""
+    same line.  `skin_distance` (not in the reference): also accumulate the distance of the readings to the skin of the
+    estimate and of the ground truth (eval/surface_metrics.py) and print it as a further table line.  The returned values
+    are the same either way."""
     if smpl_model is None:
         from em_pose_amd.bodymodels.smpl import create_default_smpl_model
         smpl_model = create_default_smpl_model(device)
@@ -177,7 +190,12 @@ def compute_loss_and_metrics(data_loader, net, preprocess_fn, model_id, smpl_mod
     if temporal or temporal_surface:
         from em_pose_amd.eval.temporal_metrics import TemporalMetricsEngine
         te = TemporalMetricsEngine(smpl_model, surface=temporal_surface)
-    losses = evaluate(data_loader, net, preprocess_fn, me, device=device, vertex_engine=ve, temporal_engine=te)
+    se = None
+    if skin_distance:
+        from em_pose_amd.eval.surface_metrics import SkinDistanceEngine
+        se = SkinDistanceEngine(smpl_model)
+    losses = evaluate(data_loader, net, preprocess_fn, me, device=device, vertex_engine=ve, temporal_engine=te,
+                      skin_engine=se)
     print('[LOSS] loss: {:.6f}'.format(losses['total_loss']))
     metrics = me.get_metrics()
     print(me.to_pretty_string(metrics, model_id))
@@ -185,6 +203,8 @@ def compute_loss_and_metrics(data_loader, net, preprocess_fn, model_id, smpl_mod
         print(ve.to_pretty_string(ve.get_metrics(), model_id))
     if te is not None:
         print(te.to_pretty_string(te.get_metrics(), model_id))
+    if se is not None:
+        print(se.to_pretty_string(se.get_metrics(), model_id))
     return losses, metrics
 
 

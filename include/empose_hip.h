@@ -1199,6 +1199,56 @@ typedef struct {
 size_t empose_render_overlay_workspace_bytes(int T, int P, int H, int W);
 int empose_render_overlay(const empose_overlay_desc* desc, void* workspace, size_t workspace_bytes, empose_stream_t stream);
 
+/* ---- point-to-mesh queries (new in this library) ------------------------------------------------ */
+/* For Q query points in each of T frames, the closest point of the frame's triangle mesh (V vertices per frame, one table
+ * of F faces) and, want_inside != 0, whether the point lies inside the mesh (csrc/surface_query.hip: one launch, a
+ * workgroup per frame and block of 12 queries, the frame's vertices in LDS).  Both definitions are this library's own:
+ *   closest   c(p, f), the closest point of the closed triangle f to p, in fp32 by Voronoi regions (Ericson, Real-Time
+ *             Collision Detection 5.1.5) tried in the order vertex 0, vertex 1, edge 01, vertex 2, edge 02, edge 12,
+ *             interior; every comparison includes its boundary, so a face without area ends in an edge or a vertex; a
+ *             quotient whose denominator is not positive counts as 0: no NaN from finite input.  d2(p, f) = |p - c|^2.
+ *   result    the face with the lowest fp32 d2, the lowest face id on an exact tie -- an integer min over the 64-bit keys
+ *             (bits of d2) << 32 | face id, no floating-point atomics.  dist = sqrt(d2); bary: the weights of c on the
+ *             face's corners in the face's own order, each >= 0; closest = c.
+ *   inside    the parity of the faces the ray from p along +z crosses.  A face counts when (a) the projection of p on the
+ *             xy plane lies in the projected triangle under a half-open rule and (b) the ray meets the face's plane
+ *             above p.  All of it in float64 on the fp32 coordinates (the values round; no exact sign is claimed).  The
+ *             edge function of an edge is formed from its
+ *             endpoint with the lower vertex id to the one with the higher, e = (hi.x - lo.x) (p.y - lo.y) - (hi.y - lo.y)
+ *             (p.x - lo.x), and negated for the face that runs it the other way; a face whose projected area (the edge
+ *             function of edge 01 at corner 2) is 0 never counts; otherwise the three values w are oriented by the sign
+ *             of the area, and p is covered where every w > 0, or w == 0 on an edge the face owns: one that runs down in
+ *             y, or level and towards +x, in the oriented direction (the side the point displaced by (+eps, +eps^2) falls
+ *             on).  (b): (w0 (z2 - p.z) + w1 (z0 - p.z)) + w2 (z1 - p.z) > 0, w_k the value of the edge opposite corner
+ *             k + 2.  A ray through a shared edge or vertex of a closed mesh is so counted once per crossing.  On a mesh
+ *             that is not closed, or that intersects itself, the flag follows the same rule and means nothing.
+ *   masked    mask [T][Q] (or NULL: none): a query whose mask is 0 gives dist +inf, face -1, bary = closest = 0,
+ *             inside 0, and its coordinates -- anything, NaN included -- are never read into arithmetic.
+ * A (query, face) pair is evaluated by one function whatever lane or workgroup holds it, and min and xor are exact in any
+ * order: a second call gives the same bits, and a query gives the same bits whatever T is and whatever other queries
+ * the frame holds.  face, bary, closest and inside are optional (NULL), inside is required with want_inside.  T is at most
+ * EMPOSE_SURFACE_MAX_FRAMES per call (a workgroup per frame in one grid dimension), V at most
+ * EMPOSE_SURFACE_MAX_VERTICES, F at most EMPOSE_SURFACE_MAX_FACES, Q at most EMPOSE_SURFACE_MAX_QUERIES; a frame of up to
+ * 12 288 vertices is staged in LDS, a larger one is gathered from L2 by the same code.  faces_host is a host copy of the
+ * device table faces_dev and is checked against [0, V) on every call (the kernel clamps an index in any case).  All
+ * other pointers are device memory.  empose_surface_query_workspace_bytes is 0 for every shape (a frame's partial results
+ * are combined inside its workgroup) and workspace may then be NULL.  The call is asynchronous on `stream`: it never
+ * synchronises, allocates or copies.  Returns EMPOSE_EINVAL, before any GPU work, for a NULL descriptor, vertices, points,
+ * faces_host, faces_dev or dist, T, V, F or Q <= 0 or above its cap, want_inside without inside, and a face index outside
+ * [0, V). */
+#define EMPOSE_SURFACE_MAX_FRAMES (1 << 22)
+#define EMPOSE_SURFACE_MAX_VERTICES (1 << 24)
+#define EMPOSE_SURFACE_MAX_FACES (1 << 26)
+#define EMPOSE_SURFACE_MAX_QUERIES 4096
+typedef struct {
+  int T, V, F, Q;
+  const float* vertices; const int* faces_host; const int* faces_dev;
+  const float* points; const float* mask; int want_inside;
+  float* dist; int* face; float* bary; float* closest; unsigned char* inside;
+} empose_surface_desc;
+size_t empose_surface_query_workspace_bytes(int T, int V, int F, int Q);
+int empose_surface_query(const empose_surface_desc* desc, void* workspace, size_t workspace_bytes, empose_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

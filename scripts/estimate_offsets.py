@@ -16,7 +16,9 @@ the spread of the rotational offsets in degrees.
 
 `--search_placement` first searches the mesh for the sites of the sensors (em_pose_amd/data/placement.py; the search runs in
 HIP, csrc/placement.hip), all recordings pooled: per sensor it prints the vertex the readings are closest to, its rms
-distance in mm, the runner-up with its rms, and whether the site is CONSTANTS.VERTEX_IDS[m].  The offsets are then
+distance in mm, the runner-up with its rms, and whether the site is CONSTANTS.VERTEX_IDS[m]; below that table, per sensor,
+the mean distance of the readings to the ground-truth SURFACE (eval/surface_metrics.py) beside the rms to the site -- a
+site whose rms is far above the skin distance is a vertex that is not under the strap.  The offsets are then
 estimated at the found sites and the files carry them as `vertex_ids`.  `--exclude_hands` leaves the vertices skinned to
 the finger joints out of the search.
 """
@@ -90,6 +92,9 @@ def search_sites(smpl, samples, exclude_hands, device):
         print('  {:>6} {:>8} {:>8} {:>10.2f} {:>10} {:>14.2f} {:>10}'.format(
             m, int(found['counts'][m]), int(site), float(found['rms_mm'][m]), int(found['runner_up_ids'][m]),
             float(found['runner_up_rms_mm'][m]), 'same' if default == int(site) else 'was {}'.format(default)))
+    print('  {:>6} {:>10} {:>10}'.format('sensor', 'skin mm', 'rms mm'))
+    for m in range(len(found['vertex_ids'])):
+        print('  {:>6} {:>10.2f} {:>10.2f}'.format(m, float(found['skin_mm'][m]), float(found['rms_mm'][m])))
     if (found['vertex_ids'] < 0).any():
         raise SystemExit('sensors {} were read in no frame: no site, no offsets'.format(
             np.nonzero(found['vertex_ids'] < 0)[0].tolist()))

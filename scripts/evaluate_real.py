@@ -215,6 +215,34 @@ def temporal_tables(net, smpl, batches, device, args):
     return te_all, per_seq, smoother
 
 
+def skin_tables(net, smpl, batches, device):
+    """`--skin_distance`: the rank's recordings go through the model once more, chunked as `temporal_tables` chunks them,
+    and feed a `SkinDistanceEngine` (eval/surface_metrics.py) with the readings as the batch holds them.
+    :return: (engine over all of the rank's recordings, [(recording id, metrics dict)])"""
+    from em_pose_amd.eval.helpers import window_generator
+    from em_pose_amd.eval.surface_metrics import SkinDistanceEngine
+    from em_pose_amd.nn.models import IterativeErrorFeedback
+    se_all = SkinDistanceEngine(smpl)
+    per_seq = []
+    with torch.no_grad():
+        for batch in batches:
+            se = SkinDistanceEngine(smpl)
+            shape_hat = None
+            for c, chunk in enumerate(window_generator(batch, 256 if isinstance(net, IterativeErrorFeedback) else None)):
+                chunk = chunk.to_gpu(device)
+                pos, masks = chunk.marker_pos_real.clone(), chunk.marker_masks      # as recorded: the forward may suppress
+                out = net(chunk, is_new_sequence=(c == 0))
+                if c == 0:
+                    shape_hat = out['shape_hat'][:, 0] if out['shape_hat'] is not None else None
+                pose_hat = out['pose_hat'] if out['pose_hat'] is not None else chunk.poses_body
+                root_hat = out['root_ori_hat'] if out['root_ori_hat'] is not None else chunk.poses_root
+                se.compute(chunk.poses_body, chunk.shapes, pose_hat, shape_hat, chunk.seq_lengths, chunk.poses_root,
+                           root_hat, marker_pos=pos, marker_masks=masks)
+            per_seq.append((batch.ids[0], se.get_metrics()))
+            se_all.merge(se.state())
+    return se_all, per_seq
+
+
 def smooth_label(args):
     if args.smooth == 'window':
         return 'window (sigma {:g} frames)'.format(args.smooth_sigma)
@@ -309,6 +337,10 @@ def main():
                         'and the jitter of the joints per recording to stderr (needs a GPU); stdout is unchanged.')
     p.add_argument('--temporal_surface', action='store_true',
                    help='--temporal (which it implies) with the same figures over the vertices of the body surface.')
+    p.add_argument('--skin_distance', action='store_true',
+                   help='After the tables, run the recordings through the model once more and print, per recording, how far '
+                        'the readings are from the skin of the estimate and of the ground truth and how many lie inside '
+                        '(eval/surface_metrics.py) to stderr (needs a GPU); stdout is unchanged.')
     p.add_argument('--smooth', default=None, choices=['window', 'one_euro'],
                    help='--temporal: also filter the estimate (eval/smoothing.py) and print, in a second table on stderr, the '
                         'same columns plus MPJPE and MPJAE of the smoothed estimate.  window: a zero-phase Gaussian window over '
@@ -463,6 +495,25 @@ def main():
                     table.append([len(table), 'Overall average'] + list(sm_metrics.values()))
                     print(tabulate(table, headers=['Nr', 'E2E {} + {}'.format(name, smooth_label(args))] +
                                    list(sm_metrics.keys())), file=sys.stderr, flush=True)
+    if args.skin_distance:     # every rank; everything it prints goes to stderr
+        if device.type != 'cuda' or smpl is None:
+            if rank == 0:
+                print('--skin_distance needs a GPU: the query is a HIP kernel and has no CPU path; nothing printed',
+                      file=sys.stderr)
+        else:
+            se_all, se_seq = skin_tables(net, smpl, batches, device)
+            se_rows = [(i, sid, m) for i, (sid, m) in zip(mine, se_seq)]
+            if dist is not None:
+                se_all.gather(device=D.collective_device(device), force=args.force_dist)
+                gathered = [None] * world
+                dist.all_gather_object(gathered, se_rows)
+                se_rows = sorted(r for g in gathered for r in g)
+            if rank == 0:
+                se_metrics = se_all.get_metrics()
+                table = [[i, sid] + list(m.values()) for i, sid, m in se_rows]
+                table.append([len(table), 'Overall average'] + list(se_metrics.values()))
+                print(tabulate(table, headers=['Nr', 'E2E {}'.format(name)] + list(se_metrics.keys())), file=sys.stderr,
+                      flush=True)
     if args.visualize in mine:    # the rank that owns the recording; everything it prints goes to stderr
         visualize(net, smpl, batches[mine.index(args.visualize)], device, args)
     elif args.visualize >= len(lengths) and rank == 0:

@@ -7,12 +7,15 @@ per-vertex error of the surface and its Procrustes-aligned form (PVE, PA-PVE; ev
 the fit drifts globally, and only the aligned figures tell a rotated but well-posed body from a wrongly posed one.
 A second table holds the temporal columns of the joints (eval/temporal_metrics.py) for the same rows: the acceleration
 error and the jitter of the estimate beside the jitter of the ground truth, each window a sequence of its own.
+A third holds the skin distance of the readings (eval/surface_metrics.py): how far they are from the surface of the estimate
+and of the ground truth, how many lie inside either, and how deep -- the figure that needs no ground truth.  (On the
+stand-in body, whose surface may intersect itself, the inside columns follow the parity rule and mean little.)
 
     python scripts/fit_sensors.py --synthetic [--n_markers 6|12] [--steps K] [--refine] [--windows B] [--frames F]
                                   [--smooth {window,one_euro} [--smooth_sigma S] [--smooth_min_cutoff F --smooth_beta B]]
 
-`--smooth` adds a third table: the temporal columns, MPJPE and MPJAE of every row, raw and after the filter
-(eval/smoothing.py); the first two tables are what they are without it.
+`--smooth` adds a fourth table: the temporal columns, MPJPE and MPJAE of every row, raw and after the filter
+(eval/smoothing.py); the first three tables are what they are without it.
 
 `--synthetic` needs no data: `synthetic.make_windows` on the stand-in body model.  The script exits non-zero if the
 objective of what the fitter returns exceeds, for any window, the objective at its init.
@@ -32,6 +35,7 @@ from em_pose_amd.bodymodels.smpl import SMPLLayer  # noqa: E402
 from em_pose_amd.data.data import SyntheticBatch  # noqa: E402
 from em_pose_amd.eval.mesh_metrics import VertexErrorEngine  # noqa: E402
 from em_pose_amd.eval.metrics import MetricsEngine  # noqa: E402
+from em_pose_amd.eval.surface_metrics import SkinDistanceEngine  # noqa: E402
 from em_pose_amd.eval.smoothing import OneEuroFilter, gaussian_taps, smooth_model_output, window_filter  # noqa: E402
 from em_pose_amd.eval.temporal_metrics import TemporalMetricsEngine  # noqa: E402
 from em_pose_amd.helpers.configuration import lgd_config  # noqa: E402
@@ -70,6 +74,17 @@ def temporal_row(smpl, batch, name, out):
     return TEMPORAL_HEAD.format(name, *['{:.1f}'.format(m[k]) for k in TEMPORAL_COLUMNS])
 
 
+SKIN_HEAD = '{:<22s} {:>15s} {:>18s} {:>11s} {:>14s} {:>11s}'
+
+
+def skin_row(smpl, batch, name, out):
+    eng = SkinDistanceEngine(smpl)
+    eng.compute(batch.poses_body, batch.shapes, out['pose_hat'], out['shape_hat'], batch.seq_lengths, batch.poses_root,
+                out['root_ori_hat'], marker_pos=batch.marker_pos_synth, marker_masks=batch.marker_masks)
+    m = eng.get_metrics()
+    return SKIN_HEAD.format(name, *['{:.1f}'.format(m[k]) for k in SkinDistanceEngine.COLUMNS])
+
+
 SMOOTH_COLUMNS = TEMPORAL_COLUMNS + ('MPJPE [mm]', 'MPJAE [deg]')
 SMOOTH_HEAD = '{:<34s} {:>15s} {:>16s} {:>19s} {:>12s} {:>13s}'
 
@@ -97,7 +112,7 @@ def smoothing_filter(args):
 def main():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     p.add_argument('--smooth', default=None, choices=['window', 'one_euro'],
-                   help='a third table: the temporal columns, MPJPE and MPJAE of every row raw and after a filter of '
+                   help='a fourth table: the temporal columns, MPJPE and MPJAE of every row raw and after a filter of '
                         'eval/smoothing.py (window: zero-phase Gaussian; one_euro: the causal One-Euro filter)')
     p.add_argument('--smooth_sigma', type=float, default=2.0, help='--smooth window: sigma of the Gaussian, frames')
     p.add_argument('--smooth_min_cutoff', type=float, default=1.0, help='--smooth one_euro: cut-off at rest, Hz')
@@ -137,6 +152,9 @@ def main():
     print(TEMPORAL_HEAD.format('', *TEMPORAL_COLUMNS))
     for name, out in shown:
         print(temporal_row(smpl, batch, name, out))
+    print(SKIN_HEAD.format('', *SkinDistanceEngine.COLUMNS))
+    for name, out in shown:
+        print(skin_row(smpl, batch, name, out))
     if args.smooth:
         filt, label = smoothing_filter(args)
         valid = MetricsEngine.valid_frames(batch.seq_lengths, batch.poses_body.shape[0], batch.poses_body.shape[1])
